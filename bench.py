@@ -10,10 +10,16 @@ Multi-GPU: decode does not shard -- each rank runs an independe
 sequence through the in-library layer pipeline over all N GPUs (rwkv_mi355x_init_pipeline, driven by
 rank 0; peer copies over xGMI).  At N = 1 the same pipeline runs with every stage on GPU 0.
 
-Also reported (same run): 1024-token rwkv_eval_sequence throughput, ABI-level decode
+A plain run (--gpus 1 --steps K --warmup W) does that and nothing else: it loads the model, warms
+up, times the K steps and prints the result line.  --dump-outputs DIR additionally writes the
+logits and the recurrent state left by the last timed step (DIR/logits.npy, DIR/state.npy); the
+tokens are seeded, so two builds run with the same arguments can be compared output for output.
+
+With --full the same run also reports: the decode == sequence self-check, batched decode,
+1024-token rwkv_eval_sequence throughput, ABI-level decode
 (13 MB of host state in and out per token, the reference's contract), the dominant kernel's
 roofline (HIP events on the context stream, algorithmic bytes), and the CPU restatement of
-the reference arithmetic (oracle/) timed on this host's cores.
+the reference arithmetic (oracle/) timed on this host's cores, with the parity against it.
 
 Synthetic weights (no checkpoint can be downloaded): rwkv_mi355x_write_synthetic_model
 writes an rwkv.cpp file with the exact tensor shapes of the real checkpoint.
@@ -173,7 +179,20 @@ def main():
     ap.add_argument('--decode-only', action='store_true',
                     help='only the timed device-resident decode (warmup + steps, graph replays): the run a '
                          'rocprofv3 kernel trace of the decode chain is taken from (profiles/)')
+    ap.add_argument('--full', action='store_true',
+                    help='after the timed decode steps also run every other leg: self-check, batched decode, '
+                         'sequence evaluation (serial, chunked wkv, layer pipeline), ABI-level decode, kernel '
+                         'rooflines, CPU baseline and parity against the oracle.  Without it the run is the '
+                         'headline only: set-up, warm-up, the timed steps, the result line')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps write what the last timed step computed -- the logits and the '
+                         'recurrent state a caller of the device-resident decode holds -- as DIR/logits.npy and '
+                         'DIR/state.npy (float32; rank 0 only)')
     args = ap.parse_args()
+    if args.roofline_only and not args.full:
+        ap.error('--roofline-only is one of the --full legs: pass --full with it')
+    if args.steps < 1 or args.warmup < 0:
+        ap.error('--steps must be at least 1 and --warmup at least 0')
     errors = []  # any entry makes the run exit non-zero after the JSON line
 
     world = int(os.environ.get('WORLD_SIZE', '1'))
@@ -236,8 +255,10 @@ def main():
     # serial decode (the matvec kernels) and one sequence evaluation (the GEMM / sequence kernels) must
     # give the same bits on the same tokens -- the library's invariant; a fast kernel that drops work
     # breaks it, so no speed is reported from a build that fails it
-    # (skipped in the roofline-only profiling pass, whose kernel trace must hold the timed launches only)
-    sc_toks = [int(t) for t in np.random.default_rng(99).integers(0, n_vocab, 0 if args.roofline_only else 12)]
+    # (skipped in the roofline-only profiling pass, whose kernel trace must hold the timed launches only,
+    # and in a run without --full, which reports the decode rate alone)
+    sc_toks = [int(t) for t in np.random.default_rng(99).integers(0, n_vocab,
+                                                                  0 if args.roofline_only or not args.full else 12)]
     sc_st, sc_st2 = np.zeros(state_len, np.float32), np.zeros(state_len, np.float32)
     sc_lg, sc_lg2 = np.zeros(n_vocab, np.float32), np.zeros(n_vocab, np.float32)
     L.rwkv_init_state(ctx.ptr, sc_st.ctypes.data_as(P_F))
@@ -250,8 +271,9 @@ def main():
     self_check = {'decode_equals_sequence_bits': bool(np.array_equal(sc_lg.view(np.uint32), sc_lg2.view(np.uint32)) and
                                                       np.array_equal(sc_st.view(np.uint32), sc_st2.view(np.uint32))),
                   'tokens': len(sc_toks)}
-    log(f"self-check: serial decode == sequence eval bit for bit over {len(sc_toks)} tokens: "
-        f"{self_check['decode_equals_sequence_bits']}")
+    if args.full:
+        log(f"self-check: serial decode == sequence eval bit for bit over {len(sc_toks)} tokens: "
+            f"{self_check['decode_equals_sequence_bits']}")
 
     assert L.rwkv_mi355x_state_upload(ctx.ptr, None)
 
@@ -285,6 +307,41 @@ def main():
         ms_per_step = elapsed * 1e3 / args.steps
         value = world * args.steps / elapsed
         log(f'decode: {ms_per_step * 1e3:.1f} us/token, {value:.1f} tok/s aggregate over {world} GPU(s)')
+
+    # ---------------- what the last timed step computed (--dump-outputs) ----------------
+    # the caller of the device-resident decode holds the logits of the last token and the recurrent
+    # state, both in HBM; they are read back here, before any other leg touches the context
+    if args.dump_outputs and rank == 0:
+        dump_logits = np.zeros(n_vocab, np.float32)
+        dump_state = np.zeros(state_len, np.float32)
+        if L.rwkv_mi355x_debug_buffer(ctx.ptr, b'logits', dump_logits.ctypes.data, dump_logits.nbytes) != dump_logits.nbytes:
+            raise RuntimeError('reading the logits back failed')
+        if not L.rwkv_mi355x_state_download(ctx.ptr, dump_state.ctypes.data_as(P_F)):
+            raise RuntimeError('reading the state back failed')
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, 'logits.npy'), dump_logits)
+        np.save(os.path.join(args.dump_outputs, 'state.npy'), dump_state)
+        log(f'wrote logits.npy ({dump_logits.nbytes / 1e6:.2f} MB) and state.npy ({dump_state.nbytes / 1e6:.2f} MB) '
+            f'to {args.dump_outputs}')
+
+    head = {
+        'metric': METRIC, 'value': round(value, 2) if value is not None else None, 'unit': 'tokens/s',
+        'n_gpus': world, 'steps': args.steps,
+        'warmup': args.warmup, 'ms_per_step': round(ms_per_step, 5) if ms_per_step is not None else None,
+        'higher_is_better': True,
+        'scaling': 'weak', 'vs_baseline': None, 'dtype': f'i8 ({fmt[:2].lower()} x q8 int8 dot) + f32', 'data': 'synthetic',
+        'config': {'workload': f'{label} single-token decode (rwkv_eval semantics, logits on), '
+                               f'state resident in HBM', 'n_embed': C, 'n_layer': NL, 'n_vocab': V,
+                   'weights': fmt, 'parallelism': f'replicas x{world}'},
+    }
+    if not args.full:
+        # the plain run ends here: the headline figure and nothing else (the other legs: --full)
+        L.rwkv_free(ctx.ptr)
+        if rank == 0:
+            print(json.dumps(head), flush=True)
+        if world > 1:
+            dist.destroy_process_group()
+        return
     if args.decode_only or args.roofline_only:
         args.batch, args.seq_reps, args.abi_steps, args.skip_cpu = '', 0, 0, True
 
@@ -629,14 +686,7 @@ def main():
     L.rwkv_free(ctx.ptr)
     if rank == 0:
         out = {
-            'metric': METRIC, 'value': round(value, 2) if value is not None else None, 'unit': 'tokens/s',
-            'n_gpus': world, 'steps': args.steps,
-            'warmup': args.warmup, 'ms_per_step': round(ms_per_step, 5) if ms_per_step is not None else None,
-            'higher_is_better': True,
-            'scaling': 'weak', 'vs_baseline': None, 'dtype': f'i8 ({fmt[:2].lower()} x q8 int8 dot) + f32', 'data': 'synthetic',
-            'config': {'workload': f'{label} single-token decode (rwkv_eval semantics, logits on), '
-                                   f'state resident in HBM', 'n_embed': C, 'n_layer': NL, 'n_vocab': V,
-                       'weights': fmt, 'parallelism': f'replicas x{world}'},
+            **head,
             'seq_eval': {'tokens_per_s': round(seq_tps * world, 1), 'T': args.seq_len,
                          'ms_per_sequence': round(seq_s * 1e3, 3), 'parallelism': f'replicas x{world}',
                          'pipeline': pipe, 'wkv_chunked': wkvc},

@@ -74,30 +74,30 @@ def check(path, toks, in_place, chunk=None):
     lib.rwkv_free(ref)
 
 
-def test_pinned_real_width():
+def test_pinned_real_width(tmp_path):
     """v6 at the 1B6 width (2 layers): the per-layer slices are real-sized."""
     lib = library()
-    p = '/tmp/rwkv_pinned_v6.bin'
+    p = str(tmp_path / 'rwkv_pinned_v6.bin')
     assert lib.library.rwkv_mi355x_write_synthetic_model(p.encode(), 6, 4096, 2048, 2, 0, b'Q4_0', 3)
     check(p, [1, 2, 3, 400, 5], True)
 
 
 @pytest.mark.parametrize('chunk', [1, 4])
-def test_chunk_sizes(chunk):
+def test_chunk_sizes(tmp_path, chunk):
     """Layer chunks of 1 (every layer its own graph) and uneven chunks (the last one shorter)."""
     lib = library()
-    p = '/tmp/rwkv_pinned_v5.bin'
+    p = str(tmp_path / 'rwkv_pinned_v5.bin')
     assert lib.library.rwkv_mi355x_write_synthetic_model(p.encode(), 5, 1024, 512, 6, 0, b'Q5_1', 4)
     check(p, [9, 8, 7], False, chunk=chunk)
 
 
-def test_host_state_after_async_device_eval():
+def test_host_state_after_async_device_eval(tmp_path):
     """rwkv_eval with a host state_in right after rwkv_mi355x_eval_device(sync = false): the chunked
     upload must wait for the decode steps still queued on the context's stream (they write the
     buffer the upload fills).  Equal to a fresh context given the same host state, bit for bit."""
     lib = library()
     L = lib.library
-    p = '/tmp/rwkv_async_v6.bin'
+    p = str(tmp_path / 'rwkv_async_v6.bin')
     assert L.rwkv_mi355x_write_synthetic_model(p.encode(), 6, 4096, 2048, 4, 0, b'Q4_0', 6)
     ctx = lib.rwkv_init_from_file(p, 1, 99)
     ref = lib.rwkv_init_from_file(p, 1, 99)

@@ -388,7 +388,7 @@ def test_v6_1b6_width_token1_vs_ggml_order(tmp_path):
     the FIRST token -- before any Q8 re-quantization flip can be amplified by the recurrence -- must
     sit within 1e-4 of the ggml-order oracle (variant 0): max|dlogit| <= 1e-4 and max|dstate| <= 1e-4
     relative to max|state|.  This is where a systematic error of the GPU association would show;
-    later tokens are bounded by the oracle's noise band (bench.py's parity reports the growth).
+    later tokens are bounded by the oracle's noise band (bench.py --full's parity reports the growth).
     Measured on the oracle's GPU-association variant (which the GPU equals bit for bit): 1.7e-5 and
     3.6e-7 relative."""
     L = library()

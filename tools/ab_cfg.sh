@@ -4,5 +4,5 @@
 cd $GRAFT_REPO_ROOT
 CFG=$1; shift
 for v in "$@"; do
-  env $v timeout -k 10 300 python3 bench.py --config $CFG --steps 128 --warmup 8 --skip-cpu --seq-reps 2 --abi-steps 0 --batch "" 2>&1 | grep -E "decode:|seq-eval" | sed "s/^/[$v] /" || exit 1
+  env $v timeout -k 10 300 python3 bench.py --full --config $CFG --steps 128 --warmup 8 --skip-cpu --seq-reps 2 --abi-steps 0 --batch "" 2>&1 | grep -E "decode:|seq-eval" | sed "s/^/[$v] /" || exit 1
 done

@@ -1,15 +1,18 @@
 #!/bin/bash
 # One GPU cycle on the box: parity tests, bench (with the CPU baseline), rocprofv3 kernel trace.
 # Usage: tools/gpu_cycle.sh TAG [skip-tests]
+REPO=$(cd "$(dirname "$0")/.." && pwd)
+OUT=${OUT:-$REPO/bench_out}  # where this script writes; override with OUT=...
+mkdir -p "$OUT"
 TAG=${1:-x}
-cd $GRAFT_REPO_ROOT
+cd $REPO
 if [ "$2" != "skip-tests" ]; then
-  timeout -k 10 600 python -u -m pytest tests -m gpu -q -p no:cacheprovider --timeout 300 --timeout-method thread -x > gpurun_out/gpu_$TAG.log 2>&1
+  timeout -k 10 600 python -u -m pytest tests -m gpu -q -p no:cacheprovider --timeout 300 --timeout-method thread -x > $OUT/gpu_$TAG.log 2>&1
   rc=$?
-  echo EXIT $rc >> gpurun_out/gpu_$TAG.log
+  echo EXIT $rc >> $OUT/gpu_$TAG.log
   # test failures (1) still allow a measurement; a fault, abort or timeout ends the call
   if [ $rc -ne 0 ] && [ $rc -ne 1 ]; then exit $rc; fi
 fi
-timeout -k 10 400 python bench.py > gpurun_out/bench_$TAG.json 2> gpurun_out/bench_$TAG.err || exit 1
+timeout -k 10 400 python bench.py --full > $OUT/bench_$TAG.json 2> $OUT/bench_$TAG.err || exit 1
 cd /tmp && export TMPDIR=/tmp
-timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $GRAFT_REPO_ROOT/gpurun_out/prof_$TAG -o run --output-format csv -- python3 $GRAFT_REPO_ROOT/bench.py --steps 64 --skip-cpu --seq-reps 1 > $GRAFT_REPO_ROOT/gpurun_out/prof_$TAG.log 2>&1
+timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $OUT/prof_$TAG -o run --output-format csv -- python3 $REPO/bench.py --full --steps 64 --skip-cpu --seq-reps 1 > $OUT/prof_$TAG.log 2>&1

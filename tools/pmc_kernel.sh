@@ -1,12 +1,15 @@
 #!/bin/bash
 # One PMC pass (SQ counters) over the kernels matching REGEX in a short sequence-eval bench run.
 # Usage: tools/pmc_kernel.sh TAG REGEX
-ROOT=$GRAFT_REPO_ROOT
+REPO=$(cd "$(dirname "$0")/.." && pwd)
+OUT=${OUT:-$REPO/bench_out}  # where this script writes; override with OUT=...
+mkdir -p "$OUT"
+ROOT=$REPO
 cd /tmp && export TMPDIR=/tmp
 timeout -s KILL 120 rocprofv3 --pmc SQ_WAVES SQ_INSTS_VALU SQ_INSTS_LDS SQ_INSTS_SALU SQ_WAVE_CYCLES SQ_WAIT_INST_ANY SQ_INSTS_VMEM_WR SQ_INSTS_VMEM_RD \
-  --kernel-include-regex "$2" -d $ROOT/gpurun_out/pmc_$1 -o run --output-format csv -- \
-  python3 $ROOT/bench.py --steps 4 --warmup 1 --skip-cpu --seq-reps 1 --batch "" --abi-steps 0 --timing-steps 0 > $ROOT/gpurun_out/pmc_$1.log 2>&1 || exit 6
-python3 - $ROOT/gpurun_out/pmc_$1 <<'PY'
+  --kernel-include-regex "$2" -d $OUT/pmc_$1 -o run --output-format csv -- \
+  python3 $ROOT/bench.py --full --steps 4 --warmup 1 --skip-cpu --seq-reps 1 --batch "" --abi-steps 0 --timing-steps 0 > $OUT/pmc_$1.log 2>&1 || exit 6
+python3 - $OUT/pmc_$1 <<'PY'
 import csv, glob, sys, collections
 f = glob.glob(sys.argv[1] + '/**/*counter_collection.csv', recursive=True)
 agg = collections.defaultdict(lambda: collections.defaultdict(float)); n = collections.Counter()

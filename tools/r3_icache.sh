@@ -16,7 +16,7 @@ pass() {  # pass NAME COUNTERS...
   echo "pass $name:$have"
   timeout -s KILL 90 rocprofv3 --pmc $have --kernel-include-regex 'k_mv|k_mva|att6|maa|k_embed' \
     -d $ROOT/gpurun_out/pmc_${TAG}_$name -o run --output-format csv -- \
-    python3 $ROOT/bench.py --steps 32 --warmup 2 --skip-cpu --seq-reps 1 --seq-len 64 --batch "" --abi-steps 0 --timing-steps 0 \
+    python3 $ROOT/bench.py --full --steps 32 --warmup 2 --skip-cpu --seq-reps 1 --seq-len 64 --batch "" --abi-steps 0 --timing-steps 0 \
     > $ROOT/gpurun_out/pmc_${TAG}_$name.log 2>&1 || { echo "pass $name failed"; tail -3 $ROOT/gpurun_out/pmc_${TAG}_$name.log; return 1; }
   python3 $ROOT/tools/pmc_agg.py $ROOT/gpurun_out/pmc_${TAG}_$name > $ROOT/gpurun_out/pmc_${TAG}_$name.txt 2>&1 || true
 }

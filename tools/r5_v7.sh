@@ -5,5 +5,5 @@ timeout -k 10 600 python -u -m pytest tests/test_gpu_parity.py tests/test_gpu_co
 rc=$?; tail -5 gpurun_out/v7_tests.log
 if [ $rc -ne 0 ]; then exit $rc; fi
 for v in RWKV_MI355X_ATT7_LORA=0 RWKV_MI355X_ATT7_LORA=1; do
-  env $v timeout -k 10 300 python3 bench.py --config v7-2b9-q5_1 --steps 64 --warmup 8 --skip-cpu --seq-reps 1 --abi-steps 0 --batch "" --timing-steps 2 --pipe-stages 0 2>&1 | grep -E "decode:|k_att7|k_mv |k_mva" | sed "s/^/[$v] /"
+  env $v timeout -k 10 300 python3 bench.py --full --config v7-2b9-q5_1 --steps 64 --warmup 8 --skip-cpu --seq-reps 1 --abi-steps 0 --batch "" --timing-steps 2 --pipe-stages 0 2>&1 | grep -E "decode:|k_att7|k_mv |k_mva" | sed "s/^/[$v] /"
 done

@@ -13,6 +13,6 @@ timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $O/wkvc_prof -o run --outp
 grep "relative" $O/wkvc_prof.log
 grep -E "wkv" $(find $O/wkvc_prof -name "*kernel_stats.csv") | cut -c1-150
 cd $GRAFT_REPO_ROOT
-timeout -k 10 400 python3 bench.py --steps 16 --warmup 4 --batch "" --abi-steps 0 --skip-cpu --pipe-stages 0 --seq-reps 3 \
+timeout -k 10 400 python3 bench.py --full --steps 16 --warmup 4 --batch "" --abi-steps 0 --skip-cpu --pipe-stages 0 --seq-reps 3 \
   > $O/wkvc_bench.json 2> $O/wkvc_bench.err || { tail -5 $O/wkvc_bench.err; exit 1; }
 grep -E "seq-eval" $O/wkvc_bench.err

@@ -23,13 +23,13 @@ for s in $STEPS; do
       if [ $rc -ne 0 ] && [ $rc -ne 1 ]; then echo "tests rc $rc"; exit $rc; fi
       ;;
     bench)
-      timeout -k 10 500 python bench.py > $O/r6_${TAG}_bench.json 2> $O/r6_${TAG}_bench.err || { tail -5 $O/r6_${TAG}_bench.err; exit 1; }
+      timeout -k 10 500 python bench.py --full > $O/r6_${TAG}_bench.json 2> $O/r6_${TAG}_bench.err || { tail -5 $O/r6_${TAG}_bench.err; exit 1; }
       grep -E "decode:|seq-eval|pipeline|seq GEMM|ABI" $O/r6_${TAG}_bench.err
       ;;
     prof)
       cd /tmp && export TMPDIR=/tmp
       timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $O/r6_${TAG}_profr -o run --output-format csv -- \
-        python3 $ROOT/bench.py --roofline-only --timing-steps 32 --warmup 0 --pipe-stages 0 > $O/r6_${TAG}_profr.log 2>&1 \
+        python3 $ROOT/bench.py --full --roofline-only --timing-steps 32 --warmup 0 --pipe-stages 0 > $O/r6_${TAG}_profr.log 2>&1 \
         || { tail -5 $O/r6_${TAG}_profr.log; exit 1; }
       cd $ROOT
       CSV=$(find $O/r6_${TAG}_profr -name "*kernel_stats.csv" | head -1)
@@ -52,7 +52,7 @@ for s in $STEPS; do
     configs)
       # the other BASELINE configurations' lines (decode, seq-eval, batched B = 8 / 64, ABI decode)
       for c in ${CONFIGS:-v4-169m-q8_0 v7-2b9-q5_1 v5-7b-q4_1}; do
-        timeout -k 10 400 python3 bench.py --config $c --steps 64 --warmup 8 --batch "8,64" --seq-reps 2 --abi-steps 8 \
+        timeout -k 10 400 python3 bench.py --full --config $c --steps 64 --warmup 8 --batch "8,64" --seq-reps 2 --abi-steps 8 \
           --skip-cpu --pipe-stages 0 > $O/r6_${TAG}_$c.log 2>&1 || { tail -5 $O/r6_${TAG}_$c.log; exit 1; }
         grep '^{' $O/r6_${TAG}_$c.log > $O/r6_${TAG}_$c.json
         grep -E "decode:|seq-eval" $O/r6_${TAG}_$c.log | sed "s/^/[$c] /" | cut -c1-160
@@ -60,7 +60,7 @@ for s in $STEPS; do
       ;;
     pipe8)
       # BASELINE config 5's pipeline: v5-7B, 8 stages on this box's one GPU, 4096 tokens
-      timeout -k 10 400 python3 bench.py --config v5-7b-q4_1 --steps 8 --warmup 2 --batch "" --seq-len 4096 --seq-reps 1 \
+      timeout -k 10 400 python3 bench.py --full --config v5-7b-q4_1 --steps 8 --warmup 2 --batch "" --seq-len 4096 --seq-reps 1 \
         --abi-steps 0 --skip-cpu --timing-steps 1 --pipe-stages 8 > $O/r6_${TAG}_pipe8.log 2>&1 || { tail -5 $O/r6_${TAG}_pipe8.log; exit 1; }
       grep -E "pipeline|seq-eval" $O/r6_${TAG}_pipe8.log | cut -c1-200
       ;;
