@@ -1,4 +1,5 @@
-// engine.hip -- device model upload and the per-version forward programs.
+// engine.hip -- device model upload, the per-version sequence / batched forward programs and the
+// evaluation entry points (the single-token decode program: engine_decode.hip).
 //
 // A token step is a fixed sequence of launches on the context's stream.  The T == 1 step
 // is captured once into a hipGraph per (state parity, logits) and replayed, so decode pays
@@ -628,18 +629,6 @@ struct MMBatch {
     }
 };
 
-static double act_bytes(const ActBuf & a, double T) {
-    const double K = a.K;
-    switch (a.fmt) {
-        case A_F32: return T * K * 4;
-        case A_F16: return T * K * 2;
-        case A_Q8_1: return T * K + T * K / 32 * 12;
-        default: return T * K + T * K / 32 * 8;
-    }
-}
-
-static double wbytes(const DMat & W) { return (double)type_nbytes((uint32_t)W.type, (uint64_t)W.M * W.K); }
-
 void Engine::set_timing(bool on) {
     (void)hipStreamSynchronize(stream_);
     collect_timing();
@@ -832,19 +821,26 @@ const std::vector<KernelStat> & Engine::stats() {
     return stats_;
 }
 
-bool Engine::ffn(int l, int T, const float * si, float * so) {
-    const DLayer & L = m_->layers[l];
-    const int C = (int)m_->n_embed;
+// The LayerNorm + token shift + mix launch of a sequence / batched layer, up to its outputs:
+// carry_in / carry_out = the layer's *_xx state row (context t's at + t * bs_ in a batched step)
+LnMixArgs Engine::ln_mix_args(int T, const float * carry_in, float * carry_out, const float * lnw, const float * lnb) const {
     LnMixArgs a;
     memset(&a, 0, sizeof(a));
     a.T = T;
-    a.C = C;
+    a.C = (int)m_->n_embed;
     a.x = x_;
-    a.carry_in = si;        // ffn_xx at layer offset 0
-    a.carry_out = so;
+    a.carry_in = carry_in;
+    a.carry_out = carry_out;
     a.bs = bs_;
-    a.lnw = L.ln2_w;
-    a.lnb = L.ln2_b;
+    a.lnw = lnw;
+    a.lnb = lnb;
+    return a;
+}
+
+bool Engine::ffn(int l, int T, const float * si, float * so) {
+    const DLayer & L = m_->layers[l];
+    const int C = (int)m_->n_embed;
+    LnMixArgs a = ln_mix_args(T, si, so, L.ln2_w, L.ln2_b);  // ffn_xx at layer offset 0
     MMBatch b;
     if (m_->major == 7) {
         // rwkv_graph.inc:533-543
@@ -875,31 +871,33 @@ bool Engine::ffn(int l, int T, const float * si, float * so) {
     return b.run(*this, T);
 }
 
+static bool launch_att_dec(hipStream_t st, const Att6Dec & a) { return launch_att6_dec(st, a); }
+static bool launch_att_dec(hipStream_t st, const Att7Dec & a) { return launch_att7_dec(st, a); }
+
 // Batched decode (bs_ > 0): the attention core of every context is the decode kernel itself (one
 // workgroup per head and context, k_att6_dec / k_att7_dec); its output goes to Wo's input `o`
 // (emitted by the kernel when heads are whole quantization blocks, else fp32 y_ converted).
+// The rest of such a layer: a = att6_args / att7_args, then Wo (input slot wo_slot) and the FFN.
 template <class Att>
-static void batch_att(Att & a, int T, size_t bs, float * y, const ActBuf & o, int S) {
+bool Engine::batch_att_tail(Att a, int wo_slot, int l, int T, const float * si, float * so) {
+    const DLayer & L = m_->layers[l];
+    const int C = (int)m_->n_embed;
+    ActBuf o = A(wo_slot, L.att_o);
     a.nb = T;
-    a.bs = bs;
-    a.y = y;
-    a.yq.fmt = -1;
-    if (S >= 32) a.yq = o;
+    a.bs = bs_;
+    if (a.S >= 32) a.yq = o;
+    if (!launch_att_dec(stream_, a)) return false;
+    if (a.S < 32 && !launch_act_from_f32(stream_, y_, T, C, o)) return false;
+    MMBatch b;
+    b.add(L.att_o, o, x_, C, EPI_ADD);
+    if (!b.run(*this, T)) return false;
+    return ffn(l, T, si, so);
 }
 
 bool Engine::layer_v4(int l, int T, const float * si, float * so) {
     const DLayer & L = m_->layers[l];
     const int C = (int)m_->n_embed;
-    LnMixArgs a;
-    memset(&a, 0, sizeof(a));
-    a.T = T;
-    a.C = C;
-    a.x = x_;
-    a.carry_in = si + C;
-    a.carry_out = so + C;
-    a.bs = bs_;
-    a.lnw = L.ln1_w;
-    a.lnb = L.ln1_b;
+    LnMixArgs a = ln_mix_args(T, si + C, so + C, L.ln1_w, L.ln1_b);
     a.form = 0;
     a.n_out = 3;
     a.mu[0] = L.att_mix_k;
@@ -953,16 +951,7 @@ bool Engine::layer_v5(int l, int T, const float * si, float * so) {
     const DLayer & L = m_->layers[l];
     const int C = (int)m_->n_embed, H = (int)m_->H, S = (int)m_->S;
     const bool v52 = m_->minor >= 2;
-    LnMixArgs a;
-    memset(&a, 0, sizeof(a));
-    a.T = T;
-    a.C = C;
-    a.x = x_;
-    a.carry_in = si + C;
-    a.carry_out = so + C;
-    a.bs = bs_;
-    a.lnw = L.ln1_w;
-    a.lnb = L.ln1_b;
+    LnMixArgs a = ln_mix_args(T, si + C, so + C, L.ln1_w, L.ln1_b);
     a.form = 0;
     a.n_out = v52 ? 4 : 3;
     a.mu[0] = L.att_mix_k;
@@ -982,30 +971,7 @@ bool Engine::layer_v5(int l, int T, const float * si, float * so) {
     b.add(L.att_v, A(1, L.att_v), v_, C, EPI_STORE);
     if (v52) b.add(L.att_g, A(3, L.att_g), g_, C, EPI_SILU);
     if (!b.run(*this, T)) return false;
-    if (bs_) {
-        Att6Dec d;
-        memset(&d, 0, sizeof(d));
-        d.H = H;
-        d.S = S;
-        d.r = r_;
-        d.k = k_;
-        d.v = v_;
-        d.g = v52 ? g_ : nullptr;
-        d.u = L.att_u;
-        d.w = L.att_w;
-        d.sin = si + 2 * C;
-        d.sout = so + 2 * C;
-        d.lnx_w = L.att_lnx_w;
-        d.lnx_b = L.att_lnx_b;
-        d.eps = 1e-5f;
-        ActBuf o = A(4, L.att_o);
-        batch_att(d, T, bs_, y_, o, S);
-        if (!launch_att6_dec(stream_, d)) return false;
-        if (S < 32 && !launch_act_from_f32(stream_, y_, T, C, o)) return false;
-        b.add(L.att_o, o, x_, C, EPI_ADD);
-        if (!b.run(*this, T)) return false;
-        return ffn(l, T, si, so);
-    }
+    if (bs_) return batch_att_tail(att6_args(L, si, so), 4, l, T, si, so);
     if (!wkv6(T, H, S, L.att_u, L.att_w, 0, si + 2 * C, so + 2 * C)) return false;
     ActBuf o = A(4, L.att_o);
     if (!launch_groupnorm(stream_, T, H, S, 1e-5f, y_, L.att_lnx_w, L.att_lnx_b, v52 ? 1 : 0, g_, nullptr, nullptr, o))
@@ -1018,16 +984,7 @@ bool Engine::layer_v5(int l, int T, const float * si, float * so) {
 bool Engine::layer_v6(int l, int T, const float * si, float * so) {
     const DLayer & L = m_->layers[l];
     const int C = (int)m_->n_embed, H = (int)m_->H, S = (int)m_->S, D = m_->maa_D;
-    LnMixArgs a;
-    memset(&a, 0, sizeof(a));
-    a.T = T;
-    a.C = C;
-    a.x = x_;
-    a.carry_in = si + C;
-    a.carry_out = so + C;
-    a.bs = bs_;
-    a.lnw = L.ln1_w;
-    a.lnb = L.ln1_b;
+    LnMixArgs a = ln_mix_args(T, si + C, so + C, L.ln1_w, L.ln1_b);
     a.form = 1;
     a.n_out = 1;
     a.mu[0] = L.maa_x;
@@ -1059,31 +1016,7 @@ bool Engine::layer_v6(int l, int T, const float * si, float * so) {
         b.add(L.att_g, outs[4], g_, C, EPI_SILU);
         b.add(L.decay_w1, outs[0], lora_, L.decay_w1.M, EPI_TANH);
         if (!b.run(*this, T)) return false;
-        Att6Dec d;
-        memset(&d, 0, sizeof(d));
-        d.H = H;
-        d.S = S;
-        d.r = r_;
-        d.k = k_;
-        d.v = v_;
-        d.g = g_;
-        d.u = L.att_u;
-        d.wd2 = L.decay_w2;
-        d.dl = lora_;
-        d.ldd = L.decay_w1.M;
-        d.decay = L.decay6;
-        d.sin = si + 2 * C;
-        d.sout = so + 2 * C;
-        d.lnx_w = L.att_lnx_w;
-        d.lnx_b = L.att_lnx_b;
-        d.eps = 64e-5f;
-        ActBuf o = A(7, L.att_o);
-        batch_att(d, T, bs_, y_, o, S);
-        if (!launch_att6_dec(stream_, d)) return false;
-        if (S < 32 && !launch_act_from_f32(stream_, y_, T, C, o)) return false;
-        b.add(L.att_o, o, x_, C, EPI_ADD);
-        if (!b.run(*this, T)) return false;
-        return ffn(l, T, si, so);
+        return batch_att_tail(att6_args(L, si, so), 7, l, T, si, so);
     }
     b.add(L.att_r, outs[3], r_, C, EPI_STORE);
     b.add(L.att_k, outs[1], k_, C, EPI_STORE);
@@ -1109,16 +1042,7 @@ bool Engine::layer_v6(int l, int T, const float * si, float * so) {
 bool Engine::layer_v7(int l, int T, const float * si, float * so) {
     const DLayer & L = m_->layers[l];
     const int C = (int)m_->n_embed, H = (int)m_->H, S = (int)m_->S;
-    LnMixArgs a;
-    memset(&a, 0, sizeof(a));
-    a.T = T;
-    a.C = C;
-    a.x = x_;
-    a.carry_in = si + C;
-    a.carry_out = so + C;
-    a.bs = bs_;
-    a.lnw = L.ln1_w;
-    a.lnb = L.ln1_b;
+    LnMixArgs a = ln_mix_args(T, si + C, so + C, L.ln1_w, L.ln1_b);
     a.form = 1;
     // order r, w, k, v, a, g (rwkv_graph.inc:404-413)
     const DMat * cons[6] = {&L.att_r, &L.w1, &L.att_k, &L.att_v, &L.a1, &L.g1};
@@ -1168,32 +1092,7 @@ bool Engine::layer_v7(int l, int T, const float * si, float * so) {
     b.add(L.g2, lg, g_, C, EPI_STORE);
     if (vlora) b.add(L.v2, lvv, v_, C, EPI_VMIX7, vfirst_, L.v0);
     if (!b.run(*this, T)) return false;
-    if (bs_) {
-        Att7Dec d;
-        memset(&d, 0, sizeof(d));
-        d.H = H;
-        d.S = S;
-        d.r = r_;
-        d.w = w_;
-        d.k = k_;
-        d.v = v_;
-        d.a = a_;
-        d.g = g_;
-        d.k_k = L.k_k;
-        d.k_a = L.k_a;
-        d.r_k = L.r_k;
-        d.sin = si + 2 * C;
-        d.sout = so + 2 * C;
-        d.lnx_w = L.att_lnx_w;
-        d.lnx_b = L.att_lnx_b;
-        ActBuf o = A(0, L.att_o);
-        batch_att(d, T, bs_, y_, o, S);
-        if (!launch_att7_dec(stream_, d)) return false;
-        if (S < 32 && !launch_act_from_f32(stream_, y_, T, C, o)) return false;
-        b.add(L.att_o, o, x_, C, EPI_ADD);
-        if (!b.run(*this, T)) return false;
-        return ffn(l, T, si, so);
-    }
+    if (bs_) return batch_att_tail(att7_args(L, si, so), 0, l, T, si, so);
     if (!launch_v7_prep(stream_, T, H, S, k_, a_, r_, L.k_k, L.k_a, L.r_k, nb_, bb_, bonus_)) return false;
     // the serial recurrence (bit-exact with decode), or behind the wkv_chunk_ switch the chunk-parallel
     // form (wkv7_chunk.hip; scratch in wkvc_)
@@ -1221,7 +1120,7 @@ bool Engine::forward_range(int T, const float * sin, float * sout, uint32_t l0, 
     const size_t C = m_->n_embed;
     last_decode_ = false;
     if (l0 == 0 && !launch_embed_ln(stream_, dtokens_, T, m_->emb, m_->ln0_w, m_->ln0_b, x_)) return false;
-    const size_t per_layer = m_->major >= 5 ? C * (2 + (size_t)m_->S) : 5 * C;
+    const size_t per_layer = layer_state_len();
     // layer matmuls run over all T tokens: Q8 activations go straight into GEMM tiles
     tile_acts_ = T >= 2 && !use_mm_ && (!bs_ || T >= batch_gemm_min_);
     for (uint32_t l = l0; l < l1; l++) {
@@ -1252,23 +1151,6 @@ bool Engine::forward_range(int T, const float * sin, float * sout, uint32_t l0, 
         if (!b.run(*this, rows)) return false;
     }
     return true;
-}
-
-bool Engine::mv(MVGroup & g, hipStream_t st) {
-    if (timing_) {
-        // the group's single launch is timed by its own dispatch events (RK_LAUNCH, g_klt)
-        double bytes = 0, flops = 0;
-        for (int i = 0; i < g.n; i++) {
-            const MVEntry & e = g.e[i];
-            bytes += (double)type_nbytes((uint32_t)e.W.type, (uint64_t)e.W.M * e.W.K);
-            bytes += e.src == SRC_ACT ? act_bytes(e.act, 1) : (double)e.W.K * 4 * (e.src == SRC_LNMIX ? 5 : 1);
-            bytes += (double)e.W.M * 4 * ((e.epi == EPI_ADD || e.epi == EPI_SIGMUL_ADD || e.epi == EPI_VMIX7) ? 2 : 1);
-            flops += 2.0 * e.W.M * e.W.K;
-        }
-        kt_bytes_ = bytes;
-        kt_flops_ = flops;
-    }
-    return launch_mv_group(st ? st : stream_, g);
 }
 
 // KLaunchTimer (common.hpp): while a decode step is timed, every RK_LAUNCH takes an event pair
@@ -1304,533 +1186,20 @@ void Engine::end(const char * kernel) {
     kt_bytes_ = kt_flops_ = 0;
 }
 
-// Builder for decode matvec groups.
-struct MV {
-    MVGroup g;
-    MV() { memset(&g, 0, sizeof(g)); }
-    MVEntry & add(const DMat & W, float * y, int epi, const float * aux = nullptr, const float * bias = nullptr) {
-        MVEntry & e = g.e[g.n++];
-        e.W = W;
-        e.y = y;
-        e.epi = epi;
-        e.aux = aux;
-        e.bias = bias;
-        return e;
+// Captures what build() enqueues on stream_ and instantiates it as ge.  A failed build still ends
+// the capture (the stream has to leave capture mode) before its graph is dropped.
+template <class F>
+bool Engine::capture(hipGraphExec_t & ge, F && build) {
+    hipGraph_t g = nullptr;
+    HIP_OK(hipStreamBeginCapture(stream_, hipStreamCaptureModeThreadLocal));
+    const bool ok = build();
+    HIP_OK(hipStreamEndCapture(stream_, &g));
+    if (!ok) {
+        (void)hipGraphDestroy(g);
+        return false;
     }
-};
-
-static void src_lnmix(MVEntry & e, const float * x, const float * carry, const float * lnw, const float * lnb,
-                      const float * mu, int form, float * carry_out = nullptr) {
-    e.src = SRC_LNMIX;
-    e.x = x;
-    e.carry = carry;
-    e.lnw = lnw;
-    e.lnb = lnb;
-    e.mu = mu;
-    e.form = form;
-    e.carry_out = carry_out;
-}
-
-static void src_f32(MVEntry & e, const float * f) {
-    e.src = SRC_F32;
-    e.f = f;
-}
-
-// Single-token forward: the fused decode program (kernels_decode.hip).  Per layer:
-//   v6: W1+LN (1) -> mix5 (1) -> r,k,v,g,Wd1 (1) -> decay tail+wkv+GN (1) -> Wo (1) -> FFN k,r+LN (1) -> FFN v (1)
-//   v5: r,k,v,g+LN (1) -> wkv+GN (1) -> Wo (1) -> FFN (2)      v4: r,k,v+LN (1) -> wkv4 (1) -> Wo (1) -> FFN (2)
-//   v7: r,k,v,LoRA-in+LN (1) -> LoRA-out (1) -> prep+wkv7+GN (1) -> Wo (1) -> FFN (2)
-// Layers [l0, l1) (embedding when l0 == 0, head when l1 == n_layer and logits).
-bool Engine::forward_decode(const float * sin, float * sout, bool logits, uint32_t l0, uint32_t l1) {
-    const int C = (int)m_->n_embed, H = (int)m_->H, S = (int)m_->S;
-    l1 = std::min(l1, m_->n_layer);
-    // v6: layer 0's maa launch computes the embedding LayerNorm itself (k_v6_maa_dec4 EMB: the same
-    // bits as k_embed_ln; one launch and one boundary less per token)
-    MaaDec emaa;
-    bool emb_in = false;
-    if (l0 == 0 && l1 > 0 && m_->major == 6 && (fuse_ & FUSE_EMBMAA) && !split_maa_) {
-        const DLayer & F = m_->layers[0];
-        const ActBuf o0[5] = {A(1, F.decay_w1), A(2, F.att_k), A(3, F.att_v), A(4, F.att_r), A(5, F.att_g)};
-        v6_maa_dec_args(emaa, C, m_->maa_D, F.maa_w1, x_, sin + C, sout + C, F.ln1_w, F.ln1_b, F.maa_x, F.maa_w2t,
-                        F.maa, o0);
-        emaa.tok = dtokens_;
-        emaa.emb = m_->emb;
-        emaa.ln0w = m_->ln0_w;
-        emaa.ln0b = m_->ln0_b;
-        emaa.xout = x_;
-        emb_in = v6_maa_emb_supported(emaa);
-    }
-    // v4: the same inside layer 0's fused attention launch (with Wo fused: the Wo rows store x)
-    bool emb4_in = false;
-    if (l0 == 0 && l1 > 0 && m_->major == 4 && (fuse_ & FUSE_EMBMAA) && (fuse_ & FUSE_ATT4) && (fuse_ & FUSE_WO4)) {
-        const DLayer & F = m_->layers[0];
-        emb4_in = v4_att_fused_supported(C, F.att_r, F.att_k, F.att_v, A(0, F.att_o)) && F.att_o.type == F.att_r.type &&
-                  C % 8 == 0 && (m_->emb.type == W_F16 || m_->emb.type == W_F32) && (int)m_->emb.K == C;
-        emb_in = emb4_in;
-    }
-    if (l0 == 0 && !emb_in && !launch_embed_ln(stream_, dtokens_, 1, m_->emb, m_->ln0_w, m_->ln0_b, x_)) return false;
-    v7_fused_lora_ = false;
-    const size_t per_layer = m_->major >= 5 ? (size_t)C * (2 + (size_t)S) : 5 * (size_t)C;
-    bool maa_done = false;  // this layer's maa ran in the previous layer's channel-mix launch (k_sig_maa)
-    for (uint32_t l = l0; l < l1; l++) {
-        const DLayer & L = m_->layers[l];
-        const float * si = sin + l * per_layer;
-        float * so = sout + l * per_layer;
-        // Wo matvec: input emitted by the attention kernel in Wo's format when heads are
-        // whole 32-blocks, else read as fp32 by its own prologue
-        MV c_wo;
-        auto att_out = [&](auto & a, MV & wo, const DMat & Wo) {
-            MVEntry & e = wo.add(Wo, x_, EPI_ADD);
-            a.yq.fmt = -1;
-            a.y = y_;
-            if (S >= 32) {
-                a.yq = A(6, Wo);
-                e.src = SRC_ACT;
-                e.act = a.yq;
-            } else {
-                src_f32(e, y_);
-            }
-            return true;
-        };
-        // ---------------- time mixing ----------------
-        if (m_->major == 4) {
-            ActBuf o = A(0, L.att_o);
-            if ((fuse_ & FUSE_ATT4) && v4_att_fused_supported(C, L.att_r, L.att_k, L.att_v, o)) {
-                // LN + r, k, v rows + WKV-4 in one launch, 8 channels per workgroup (mv_att4f.hip)
-                if (timing_) {
-                    kt_bytes_ = 3 * wbytes(L.att_r) + 9.0 * C * 4 + 6.0 * C * 4 + C * 4.0 + act_bytes(o, 1);
-                    kt_flops_ = 6.0 * C * C;
-                }
-                V4WoFused wf;
-                memset(&wf, 0, sizeof(wf));
-                const bool wo_in = (fuse_ & FUSE_WO4) && L.att_o.type == L.att_r.type && C % 8 == 0;
-                if (wo_in && emb4_in && l == 0) {
-                    wf.tok = dtokens_;
-                    wf.emb = m_->emb;
-                    wf.ln0w = m_->ln0_w;
-                    wf.ln0b = m_->ln0_b;
-                    if (timing_) kt_bytes_ += (double)C * (m_->emb.type == W_F16 ? 2 : 4) + 2.0 * C * 4;
-                }
-                if (wo_in) {
-                    wf.wo = L.att_o;
-                    wf.xres = x_;
-                    wf.ygran = ygran_;
-                    wf.ytag = (unsigned)(l + 1) | ((unsigned)(cur_ + 1) << 16);
-                    wf.err = herr_d_;
-                    wf.spin_max = spin_max_;
-                    if (timing_) {
-                        kt_bytes_ += wbytes(L.att_o) + 2.0 * C * 8 + 2.0 * C * 4;
-                        kt_flops_ += 2.0 * C * C;
-                    }
-                }
-                if (!launch_v4_att_fused(stream_, C, L.att_r, L.att_k, L.att_v, x_, si + C, so + C, L.ln1_w, L.ln1_b,
-                                         L.att_mix_r, L.att_mix_k, L.att_mix_v, L.att_first, L.att_decay, si, so, o, y_,
-                                         wo_in ? &wf : nullptr))
-                    return false;
-                if (wo_in) goto v4_att_done;
-                {
-                    // y fp32: Wo quantizes it in its own prologue (the same Q8 bits as the emission)
-                    MV c;
-                    src_f32(c.add(L.att_o, x_, EPI_ADD), y_);
-                    if (!mv(c.g)) return false;
-                    goto v4_att_done;
-                }
-            } else {
-                MV b;
-                src_lnmix(b.add(L.att_r, r_, EPI_SIGMOID), x_, si + C, L.ln1_w, L.ln1_b, L.att_mix_r, 0, so + C);
-                src_lnmix(b.add(L.att_k, k_, EPI_STORE), x_, si + C, L.ln1_w, L.ln1_b, L.att_mix_k, 0);
-                src_lnmix(b.add(L.att_v, v_, EPI_STORE), x_, si + C, L.ln1_w, L.ln1_b, L.att_mix_v, 0);
-                if (!mv(b.g)) return false;
-                if (!launch_wkv4(stream_, 1, C, r_, k_, v_, L.att_first, L.att_decay, si, so, o)) return false;
-            }
-            {
-                MV c;
-                MVEntry & e = c.add(L.att_o, x_, EPI_ADD);
-                e.src = SRC_ACT;
-                e.act = o;
-                if (!mv(c.g)) return false;
-            }
-        v4_att_done:;
-        } else if (m_->major == 5) {
-            const bool v52 = m_->minor >= 2;
-            MV b;
-            src_lnmix(b.add(L.att_r, r_, EPI_STORE), x_, si + C, L.ln1_w, L.ln1_b, L.att_mix_r, 0, so + C);
-            src_lnmix(b.add(L.att_k, k_, EPI_STORE), x_, si + C, L.ln1_w, L.ln1_b, L.att_mix_k, 0);
-            src_lnmix(b.add(L.att_v, v_, EPI_STORE), x_, si + C, L.ln1_w, L.ln1_b, L.att_mix_v, 0);
-            if (v52) src_lnmix(b.add(L.att_g, g_, EPI_SILU), x_, si + C, L.ln1_w, L.ln1_b, L.att_mix_g, 0);
-            if (!mv(b.g)) return false;
-            Att6Dec a;
-            memset(&a, 0, sizeof(a));
-            a.H = H;
-            a.S = S;
-            a.r = r_;
-            a.k = k_;
-            a.v = v_;
-            a.g = v52 ? g_ : nullptr;
-            a.u = L.att_u;
-            a.w = L.att_w;
-            a.sin = si + 2 * C;
-            a.sout = so + 2 * C;
-            a.lnx_w = L.att_lnx_w;
-            a.lnx_b = L.att_lnx_b;
-            a.eps = 1e-5f;
-            if (!att_out(a, c_wo, L.att_o)) return false;
-            if (!launch_att6_dec(stream_, a)) return false;
-            if (!mv(c_wo.g)) return false;
-        } else if (m_->major == 6) {
-            const int D = m_->maa_D;
-            ActBuf outs[5] = {A(1, L.decay_w1), A(2, L.att_k), A(3, L.att_v), A(4, L.att_r), A(5, L.att_g)};
-            if (maa_done) {
-                maa_done = false;
-            } else if (emb_in && l == 0) {
-                if (timing_) {
-                    // + the embedding row, LN0 vectors and x written
-                    kt_bytes_ = wbytes(L.maa_w1) + 5.0 * D * C * 4 + 11.0 * C * 4 + C * 4.0 + 5 * act_bytes(outs[0], 1) +
-                                (double)C * (m_->emb.type == W_F16 ? 2 : 4) + 3.0 * C * 4;
-                    kt_flops_ = 2.0 * L.maa_w1.M * L.maa_w1.K + 2.0 * 5 * D * C;
-                }
-                if (!launch_v6_maa_dec_emb(stream_, emaa)) return false;
-            } else if (v6_maa_dec_supported(C, D, L.maa_w1.type) && !split_maa_) {
-                // W1 rows + mix in one launch (mv_maa.hip)
-                if (timing_) {
-                    // W1, W2 (fp32), x / carry / LN / maa vectors in, carry and 5 Q8 mixes out
-                    kt_bytes_ = wbytes(L.maa_w1) + 5.0 * D * C * 4 + 11.0 * C * 4 + C * 4.0 + 5 * act_bytes(outs[0], 1);
-                    kt_flops_ = 2.0 * L.maa_w1.M * L.maa_w1.K + 2.0 * 5 * D * C;
-                }
-                if (!launch_v6_maa_dec(stream_, C, D, L.maa_w1, x_, si + C, so + C, L.ln1_w, L.ln1_b, L.maa_x,
-                                       L.maa_w2t, L.maa, outs))
-                    return false;
-            } else {
-                MV b;
-                src_lnmix(b.add(L.maa_w1, lora_, EPI_TANH), x_, si + C, L.ln1_w, L.ln1_b, L.maa_x, 1, so + C);
-                if (!mv(b.g)) return false;
-                if (!launch_v6_mix5_dec(stream_, C, D, so + C, si + C, lora_, L.maa_w2t, L.maa, outs))
-                    return false;
-            }
-            const int mats[5] = {3, 1, 2, 4, 0};  // r, k, v, g, w
-            float * ys[5] = {r_, k_, v_, g_, dsmall_[0]};
-            const DMat * Ws[5] = {&L.att_r, &L.att_k, &L.att_v, &L.att_g, &L.decay_w1};
-            const int epis[5] = {EPI_STORE, EPI_STORE, EPI_STORE, EPI_SILU, EPI_TANH};
-            Att6Dec a;
-            memset(&a, 0, sizeof(a));
-            a.H = H;
-            a.S = S;
-            a.r = r_;
-            a.k = k_;
-            a.v = v_;
-            a.g = g_;
-            a.u = L.att_u;
-            a.w = nullptr;
-            a.wd2 = L.decay_w2;
-            a.dl = dsmall_[0];
-            a.decay = L.decay6;
-            a.sin = si + 2 * C;
-            a.sout = so + 2 * C;
-            a.lnx_w = L.att_lnx_w;
-            a.lnx_b = L.att_lnx_b;
-            a.eps = 64e-5f;
-            if (!att_out(a, c_wo, L.att_o)) return false;
-            // r, k, v, g, Wd1 rows and the per-head attention in one launch (mv_att6f.hip), else
-            // the k_mva group + k_att6_dec pair (the same bits)
-            Att6Fused f;
-            memset(&f, 0, sizeof(f));
-            f.H = H;
-            f.C = C;
-            f.D = L.decay_w1.M;
-            for (int i = 0; i < 4; i++) {
-                f.W[i] = *Ws[i];
-                f.x[i] = outs[mats[i]];
-            }
-            f.wd1 = L.decay_w1;
-            f.xw = outs[mats[4]];
-            f.att = a;
-            f.gran = hgran_;
-            f.err = herr_d_;
-            f.spin_max = spin_max_;
-            f.skip_wg = dbg_skip_gran_;
-            // Wo inside the same launch (the head outputs handed to the non-reducer workgroups as
-            // granules tagged by layer and state parity); else Wo is its own k_mva launch below
-            bool wo_in = false;
-            if ((fuse_ & FUSE_WO6) && (fuse_ & FUSE_ATT6)) {
-                f.wo = L.att_o;
-                f.xres = x_;
-                f.ygran = ygran_;
-                f.ytag = (unsigned)(l + 1) | ((unsigned)(cur_ + 1) << 16);
-                f.wo_rows = wo_rows_;
-                f.wo_prepoll = wo_prepoll_;
-                wo_in = v6_att_fused_supported(f);
-                if (!wo_in) {
-                    memset(&f.wo, 0, sizeof(f.wo));
-                    f.xres = nullptr;
-                    f.ygran = nullptr;
-                }
-            }
-            if ((fuse_ & FUSE_ATT6) && v6_att_fused_supported(f)) {
-                if (timing_) {
-                    // r, k, v, g, Wd1, Wd2 weights, their 5 Q8 inputs, the head state in and out,
-                    // u / decay / ln_x vectors, r / k / v / g / dl written (sc1) and read back, Wo's input out
-                    kt_bytes_ = 4 * wbytes(L.att_r) + wbytes(L.decay_w1) + wbytes(L.decay_w2) + 5 * act_bytes(outs[0], 1) +
-                                2.0 * H * S * S * 4 + 4.0 * C * 4 + 2.0 * (4.0 * C + f.D) * 4 + act_bytes(a.yq, 1);
-                    kt_flops_ = 2.0 * (4.0 * C + f.D) * C + 2.0 * C * f.D;
-                    if (wo_in) {
-                        // Wo weights, the y granules (Q8 blocks) written and gathered, x read and written
-                        kt_bytes_ += wbytes(L.att_o) + 2.0 * KG_STRIDE * (C / 32) * 8 + 2.0 * C * 4 - act_bytes(a.yq, 1);
-                        kt_flops_ += 2.0 * C * C;
-                    }
-                }
-                // the co-resident layout when this context has the device to itself (choose_co)
-                if (co_ && v6_att_co_supported(f) ? !launch_v6_att_co(stream_, f) : !launch_v6_att_fused(stream_, f))
-                    return false;
-            } else {
-                MV c;
-                for (int i = 0; i < 5; i++) {
-                    MVEntry & e = c.add(*Ws[i], ys[i], epis[i]);
-                    e.src = SRC_ACT;
-                    e.act = outs[mats[i]];
-                }
-                if (!mv(c.g)) return false;
-                if (!launch_att6_dec(stream_, a)) return false;
-            }
-            if (!wo_in && !mv(c_wo.g)) return false;
-        } else {
-            // v7, order r, w, k, v, a, g of x_rwkvag (rwkv_graph.inc:404-413)
-            MV b;
-            const float * mu = L.x_rwkvag;
-            src_lnmix(b.add(L.att_r, r_, EPI_STORE), x_, si + C, L.ln1_w, L.ln1_b, mu, 1, so + C);
-            src_lnmix(b.add(L.att_k, k_, EPI_STORE), x_, si + C, L.ln1_w, L.ln1_b, mu + 2 * (size_t)C, 1);
-            src_lnmix(b.add(L.att_v, v_, EPI_STORE), x_, si + C, L.ln1_w, L.ln1_b, mu + 3 * (size_t)C, 1);
-            // the LoRA first stages (F16 in the released files) as their own launch when their type
-            // differs from r,k,v: one weight type per launch keeps the fixed-type kernels (fewer
-            // registers, no per-entry type switch, no padded units)
-            MV lb;
-            MV & bl = L.w1.type == L.att_r.type ? b : lb;
-            src_lnmix(bl.add(L.w1, dsmall_[0], EPI_TANH), x_, si + C, L.ln1_w, L.ln1_b, mu + 1 * (size_t)C, 1);
-            src_lnmix(bl.add(L.a1, dsmall_[1], EPI_STORE), x_, si + C, L.ln1_w, L.ln1_b, mu + 4 * (size_t)C, 1);
-            src_lnmix(bl.add(L.g1, dsmall_[2], EPI_SIGMOID), x_, si + C, L.ln1_w, L.ln1_b, mu + 5 * (size_t)C, 1);
-            if (l != 0) src_lnmix(bl.add(L.v1, dsmall_[3], EPI_STORE), x_, si + C, L.ln1_w, L.ln1_b, mu + 3 * (size_t)C, 1);
-            if (!mv(b.g)) return false;
-            if (lb.g.n && !mv(lb.g)) return false;
-            if (l == 0) HIP_OK(hipMemcpyAsync(vfirst_, v_, (size_t)C * 4, hipMemcpyDeviceToDevice, stream_));
-            Att7Dec a;
-            memset(&a, 0, sizeof(a));
-            a.H = H;
-            a.S = S;
-            a.r = r_;
-            a.w = w_;
-            a.k = k_;
-            a.v = v_;
-            a.a = a_;
-            a.g = g_;
-            a.k_k = L.k_k;
-            a.k_a = L.k_a;
-            a.r_k = L.r_k;
-            a.sin = si + 2 * C;
-            a.sout = so + 2 * C;
-            a.lnx_w = L.att_lnx_w;
-            a.lnx_b = L.att_lnx_b;
-            if (!att_out(a, c_wo, L.att_o)) return false;
-            // LoRA second stages + attention in one launch (mv_att7f.hip), else the LoRA-out matvec
-            // group + k_att7_dec (the same bits)
-            Att7Lora f;
-            memset(&f, 0, sizeof(f));
-            f.att = a;
-            f.W2[0] = L.w2;
-            f.W2[1] = L.a2;
-            f.W2[2] = L.g2;
-            f.W2[3] = L.v2;
-            for (int i = 0; i < 4; i++) f.lin[i] = dsmall_[i];
-            f.bias[0] = L.w0;
-            f.bias[1] = L.a0;
-            f.bias[2] = nullptr;
-            f.bias[3] = L.v0;
-            f.vfirst = vfirst_;
-            f.has_v = l != 0;
-            if ((fuse_ & FUSE_ATT7) && att7_lora_supported(f)) {
-                if (timing_) {
-                    double lb = wbytes(L.w2) + wbytes(L.a2) + wbytes(L.g2) + (l ? wbytes(L.v2) : 0.0);
-                    kt_bytes_ = lb + 2.0 * H * S * S * 4 + 12.0 * C * 4 + act_bytes(a.yq, 1);
-                    kt_flops_ = 2.0 * (L.w2.K + L.a2.K + L.g2.K + (l ? L.v2.K : 0)) * C;
-                }
-                if (!launch_att7_lora(stream_, f)) return false;
-                v7_fused_lora_ = true;  // w, a, g and the mixed v never leave the launch (debug_copy)
-            } else {
-                MV c;
-                src_f32(c.add(L.w2, w_, EPI_DECAY7, nullptr, L.w0), dsmall_[0]);
-                src_f32(c.add(L.a2, a_, EPI_SIGMOID_BIAS, nullptr, L.a0), dsmall_[1]);
-                src_f32(c.add(L.g2, g_, EPI_STORE), dsmall_[2]);
-                if (l != 0) src_f32(c.add(L.v2, v_, EPI_VMIX7, vfirst_, L.v0), dsmall_[3]);
-                if (!mv(c.g)) return false;
-                if (!launch_att7_dec(stream_, a)) return false;
-            }
-            if (!mv(c_wo.g)) return false;
-        }
-        // ---------------- channel mixing ----------------
-        if (m_->major == 7) {
-            ActBuf kin = A(0, L.ffn_v);
-            const bool ffco7 = co_ && (fuse_ & FUSE_FFNCO);
-            if ((fuse_ & FUSE_FFN) || ffco7) {
-                FfnFused ff;
-                memset(&ff, 0, sizeof(ff));
-                ff.co = ffco7;
-                MVEntry & fk = ff.e[0];
-                fk.W = L.ffn_k;
-                fk.epi = EPI_RELU_SQ;
-                src_lnmix(fk, x_, si, L.ln2_w, L.ln2_b, L.ffn_x_k, 1, so);
-                fk.emit = 1;
-                fk.act_out = kin;
-                ff.wv = L.ffn_v;
-                ff.x = x_;
-                ff.kg = kgran_;
-                ff.tag = (unsigned)(l + 1) | ((unsigned)(cur_ + 1) << 16);
-                ff.err = herr_d_;
-                ff.spin_max = spin_max_;
-                ff.wdelay = ffn_wdelay_ >= 0 ? ffn_wdelay_ : (int)std::min(2000.0, wbytes(L.ffn_k) / 4e4);
-                ff.prepoll = ffn_prepoll_;
-                if (ff.co && !ffn_fused_supported(ff, 1, false)) ff.co = 0;  // the ordered form, if on
-                if ((ff.co || (fuse_ & FUSE_FFN)) && ffn_fused_supported(ff, 1, false)) {
-                    if (timing_) {
-                        kt_bytes_ = wbytes(L.ffn_k) + wbytes(L.ffn_v) + 5.0 * C * 4 + 2.0 * C * 4 +
-                                    (double)L.ffn_k.M / 32 * KG_STRIDE * 8 * 2;
-                        kt_flops_ = 2.0 * ((double)L.ffn_k.M * L.ffn_k.K + (double)L.ffn_v.M * L.ffn_v.K);
-                    }
-                    if (!launch_ffn_fused(stream_, ff, 1, false)) return false;
-                    continue;
-                }
-            }
-            MV b;
-            MVEntry & ek = b.add(L.ffn_k, nullptr, EPI_RELU_SQ);
-            src_lnmix(ek, x_, si, L.ln2_w, L.ln2_b, L.ffn_x_k, 1, so);
-            ek.emit = 1;
-            ek.act_out = kin;
-            if (!mv(b.g)) return false;
-            MV c;
-            MVEntry & ev = c.add(L.ffn_v, x_, EPI_ADD);
-            ev.src = SRC_ACT;
-            ev.act = kin;
-            if (!mv(c.g)) return false;
-        } else {
-            const int form = m_->major == 6 ? 1 : 0;
-            const float * muk = m_->major == 6 ? L.ffn_maa_k : L.ffn_mix_k;
-            const float * mur = m_->major == 6 ? L.ffn_maa_r : L.ffn_mix_r;
-            MV b;
-            ActBuf kin = A(0, L.ffn_v);
-            MVEntry & ek = b.add(L.ffn_k, nullptr, EPI_RELU_SQ);
-            src_lnmix(ek, x_, si, L.ln2_w, L.ln2_b, muk, form, so);
-            ek.emit = 1;
-            ek.act_out = kin;
-            // the receptance rows go with the value rows (k_mvsig) when the key launch can emit
-            // their input: one launch of 224 workgroups for the key instead of 288 for key +
-            // receptance (more workgroups than CUs), and fr_ never leaves the wave
-            MVEntry sv, sr;
-            memset(&sv, 0, sizeof(sv));
-            memset(&sr, 0, sizeof(sr));
-            sv.W = L.ffn_v;
-            sv.src = SRC_ACT;
-            sv.act = kin;
-            sv.y = x_;
-            sv.epi = EPI_SIGMUL_ADD;
-            sr.W = L.ffn_r;
-            sr.src = SRC_ACT;
-            sr.act = A(7, L.ffn_r);
-            sr.epi = EPI_STORE;
-            // the whole channel mix in one launch (mv_ffnf.hpp), else the key group + k_mvsig
-            const bool ffco = co_ && (fuse_ & FUSE_FFNCO);
-            if ((fuse_ & FUSE_FFN) || ffco) {
-                FfnFused ff;
-                memset(&ff, 0, sizeof(ff));
-                ff.co = ffco;
-                MVEntry & fk = ff.e[0];
-                fk.W = L.ffn_k;
-                fk.epi = EPI_RELU_SQ;
-                src_lnmix(fk, x_, si, L.ln2_w, L.ln2_b, muk, form, so);
-                fk.emit = 1;
-                fk.act_out = kin;
-                MVEntry & fr = ff.e[1];
-                fr.W = L.ffn_r;
-                fr.epi = EPI_STORE;
-                src_lnmix(fr, x_, si, L.ln2_w, L.ln2_b, mur, form);
-                ff.wv = L.ffn_v;
-                ff.x = x_;
-                ff.kg = kgran_;
-                ff.rg = rgran_;
-                ff.tag = (unsigned)(l + 1) | ((unsigned)(cur_ + 1) << 16);
-                ff.err = herr_d_;
-                ff.spin_max = spin_max_;
-                ff.wdelay = ffn_wdelay_ >= 0 ? ffn_wdelay_ : (int)std::min(2000.0, (wbytes(L.ffn_k) + wbytes(L.ffn_r)) / 4e4);
-                ff.prepoll = ffn_prepoll_;
-                if (ff.co && !ffn_fused_supported(ff, form, true)) ff.co = 0;  // the ordered form, if on
-                if ((ff.co || (fuse_ & FUSE_FFN)) && ffn_fused_supported(ff, form, true)) {
-                    if (timing_) {
-                        kt_bytes_ = wbytes(L.ffn_k) + wbytes(L.ffn_r) + wbytes(L.ffn_v) + 5.0 * C * 4 + 2.0 * C * 4 +
-                                    (double)L.ffn_k.M / 32 * KG_STRIDE * 8 * 2 + 2.0 * C * 8 + C * 4.0;
-                        kt_flops_ = 2.0 * ((double)L.ffn_k.M * L.ffn_k.K + (double)L.ffn_r.M * L.ffn_r.K +
-                                           (double)L.ffn_v.M * L.ffn_v.K);
-                    }
-                    if (!launch_ffn_fused(stream_, ff, form, true)) return false;
-                    continue;
-                }
-            }
-            const bool sig = (fuse_ & FUSE_SIG) && L.ffn_r.type == L.ffn_k.type && mv_sigmul_supported(sv, sr);
-            if (sig) {
-                ek.mu2 = mur;
-                ek.act2_out = sr.act;
-            } else {
-                src_lnmix(b.add(L.ffn_r, fr_, EPI_STORE), x_, si, L.ln2_w, L.ln2_b, mur, form);
-            }
-            if (!mv(b.g)) return false;
-            // co-resident: the next layer's maa in this launch (mv_sigmaa.hip), its x from granules
-            bool sm_in = false;
-            if (sig && co_ && (fuse_ & FUSE_SIGMAA) && m_->major == 6 && l + 1 < l1 && !split_maa_) {
-                const DLayer & N = m_->layers[l + 1];
-                const float * si1 = sin + (l + 1) * per_layer;
-                float * so1 = sout + (l + 1) * per_layer;
-                const ActBuf outs1[5] = {A(1, N.decay_w1), A(2, N.att_k), A(3, N.att_v), A(4, N.att_r), A(5, N.att_g)};
-                SigMaa sm;
-                memset(&sm, 0, sizeof(sm));
-                mv_fill_hot(sv, sm.hv);
-                mv_fill_hot(sr, sm.hr);
-                sm.wtype = L.ffn_v.type;
-                v6_maa_dec_args(sm.maa, C, m_->maa_D, N.maa_w1, x_, si1 + C, so1 + C, N.ln1_w, N.ln1_b, N.maa_x,
-                                N.maa_w2t, N.maa, outs1);
-                sm.nm = 5 * (C / 64);
-                sm.xg = xgran_;
-                sm.xtag = (unsigned)(l + 1) | ((unsigned)(cur_ + 1) << 16);
-                sm.err = herr_d_;
-                sm.spin_max = spin_max_;
-                if (sig_maa_supported(sm)) {
-                    if (timing_) {
-                        // + the maa's W1, W2 (fp32), LayerNorm vectors, carry and mixes; x granules out / in
-                        kt_bytes_ = wbytes(L.ffn_v) + wbytes(L.ffn_r) + act_bytes(kin, 1) + act_bytes(sr.act, 1) +
-                                    2.0 * C * 4 + wbytes(N.maa_w1) + 5.0 * m_->maa_D * C * 4 + 11.0 * C * 4 +
-                                    5 * act_bytes(outs1[0], 1) + 2.0 * C * 8;
-                        kt_flops_ = 2.0 * ((double)L.ffn_v.M * L.ffn_v.K + (double)L.ffn_r.M * L.ffn_r.K) +
-                                    2.0 * N.maa_w1.M * N.maa_w1.K + 2.0 * 5 * m_->maa_D * C;
-                    }
-                    if (!launch_sig_maa(stream_, sm)) return false;
-                    sm_in = maa_done = true;
-                }
-            }
-            if (sm_in) {
-            } else if (sig) {
-                if (timing_) {
-                    kt_bytes_ = wbytes(L.ffn_v) + wbytes(L.ffn_r) + act_bytes(kin, 1) + act_bytes(sr.act, 1) + 2.0 * C * 4;
-                    kt_flops_ = 2.0 * ((double)L.ffn_v.M * L.ffn_v.K + (double)L.ffn_r.M * L.ffn_r.K);
-                }
-                if (!launch_mv_sigmul(stream_, sv, sr)) return false;
-            } else {
-                MV c;
-                MVEntry & ev = c.add(L.ffn_v, x_, EPI_SIGMUL_ADD, fr_);
-                ev.src = SRC_ACT;
-                ev.act = kin;
-                if (!mv(c.g)) return false;
-            }
-        }
-    }
-    if (logits && l1 == m_->n_layer) {
-        MV h;
-        src_lnmix(h.add(m_->head, logits_, EPI_STORE), x_, nullptr, m_->lnout_w, m_->lnout_b, nullptr, 2);
-        if (!mv(h.g)) return false;
-    }
+    HIP_OK(hipGraphInstantiate(&ge, g, nullptr, nullptr, 0));
+    (void)hipGraphDestroy(g);
     return true;
 }
 
@@ -1882,18 +1251,7 @@ bool Engine::run_tokens_impl(const uint32_t * tokens, size_t T, bool want_logits
             if (!ok) return false;
         } else if (n == 1 && use_graphs_) {
             hipGraphExec_t & ge = graphs_[co][cur_][lg ? 1 : 0];
-            if (!ge) {
-                hipGraph_t g = nullptr;
-                HIP_OK(hipStreamBeginCapture(stream_, hipStreamCaptureModeThreadLocal));
-                const bool ok = forward(1, dstate_[cur_], dstate_[cur_ ^ 1], lg);
-                HIP_OK(hipStreamEndCapture(stream_, &g));
-                if (!ok) {
-                    (void)hipGraphDestroy(g);
-                    return false;
-                }
-                HIP_OK(hipGraphInstantiate(&ge, g, nullptr, nullptr, 0));
-                (void)hipGraphDestroy(g);
-            }
+            if (!ge && !capture(ge, [&] { return forward(1, dstate_[cur_], dstate_[cur_ ^ 1], lg); })) return false;
             HIP_OK(hipGraphLaunch(ge, stream_));
         } else {
             if (!forward((int)n, dstate_[cur_], dstate_[cur_ ^ 1], lg)) return false;
@@ -2040,7 +1398,7 @@ bool Engine::pinned_io(const float * state_in, const float * state_out) {
 
 bool Engine::eval_host_chunked(uint32_t token, const float * state_in, float * state_out, float * logits_out) {
     const uint32_t NL = m_->n_layer, K = (uint32_t)io_chunk_, NC = (NL + K - 1) / K;
-    const size_t C = m_->n_embed, per_layer = m_->major >= 5 ? C * (2 + (size_t)m_->S) : 5 * C;
+    const size_t per_layer = layer_state_len();
     if (!ensure_workspace(1)) return false;
     if (!io_stream_[0]) {
         // copy streams (high-priority queues and CU-masked download queues measured no better)
@@ -2067,17 +1425,7 @@ bool Engine::eval_host_chunked(uint32_t token, const float * state_in, float * s
     }
     float * din = dstate_[cur_], * dout = dstate_[cur_ ^ 1];
     for (uint32_t c = 0; c < NC; c++) {
-        if (gs[c]) continue;
-        hipGraph_t g = nullptr;
-        HIP_OK(hipStreamBeginCapture(stream_, hipStreamCaptureModeThreadLocal));
-        const bool ok = forward_decode(din, dout, lg, c * K, (c + 1) * K);
-        HIP_OK(hipStreamEndCapture(stream_, &g));
-        if (!ok) {
-            (void)hipGraphDestroy(g);
-            return false;
-        }
-        HIP_OK(hipGraphInstantiate(&gs[c], g, nullptr, nullptr, 0));
-        (void)hipGraphDestroy(g);
+        if (!gs[c] && !capture(gs[c], [&] { return forward_decode(din, dout, lg, c * K, (c + 1) * K); })) return false;
     }
     auto slice = [&](uint32_t c, size_t & off, size_t & bytes) {
         const uint32_t l0 = c * K, l1 = std::min(NL, l0 + K);
@@ -2214,7 +1562,7 @@ bool Engine::eval_layers(const uint32_t * tokens, size_t T, uint32_t l0, uint32_
     if (!forward_range((int)T, dstate_[cur_], dstate_[cur_ ^ 1], l0, l1, lg)) return false;
     // only this range's slices were written: copy them back instead of flipping the ping-pong
     // pair, so later calls on other ranges still read a complete current state
-    const size_t C = m_->n_embed, per_layer = m_->major >= 5 ? C * (2 + (size_t)m_->S) : 5 * C;
+    const size_t per_layer = layer_state_len();
     HIP_OK(hipMemcpyAsync(dstate_[cur_] + l0 * per_layer, dstate_[cur_ ^ 1] + l0 * per_layer,
                           (size_t)(l1 - l0) * per_layer * 4, hipMemcpyDeviceToDevice, stream_));
     if (x_io) HIP_OK(hipMemcpyAsync(x_io, x_, bytes, hipMemcpyDeviceToDevice, stream_));
@@ -2334,6 +1682,15 @@ bool Engine::eval_batch(const uint32_t * tokens, size_t B, const float * state_i
     float * sout = (dev && state_out) ? state_out : bstate_[1];
     float * lout = (dev && logits_out) ? logits_out : blogits_;
     const bool lg = logits_out != nullptr;
+    // the batched forward: bs_ / head_out_ are set only while it is being enqueued
+    auto step = [&] {
+        bs_ = n;
+        head_out_ = lout;
+        const bool ok = forward_range((int)B, sin, sout, 0, m_->n_layer, lg);
+        bs_ = 0;
+        head_out_ = nullptr;
+        return ok;
+    };
     bool ok;
     if (use_graphs_ && !timing_) {
         // one graph per (B, state pointers, logits pointer): a decode loop alternating two state
@@ -2344,41 +1701,19 @@ bool Engine::eval_batch(const uint32_t * tokens, size_t B, const float * state_i
         if (!ge) {
             // first step with these buffers: run it eagerly (lazy GEMM scratch allocations happen
             // here, outside any capture), then capture the graph the next steps replay
-            bs_ = n;
-            head_out_ = lout;
-            ok = forward_range((int)B, sin, sout, 0, m_->n_layer, lg);
-            bs_ = 0;
-            head_out_ = nullptr;
-            if (!ok) {
+            if (!step()) {
                 (void)hipStreamSynchronize(stream_);
                 return false;
             }
             if (bgraphs_.size() >= 8) drop_batch_graphs();
-            hipGraph_t g = nullptr;
-            HIP_OK(hipStreamBeginCapture(stream_, hipStreamCaptureModeThreadLocal));
-            bs_ = n;
-            head_out_ = lout;
-            ok = forward_range((int)B, sin, sout, 0, m_->n_layer, lg);
-            bs_ = 0;
-            head_out_ = nullptr;
-            HIP_OK(hipStreamEndCapture(stream_, &g));
-            if (!ok) {
-                (void)hipGraphDestroy(g);
-                return false;
-            }
-            HIP_OK(hipGraphInstantiate(&ge, g, nullptr, nullptr, 0));
-            (void)hipGraphDestroy(g);
+            if (!capture(ge, step)) return false;
             bgraphs_.push_back(BatchGraph{B, sin, sout, lg ? lout : nullptr, ge});
         } else {
             HIP_OK(hipGraphLaunch(ge, stream_));
         }
         ok = true;
     } else {
-        bs_ = n;
-        head_out_ = lout;
-        ok = forward_range((int)B, sin, sout, 0, m_->n_layer, lg);
-        bs_ = 0;
-        head_out_ = nullptr;
+        ok = step();
     }
     if (!ok) {
         (void)hipStreamSynchronize(stream_);

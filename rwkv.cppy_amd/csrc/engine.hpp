@@ -76,6 +76,19 @@ struct KernelStat {
     double total_flops = 0;
 };
 
+// algorithmic bytes of T rows of an activation buffer (roofline formulas)
+inline double act_bytes(const ActBuf & a, double T) {
+    const double K = a.K;
+    switch (a.fmt) {
+        case A_F32: return T * K * 4;
+        case A_F16: return T * K * 2;
+        case A_Q8_1: return T * K + T * K / 32 * 12;
+        default: return T * K + T * K / 32 * 8;
+    }
+}
+
+struct DecodeRun;  // engine_decode.hip
+
 class Engine : public KLaunchTimer {
   public:
     explicit Engine(DeviceModel * m) : m_(m) {}
@@ -126,8 +139,25 @@ class Engine : public KLaunchTimer {
     bool init_state(float * st, size_t n = 0);
     bool forward(int T, const float * sin, float * sout, bool logits);
     bool forward_range(int T, const float * sin, float * sout, uint32_t l0, uint32_t l1, bool logits);
+    // the decode program (engine_decode.hip): per layer one decode_att_v* and decode_ffn
     bool forward_decode(const float * sin, float * sout, bool logits, uint32_t l0 = 0, uint32_t l1 = UINT32_MAX);
+    bool decode_att_v4(DecodeRun & d, uint32_t l);
+    bool decode_att_v5(DecodeRun & d, uint32_t l);
+    bool decode_att_v6(DecodeRun & d, uint32_t l);
+    bool decode_att_v7(DecodeRun & d, uint32_t l);
+    bool decode_ffn(DecodeRun & d, uint32_t l);
     bool mv(MVGroup & g, hipStream_t st = nullptr);
+    // argument blocks shared by the decode program and the batched step (bs_ > 0) of layer_v5/6/7
+    Att6Dec att6_args(const DLayer & L, const float * si, float * so) const;
+    Att7Dec att7_args(const DLayer & L, const float * si, float * so) const;
+    LnMixArgs ln_mix_args(int T, const float * carry_in, float * carry_out, const float * lnw, const float * lnb) const;
+    template <class Att>
+    bool batch_att_tail(Att a, int wo_slot, int l, int T, const float * si, float * so);
+    // the tag of layer l's in-launch hand-offs at the current state parity
+    unsigned handoff_tag(uint32_t l) const { return (unsigned)(l + 1) | ((unsigned)(cur_ + 1) << 16); }
+    // captures what build() enqueues on stream_ into an executable graph
+    template <class F>
+    bool capture(hipGraphExec_t & ge, F && build);
     bool run_tokens(const uint32_t * tokens, size_t T, bool want_logits);
     bool run_tokens_impl(const uint32_t * tokens, size_t T, bool want_logits);
     bool layer_v4(int l, int T, const float * si, float * so);
