@@ -54,6 +54,44 @@ RWKV_API bool rwkv_mi355x_eval_device(struct rwkv_context * ctx, const uint32_t 
                                       bool compute_logits, float * logits_out, bool sync);
 RWKV_API bool rwkv_mi355x_sync(struct rwkv_context * ctx);
 
+/* Token sampling on the device (the reference samples on the host from downloaded logits:
+ * sampling.py:18-52).  Per draw: l = logits + bias; temperature == 0 returns the lowest index holding
+ * the maximum l (np.argmax); otherwise p = softmax(l), the top_p filter keeps every p_i >= c where c
+ * is the largest p_i with sum{p >= c} > top_p (ties at the cutoff are all kept; top_p == 0 means 1),
+ * w_i = p_i^(1/temperature) for kept i, and the draw returns the smallest index t with
+ * sum_{i<=t} w_i > u * sum w, in vocabulary order.  The uniform draw is stateless, so a caller can
+ * reproduce it: draw number `counter` of stream `seed` is
+ *   z = seed + 0x9E3779B97F4A7C15 * (counter + 1);  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9;
+ *   z = (z ^ (z >> 27)) * 0x94D049BB133111EB;  z ^= z >> 31;  u = (z >> 40) * 2^-24   (mod 2^64).
+ * bias_ids / bias_values are host arrays of n_bias <= 256 entries, each id < n_vocab, values added
+ * to the logits. */
+struct rwkv_mi355x_sampling {
+    float temperature, top_p;            /* reference defaults: 1.0, 0.8 */
+    uint32_t n_bias;                     /* <= 256 */
+    const uint32_t * bias_ids;           /* host; each id < n_vocab */
+    const float * bias_values;           /* host */
+    uint64_t seed, offset;               /* draw i uses counter offset + i */
+};
+/* Draws one token from the context's device logits with counter `offset`; the state and the logits
+ * are untouched.  Synchronous (4 bytes cross PCIe).  The device logits must follow the device state:
+ * the last evaluation on the context computed them and no state was uploaded since; otherwise, and
+ * for temperature < 0 or NaN, top_p outside [0, 1], n_bias > 256, a bias id >= n_vocab or a NULL
+ * pointer, the call fails with RWKV_ERROR_ARGS.  A pipeline context fails with
+ * RWKV_ERROR_CTX | RWKV_ERROR_UNSUPPORTED. */
+RWKV_API bool rwkv_mi355x_sample(struct rwkv_context * ctx, const struct rwkv_mi355x_sampling * params,
+                                 uint32_t * token_out);
+/* The generation loop on the device: for i in [0, n): draw token i from the device logits with
+ * counter offset + i, then evaluate it (rwkv_mi355x_eval_device of that one token with logits).
+ * Nothing crosses PCIe and the host does not wait inside the loop; at the end the n tokens (and, when
+ * logits_out != NULL, the final logits) are copied out and the stream is synchronised.  1 <= n <=
+ * 65536 (else RWKV_ERROR_ARGS; the other argument errors as rwkv_mi355x_sample).  On return the
+ * state has consumed all n tokens and the device logits are those following the last one, so a
+ * second call with offset + n continues the same stream.  An in-launch hand-off timeout anywhere in
+ * the chain fails the call with RWKV_ERROR_CTX, as rwkv_mi355x_eval_device(sync = false) followed by
+ * rwkv_mi355x_sync does: nothing is re-run and the state is unspecified until it is uploaded again. */
+RWKV_API bool rwkv_mi355x_generate(struct rwkv_context * ctx, const struct rwkv_mi355x_sampling * params, size_t n,
+                                   uint32_t * tokens_out, float * logits_out);
+
 /* Debugging aid: copies `bytes` of the named workspace buffer of the last evaluation to host `out`
  * (names: x xa sx r k v g w y a nb bb vfirst fr lora bonus logits, slot<i>.<q|d|s|qsum|h|f>).
  * Returns the bytes copied, or -1 (unknown name / copy failure).  Not part of rwkv.h. */
@@ -207,6 +245,14 @@ RWKV_API bool rwkv_mi355x_selftest_wkv6(int T, int H, int chunked, int w_per_tok
 RWKV_API bool rwkv_mi355x_selftest_wkv7(int T, int H, int chunked, const float * r, const float * w, const float * k,
                                        const float * v, const float * a, const float * b, const float * state_in,
                                        float * state_out, float * y);
+
+/* The sampler kernel of rwkv_mi355x_sample on host operands: logits [rows][V] (V <= 262144), one
+ * uniform draw u[r] in [0, 1) per row, params' seed / offset unused.  tokens [rows]; kept [rows] (the
+ * tokens that passed the top-p filter; 1 for greedy) and cutoff [rows] (the smallest kept
+ * probability) may be NULL. */
+RWKV_API bool rwkv_mi355x_selftest_sample(const float * logits, int rows, int V,
+                                          const struct rwkv_mi355x_sampling * params, const float * u,
+                                          uint32_t * tokens, uint32_t * kept, float * cutoff);
 
 #if defined(__cplusplus)
 }

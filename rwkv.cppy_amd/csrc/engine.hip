@@ -375,6 +375,9 @@ Engine::~Engine() {
     if (part_) (void)hipFree(part_);
     if (m2_) (void)hipFree(m2_);
     if (wkvc_) (void)hipFree(wkvc_);
+    if (gen_tokens_) (void)hipFree(gen_tokens_);
+    if (bias_ids_) (void)hipFree(bias_ids_);
+    if (bias_vals_) (void)hipFree(bias_vals_);
     for (void * p : ws_allocs_) (void)hipFree(p);
     if (htokens_) (void)hipHostFree(htokens_);
     if (herr_h_) (void)hipHostFree(herr_h_);
@@ -1209,6 +1212,7 @@ bool Engine::run_tokens(const uint32_t * tokens, size_t T, bool want_logits) {
     // (every rwkv_eval with state_in, rwkv_mi355x_state_upload) lands where the next step reads;
     // the device state's contents after a failure are unspecified (re-upload it)
     const int cur0 = cur_;
+    logits_valid_ = false;
     if (!run_tokens_impl(tokens, T, want_logits)) {
         (void)hipStreamSynchronize(stream_);
         // the call's tagged Wo-input granules must not satisfy a replay of the same parity
@@ -1218,6 +1222,7 @@ bool Engine::run_tokens(const uint32_t * tokens, size_t T, bool want_logits) {
         cur_ = cur0;
         return false;
     }
+    logits_valid_ = want_logits;
     return true;
 }
 
@@ -1228,7 +1233,9 @@ bool Engine::run_tokens_impl(const uint32_t * tokens, size_t T, bool want_logits
         const size_t n = std::min(T - done, kChunkMax);
         const bool last = done + n == T;
         if (!ensure_workspace((int)n)) return false;
-        if (n == 1) {
+        if (!tokens) {
+            // generate: the sampler enqueued just before this step writes dtokens_[0]
+        } else if (n == 1) {
             // one token: a CP write packet in stream order (no blit kernel, no pinned buffer)
             HIP_OK(hipStreamWriteValue32(stream_, dtokens_, tokens[done], 0));
         } else {
@@ -1272,6 +1279,7 @@ bool Engine::run_tokens_impl(const uint32_t * tokens, size_t T, bool want_logits
 }
 
 bool Engine::state_upload(const float * state) {
+    logits_valid_ = false;
     if (state) {
         HIP_OK(hipMemcpyAsync(dstate_[cur_], state, m_->state_len * 4, hipMemcpyHostToDevice, stream_));
         io_h2d_ += m_->state_len * 4.0;
@@ -1291,6 +1299,7 @@ bool Engine::state_download(float * state) {
 // range of the device-resident state: only that range crosses PCIe.
 bool Engine::state_upload_layers(const float * slice, uint32_t l0, uint32_t l1) {
     const size_t per = layer_state_len(), off = (size_t)l0 * per, n = (size_t)(l1 - l0) * per;
+    logits_valid_ = false;
     if (slice) {
         HIP_OK(hipMemcpyAsync(dstate_[cur_] + off, slice, n * 4, hipMemcpyHostToDevice, stream_));
         io_h2d_ += n * 4.0;
@@ -1323,6 +1332,7 @@ bool Engine::handoff_check() {
     const bool co_seen = co_pending_ > 0;
     co_pending_ = 0;
     if (*(volatile unsigned *)herr_h_ == 0) return true;
+    logits_valid_ = false;
     (void)hipStreamSynchronize(stream_);
     (void)hipMemsetAsync(hgran_, 0, hgran_n_ * 8, stream_);
     (void)hipMemsetAsync(ygran_, 0, tgran_n_ * 8, stream_);
@@ -1399,6 +1409,7 @@ bool Engine::pinned_io(const float * state_in, const float * state_out) {
 bool Engine::eval_host_chunked(uint32_t token, const float * state_in, float * state_out, float * logits_out) {
     const uint32_t NL = m_->n_layer, K = (uint32_t)io_chunk_, NC = (NL + K - 1) / K;
     const size_t per_layer = layer_state_len();
+    logits_valid_ = false;
     if (!ensure_workspace(1)) return false;
     if (!io_stream_[0]) {
         // copy streams (high-priority queues and CU-masked download queues measured no better)
@@ -1487,6 +1498,7 @@ bool Engine::eval_host_chunked(uint32_t token, const float * state_in, float * s
     HIP_OK(hipStreamSynchronize(stream_));
     if (!handoff_check()) return false;
     cur_ ^= 1;
+    logits_valid_ = lg;
     return true;
 }
 
@@ -1559,6 +1571,7 @@ bool Engine::eval_layers(const uint32_t * tokens, size_t T, uint32_t l0, uint32_
         if (m_->major == 7) HIP_OK(hipMemcpyAsync(vfirst_, vfirst_io, bytes, hipMemcpyDeviceToDevice, stream_));
     }
     const bool lg = (want_logits || logits_out) && l1 == m_->n_layer;
+    logits_valid_ = false;
     if (!forward_range((int)T, dstate_[cur_], dstate_[cur_ ^ 1], l0, l1, lg)) return false;
     // only this range's slices were written: copy them back instead of flipping the ping-pong
     // pair, so later calls on other ranges still read a complete current state
@@ -1569,6 +1582,7 @@ bool Engine::eval_layers(const uint32_t * tokens, size_t T, uint32_t l0, uint32_
     if (vfirst_io && m_->major == 7) HIP_OK(hipMemcpyAsync(vfirst_io, vfirst_, bytes, hipMemcpyDeviceToDevice, stream_));
     if (lg && logits_out)
         HIP_OK(hipMemcpyAsync(logits_out, logits_, (size_t)m_->n_vocab * 4, hipMemcpyDeviceToHost, stream_));
+    logits_valid_ = lg;
     if (sync) {
         HIP_OK(hipStreamSynchronize(stream_));
         return handoff_check();
@@ -1751,6 +1765,87 @@ bool Engine::eval_device(const uint32_t * tokens, size_t T, bool want_logits, fl
         co_retry_ = false;
         cur_ = cur0;
     }
+}
+
+// ---------------------------------------------------------------- sampling / generation
+// The sampler's device buffers, allocated or grown before anything is enqueued (never inside the
+// loop): n token slots and the bias arrays, which are uploaded in stream order.
+bool Engine::sampler_buffers(const SamplingParams & p, size_t n, SampleArgs & a) {
+    if (p.n_bias > (uint32_t)SAMPLE_MAX_BIAS) return false;
+    if (n > gen_cap_) {
+        HIP_OK(hipStreamSynchronize(stream_));
+        if (gen_tokens_) (void)hipFree(gen_tokens_);
+        gen_tokens_ = nullptr;
+        gen_cap_ = 0;
+        size_t cap = 64;
+        while (cap < n) cap *= 2;
+        HIP_OK(hipMalloc(&gen_tokens_, cap * 4));
+        gen_cap_ = cap;
+    }
+    if (!bias_ids_) HIP_OK(hipMalloc(&bias_ids_, SAMPLE_MAX_BIAS * 4));
+    if (!bias_vals_) HIP_OK(hipMalloc(&bias_vals_, SAMPLE_MAX_BIAS * 4));
+    if (p.n_bias) {
+        HIP_OK(hipMemcpyAsync(bias_ids_, p.bias_ids, p.n_bias * 4, hipMemcpyHostToDevice, stream_));
+        HIP_OK(hipMemcpyAsync(bias_vals_, p.bias_values, p.n_bias * 4, hipMemcpyHostToDevice, stream_));
+    }
+    memset(&a, 0, sizeof(a));
+    a.logits = logits_;
+    a.rows = 1;
+    a.V = (int)m_->n_vocab;
+    a.temperature = p.temperature;
+    a.top_p = p.top_p;
+    a.n_bias = (int)p.n_bias;
+    a.bias_ids = bias_ids_;
+    a.bias_vals = bias_vals_;
+    a.seed = p.seed;
+    a.counter = p.offset;
+    a.tok = gen_tokens_;
+    return true;
+}
+
+bool Engine::sample(const SamplingParams & p, uint32_t * token_out) {
+    HIP_OK(hipSetDevice(m_->device));
+    if (!logits_valid_ || !token_out) return false;
+    SampleArgs a;
+    if (!sampler_buffers(p, 1, a) || !launch_sample(stream_, a)) return false;
+    HIP_OK(hipMemcpyAsync(token_out, gen_tokens_, 4, hipMemcpyDeviceToHost, stream_));
+    HIP_OK(hipStreamSynchronize(stream_));
+    return handoff_check();
+}
+
+bool Engine::generate(const SamplingParams & p, size_t n, uint32_t * tokens_out, float * logits_out) {
+    HIP_OK(hipSetDevice(m_->device));
+    if (!logits_valid_ || !tokens_out || n == 0) return false;
+    SampleArgs a;
+    // dtokens_ moves when the workspace grows (the graphs are dropped with it): settle it first
+    if (!ensure_workspace(1) || !sampler_buffers(p, n, a)) return false;
+    const int cur0 = cur_;
+    co_retry_ = false;
+    bool ok = true;
+    for (size_t i = 0; ok && i < n; i++) {
+        // the counter is a kernel argument of an eager launch between the decode graphs' replays:
+        // nothing per step is baked into a captured node
+        a.counter = p.offset + i;
+        a.tok = gen_tokens_ + i;
+        a.tok2 = dtokens_;
+        if (timing_) g_klt = this;
+        ok = launch_sample(stream_, a);
+        g_klt = nullptr;
+        ok = ok && run_tokens(nullptr, 1, true);
+    }
+    if (ok) {
+        ok = hipMemcpyAsync(tokens_out, gen_tokens_, n * 4, hipMemcpyDeviceToHost, stream_) == hipSuccess;
+        if (ok && logits_out)
+            ok = hipMemcpyAsync(logits_out, logits_, (size_t)m_->n_vocab * 4, hipMemcpyDeviceToHost, stream_) == hipSuccess;
+    }
+    ok = (hipStreamSynchronize(stream_) == hipSuccess) && ok;
+    ok = handoff_check() && ok;
+    if (!ok) {
+        // as run_tokens: the parity the call started with; state and logits are unspecified
+        cur_ = cur0;
+        logits_valid_ = false;
+    }
+    return ok;
 }
 
 }  // namespace rwkvmi

@@ -89,6 +89,15 @@ inline double act_bytes(const ActBuf & a, double T) {
 
 struct DecodeRun;  // engine_decode.hip
 
+// rwkv_mi355x_sampling with the bias arrays still on the host (include/rwkv_mi355x.h)
+struct SamplingParams {
+    float temperature = 1.0f, top_p = 0.8f;
+    uint32_t n_bias = 0;
+    const uint32_t * bias_ids = nullptr;
+    const float * bias_values = nullptr;
+    uint64_t seed = 0, offset = 0;
+};
+
 class Engine : public KLaunchTimer {
   public:
     explicit Engine(DeviceModel * m) : m_(m) {}
@@ -104,6 +113,17 @@ class Engine : public KLaunchTimer {
     bool eval_device(const uint32_t * tokens, size_t T, bool want_logits, float * logits_out, bool sync);
     bool eval_layers(const uint32_t * tokens, size_t T, uint32_t l0, uint32_t l1, float * x_io, float * vfirst_io,
                      bool want_logits, float * logits_out, bool sync = true);
+    // Token sampling on the device logits (sample.hip).  sample: one draw with counter p.offset, the
+    // state is untouched.  generate: n times { draw i with counter p.offset + i, one decode step on
+    // the drawn token with logits on }, all enqueued without a host synchronisation; one copy of the
+    // n tokens (and, logits_out != NULL, of the final logits) and one synchronisation at the end.  A
+    // hand-off timeout anywhere in the chain fails the call (no re-run: the state has moved on).
+    // Both need logits_valid().
+    bool sample(const SamplingParams & p, uint32_t * token_out);
+    bool generate(const SamplingParams & p, size_t n, uint32_t * tokens_out, float * logits_out);
+    // the device logits follow the device state: set by an evaluation that ran the head, cleared by
+    // one that did not and by every state upload
+    bool logits_valid() const { return logits_valid_; }
     // batched decode: B contexts, one token each; states [B][state_len] (host or device, see dev)
     bool eval_batch(const uint32_t * tokens, size_t B, const float * state_in, float * state_out, float * logits_out,
                     bool dev);
@@ -158,8 +178,10 @@ class Engine : public KLaunchTimer {
     // captures what build() enqueues on stream_ into an executable graph
     template <class F>
     bool capture(hipGraphExec_t & ge, F && build);
+    // tokens == NULL (T == 1): the token is already in dtokens_[0] (generate: the sampler wrote it)
     bool run_tokens(const uint32_t * tokens, size_t T, bool want_logits);
     bool run_tokens_impl(const uint32_t * tokens, size_t T, bool want_logits);
+    bool sampler_buffers(const SamplingParams & p, size_t n, SampleArgs & a);
     bool layer_v4(int l, int T, const float * si, float * so);
     bool wkv6(int T, int H, int S, const float * u, const float * w, int wpt, const float * sin, float * sout);
     bool layer_v5(int l, int T, const float * si, float * so);
@@ -180,6 +202,11 @@ class Engine : public KLaunchTimer {
     float *dsmall_[4] = {nullptr, nullptr, nullptr, nullptr};  // decode LoRA intermediates [kmax]
     uint32_t * dtokens_ = nullptr;
     uint32_t * htokens_ = nullptr;  // pinned
+    bool logits_valid_ = false;
+    uint32_t * gen_tokens_ = nullptr;  // generate: the drawn tokens [gen_cap_]
+    size_t gen_cap_ = 0;
+    uint32_t * bias_ids_ = nullptr;    // the sampler's logit bias [SAMPLE_MAX_BIAS]
+    float * bias_vals_ = nullptr;
     static constexpr int kSlots = 12;
     ActSlot slots_[kSlots];
     float * dstate_[2] = {nullptr, nullptr};

@@ -174,6 +174,36 @@ bool launch_delay(hipStream_t st, int us);
 
 void set_mv_device_cus(int n);
 
+// ---- token sampling (sample.hip) ----------------------------------------------------------
+// The stateless uniform draw of rwkv_mi355x_sampling: splitmix64 of (seed, counter), top 24 bits.
+__host__ __device__ inline float sample_uniform(uint64_t seed, uint64_t counter) {
+    uint64_t z = seed + 0x9E3779B97F4A7C15ull * (counter + 1);
+    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+    z = z ^ (z >> 31);
+    return (float)(z >> 40) * 0x1p-24f;
+}
+
+constexpr int SAMPLE_MAX_BIAS = 256;
+constexpr int SAMPLE_MAX_VOCAB = 256 * 1024;  // k_sample's row x wave table (LDS)
+
+struct SampleArgs {
+    const float * logits;        // [rows][V]
+    int rows, V;
+    float temperature, top_p;
+    int n_bias;                  // <= SAMPLE_MAX_BIAS; ids < V
+    const uint32_t * bias_ids;   // device
+    const float * bias_vals;     // device
+    const float * u;             // device [rows], or NULL: row r draws sample_uniform(seed, counter + r)
+    uint64_t seed, counter;
+    uint32_t * tok;              // [rows]
+    uint32_t * tok2;             // optional second copy of the tokens (the decode step's input)
+    uint32_t * kept;             // optional [rows]: tokens that passed the top-p filter
+    float * cutoff;              // optional [rows]: the smallest kept probability
+};
+// One workgroup per row: bias, greedy or top-p / temperature sampling (rwkv_mi355x.h).
+bool launch_sample(hipStream_t st, const SampleArgs & a);
+
 bool launch_mv_group(hipStream_t st, MVGroup & g);
 int mva_rows();
 

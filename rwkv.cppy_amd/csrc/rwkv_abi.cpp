@@ -587,6 +587,58 @@ RWKV_API bool rwkv_mi355x_eval_device(struct rwkv_context * ctx, const uint32_t 
     return true;
 }
 
+// The checks rwkv_mi355x_sample and rwkv_mi355x_generate share; all of them return before any GPU call.
+static bool sampling_ok(struct rwkv_context * ctx, const struct rwkv_mi355x_sampling * p, SamplingParams & sp) {
+    CTX_CHECK(ctx, RWKV_ERROR_CTX | RWKV_ERROR_UNSUPPORTED, false, ctx->pipe == nullptr && !ctx->model->dm.partial(),
+              "Sampling is not supported on a pipeline context");
+    CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, p != nullptr, "NULL sampling parameters");
+    CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, p->temperature >= 0.0f, "Temperature %f is negative or NaN", p->temperature);
+    CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, p->top_p >= 0.0f && p->top_p <= 1.0f, "top_p %f is outside [0, 1]", p->top_p);
+    CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, p->n_bias <= (uint32_t)SAMPLE_MAX_BIAS, "More than %d logit biases", SAMPLE_MAX_BIAS);
+    CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, p->n_bias == 0 || (p->bias_ids != nullptr && p->bias_values != nullptr),
+              "NULL logit bias arrays");
+    for (uint32_t i = 0; i < p->n_bias; i++)
+        CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, p->bias_ids[i] < ctx->model->dm.n_vocab, "Logit bias token %u out of range",
+                  p->bias_ids[i]);
+    CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, ctx->model->dm.n_vocab <= (uint32_t)SAMPLE_MAX_VOCAB,
+              "The sampler takes vocabularies up to %d tokens", SAMPLE_MAX_VOCAB);
+    CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, ctx->engine->logits_valid(),
+              "The device logits do not follow the device state (evaluate with logits first)");
+    sp.temperature = p->temperature;
+    sp.top_p = p->top_p;
+    sp.n_bias = p->n_bias;
+    sp.bias_ids = p->bias_ids;
+    sp.bias_values = p->bias_values;
+    sp.seed = p->seed;
+    sp.offset = p->offset;
+    return true;
+}
+
+RWKV_API bool rwkv_mi355x_sample(struct rwkv_context * ctx, const struct rwkv_mi355x_sampling * params,
+                                 uint32_t * token_out) {
+    if (!ctx || !ctx->engine) return false;
+    ctx->last_error = RWKV_ERROR_NONE;
+    SamplingParams sp;
+    if (!sampling_ok(ctx, params, sp)) return false;
+    CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, token_out != nullptr, "NULL token_out");
+    use_device(ctx);
+    CTX_CHECK(ctx, RWKV_ERROR_CTX, false, ctx->engine->sample(sp, token_out), "GPU sampling failed");
+    return true;
+}
+
+RWKV_API bool rwkv_mi355x_generate(struct rwkv_context * ctx, const struct rwkv_mi355x_sampling * params, size_t n,
+                                   uint32_t * tokens_out, float * logits_out) {
+    if (!ctx || !ctx->engine) return false;
+    ctx->last_error = RWKV_ERROR_NONE;
+    SamplingParams sp;
+    if (!sampling_ok(ctx, params, sp)) return false;
+    CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, n > 0 && n <= 65536, "Token count %zu is outside [1, 65536]", n);
+    CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, tokens_out != nullptr, "NULL tokens_out");
+    use_device(ctx);
+    CTX_CHECK(ctx, RWKV_ERROR_CTX, false, ctx->engine->generate(sp, n, tokens_out, logits_out), "GPU generation failed");
+    return true;
+}
+
 static bool eval_layers(struct rwkv_context * ctx, const uint32_t * tokens, size_t T, uint32_t layer_begin,
                         uint32_t layer_end, float * x_dev, float * vfirst_dev, bool compute_logits, float * logits_out,
                         bool sync) {

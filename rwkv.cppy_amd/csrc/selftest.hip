@@ -187,3 +187,48 @@ extern "C" RWKV_API bool rwkv_mi355x_selftest_wkv7(int T, int H, int chunked, co
     return hipMemcpy(y, dy, TC * 4, hipMemcpyDeviceToHost) == hipSuccess &&
            hipMemcpy(state_out, dso, SN * 4, hipMemcpyDeviceToHost) == hipSuccess;
 }
+
+// The sampler kernel (sample.hip) on host logits with the uniform draws given: what
+// rwkv_mi355x_sample / _generate launch, one workgroup per row.
+extern "C" RWKV_API bool rwkv_mi355x_selftest_sample(const float * logits, int rows, int V,
+                                                    const struct rwkv_mi355x_sampling * p, const float * u,
+                                                    uint32_t * tokens, uint32_t * kept, float * cutoff) {
+    if (!logits || !p || !u || !tokens || rows < 1 || V < 1 || V > SAMPLE_MAX_VOCAB) return false;
+    if (!(p->temperature >= 0.0f) || !(p->top_p >= 0.0f && p->top_p <= 1.0f) || p->n_bias > (uint32_t)SAMPLE_MAX_BIAS)
+        return false;
+    if (p->n_bias && (!p->bias_ids || !p->bias_values)) return false;
+    for (uint32_t i = 0; i < p->n_bias; i++)
+        if (p->bias_ids[i] >= (uint32_t)V) return false;
+    const size_t n = (size_t)rows * V;
+    DevBufs b;
+    SampleArgs a;
+    memset(&a, 0, sizeof(a));
+    float * dl = (float *)b.alloc(n * 4);
+    float * du = (float *)b.alloc((size_t)rows * 4);
+    uint32_t * bi = (uint32_t *)b.alloc(SAMPLE_MAX_BIAS * 4);
+    float * bv = (float *)b.alloc(SAMPLE_MAX_BIAS * 4);
+    a.tok = (uint32_t *)b.alloc((size_t)rows * 4);
+    a.kept = (uint32_t *)b.alloc((size_t)rows * 4);
+    a.cutoff = (float *)b.alloc((size_t)rows * 4);
+    if (!dl || !du || !bi || !bv || !a.tok || !a.kept || !a.cutoff) return false;
+    if (hipMemcpy(dl, logits, n * 4, hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemcpy(du, u, (size_t)rows * 4, hipMemcpyHostToDevice) != hipSuccess)
+        return false;
+    if (p->n_bias && (hipMemcpy(bi, p->bias_ids, p->n_bias * 4, hipMemcpyHostToDevice) != hipSuccess ||
+                      hipMemcpy(bv, p->bias_values, p->n_bias * 4, hipMemcpyHostToDevice) != hipSuccess))
+        return false;
+    a.logits = dl;
+    a.rows = rows;
+    a.V = V;
+    a.temperature = p->temperature;
+    a.top_p = p->top_p;
+    a.n_bias = (int)p->n_bias;
+    a.bias_ids = bi;
+    a.bias_vals = bv;
+    a.u = du;
+    if (!launch_sample(nullptr, a) || hipDeviceSynchronize() != hipSuccess) return false;
+    if (hipMemcpy(tokens, a.tok, (size_t)rows * 4, hipMemcpyDeviceToHost) != hipSuccess) return false;
+    if (kept && hipMemcpy(kept, a.kept, (size_t)rows * 4, hipMemcpyDeviceToHost) != hipSuccess) return false;
+    if (cutoff && hipMemcpy(cutoff, a.cutoff, (size_t)rows * 4, hipMemcpyDeviceToHost) != hipSuccess) return false;
+    return true;
+}

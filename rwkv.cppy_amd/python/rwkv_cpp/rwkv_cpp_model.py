@@ -148,6 +148,41 @@ class RWKVModel:
                                              states.ctypes.data, logits.ctypes.data)
         return logits, states
 
+    def sample(self, temperature: float = 1.0, top_p: float = 0.8, logit_bias=None, seed: int = 0,
+               offset: int = 0) -> int:
+        """MI355X extension (rwkv_mi355x_sample): draws one token on the device from the logits of the
+        last evaluation on this model (sampling.sample_logits semantics; draw `offset` of the stream
+        `seed`, sampling.uniform).  The state is untouched."""
+        if not self._valid:
+            raise ValueError('Model was freed')
+        return self._library.rwkv_mi355x_sample(self._ctx, temperature, top_p, logit_bias, seed, offset)
+
+    def generate(self, n: int, temperature: float = 1.0, top_p: float = 0.8, logit_bias=None, seed: int = 0,
+                 offset: int = 0, stop_tokens=(), block: int = 16) -> List[int]:
+        """MI355X extension (rwkv_mi355x_generate): generates up to n tokens on the device, continuing
+        from the state and logits the last evaluation on this model left there (eval, eval_sequence, or
+        an earlier generate).  Sampling and decoding run back to back on the GPU in blocks of `block`
+        tokens; only the tokens come back.  Draw i uses sampling.uniform(seed, offset + i).
+
+        Generation stops after a block that contains one of stop_tokens, and the tokens up to and
+        including the first stop token are returned.  The device state has then consumed the whole
+        block: it may have run up to block - 1 tokens past the stop token.  block=1 stops exactly."""
+        if not self._valid:
+            raise ValueError('Model was freed')
+        if not block > 0:
+            raise ValueError('block must be > 0')
+        stop = set(stop_tokens)
+        out: List[int] = []
+        while len(out) < n:
+            m = min(block, n - len(out))
+            tokens = self._library.rwkv_mi355x_generate(self._ctx, m, temperature, top_p, logit_bias, seed,
+                                                        offset + len(out))
+            for i, t in enumerate(tokens):
+                if t in stop:
+                    return out + tokens[:i + 1]
+            out += tokens
+        return out
+
     def free(self) -> None:
         if not self._valid:
             raise ValueError('Already freed')

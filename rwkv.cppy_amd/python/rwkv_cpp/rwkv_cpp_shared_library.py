@@ -24,6 +24,26 @@ class RWKVContext:
         self.ptr = ptr
 
 
+class RWKVSampling(ctypes.Structure):
+    """struct rwkv_mi355x_sampling (include/rwkv_mi355x.h)."""
+    _fields_ = [('temperature', ctypes.c_float), ('top_p', ctypes.c_float), ('n_bias', ctypes.c_uint32),
+                ('bias_ids', ctypes.POINTER(ctypes.c_uint32)), ('bias_values', P_FLOAT),
+                ('seed', ctypes.c_uint64), ('offset', ctypes.c_uint64)]
+
+
+def make_sampling(temperature: float = 1.0, top_p: float = 0.8, logit_bias=None, seed: int = 0,
+                  offset: int = 0) -> RWKVSampling:
+    """Fills an RWKVSampling; logit_bias: {token id: value}.  The bias arrays stay referenced by the
+    returned structure."""
+    bias = dict(logit_bias or {})
+    ids = (ctypes.c_uint32 * max(1, len(bias)))(*bias.keys())
+    values = (ctypes.c_float * max(1, len(bias)))(*bias.values())
+    p = RWKVSampling(temperature, top_p, len(bias), ctypes.cast(ids, ctypes.POINTER(ctypes.c_uint32)),
+                     ctypes.cast(values, P_FLOAT), seed & 0xFFFFFFFFFFFFFFFF, offset & 0xFFFFFFFFFFFFFFFF)
+    p._keep = (ids, values)
+    return p
+
+
 class RWKVSharedLibrary:
     """Python wrapper around librwkv.so."""
 
@@ -129,6 +149,14 @@ class RWKVSharedLibrary:
         L.rwkv_mi355x_pipeline_peer_pairs.restype = ctypes.c_int
         L.rwkv_mi355x_debug_set.argtypes = [vp, ctypes.c_char_p, ctypes.c_longlong]
         L.rwkv_mi355x_debug_set.restype = ctypes.c_bool
+        P_SAMPLING, P_U32 = ctypes.POINTER(RWKVSampling), ctypes.POINTER(ctypes.c_uint32)
+        L.rwkv_mi355x_sample.argtypes = [vp, P_SAMPLING, P_U32]
+        L.rwkv_mi355x_sample.restype = ctypes.c_bool
+        L.rwkv_mi355x_generate.argtypes = [vp, P_SAMPLING, sz, P_U32, P_FLOAT]
+        L.rwkv_mi355x_generate.restype = ctypes.c_bool
+        L.rwkv_mi355x_selftest_sample.argtypes = [P_FLOAT, ctypes.c_int, ctypes.c_int, P_SAMPLING, P_FLOAT, P_U32, P_U32,
+                                                  P_FLOAT]
+        L.rwkv_mi355x_selftest_sample.restype = ctypes.c_bool
 
         self.nullptr = ctypes.cast(0, ctypes.c_void_p)
 
@@ -217,6 +245,47 @@ class RWKVSharedLibrary:
         out = (ctypes.c_double * 2)()
         self.library.rwkv_mi355x_state_io_bytes(ctx.ptr, out)
         return out[0], out[1]
+
+    # ---- additive: sampling and the generation loop on the device ---------------------------
+    def rwkv_mi355x_sample(self, ctx: RWKVContext, temperature: float = 1.0, top_p: float = 0.8, logit_bias=None,
+                           seed: int = 0, offset: int = 0) -> int:
+        """One token drawn on the device from the context's logits (draw `offset` of stream `seed`);
+        the state is untouched."""
+        token = ctypes.c_uint32(0)
+        p = make_sampling(temperature, top_p, logit_bias, seed, offset)
+        if not self.library.rwkv_mi355x_sample(ctx.ptr, ctypes.byref(p), ctypes.byref(token)):
+            raise ValueError('rwkv_mi355x_sample failed, check stderr')
+        return token.value
+
+    def rwkv_mi355x_generate(self, ctx: RWKVContext, n: int, temperature: float = 1.0, top_p: float = 0.8,
+                             logit_bias=None, seed: int = 0, offset: int = 0,
+                             logits_out_address: Optional[int] = None) -> List[int]:
+        """n times (draw a token on the device, evaluate it) without a host round trip; returns the
+        tokens.  Draw i uses counter offset + i, so a call with offset + n continues the stream."""
+        tokens = (ctypes.c_uint32 * max(1, n))()
+        p = make_sampling(temperature, top_p, logit_bias, seed, offset)
+        if not self.library.rwkv_mi355x_generate(ctx.ptr, ctypes.byref(p), n, tokens,
+                                                 ctypes.cast(logits_out_address or 0, P_FLOAT)):
+            raise ValueError('rwkv_mi355x_generate failed, check stderr')
+        return list(tokens[:n])
+
+    def rwkv_mi355x_selftest_sample(self, logits, u, temperature: float = 1.0, top_p: float = 0.8, logit_bias=None):
+        """The sampler kernel on host logits [rows][V] (float32 numpy) with the draws u [rows] given.
+        Returns (tokens, kept, cutoff) numpy arrays [rows]."""
+        import numpy as np
+        logits = np.ascontiguousarray(logits, dtype=np.float32)
+        if logits.ndim == 1:
+            logits = logits[None, :]
+        rows, V = logits.shape
+        u = np.ascontiguousarray(np.broadcast_to(np.asarray(u, dtype=np.float32), (rows,)))
+        tokens, kept, cutoff = np.zeros(rows, np.uint32), np.zeros(rows, np.uint32), np.zeros(rows, np.float32)
+        p = make_sampling(temperature, top_p, logit_bias)
+        P_U32 = ctypes.POINTER(ctypes.c_uint32)
+        if not self.library.rwkv_mi355x_selftest_sample(
+                logits.ctypes.data_as(P_FLOAT), rows, V, ctypes.byref(p), u.ctypes.data_as(P_FLOAT),
+                tokens.ctypes.data_as(P_U32), kept.ctypes.data_as(P_U32), cutoff.ctypes.data_as(P_FLOAT)):
+            raise ValueError('rwkv_mi355x_selftest_sample failed')
+        return tokens, kept, cutoff
 
     def rwkv_get_system_info_string(self) -> str:
         return self.library.rwkv_get_system_info_string().decode('utf-8')

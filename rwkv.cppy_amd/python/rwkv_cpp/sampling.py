@@ -46,3 +46,33 @@ def sample_probs(probs: np.ndarray, temperature: float = 1.0, top_p: float = 0.8
     probs = probs / np.sum(probs)
     choice = rng.choice if rng is not None else np.random.choice
     return int(choice(a=len(probs), p=probs))
+
+
+def uniform(seed: int, counter: int) -> float:
+    """Draw `counter` of the stream `seed` as librwkv.so's sampler makes it (rwkv_mi355x_sampling):
+    splitmix64 of the pair, the top 24 bits as a float32 in [0, 1)."""
+    return float(np.float32(splitmix64(seed, counter) >> 40) * np.float32(2.0 ** -24))
+
+
+def splitmix64(seed: int, counter: int) -> int:
+    """The 64-bit word behind uniform(seed, counter)."""
+    mask = (1 << 64) - 1
+    z = (seed + 0x9E3779B97F4A7C15 * (counter + 1)) & mask
+    z = ((z ^ (z >> 30)) * 0xBF58476D1CE4E5B9) & mask
+    z = ((z ^ (z >> 27)) * 0x94D049BB133111EB) & mask
+    return z ^ (z >> 31)
+
+
+def sample_probs_u(probs: np.ndarray, u: float, temperature: float = 1.0, top_p: float = 0.8,
+                   logit_bias: Optional[Dict[int, float]] = None) -> int:
+    """sample_probs with the uniform draw u in [0, 1) given instead of an rng: the same bias, top-p
+    and temperature filtering, then the first index whose cumulative weight exceeds u times the total
+    (what np.random.choice does with its draw)."""
+
+    class _Fixed:
+        @staticmethod
+        def choice(a, p):
+            cdf = np.cumsum(p)
+            return min(int(cdf.searchsorted(u * cdf[-1], side='right')), a - 1)
+
+    return sample_probs(probs, temperature, top_p, logit_bias, _Fixed)
