@@ -25,6 +25,12 @@
 // fails the evaluation that synchronises next, then clears every granule (a late producer may
 // have left one tagged) -- never a hang, never a silently wrong result.
 //
+// The reducer is mv_att6.hpp's att6_reduce, the same function the co-resident layout calls: y is
+// published (or, without a fused Wo, emitted as the Wo launch's input) before the decay tail's w is
+// needed -- waves 0..3 meet on an LDS arrival counter, run the output half of wkv6, GroupNorm and the
+// publish; wave 4's decay path joins at one __syncthreads, after which the new state is stored.  The
+// Wo workgroups' tail after that is the gather of y, the qsum pass and 4 WOR rows' dots.
+//
 // The state update uses 16-byte accesses: wave g owns keys 16g..16g+15, lane (kk, jq) keys
 // 16g + 4kk + q (q < 4) of value columns 4jq..4jq+3.  Each output column's sum keeps
 // k_att6_dec's association: ((t0 + t1) + t2) + t3 per 4-key run (from +0), (p0 + p1) + (p2 + p3)
@@ -42,8 +48,7 @@ template <int WF, int U, int WD, int WOR>
 __global__ __launch_bounds__(320) void k_v6_att_fused(Att6Fused a) {
     constexpr bool WO = WOR > 0;
     extern __shared__ __attribute__((aligned(16))) char smem[];  // Q8 image of dl (decay tail input)
-    __shared__ __attribute__((aligned(16))) float sr[64], sk[64], sv[64], sg[64], sw[64], su[64];
-    __shared__ __attribute__((aligned(16))) float part[16][64];
+    __shared__ Att6Lds L;
     constexpr int S = 64;
     const int wg = (int)blockIdx.x, H = a.H, C = a.C, D = a.D;
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);  // wave-uniform branches
@@ -97,8 +102,6 @@ __global__ __launch_bounds__(320) void k_v6_att_fused(Att6Fused a) {
     const int h = red ? wg - NP : wg % H, sidx = red ? 0 : wg / H;
     const int c0 = h * S;
     const Att6Dec & at = a.att;
-    const size_t hb = (size_t)h * S * S;
-    const int jq = lane & 15, kk = lane >> 4;
     unsigned long long * const gdl = a.gran + 4 * (size_t)C;
     STAMP_BEGIN();
     // the reducer's late scalars (Wo input record, hand-off words, eps) in SGPRs now
@@ -113,27 +116,8 @@ __global__ __launch_bounds__(320) void k_v6_att_fused(Att6Fused a) {
     const bool publish = wg != a.skip_wg;  // test hook (Engine debug knob "skip_granule")
     // ---- the reducer's head operands first (state rows, per-channel vectors, decay-tail weights):
     // they stream in with this workgroup's own weight rows
-    float4 st[4];
-    WBlk wp[4];
-    float lnw_c = 0.0f, lnb_c = 0.0f, dec_c = 0.0f, u_c = 0.0f;
-    if (red) {
-        if (wave < 4) {
-#pragma unroll
-            for (int q = 0; q < 4; q++)
-                st[q] = *(const float4 *)(at.sin + hb + (size_t)(16 * wave + 4 * kk + q) * S + 4 * jq);
-        }
-        if (wave == 0) {
-            lnw_c = at.lnx_w[c0 + lane];
-            lnb_c = at.lnx_b[c0 + lane];
-            u_c = at.u[c0 + lane];
-        }
-        if (wave == 4) {
-            dec_c = at.decay[c0 + lane];
-            const int nb = at.wd2.K >> 5;
-#pragma unroll
-            for (int l = 0; l < 4; l++) wp[l] = load_wblk<WD>(at.wd2, (size_t)(c0 + lane) * nb + min(l, nb - 1));
-        }
-    }
+    Att6RedOps ops;
+    if (red) att6_red_begin<WD>(at, L, ops, h, lane, wave);
     // ---- a producer's rows, each published as a granule: wave w -> matrix (4 s + w) / 8 (r, k, v,
     // g), rows of head h; wave 4 -> decay LoRA rows (EPI_TANH) of its slots wg, wg + 8H, ...
     if (red) {
@@ -154,86 +138,8 @@ __global__ __launch_bounds__(320) void k_v6_att_fused(Att6Fused a) {
         STAMP_END_NS(6);
         return;
     }
-    // ---- reducer.  Waves 0..3 sweep r, k, v, g of the head's channels (lane = channel); wave 4
-    // sweeps the decay LoRA values and runs the decay tail (k_att6_dec's arithmetic) meanwhile.
-    if (wave < 4) {
-        unsigned long long * g = a.gran + (size_t)wave * C + c0 + lane;
-        bool live[1] = {true};
-        float v[1];
-        gran_sweep<1>(g, 0, live, v, err, spin_max);
-        float * dst = wave == 0 ? sr : wave == 1 ? sk : wave == 2 ? sv : sg;
-        dst[lane] = v[0];
-        gran_clear(g);
-        if (wave == 0) {
-            su[lane] = u_c;
-            STAMP_MID();
-        }
-    } else {
-        bool live[2] = {lane < D, lane + 64 < D};
-        float v[2];
-        unsigned long long * const own = gdl + (size_t)h * D + lane;  // this head's copy
-        gran_sweep<2>(own, 64, live, v, err, spin_max);
-        if (live[0]) gran_clear(own);
-        if (live[1]) gran_clear(own + 64);
-        const ActBuf act = lds_act(smem, act_fmt_for(WD), D);
-        if (lane < D) emit32(act, 0, lane, v[0]);  // lanes 0..31 / 32..63: whole quantization blocks
-        if (lane + 64 < D) emit32(act, 0, lane + 64, v[1]);
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        __builtin_amdgcn_wave_barrier();
-        // decay tail of channel c0 + lane: w = exp(-exp(Wd2 . dl + decay)), rwkv_graph.inc:357-367
-        const float s = decay_row_thread<WD, 4, 4>(at.wd2, c0 + lane, act, at.wd2.K >> 5, wp);
-        sw[lane] = rk_expf(-rk_expf(s + dec_c));
-    }
-    __syncthreads();
-    STAMP_X(0);
-    // wkv6 (ggml_rwkv_wkv6): keys 16 wave + 4 kk + q, value columns 4 jq + c
-    if (wave < 4) {
-        const int i0 = 16 * wave + 4 * kk;
-        const float4 k4 = *(const float4 *)(sk + i0), u4 = *(const float4 *)(su + i0);
-        const float4 r4 = *(const float4 *)(sr + i0), w4 = *(const float4 *)(sw + i0);
-        const float4 v4 = *(const float4 *)(sv + 4 * jq);
-        const float kq[4] = {k4.x, k4.y, k4.z, k4.w}, uq[4] = {u4.x, u4.y, u4.z, u4.w};
-        const float rq[4] = {r4.x, r4.y, r4.z, r4.w}, wq[4] = {w4.x, w4.y, w4.z, w4.w};
-        const float vj[4] = {v4.x, v4.y, v4.z, v4.w};
-        float p[4] = {0.0f, 0.0f, 0.0f, 0.0f};
-#pragma unroll
-        for (int q = 0; q < 4; q++) {
-            const float prev[4] = {st[q].x, st[q].y, st[q].z, st[q].w};
-            float nw[4];
-#pragma unroll
-            for (int c = 0; c < 4; c++) {
-                const float kv = vj[c] * kq[q];
-                const float temp = kv * uq[q] + prev[c];
-                const float t = temp * rq[q];
-                p[c] += t;
-                nw[c] = prev[c] * wq[q] + kv;
-            }
-            *(float4 *)(at.sout + hb + (size_t)(i0 + q) * S + 4 * jq) = make_float4(nw[0], nw[1], nw[2], nw[3]);
-        }
-        *(float4 *)&part[4 * wave + kk][4 * jq] = make_float4(p[0], p[1], p[2], p[3]);
-    }
-    __syncthreads();
-    STAMP_X(1);
-    // GroupNorm over the head (ggml_norm, fp64 sums) * ln_x + b, * g; emitted as Wo's input
-    if (wave == 0) {
-        float sgp[4];
-#pragma unroll
-        for (int gg = 0; gg < 4; gg++)
-            sgp[gg] = (part[4 * gg][lane] + part[4 * gg + 1][lane]) + (part[4 * gg + 2][lane] + part[4 * gg + 3][lane]);
-        const float x = (sgp[0] + sgp[2]) + (sgp[1] + sgp[3]);
-        const double s = group_tree_sum_d((double)x, S);
-        const float mean = (float)div_count(s, S);
-        const float d = x - mean;
-        const double s2 = group_tree_sum_d((double)(d * d), S);
-        const float var = (float)div_count(s2, S);
-        const float scale = 1.0f / sqrtf(var + eps);
-        float o = d * scale;
-        o = o * lnw_c;
-        o = o + lnb_c;
-        o = o * sg[lane];
-        if constexpr (WO) pub_q8(a.ygran, (c0 >> 5) + (lane >> 5), o, a.ytag, lane);  // the head's 2 blocks
-        else emit32(yq, 0, c0 + lane, o);
-    }
+    // ---- reducer (mv_att6.hpp att6_reduce: y first, then the decay tail's w and the state)
+    att6_reduce<WD, WO>(a, L, ops, smem, h, lane, wave, yq, err, spin_max, eps ATT6_STAMP_ARGS);
     STAMP_END(6);
 }
 
