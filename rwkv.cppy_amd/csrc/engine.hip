@@ -387,6 +387,21 @@ Engine::~Engine() {
     if (stream_) (void)hipStreamDestroy(stream_);
 }
 
+bool GranuleMem::alloc(size_t C, size_t F, std::vector<void *> & allocs) {
+    cleared_n = 6 * C;  // 4 C + H D (D <= 128, H = C / 64)
+    const size_t kg = (size_t)KG_STRIDE * (F / 32);
+    tagged_n = C + kg + C + C;
+    for (auto [p, n] : {std::pair{&cleared, cleared_n}, std::pair{&y, tagged_n}}) {
+        HIP_OK(hipMalloc(p, n * 8));
+        allocs.push_back(*p);
+        HIP_OK(hipMemset(*p, 0, n * 8));
+    }
+    k = y + C;
+    r = k + kg;
+    x = r + C;
+    return true;
+}
+
 bool Engine::init() {
     HIP_OK(hipSetDevice(m_->device));
     stamp_init();
@@ -404,26 +419,12 @@ bool Engine::init() {
     }
     HIP_OK(hipMalloc(&logits_, (size_t)m_->n_vocab * sizeof(float) + 16));
     ws_allocs_.push_back(logits_);
-    // in-launch hand-off (k_v6_att_fused): granules zeroed once here and re-armed by their readers;
-    // the timeout flag is a host-mapped word, so checking it costs the host one load after a sync
+    // in-launch hand-offs (handoff.hpp): the timeout flag is a host-mapped word, so checking it
+    // costs the host one load after a sync
     HIP_OK(hipHostMalloc((void **)&herr_h_, 64, hipHostMallocMapped | hipHostMallocCoherent));
     *(volatile unsigned *)herr_h_ = 0;
     HIP_OK(hipHostGetDevicePointer((void **)&herr_d_, herr_h_, 0));
-    {
-        hgran_n_ = 6 * (size_t)m_->n_embed;  // k_v6_att_fused granules: 4 C + H D (D <= 128, H = C / 64)
-        HIP_OK(hipMalloc(&hgran_, hgran_n_ * 8));
-        ws_allocs_.push_back(hgran_);
-        HIP_OK(hipMemset(hgran_, 0, hgran_n_ * 8));
-        // the tagged hand-offs (fused Wo, fused channel mix): tagged per (layer, state parity)
-        const size_t C = m_->n_embed, kg = (size_t)KG_STRIDE * ((size_t)std::max(m_->F, 32) / 32);
-        tgran_n_ = C + kg + C + C;
-        HIP_OK(hipMalloc(&ygran_, tgran_n_ * 8));
-        ws_allocs_.push_back(ygran_);
-        HIP_OK(hipMemset(ygran_, 0, tgran_n_ * 8));
-        kgran_ = ygran_ + C;
-        rgran_ = kgran_ + kg;
-        xgran_ = rgran_ + C;
-    }
+    if (!gran_.alloc(m_->n_embed, (size_t)std::max(m_->F, 32), ws_allocs_)) return false;
     // Per-context switches read when the context is created (each arm tested):
     const char * io = getenv("RWKV_MI355X_STATE_PIPELINE");  // 0: host state copied whole
     io_pipeline_ = !(io && io[0] == '0');
@@ -490,7 +491,7 @@ bool Engine::ensure_workspace(int T) {
     // keep state and logits, drop the rest; until every allocation below has succeeded the
     // workspace counts as absent (tcap_ = 0, pointers null), so a failed grow can never leave a
     // capacity that points at freed or missing buffers
-    std::vector<void *> keep = {dstate_[0], dstate_[1], logits_, hgran_, ygran_};
+    std::vector<void *> keep = {dstate_[0], dstate_[1], logits_, gran_.cleared, gran_.y};
     for (void * p : ws_allocs_) {
         bool k = false;
         for (void * q : keep) k |= (p == q);
@@ -1215,8 +1216,7 @@ bool Engine::run_tokens(const uint32_t * tokens, size_t T, bool want_logits) {
     logits_valid_ = false;
     if (!run_tokens_impl(tokens, T, want_logits)) {
         (void)hipStreamSynchronize(stream_);
-        // the call's tagged Wo-input granules must not satisfy a replay of the same parity
-        (void)hipMemsetAsync(ygran_, 0, tgran_n_ * 8, stream_);
+        (void)gran_.clear_tagged(stream_);  // a replay runs at the same parity (GranuleMem::clear_tagged)
         (void)hipStreamSynchronize(stream_);
         release_device();
         cur_ = cur0;
@@ -1263,13 +1263,8 @@ bool Engine::run_tokens_impl(const uint32_t * tokens, size_t T, bool want_logits
         } else {
             if (!forward((int)n, dstate_[cur_], dstate_[cur_ ^ 1], lg)) return false;
         }
-        // The fused decode's Wo granules are tagged (layer, state parity) and never cleared by their
-        // readers.  A step that did not run the fused decode flips the parity without writing them,
-        // so the next decode would run at the parity of the decode before this step and could take
-        // a value that step left (one-layer engines: the same layer tag).  Clear them in stream order.
-        if (n > 1 || generic_decode_) {
-            HIP_OK(hipMemsetAsync(ygran_, 0, tgran_n_ * 8, stream_));
-        }
+        // a step without the fused decode flips the parity (GranuleMem::clear_tagged)
+        if (n > 1 || generic_decode_) HIP_OK(gran_.clear_tagged(stream_));
         // tokens buffer is reused by the next chunk: wait before overwriting the pinned copy
         if (!last) HIP_OK(hipStreamSynchronize(stream_));
         cur_ ^= 1;
@@ -1321,11 +1316,12 @@ bool Engine::sync() {
     return handoff_check();
 }
 
-// k_v6_att_fused's reducer gives up after spin_max_ sweep passes and sets the host-mapped flag
-// (mv_att6f.hip).  Every call that synchronises the stream reads it: a set flag fails that call
-// (the reference's error convention: false + RWKV_ERROR_CTX, rwkv_error_handling.inc:1-54).  A
-// producer that arrives after the timeout leaves its granule tagged, which the next launch would
-// read as its own value, so every granule is cleared before the flag is re-armed.
+// Every waiting loop of an in-launch hand-off gives up after spin_max_ passes and sets the
+// host-mapped flag (handoff.hpp: gran_wait, handoff_fail).  Every call that synchronises the
+// stream reads it: a set flag fails that call (the reference's error convention: false +
+// RWKV_ERROR_CTX, rwkv_error_handling.inc:1-54).  A producer that arrives after the timeout leaves
+// its granule tagged, which the next launch would read as its own value, so every granule is
+// cleared before the flag is re-armed.
 bool Engine::handoff_check() {
     // called after the stream has drained: nothing of this context is queued any more
     release_device();
@@ -1334,8 +1330,7 @@ bool Engine::handoff_check() {
     if (*(volatile unsigned *)herr_h_ == 0) return true;
     logits_valid_ = false;
     (void)hipStreamSynchronize(stream_);
-    (void)hipMemsetAsync(hgran_, 0, hgran_n_ * 8, stream_);
-    (void)hipMemsetAsync(ygran_, 0, tgran_n_ * 8, stream_);
+    gran_.clear_all(stream_);
     (void)hipStreamSynchronize(stream_);
     *(volatile unsigned *)herr_h_ = 0;
     if (co_seen && co_knob_ < 0) {
@@ -1371,12 +1366,12 @@ bool Engine::debug_set(const char * name, long long value) {
     else if (n == "ffn_wdelay" && value >= -1 && value <= 10000) ffn_wdelay_ = (int)value;
     else if (n == "ffn_prepoll") ffn_prepoll_ = value != 0;
     else return false;
-    // the decode graphs captured the old values; a decode program without the fused Wo flips the
-    // state parity without writing the Wo granules (see run_tokens_impl): clear them
+    // the decode graphs captured the old values; the new decode program may lack a hand-off
+    // (GranuleMem::clear_tagged)
     (void)hipStreamSynchronize(stream_);
     drop_graphs();
     drop_io_graphs();
-    (void)hipMemsetAsync(ygran_, 0, tgran_n_ * 8, stream_);
+    (void)gran_.clear_tagged(stream_);
     (void)hipStreamSynchronize(stream_);
     return true;
 }
@@ -1610,7 +1605,7 @@ long long Engine::debug_copy(const char * name, void * out, size_t bytes) {
     if (n == "lora") src = lora_, cap_bytes = cap * kmax * 4;
     if (n == "bonus") src = bonus_, cap_bytes = cap * (size_t)std::max<int64_t>(1, m_->H) * 4;
     if (n == "logits") src = logits_, cap_bytes = (size_t)m_->n_vocab * 4;
-    if (n == "granules") src = hgran_, cap_bytes = 6 * C * 8;  // k_v6_att_fused hand-off granules
+    if (n == "granules") src = gran_.cleared, cap_bytes = gran_.cleared_n * 8;  // the fused v6 attention's
     if (!src && n.rfind("slot", 0) == 0) {
         const size_t dot = n.find('.');
         const int i = atoi(n.c_str() + 4);

@@ -67,6 +67,31 @@ struct ActSlot {
     uint8_t * tq = nullptr;  // sequence-GEMM token-tile records
 };
 
+// The granule memory of the in-launch hand-offs (handoff.hpp; DESIGN.md "The hand-off protocol").
+struct GranuleMem {
+    // cleared granules (tag 1, zeroed here and re-armed by their one reader): the fused v6
+    // attention's r, k, v, g [4 C] and decay-LoRA values [H D]
+    unsigned long long * cleared = nullptr;
+    // tagged granules (Engine::handoff_tag, never cleared by their readers), one allocation: y [C]
+    // head / channel outputs -> fused Wo rows; k [KG_STRIDE F / 32] FFN key blocks and r [C]
+    // receptance rows -> fused FFN value rows; x [C] v6 x rows -> the next layer's maa (k_sig_maa)
+    unsigned long long *y = nullptr, *k = nullptr, *r = nullptr, *x = nullptr;
+    size_t cleared_n = 0, tagged_n = 0;
+    bool alloc(size_t C, size_t F, std::vector<void *> & allocs);
+    // A tag names a layer and a state parity, so a step that flips the parity without running the
+    // fused decode (a sequence chunk, the generic decode, a decode program without the hand-off
+    // after a debug knob changed) leaves the granules of the decode before it in place: the next
+    // decode runs at that decode's parity again and could take a stale value for its own (one-layer
+    // engines: the same layer tag).  So does a failed call that is replayed at the parity it started
+    // with.  Every such step clears the tagged granules in stream order.
+    hipError_t clear_tagged(hipStream_t st) const { return hipMemsetAsync(y, 0, tagged_n * 8, st); }
+    // after a timeout: a producer that arrived late left its granule set, cleared or tagged
+    void clear_all(hipStream_t st) const {
+        (void)hipMemsetAsync(cleared, 0, cleared_n * 8, st);
+        (void)clear_tagged(st);
+    }
+};
+
 // Per-kernel-class timing collected with hipEvents on the context stream (bench roofline).
 struct KernelStat {
     std::string name;
@@ -173,8 +198,9 @@ class Engine : public KLaunchTimer {
     LnMixArgs ln_mix_args(int T, const float * carry_in, float * carry_out, const float * lnw, const float * lnb) const;
     template <class Att>
     bool batch_att_tail(Att a, int wo_slot, int l, int T, const float * si, float * so);
-    // the tag of layer l's in-launch hand-offs at the current state parity
+    // the tag of layer l's in-launch hand-offs at the current state parity, and what its launches poll with
     unsigned handoff_tag(uint32_t l) const { return (unsigned)(l + 1) | ((unsigned)(cur_ + 1) << 16); }
+    Handoff handoff(uint32_t l) const { return Handoff{handoff_tag(l), herr_d_, spin_max_}; }
     // captures what build() enqueues on stream_ into an executable graph
     template <class F>
     bool capture(hipGraphExec_t & ge, F && build);
@@ -213,16 +239,7 @@ class Engine : public KLaunchTimer {
     int cur_ = 0;
     unsigned * herr_h_ = nullptr;  // hand-off timeout flag, host-mapped (herr_d_ = its device address)
     unsigned * herr_d_ = nullptr;
-    unsigned long long * hgran_ = nullptr;  // in-launch hand-off granules (k_v6_att_fused)
-    // tagged granules (per layer and state parity, never cleared by their readers): ygran_ [C] head
-    // outputs -> fused Wo rows; kgran_ [KG_STRIDE F / 32] FFN key blocks and rgran_ [C] receptance
-    // rows -> fused FFN value rows.  One allocation of tgran_n_ granules, cleared as a whole.
-    unsigned long long * ygran_ = nullptr;
-    unsigned long long * kgran_ = nullptr;
-    unsigned long long * rgran_ = nullptr;
-    unsigned long long * xgran_ = nullptr;  // [C] v6 x rows -> the next layer's maa (k_sig_maa)
-    size_t tgran_n_ = 0;
-    size_t hgran_n_ = 0;
+    GranuleMem gran_;
     int dbg_skip_gran_ = -1;
     unsigned spin_max_ = 1u << 20;
     // chunk-parallel wkv6 for sequences (wkv_chunk.hip; re-associated, not bit-exact): 0 = serial

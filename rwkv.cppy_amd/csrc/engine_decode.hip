@@ -195,10 +195,8 @@ bool Engine::decode_att_v4(DecodeRun & d, uint32_t l) {
         if (wo_in) {
             wf.wo = L.att_o;
             wf.xres = x_;
-            wf.ygran = ygran_;
-            wf.ytag = handoff_tag(l);
-            wf.err = herr_d_;
-            wf.spin_max = spin_max_;
+            wf.ygran = gran_.y;
+            wf.h = handoff(l);
             if (timing_) {
                 kt_bytes_ += wbytes(L.att_o) + 2.0 * C * 8 + 2.0 * C * 4;
                 kt_flops_ += 2.0 * C * C;
@@ -294,9 +292,8 @@ bool Engine::decode_att_v6(DecodeRun & d, uint32_t l) {
     f.wd1 = L.decay_w1;
     f.xw = outs[mats[4]];
     f.att = a;
-    f.gran = hgran_;
-    f.err = herr_d_;
-    f.spin_max = spin_max_;
+    f.gran = gran_.cleared;
+    f.h = handoff(l);
     f.skip_wg = dbg_skip_gran_;
     // Wo inside the same launch (the head outputs handed to the non-reducer workgroups as
     // granules tagged by layer and state parity); else Wo is its own k_mva launch below
@@ -304,8 +301,7 @@ bool Engine::decode_att_v6(DecodeRun & d, uint32_t l) {
     if ((fuse_ & FUSE_WO6) && (fuse_ & FUSE_ATT6)) {
         f.wo = L.att_o;
         f.xres = x_;
-        f.ygran = ygran_;
-        f.ytag = handoff_tag(l);
+        f.ygran = gran_.y;
         f.wo_rows = wo_rows_;
         f.wo_prepoll = wo_prepoll_;
         wo_in = v6_att_fused_supported(f);
@@ -435,14 +431,12 @@ bool Engine::decode_ffn(DecodeRun & d, uint32_t l) {
             fr.W = L.ffn_r;
             fr.epi = EPI_STORE;
             mix(fr, mur);
-            ff.rg = rgran_;
+            ff.rg = gran_.r;
         }
         ff.wv = L.ffn_v;
         ff.x = x_;
-        ff.kg = kgran_;
-        ff.tag = handoff_tag(l);
-        ff.err = herr_d_;
-        ff.spin_max = spin_max_;
+        ff.kg = gran_.k;
+        ff.h = handoff(l);
         const double wr = hasr ? wbytes(L.ffn_r) : 0.0;
         ff.wdelay = ffn_wdelay_ >= 0 ? ffn_wdelay_ : (int)std::min(2000.0, (wbytes(L.ffn_k) + wr) / 4e4);
         ff.prepoll = ffn_prepoll_;
@@ -504,10 +498,8 @@ bool Engine::decode_ffn(DecodeRun & d, uint32_t l) {
         v6_maa_dec_args(sm.maa, C, m_->maa_D, N.maa_w1, x_, si1 + C, so1 + C, N.ln1_w, N.ln1_b, N.maa_x,
                         N.maa_w2t, N.maa, outs1);
         sm.nm = 5 * (C / 64);
-        sm.xg = xgran_;
-        sm.xtag = handoff_tag(l);
-        sm.err = herr_d_;
-        sm.spin_max = spin_max_;
+        sm.xg = gran_.x;
+        sm.h = handoff(l);
         if (sig_maa_supported(sm)) {
             if (timing_) {
                 // + the maa's W1, W2 (fp32), LayerNorm vectors, carry and mixes; x granules out / in

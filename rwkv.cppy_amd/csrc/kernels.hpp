@@ -254,18 +254,25 @@ bool launch_v6_maa_dec_emb(hipStream_t st, const MaaDec & a);
 bool launch_v6_maa_dec(hipStream_t st, int C, int D, const DMat & w1, const float * x, const float * carry,
                        float * carry_out, const float * lnw, const float * lnb, const float * maa_x,
                        const float * w2t, const float * const * maa, const ActBuf * outs);
+// What a launch with an in-launch hand-off polls with (handoff.hpp): the tag of its tagged granules
+// (Engine::handoff_tag: unique per layer and state parity), the host-mapped word a timeout sets
+// (system scope; Engine::handoff_check reads it after every synchronising call) and the bound, in
+// passes, of every waiting loop.
+struct Handoff {
+    unsigned tag;
+    unsigned * err;
+    unsigned spin_max;
+};
 // v6 decode, co-resident form (mv_sigmaa.hip): layer l's k_mvsig rows (hv: Wv / k / y = x, hr: Wr /
 // xr) and layer l + 1's maa workgroups (maa, x gathered from the granules xg the rows publish, tag
-// xtag) in one launch of C / 8 workgroups; the same bits as k_mvsig + k_v6_maa_dec4.
+// h.tag) in one launch of C / 8 workgroups; the same bits as k_mvsig + k_v6_maa_dec4.
 struct SigMaa {
     MVHot hv, hr;
     int wtype;
     MaaDec maa;
     int nm;                      // maa workgroups: 5 C / 64
     unsigned long long * xg;     // C granules
-    unsigned xtag;
-    unsigned * err;
-    unsigned spin_max;
+    Handoff h;
 };
 bool sig_maa_supported(const SigMaa & a);
 bool launch_sig_maa(hipStream_t st, const SigMaa & a);
@@ -302,18 +309,15 @@ struct Att6Fused {
     ActBuf xw;       // its input
     Att6Dec att;     // wd2, decay, u, sin, sout, lnx_w, lnx_b, eps, yq
     unsigned long long * gran;  // 4 C + H D zeroed 8-byte granules: r, k, v, silu(g), tanh(Wd1 . xw)
-    unsigned * err;  // set (system scope) on a hand-off timeout: a host-mapped word the engine reads
-                     // after every synchronising call (Engine::handoff_check)
-    unsigned spin_max;  // sweep bound (passes) before a timeout
+    Handoff h;       // h.tag: the y granules' (Wo fused)
     int skip_wg;     // test hook: this producer workgroup publishes nothing (-1: none)
-    // Wo fused (wo.qs != null): the reducers publish the head outputs y as granules tagged ytag
+    // Wo fused (wo.qs != null): the reducers publish the head outputs y as granules tagged h.tag
     // (unique per layer and state parity, so they need no clearing) instead of emitting Wo's Q8
     // input; the non-reducer workgroups then gather y, quantize it (the matvec prologue's
     // arithmetic) and run Wo's rows with x += Wo . y (EPI_ADD) -- the Wo launch disappears
     DMat wo;
     float * xres;                 // the residual stream x [C]
     unsigned long long * ygran;   // C granules
-    unsigned ytag;
     int wo_rows;                  // Wo rows per wave of a Wo workgroup: 4 or 8
     int wo_prepoll;               // 1: one wave polls a granule per head before the gather
 };
@@ -328,15 +332,13 @@ bool launch_v6_att_co(hipStream_t st, const Att6Fused & a);
 // is written as fp32 y (Wo quantizes it in its prologue).
 bool v4_att_fused_supported(int C, const DMat & Wr, const DMat & Wk, const DMat & Wv, const ActBuf & out);
 // wf: Wo in the same launch -- the producers publish their channels' outputs as granules tagged
-// ytag (per layer and state parity); Wo workgroups after them in the grid gather all C, quantize
+// h.tag (per layer and state parity); Wo workgroups after them in the grid gather all C, quantize
 // them as Wo's fp32-input prologue does and run 2 Wo rows per wave, x += Wo . y
 struct V4WoFused {
     DMat wo;
     float * xres;
     unsigned long long * ygran;
-    unsigned ytag;
-    unsigned * err;
-    unsigned spin_max;
+    Handoff h;
     // layer 0 of a decode: x = LN0(emb[*tok]) computed in the launch (k_embed_ln's arithmetic)
     const uint32_t * tok;
     DMat emb;
@@ -351,7 +353,7 @@ bool launch_v4_att_fused(hipStream_t st, int C, const DMat & Wr, const DMat & Wk
 // The decode channel mix in one launch (mv_ffnf.hpp): e[0] the FFN key (SRC_LNMIX, relu^2, emit = 1,
 // act_out's format = the value's input format), e[1] the receptance (SRC_LNMIX, EPI_STORE; hasr
 // only), wv the FFN value; x += sigmoid(r) * (Wv . relu^2(Wk . xk))  (v7: x += Wv . relu^2(...)).
-// kg: KG_STRIDE * F / 32 granules, rg: C granules, both tagged `tag` (unique per layer and state
+// kg: KG_STRIDE * F / 32 granules, rg: C granules, both tagged h.tag (unique per layer and state
 // parity; the engine clears them whenever the parity flips without a fused decode).
 constexpr int KG_STRIDE = 10;  // granules per published Q8 block: 8 q dwords, d, s (Q8_1's d * sum)
 struct FfnFused {
@@ -360,9 +362,7 @@ struct FfnFused {
     float * x;
     unsigned long long * kg;
     unsigned long long * rg;
-    unsigned tag;
-    unsigned * err;
-    unsigned spin_max;
+    Handoff h;
     int np;       // producer workgroups (set by launch_ffn_fused)
     int wdelay;   // consumers issue their value rows this many 100 MHz ticks after starting
     int prepoll;  // 1: one wave polls each key block's d granule before the gather

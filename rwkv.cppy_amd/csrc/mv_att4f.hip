@@ -43,9 +43,7 @@ struct Att4Fused {
     DMat wo;
     float * xres;
     unsigned long long * ygran;
-    unsigned ytag;
-    unsigned * err;
-    unsigned spin_max;
+    Handoff h;
     // EMB (layer 0, Wo fused): x = LN0(emb[*tok]) -- the producers' image waves normalise the
     // embedding row (k_embed_ln's loads, chunk sums in chunk order, ln_apply: the same bits) through
     // one more barrier, and each Wo wave computes its rows' x itself; the Wo rows store x + Wo . y
@@ -53,8 +51,6 @@ struct Att4Fused {
     DMat emb;
     const float * ln0w, * ln0b;
 };
-
-typedef __attribute__((address_space(1))) unsigned long long a4_gu64_t;
 
 // 8 consecutive embedding elements k .. k + 7 (clamped to the row) as fp32
 __device__ __forceinline__ void a4_emb8(float (&v)[8], const DMat & emb, size_t tok, int k, int C) {
@@ -68,7 +64,6 @@ __device__ __forceinline__ void a4_emb8(float (&v)[8], const DMat & emb, size_t 
         ln_load8(v, (const float *)emb.qs + tok * C, k, C);
     }
 }
-typedef __attribute__((address_space(1))) unsigned a4_gu32_t;
 
 // 512 threads = 8 waves, CPW channels per workgroup.  Waves 4..7 build the three images (LayerNorm
 // statistics in the chunk association, one 512-element chunk per wave, token shift per mix,
@@ -119,7 +114,7 @@ __global__ __launch_bounds__(512) void k_v4_att_fused(Att4Fused a) {
                 xr = a.xres[min(row0 + min(lane, A4_WOR - 1), C - 1)];
             }
             const ActBuf xq = lds_act(smem, act_fmt_for(WF), K);
-            gran_gather_image<WF>(a.ygran, a.ytag, C, xq, wave, 8, a.err, a.spin_max, lane);
+            gran_gather_image<WF>(a.ygran, a.h.tag, C, xq, wave, 8, a.h.err, a.h.spin_max, lane);
             __syncthreads();
             float acc[A4_WOR], acc2[A4_WOR];
 #pragma unroll
@@ -300,9 +295,7 @@ __global__ __launch_bounds__(512) void k_v4_att_fused(Att4Fused a) {
             bb = e1 * bb + e2;
             pp = qq;
             const float y = sr[lane] * (an / bn);
-            if constexpr (WO)
-                __hip_atomic_store((a4_gu64_t *)(a.ygran + c), ((unsigned long long)a.ytag << 32) | __float_as_uint(y),
-                                   __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            if constexpr (WO) gran_store(a.ygran + c, a.h.tag, y);
             else if constexpr (CPW == 32) emit32(ao, 0, c, y);  // lanes 0..31: one quantization block
             else a.y[c] = y;
             if (c < C) {
@@ -383,9 +376,7 @@ bool launch_v4_att_fused(hipStream_t st, int C, const DMat & Wr, const DMat & Wk
         a.wo = wf->wo;
         a.xres = wf->xres;
         a.ygran = wf->ygran;
-        a.ytag = wf->ytag;
-        a.err = wf->err;
-        a.spin_max = wf->spin_max;
+        a.h = wf->h;
         if (wf->tok) {
             if ((wf->emb.type != W_F16 && wf->emb.type != W_F32) || (int)wf->emb.K != C || !wf->ln0w || !wf->ln0b) {
                 fprintf(stderr, "rwkv: fused v4 attention with the embedding: unsupported embedding\n");

@@ -1,13 +1,11 @@
 // mv_att6.hpp -- pieces shared by the two v6 fused attention decode launches (mv_att6f.hip, the
 // ordered layout that needs no co-residency; mv_att6c.hip, the co-resident layout): the producer
-// rows (k_mva's arithmetic), the single-reader granules of the r / k / v / g / decay-LoRA
-// hand-off, and the head reducer both layouts call (att6_reduce: y first, state last).
+// rows (k_mva's arithmetic) and the head reducer both layouts call (att6_reduce: y first, state
+// last).  r / k / v / g / decay-LoRA are handed over as handoff.hpp's cleared granules.
 #pragma once
 #include "mv_common.hpp"
 
 namespace rwkvmi {
-
-typedef __attribute__((address_space(1))) unsigned gunsigned_t;
 
 constexpr int AF_P = 8;   // workgroups per head
 constexpr int AF_R = 8;   // rows per wave (4 waves x 8 rows x 8 workgroups = 4 x 64 rows)
@@ -48,51 +46,6 @@ __device__ __forceinline__ float af_rows(const DMat & W, const ActBuf & x, int r
     for (int r = 0; r < R; r++) sr[r] = one ? wave_sum63(acc[r]) + wave_sum63(acc2[r]) : wave_sum63(acc[r]) + 0.0f;
     const float s = lane_row_sum<R>(sr, lane);
     return epi == EPI_SILU ? siluf_(s) : epi == EPI_TANH ? rk_tanhf(s) : s;
-}
-
-typedef __attribute__((address_space(1))) unsigned long long gu64_t;
-
-// One granule = {tag 1 (high word), value bits (low word)}, ONE aligned 8-byte sc1 store: the data is
-// its own flag (MI355X_MICROARCH.md hand-off R2, guide Guideline 16).  A consumer sweeps its
-// granules until every tag reads 1 and then clears them to 0 (sc1), so the next launch can never
-// see a stale value: a granule is only ever 0 (empty) or this launch's value.
-__device__ __forceinline__ void gran_put(unsigned long long * g, float v) {
-    __hip_atomic_store((gu64_t *)g, (1ull << 32) | (unsigned long long)__float_as_uint(v), __ATOMIC_RELAXED,
-                       __HIP_MEMORY_SCOPE_AGENT);
-}
-__device__ __forceinline__ void gran_put_tag(unsigned long long * g, float v, unsigned tag) {
-    __hip_atomic_store((gu64_t *)g, ((unsigned long long)tag << 32) | (unsigned long long)__float_as_uint(v),
-                       __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-__device__ __forceinline__ unsigned long long gran_get(const unsigned long long * g) {
-    return __hip_atomic_load((gu64_t *)g, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-__device__ __forceinline__ void gran_clear(unsigned long long * g) {
-    __hip_atomic_store((gu64_t *)g, 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
-// One wave sweeps N granules per lane (stride S) until every tag is set; bounded (timeout: *err, a
-// host-mapped word, stored at system scope so the host sees it after the stream synchronises).
-template <int N>
-__device__ __forceinline__ void gran_sweep(const unsigned long long * g, int stride, bool (&live)[N], float (&v)[N],
-                                           unsigned * err, unsigned spin_max) {
-    for (unsigned it = 0;; it++) {
-        bool ok = true;
-        unsigned long long x[N];
-#pragma unroll
-        for (int k = 0; k < N; k++) x[k] = live[k] ? gran_get(g + k * stride) : (1ull << 32);
-#pragma unroll
-        for (int k = 0; k < N; k++) {
-            v[k] = __uint_as_float((unsigned)x[k]);
-            ok = ok && (x[k] >> 32) == 1ull;
-        }
-        if (__all(ok)) return;
-        if (it >= spin_max) {
-            __hip_atomic_store((gunsigned_t *)err, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-            return;
-        }
-        __builtin_amdgcn_s_sleep(1);
-    }
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -242,7 +195,7 @@ __device__ __forceinline__ void att6_reduce(const Att6Fused & a, Att6Lds & L, co
             y = y * o.lnw_c;
             y = y + o.lnb_c;
             y = y * L.sg[lane];
-            if constexpr (WO) pub_q8(a.ygran, (c0 >> 5) + (lane >> 5), y, a.ytag, lane);  // the head's 2 blocks
+            if constexpr (WO) pub_q8(a.ygran, (c0 >> 5) + (lane >> 5), y, a.h.tag, lane);  // the head's 2 blocks
             else emit32(yq, 0, c0 + lane, y);
             STAMP_X(2);  // y published (the ordered layout's Wo workgroups stamp x2 / x3 too)
         }

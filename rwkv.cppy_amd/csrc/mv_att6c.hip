@@ -4,7 +4,7 @@
 //
 // Workgroup (h, s) = blockIdx h * 8 + s computes 32 of head h's 256 r / k / v / g rows (4 waves x 8
 // rows, k_mva's lane/unit order, wave_sum63 tree and epilogues) and, on a fifth wave, the
-// decay-LoRA rows of its slot, each published as a single-reader granule (mv_att6.hpp).  (h, 0) --
+// decay-LoRA rows of its slot, each published as a single-reader granule (handoff.hpp).  (h, 0) --
 // which loads the head's state, decay-tail weights and per-channel operands while its own rows
 // stream -- sweeps its head's granules and runs k_att6_dec's arithmetic (decay tail, wkv6,
 // GroupNorm, gate), publishing the head's 64 outputs y as two Q8 blocks of granules tagged (layer,
@@ -56,8 +56,8 @@ __global__ __launch_bounds__(320) void k_v6_att_co(Att6Fused a) {
     STAMP_BEGIN();
     // the reducer's late scalars (Wo input record, hand-off words, eps) in SGPRs now
     const ActBuf yq = at.yq;
-    unsigned * const err = a.err;
-    const unsigned spin_max = a.spin_max;
+    unsigned * const err = a.h.err;
+    const unsigned spin_max = a.h.spin_max;
     const float eps = at.eps;
     if (red) {
         pin_act(yq);
@@ -76,12 +76,12 @@ __global__ __launch_bounds__(320) void k_v6_att_co(Att6Fused a) {
         const DMat W = m == 0 ? a.W[0] : m == 1 ? a.W[1] : m == 2 ? a.W[2] : a.W[3];
         const ActBuf x = m == 0 ? a.x[0] : m == 1 ? a.x[1] : m == 2 ? a.x[2] : a.x[3];
         const float v = af_rows<WF, AF_R, U>(W, x, row0, m == 3 ? EPI_SILU : EPI_STORE, lane);
-        if (lane < AF_R && publish) gran_put(a.gran + (size_t)m * C + row0 + lane, v);
+        if (lane < AF_R && publish) gran_store(a.gran + (size_t)m * C + row0 + lane, GRAN_ONCE, v);
     } else {
         for (int d = af_slot(sidx, h, H); d < D; d += AF_P * H) {
             const float v = af_rows<WF, 1, U>(a.wd1, a.xw, d, EPI_TANH, lane);  // in lane 0
             const float v0 = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(v)));
-            if (lane < H && publish) gran_put(gdl + (size_t)lane * D + d, v0);  // one copy per head
+            if (lane < H && publish) gran_store(gdl + (size_t)lane * D + d, GRAN_ONCE, v0);  // one copy per head
         }
     }
     if (!red) {
@@ -98,19 +98,15 @@ __global__ __launch_bounds__(320) void k_v6_att_co(Att6Fused a) {
                 for (int j = 0; j < AF_WOR; j++) wo[j][u] = load_unit<WF>(a.wo, min(gw + nwo * j, C - 1), u, lane);
             xr = a.xres[min(gw + nwo * min(lane, AF_WOR - 1), C - 1)];
         }
-        // Wait for every head: wave 0 polls the d granule of every y block (mv_common.hpp
-        // gran_prepoll) -- the other waves park at the barrier, so the 7 H waiting workgroups add
+        // Wait for every head: wave 0 polls the d granule of every y block (handoff.hpp
+        // q8_prepoll) -- the other waves park at the barrier, so the 7 H waiting workgroups add
         // little traffic beside the reducers' own sweeps; then all five waves gather y's Q8 blocks
         // (pub_q8 in the reducers: the bits Wo's fp32-input prologue would produce) into LDS
         const ActBuf xq = lds_act(smem, act_fmt_for(WF), C);
         const int nb = C >> 5;
-        if (wave == 0) {
-            for (int b0 = 0; b0 < nb; b0 += 64)
-                gran_prepoll(a.ygran + (size_t)b0 * KG_STRIDE, min(64, nb - b0), KG_STRIDE, 8, a.ytag, err, spin_max,
-                             lane);
-        }
+        if (wave == 0) q8_prepoll(a.ygran, nb, a.h.tag, err, spin_max, lane);
         __syncthreads();
-        q8_gather_image<(U > 1 ? 4 : 2)>(a.ygran, nb, a.ytag, xq, tid, 320, err, spin_max);
+        q8_gather_image<(U > 1 ? 4 : 2)>(a.ygran, nb, a.h.tag, xq, tid, 320, err, spin_max);
         __syncthreads();
         q8_image_qsum(xq, nb, tid, 320);
         __syncthreads();

@@ -76,14 +76,12 @@ __global__ __launch_bounds__(320) void k_v6_att_fused(Att6Fused a) {
             const int nb = C >> 5;
             if (a.wo_prepoll) {
                 if (wave == 0) {
-                    for (int b0 = 0; b0 < nb; b0 += 64)
-                        gran_prepoll(a.ygran + (size_t)b0 * KG_STRIDE, min(64, nb - b0), KG_STRIDE, 8, a.ytag, a.err,
-                                     a.spin_max, lane);
+                    q8_prepoll(a.ygran, nb, a.h.tag, a.h.err, a.h.spin_max, lane);
                     STAMP_XN(2);
                 }
                 __syncthreads();
             }
-            q8_gather_image<(U > 1 ? 4 : 2)>(a.ygran, nb, a.ytag, xq, threadIdx.x, 320, a.err, a.spin_max);
+            q8_gather_image<(U > 1 ? 4 : 2)>(a.ygran, nb, a.h.tag, xq, threadIdx.x, 320, a.h.err, a.h.spin_max);
             __syncthreads();
             q8_image_qsum(xq, nb, threadIdx.x, 320);
             __syncthreads();
@@ -106,8 +104,8 @@ __global__ __launch_bounds__(320) void k_v6_att_fused(Att6Fused a) {
     STAMP_BEGIN();
     // the reducer's late scalars (Wo input record, hand-off words, eps) in SGPRs now
     const ActBuf yq = at.yq;
-    unsigned * const err = a.err;
-    const unsigned spin_max = a.spin_max;
+    unsigned * const err = a.h.err;
+    const unsigned spin_max = a.h.spin_max;
     const float eps = at.eps;
     if (red) {
         pin_act(yq);
@@ -126,12 +124,12 @@ __global__ __launch_bounds__(320) void k_v6_att_fused(Att6Fused a) {
         const DMat W = m == 0 ? a.W[0] : m == 1 ? a.W[1] : m == 2 ? a.W[2] : a.W[3];
         const ActBuf x = m == 0 ? a.x[0] : m == 1 ? a.x[1] : m == 2 ? a.x[2] : a.x[3];
         const float v = af_rows<WF, AF_R, U>(W, x, row0, m == 3 ? EPI_SILU : EPI_STORE, lane);
-        if (lane < AF_R && publish) gran_put(a.gran + (size_t)m * C + row0 + lane, v);
+        if (lane < AF_R && publish) gran_store(a.gran + (size_t)m * C + row0 + lane, GRAN_ONCE, v);
     } else {
         for (int d = wg; d < D; d += NP) {
             const float v = af_rows<WF, 1, U>(a.wd1, a.xw, d, EPI_TANH, lane);  // in lane 0
             const float v0 = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(v)));
-            if (lane < H && publish) gran_put(gdl + (size_t)lane * D + d, v0);  // one copy per head
+            if (lane < H && publish) gran_store(gdl + (size_t)lane * D + d, GRAN_ONCE, v0);  // one copy per head
         }
     }
     if (!red) {
@@ -160,7 +158,7 @@ bool v6_att_fused_supported(const Att6Fused & a) {
         if (a.wo.type != t || a.wo.M != a.C || a.wo.K != a.C || !a.xres || !a.ygran || a.C % 32) return false;
         if (a.wo_rows != 4 && a.wo_rows != 8) return false;
     }
-    return a.H <= 64 && a.err;  // one decay-value copy per head: a lane per head
+    return a.H <= 64 && a.h.err;  // one decay-value copy per head: a lane per head
 }
 
 template <int WF, int U, int WO>

@@ -4,6 +4,7 @@
 #pragma once
 #include "device_common.hpp"
 #include "kernels.hpp"
+#include "handoff.hpp"
 
 #include <limits.h>
 #include <stdio.h>
@@ -313,16 +314,11 @@ __device__ __forceinline__ void chunk_store(const MVEntry & E, const ActBuf & a,
 }
 
 // Hand-off of a C-vector inside a fused decode launch (the head / channel outputs y feeding the
-// Wo rows): every element is a granule {tag (high word), value bits (low word)} written by ONE
-// aligned 8-byte agent-scope store, so the data is its own flag.  The gathering waves of a
-// workgroup (wave, wave + nwaves, ... over 512-element chunks; 8 consecutive granules per lane, so
-// a quad holds one quantization block) re-read their chunk, sleeping between passes, until every
-// tag reads `tag`, then write it into the LDS image in WF's activation format with the matvec
-// prologue's SRC_F32 arithmetic (chunk_store): Wo's input bits equal a separate Wo launch's.  The
-// poll IS the gather -- one round trip after the last value lands, not a flag poll and then a
-// gather.  Bounded: after spin_max passes *err (a host-mapped word) is set at system scope.
-typedef __attribute__((address_space(1))) unsigned long long gran_u64_t;
-typedef __attribute__((address_space(1))) unsigned gran_u32_t;
+// Wo rows; the protocol: handoff.hpp): the gathering waves of a workgroup (wave, wave + nwaves, ...
+// over 512-element chunks; 8 consecutive granules per lane, so a quad holds one quantization block)
+// re-read their chunk until every tag reads `tag`, then write it into the LDS image in WF's
+// activation format with the matvec prologue's SRC_F32 arithmetic (chunk_store): Wo's input bits
+// equal a separate Wo launch's.
 template <int WF>
 __device__ __forceinline__ void gran_gather_image(const unsigned long long * yg, unsigned tag, int C, const ActBuf & img,
                                                   int wave, int nwaves, unsigned * err, unsigned spin_max, int lane) {
@@ -332,85 +328,11 @@ __device__ __forceinline__ void gran_gather_image(const unsigned long long * yg,
         const bool valid = k0 < C;
         const unsigned long long * g = yg + max(min(k0, C - 8), 0);
         ChunkIn ci;
-        for (unsigned it = 0;; it++) {
-            unsigned long long x[8];
-#pragma unroll
-            for (int j = 0; j < 8; j++)
-                x[j] = __hip_atomic_load((gran_u64_t *)(g + j), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            bool ok = true;
-#pragma unroll
-            for (int j = 0; j < 8; j++) {
-                ci.x[j] = __uint_as_float((unsigned)x[j]);
-                ok = ok && (unsigned)(x[j] >> 32) == tag;
-            }
-            if (__all(ok || !valid)) break;
-            if (it >= spin_max) {
-                __hip_atomic_store((gran_u32_t *)err, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-                break;
-            }
-            __builtin_amdgcn_s_sleep(2);
-        }
+        gran_wait<2>(spin_max, err, [&] { return gran_read(g, tag, ci.x) || !valid; });
         chunk_store<WF, MVK_F32, 0>(none, img, ci, 0.0f, 1.0f, false, k0, valid, lane);
     }
 }
 
-// Wait before a gather: ONE wave polls n granules (lane i: yg[off + i * stride], n <= 64) with a
-// sleep between passes until every tag reads `tag` -- a few hundred bytes per pass instead of the
-// gather's whole vector, so a waiting workgroup adds little traffic beside the producers' weight
-// streams (the gather after it checks every tag again).  Bounded like the gather.  (Several passes
-// in flight at once -- a rolling poll -- measured far slower: v6-1B6 750 vs 693 us/token.)
-__device__ __forceinline__ void gran_prepoll(const unsigned long long * yg, int n, int stride, int off, unsigned tag,
-                                             unsigned * err, unsigned spin_max, int lane) {
-    for (unsigned it = 0;; it++) {
-        const unsigned long long x = lane < n ? __hip_atomic_load((gran_u64_t *)(yg + off + (size_t)lane * stride),
-                                                                  __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)
-                                              : ((unsigned long long)tag << 32);
-        if (__all((unsigned)(x >> 32) == tag)) return;
-        if (it >= spin_max) {
-            __hip_atomic_store((gran_u32_t *)err, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-            return;
-        }
-        __builtin_amdgcn_s_sleep(4);
-    }
-}
-
-// Q8 blocks published by pub_q8 (KG_STRIDE granules per 32-element block, nb blocks) -> the LDS
-// activation image: thread tid of nthr reads granules tid + nthr i (i < GI), re-reading until every
-// tag it holds reads `tag` (bounded like the gather above), then writes the q dwords, d and Q8_1's
-// s.  The caller recomputes the qsums (q8_image_qsum) after a barrier.
-template <int GI>
-__device__ __forceinline__ void q8_gather_image(const unsigned long long * kg, int nb, unsigned tag, const ActBuf & img,
-                                                int tid, int nthr, unsigned * err, unsigned spin_max) {
-    const int ng = KG_STRIDE * nb;
-    unsigned pay[GI];
-    for (unsigned it = 0;; it++) {
-        bool ok = true;
-#pragma unroll
-        for (int i = 0; i < GI; i++) {
-            const int g = tid + nthr * i;
-            unsigned long long x = (unsigned long long)tag << 32;
-            if (g < ng) x = __hip_atomic_load((gran_u64_t *)(kg + g), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            pay[i] = (unsigned)x;
-            ok = ok && (unsigned)(x >> 32) == tag;
-        }
-        if (__all(ok)) break;
-        if (it >= spin_max) {
-            __hip_atomic_store((gran_u32_t *)err, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-            break;
-        }
-        __builtin_amdgcn_s_sleep(2);
-    }
-#pragma unroll
-    for (int i = 0; i < GI; i++) {
-        const int g = tid + nthr * i;
-        if (g < ng) {
-            const int b = g / KG_STRIDE, j = g - b * KG_STRIDE;
-            if (j < 8) *(unsigned *)(img.q + (size_t)b * 32 + 4 * j) = pay[i];
-            else if (j == 8) img.d[b] = __uint_as_float(pay[i]);
-            else if (img.fmt == A_Q8_1) img.s[b] = __uint_as_float(pay[i]);
-        }
-    }
-}
 // the exact integer block sums of a gathered Q8 image (store32's qsum)
 __device__ __forceinline__ void q8_image_qsum(const ActBuf & img, int nb, int tid, int nthr) {
     for (int b = tid; b < nb; b += nthr) {
@@ -792,15 +714,11 @@ __device__ __forceinline__ void pub_q8(unsigned long long * kg, int b, float v, 
     unsigned p = ((unsigned)q.q & 0xffu) << (8 * (lane & 3));
     p |= (unsigned)__shfl_xor((int)p, 1);
     p |= (unsigned)__shfl_xor((int)p, 2);
-    const unsigned long long t = (unsigned long long)tag << 32;
     unsigned long long * const g = kg + (size_t)b * KG_STRIDE;
-    if ((lane & 3) == 0)
-        __hip_atomic_store((gran_u64_t *)(g + ((lane & 31) >> 2)), t | p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if ((lane & 3) == 0) gran_store(g + ((lane & 31) >> 2), tag, p);
     if ((lane & 31) == 0) {
-        __hip_atomic_store((gran_u64_t *)(g + 8), t | __float_as_uint(f16_round(q.d)), __ATOMIC_RELAXED,
-                           __HIP_MEMORY_SCOPE_AGENT);
-        __hip_atomic_store((gran_u64_t *)(g + 9), t | __float_as_uint(f16_round(q.d * (float)q.sum)), __ATOMIC_RELAXED,
-                           __HIP_MEMORY_SCOPE_AGENT);
+        gran_store(g + 8, tag, f16_round(q.d));
+        gran_store(g + 9, tag, f16_round(q.d * (float)q.sum));
     }
 }
 
@@ -952,10 +870,7 @@ __device__ __forceinline__ void mv_body_split(const MVEntry & Ent, int wgi, int 
                     if (row < M) {
                         vv = epi_apply(epi, red[tid], ep);
                         if constexpr (PUB) {
-                            if (!emit_on)
-                                __hip_atomic_store((gran_u64_t *)(pub->rg + row),
-                                                   ((unsigned long long)pub->tag << 32) | __float_as_uint(vv),
-                                                   __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                            if (!emit_on) gran_store(pub->rg + row, pub->tag, vv);
                         } else if (ey) {
                             ey[row] = vv;
                         }

@@ -16,7 +16,7 @@ extern int kQgCUs;
 bool ffn_fused_supported(const FfnFused & f, int form, bool hasr) {
     const MVEntry & k = f.e[0];
     const int t = k.W.type, C = k.W.K, F = k.W.M;
-    if (!wtype_quantized(t) || !f.kg || !f.x || !f.err || (hasr && !f.rg)) return false;
+    if (!wtype_quantized(t) || !f.kg || !f.x || !f.h.err || (hasr && !f.rg)) return false;
     if (!(form == 0 && hasr) && !(form == 1)) return false;
     if (k.src != SRC_LNMIX || k.form != form || !k.emit || k.act_out.fmt != act_fmt_for(t) || k.act_out.tiled) return false;
     if (C % 64 || C > 4096 || F % 32 || F / 32 > 512) return false;

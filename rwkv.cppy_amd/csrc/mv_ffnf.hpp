@@ -43,7 +43,7 @@ __global__ __launch_bounds__(512) void k_ffn_fused(FfnFused f) {
         const int e = (HASR && bx >= f.e[1].block0) ? 1 : 0;
         const MVEntry & Ent = f.e[e];
         const int b0 = e ? f.e[1].block0 : 0;
-        const GranPub pub{f.kg, f.rg, f.tag};
+        const GranPub pub{f.kg, f.rg, f.h.tag};
         STAMP_BEGIN();
         mv_body_split<WF, 4, 1, MVK_LN, FORM, true, 4, LNP, true>(Ent, bx - b0, b0, 0, smem, red, 0, &pub);
         if constexpr (!CO) {
@@ -54,9 +54,9 @@ __global__ __launch_bounds__(512) void k_ffn_fused(FfnFused f) {
     STAMP_BEGIN();
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int C = f.wv.M, F = f.wv.K, nb = F >> 5;
-    const unsigned tag = f.tag;
-    unsigned * const err = f.err;
-    const unsigned spin_max = f.spin_max;
+    const unsigned tag = f.h.tag;
+    unsigned * const err = f.h.err;
+    const unsigned spin_max = f.h.spin_max;
     const int row0 = ((CO ? bx : bx - f.np) * 8 + wave) * RC;
     // ---- this wave's value rows (all their units) and residual rows, in flight at once -- after
     // wdelay ticks of the 100 MHz clock, so they do not share the memory system with the
@@ -75,61 +75,22 @@ __global__ __launch_bounds__(512) void k_ffn_fused(FfnFused f) {
     const ActBuf img = lds_act(smem, act_fmt_for(WF), F);
     // ---- wait: wave 0 polls the d granule of every key block (64 blocks per rolling poll)
     if (wave == 0 && f.prepoll) {
-        for (int b0 = 0; b0 < nb; b0 += 64)
-            gran_prepoll(f.kg + (size_t)b0 * KG_STRIDE, min(64, nb - b0), KG_STRIDE, 8, tag, err, spin_max, lane);
+        q8_prepoll(f.kg, nb, tag, err, spin_max, lane);
         STAMP_XN(0);
     }
     __syncthreads();
     // ---- gather: granule g = tid + 512 i (g < KG_STRIDE nb); each wave re-reads its granules until
     // every tag matches (and lanes r < FF_RC their rows' receptance)
     constexpr int GI = (KG_STRIDE * 64 * UV + 511) / 512;  // granules per thread (nb <= 64 UV)
-    const int ng = KG_STRIDE * nb;
     unsigned pay[GI];
-    float rr = 0.0f;
-    for (unsigned it = 0;; it++) {
-        unsigned long long x[GI];
-#pragma unroll
-        for (int i = 0; i < GI; i++) {
-            const int g = tid + 512 * i;
-            x[i] = (unsigned long long)tag << 32;
-            if (g < ng) x[i] = __hip_atomic_load((gran_u64_t *)(f.kg + g), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        }
-        unsigned long long xr8 = (unsigned long long)tag << 32;
-        if (HASR) xr8 = __hip_atomic_load((gran_u64_t *)(f.rg + myrow), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        bool ok = (unsigned)(xr8 >> 32) == tag;
-#pragma unroll
-        for (int i = 0; i < GI; i++) {
-            pay[i] = (unsigned)x[i];
-            ok = ok && (unsigned)(x[i] >> 32) == tag;
-        }
-        rr = __uint_as_float((unsigned)xr8);
-        if (__all(ok)) break;
-        if (it >= spin_max) {
-            __hip_atomic_store((gran_u32_t *)err, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-            break;
-        }
-        __builtin_amdgcn_s_sleep(2);
-    }
+    unsigned long long xr8 = 0;
+    q8_gather<GI>(f.kg, nb, tag, pay, tid, 512, err, spin_max,
+                  [&] { return xr8 = HASR ? gran_load(f.rg + myrow) : gran_pack(tag, 0); });
+    const float rr = gran_float(xr8);
     if (wave == 0) STAMP_XN(1);
-#pragma unroll
-    for (int i = 0; i < GI; i++) {
-        const int g = tid + 512 * i;
-        if (g < ng) {
-            const int b = g / KG_STRIDE, j = g - b * KG_STRIDE;
-            if (j < 8) *(unsigned *)(img.q + (size_t)b * 32 + 4 * j) = pay[i];
-            else if (j == 8) img.d[b] = __uint_as_float(pay[i]);
-            else if (img.fmt == A_Q8_1) img.s[b] = __uint_as_float(pay[i]);
-        }
-    }
+    q8_scatter<GI>(img, nb, pay, tid, 512);
     __syncthreads();
-    for (int b = tid; b < nb; b += 512) {
-        const int4 lo = *(const int4 *)(img.q + (size_t)b * 32), hi = *(const int4 *)(img.q + (size_t)b * 32 + 16);
-        const int ws[8] = {lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
-        int s = 0;
-#pragma unroll
-        for (int k = 0; k < 8; k++) s = __builtin_amdgcn_sdot4(ws[k], 0x01010101, s, false);
-        img.qsum[b] = s;
-    }
+    q8_image_qsum(img, nb, tid, 512);
     __syncthreads();
     STAMP_MID();
     // ---- the value rows: k_mva's arithmetic; EPI_SIGMUL_ADD (aux = the receptance row) / EPI_ADD

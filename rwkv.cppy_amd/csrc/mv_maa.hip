@@ -179,7 +179,7 @@ __global__ __launch_bounds__(512) void k_v6_maa_dec4(MaaDec a) {
     __shared__ double ln_part[16];
     STAMP_BEGIN();
     maa_dec4_body<WF, U, LNP, CPW, false, EMB>(a, (int)blockIdx.x, (int)blockIdx.y, smem, s_lora, ln_part, nullptr,
-                                               0u, nullptr, 0u);
+                                               Handoff{});
     STAMP_END_NS(4 + 16 * blockIdx.y);
 }
 

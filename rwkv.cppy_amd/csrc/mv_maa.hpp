@@ -10,8 +10,8 @@
 // columns at once, dot the rows after the image barrier (k_mv's lane/unit order and wave_sum63
 // tree: the lora values are bit-identical), and wave 0 mixes CPW = 64 channels.
 //
-// XG: the residual stream x is read from granules {tag, value} (xg, tag xtag) written in the same
-// launch, each re-read until its tag matches (bounded: *err), instead of from a.x.
+// XG: the residual stream x is read from tagged granules (xg, tag h.tag; handoff.hpp) written in the
+// same launch, each re-read until its tag matches, instead of from a.x.
 // EMB (layer 0): x = LN0(emb[*a.tok]) -- k_embed_ln's loads, chunk sums in chunk order and ln_apply,
 // so the same bits -- exchanged through one more barrier; workgroup (0, 0) stores it to a.xout.
 #pragma once
@@ -21,8 +21,7 @@ namespace rwkvmi {
 
 template <int WF, int U, int LNP, int CPW, bool XG, bool EMB = false>
 __device__ __forceinline__ void maa_dec4_body(const MaaDec & a, int bx, int n, char * smem, float * s_lora,
-                                              double * ln_part, const unsigned long long * xg, unsigned xtag,
-                                              unsigned * err, unsigned spin_max) {
+                                              double * ln_part, const unsigned long long * xg, const Handoff & h) {
     constexpr int R = 8, DM = 32;
     const int C = a.C, D = a.D, K = C;
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -97,35 +96,15 @@ __device__ __forceinline__ void maa_dec4_body(const MaaDec & a, int bx, int n, c
             for (int q = 0; q < LCW; q++)
                 if (pw + 4 * q < nch) {
                     const unsigned long long * g0 = xg + (pw + 4 * q) * LN_CHUNK;
-                    for (unsigned it = 0; it < spin_max; it++) {
-                        const unsigned long long v = __hip_atomic_load((gran_u64_t *)g0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                        if ((unsigned)(v >> 32) == xtag) break;
-                        __builtin_amdgcn_s_sleep(2);
-                    }
+                    // no error store of its own: the gather below reports the timeout
+                    gran_wait_quiet<2>(h.spin_max, [&] { return gran_tag(gran_load(g0)) == h.tag; });
                 }
             // this lane's 8 elements of x from their granules (the plain loads above read the
             // previous values of x: replaced)
 #pragma unroll
             for (int q = 0; q < LCW; q++) {
                 const unsigned long long * g = xg + min(kc[q], K - 8);
-                for (unsigned it = 0;; it++) {
-                    unsigned long long v[8];
-#pragma unroll
-                    for (int j = 0; j < 8; j++)
-                        v[j] = __hip_atomic_load((gran_u64_t *)(g + j), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    bool ok = true;
-#pragma unroll
-                    for (int j = 0; j < 8; j++) {
-                        ci[q].x[j] = __uint_as_float((unsigned)v[j]);
-                        ok = ok && (unsigned)(v[j] >> 32) == xtag;
-                    }
-                    if (__all(ok || pw + 4 * q >= nch)) break;
-                    if (it >= spin_max) {
-                        __hip_atomic_store((gran_u32_t *)err, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-                        break;
-                    }
-                    __builtin_amdgcn_s_sleep(2);
-                }
+                gran_wait<2>(h.spin_max, h.err, [&] { return gran_read(g, h.tag, ci[q].x) || pw + 4 * q >= nch; });
             }
         }
         // LayerNorm statistics (chunk association, one pass); the chunk sums meet in LDS

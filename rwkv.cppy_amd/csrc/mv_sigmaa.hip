@@ -5,8 +5,8 @@
 // Before: k_mvsig (x += sigmoid(Wr . xr) * (Wv . k)), a kernel boundary, then the next layer's maa
 // launch re-reads x for its LayerNorm.  Here workgroup b (512 threads, one row per wave) computes
 // rows 8 b .. 8 b + 7 of x exactly as k_mvsig does (k_mva's lane/unit order and wave_sum63 tree per
-// product, EPI_SIGMUL_ADD), stores them and publishes each as a granule {tag, value} (one 8-byte
-// agent-scope store); workgroups [0, 5 C / 64) then run the maa workgroup (mv_maa.hpp) with x
+// product, EPI_SIGMUL_ADD), stores them and publishes each as a tagged granule (handoff.hpp);
+// workgroups [0, 5 C / 64) then run the maa workgroup (mv_maa.hpp) with x
 // gathered from those granules -- its W1 rows and W2 columns stream while the last rows of x arrive.
 // The bits equal the k_mvsig + k_v6_maa_dec4 pair.  The maa workgroups wait on workgroups of every
 // index, so all C / 8 must be resident at once (<= the compute units, one per CU; checked by
@@ -83,22 +83,20 @@ __global__ __launch_bounds__(512) void k_sig_maa(SigMaa a) {
     const float v = yv + sigmoidf_(rr) * vv;  // EPI_SIGMUL_ADD, aux = the receptance row
     if (lane == 0 && bx * 8 + wave < M) {
         hv.y[bx * 8 + wave] = v;
-        __hip_atomic_store((gran_u64_t *)(a.xg + bx * 8 + wave), ((unsigned long long)a.xtag << 32) | __float_as_uint(v),
-                           __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        gran_store(a.xg + bx * 8 + wave, a.h.tag, v);
     }
     STAMP_MID();
     // ---- the next layer's maa workgroup (cx, n), x from the granules
     if (bx < a.nm) {
         const int nx = a.maa.C >> 6, n = bx / nx;
-        maa_dec4_body<WF, U2, LNP, 64, true>(a.maa, bx - n * nx, n, smem, s_lora, ln_part, a.xg, a.xtag, a.err,
-                                             a.spin_max);
+        maa_dec4_body<WF, U2, LNP, 64, true>(a.maa, bx - n * nx, n, smem, s_lora, ln_part, a.xg, a.h);
     }
     STAMP_END_NS(10);
 }
 
 bool sig_maa_supported(const SigMaa & a) {
     const int t = a.hv.qs ? a.wtype : -1;
-    if (!wtype_quantized(t) || a.maa.w1.type != t || !a.xg || !a.err) return false;
+    if (!wtype_quantized(t) || a.maa.w1.type != t || !a.xg || !a.h.err) return false;
     const int C = a.hv.M;
     if (C != a.maa.C || a.hr.M != C || a.hr.K != C || C % 64 || C > 4096 || a.hv.K % 32) return false;
     if (mv_units(t, a.hv.K) > 8 || mv_units(t, C) > 2) return false;
