@@ -92,6 +92,22 @@ RWKV_API bool rwkv_mi355x_sample(struct rwkv_context * ctx, const struct rwkv_mi
 RWKV_API bool rwkv_mi355x_generate(struct rwkv_context * ctx, const struct rwkv_mi355x_sampling * params, size_t n,
                                    uint32_t * tokens_out, float * logits_out);
 
+/* Scoring: rwkv_mi355x_eval_device over T >= 1 tokens with the head on EVERY token.  Position t's
+ * logits row (the logits serial rwkv_eval of tokens[0..t] gives, bit for bit) is reduced on the device
+ * to losses_out[t] = -log softmax(row t)[targets[t]] (the exponentials and their sum in fp64) and
+ * argmax_out[t] = the lowest index holding the row's maximum; only those cross PCIe, plus the rows
+ * themselves when logits_out != NULL.  targets [T] and losses_out [T] are both NULL or both set (else
+ * RWKV_ERROR_ARGS), every target must be < n_vocab (else RWKV_ERROR_ARGS, checked with the tokens
+ * before anything is enqueued: the state is untouched); argmax_out [T] and logits_out [T][n_vocab]
+ * (host) may each be NULL.  Synchronous.  On return the device state has consumed all T tokens and
+ * the device logits are those of the last one, as after rwkv_mi355x_eval_device(compute_logits =
+ * true), so rwkv_mi355x_sample / _generate or another score call continue from there.  A pipeline
+ * context or a stage context without the head fails with RWKV_ERROR_CTX | RWKV_ERROR_UNSUPPORTED; an
+ * in-launch hand-off timeout in a one-token chunk fails the call with RWKV_ERROR_CTX. */
+RWKV_API bool rwkv_mi355x_score_sequence(struct rwkv_context * ctx, const uint32_t * tokens, size_t T,
+                                         const uint32_t * targets, double * losses_out,
+                                         uint32_t * argmax_out, float * logits_out);
+
 /* Debugging aid: copies `bytes` of the named workspace buffer of the last evaluation to host `out`
  * (names: x xa sx r k v g w y a nb bb vfirst fr lora bonus logits, slot<i>.<q|d|s|qsum|h|f>).
  * Returns the bytes copied, or -1 (unknown name / copy failure).  Not part of rwkv.h. */
@@ -253,6 +269,10 @@ RWKV_API bool rwkv_mi355x_selftest_wkv7(int T, int H, int chunked, const float *
 RWKV_API bool rwkv_mi355x_selftest_sample(const float * logits, int rows, int V,
                                           const struct rwkv_mi355x_sampling * params, const float * u,
                                           uint32_t * tokens, uint32_t * kept, float * cutoff);
+
+/* k_xent on host operands (tests): logits [rows][V], targets [rows]; losses / argmax may be NULL */
+RWKV_API bool rwkv_mi355x_selftest_xent(const float * logits, int rows, int V, const uint32_t * targets,
+                                        double * losses, uint32_t * argmax);
 
 #if defined(__cplusplus)
 }

@@ -165,8 +165,9 @@ bool upload_mat(DeviceModel & dm, const HostTensor * t, DMat & out, bool count_b
             if (!ds || hipMemcpy(ds, sc16.data(), sc16.size() * 2, hipMemcpyHostToDevice) != hipSuccess) return false;
             out.sc = ds;
         }
-        // the same blocks again as sequence-GEMM tile records (common.hpp qg_*); the head only
-        // ever runs on one token
+        // the same blocks again as sequence-GEMM tile records (common.hpp qg_*); the head never
+        // takes that GEMM: it runs on one token, or over rows through the batched decode's forms
+        // (eval_batch, score_chunk)
         if (!is_head) {
             const int wt = (int)t->type, R = qg_rows(wt);
             const size_t tiles = (M + R - 1) / R, rb = qg_w_bytes(wt);
@@ -378,6 +379,8 @@ Engine::~Engine() {
     if (gen_tokens_) (void)hipFree(gen_tokens_);
     if (bias_ids_) (void)hipFree(bias_ids_);
     if (bias_vals_) (void)hipFree(bias_vals_);
+    for (void * p : {(void *)score_tile_, (void *)score_targets_, (void *)score_loss_, (void *)score_argmax_})
+        if (p) (void)hipFree(p);
     for (void * p : ws_allocs_) (void)hipFree(p);
     if (htokens_) (void)hipHostFree(htokens_);
     if (herr_h_) (void)hipHostFree(herr_h_);
@@ -1143,18 +1146,23 @@ bool Engine::forward_range(int T, const float * sin, float * sout, uint32_t l0, 
             return false;
         }
     }
-    tile_acts_ = false;  // the head runs on the last token only (batched decode: on every context)
+    // the head runs on the last token only (batched decode: on every context; scoring runs it over
+    // every token afterwards, score_chunk)
+    tile_acts_ = false;
     if (logits && l1 == m_->n_layer) {
-        // rwkv_graph.inc:704-708 / :850-854
         const int rows = bs_ ? T : 1;
-        ActBuf hin = A(0, m_->head);
-        if (!launch_ln_emit(stream_, (int)C, x_ + (size_t)(T - rows) * C, m_->lnout_w, m_->lnout_b, hin, rows))
-            return false;
-        MMBatch b;
-        b.add(m_->head, hin, head_out_ ? head_out_ : logits_, (int)m_->n_vocab, EPI_STORE);
-        if (!b.run(*this, rows)) return false;
+        return head_rows(x_ + (size_t)(T - rows) * C, rows, head_out_ ? head_out_ : logits_);
     }
     return true;
+}
+
+// rwkv_graph.inc:704-708 / :850-854
+bool Engine::head_rows(const float * x, int rows, float * out) {
+    ActBuf hin = A(0, m_->head);
+    if (!launch_ln_emit(stream_, (int)m_->n_embed, x, m_->lnout_w, m_->lnout_b, hin, rows)) return false;
+    MMBatch b;
+    b.add(m_->head, hin, out, (int)m_->n_vocab, EPI_STORE);
+    return b.run(*this, rows);
 }
 
 // KLaunchTimer (common.hpp): while a decode step is timed, every RK_LAUNCH takes an event pair
@@ -1245,7 +1253,9 @@ bool Engine::run_tokens_impl(const uint32_t * tokens, size_t T, bool want_logits
             HIP_OK(hipMemcpyAsync(dtokens_, htokens_, n * 4, hipMemcpyHostToDevice, stream_));
             HIP_OK(hipEventRecord(tok_event_, stream_));
         }
-        const bool lg = last && want_logits;
+        // scoring: a one-token chunk's step writes logits_ (score_chunk reads it), longer chunks get
+        // their head from score_chunk
+        const bool lg = score_ ? n == 1 : last && want_logits;
         last_decode_ = n == 1 && !generic_decode_;
         const bool co = last_decode_ ? choose_co() : (co_ = false);
         if (timing_) {
@@ -1263,6 +1273,7 @@ bool Engine::run_tokens_impl(const uint32_t * tokens, size_t T, bool want_logits
         } else {
             if (!forward((int)n, dstate_[cur_], dstate_[cur_ ^ 1], lg)) return false;
         }
+        if (score_ && !score_chunk(done, n, last)) return false;
         // a step without the fused decode flips the parity (GranuleMem::clear_tagged)
         if (n > 1 || generic_decode_) HIP_OK(gran_.clear_tagged(stream_));
         // tokens buffer is reused by the next chunk: wait before overwriting the pinned copy
@@ -1841,6 +1852,89 @@ bool Engine::generate(const SamplingParams & p, size_t n, uint32_t * tokens_out,
         logits_valid_ = false;
     }
     return ok;
+}
+
+// ---------------------------------------------------------------- scoring
+// The scorer's device buffers, allocated or grown before anything is enqueued: T targets, losses
+// and argmaxes, and (T > 1: some chunk has more than one token) the head tile.
+bool Engine::score_buffers(size_t T) {
+    if (T > score_cap_) {
+        HIP_OK(hipStreamSynchronize(stream_));
+        for (void * p : {(void *)score_targets_, (void *)score_loss_, (void *)score_argmax_})
+            if (p) (void)hipFree(p);
+        score_targets_ = score_argmax_ = nullptr;
+        score_loss_ = nullptr;
+        score_cap_ = 0;
+        size_t cap = 1024;
+        while (cap < T) cap *= 2;
+        const bool ok = hipMalloc(&score_targets_, cap * 4) == hipSuccess && hipMalloc(&score_loss_, cap * 8) == hipSuccess &&
+                        hipMalloc(&score_argmax_, cap * 4) == hipSuccess;
+        if (!ok) {
+            (void)hipGetLastError();
+            fprintf(stderr, "rwkv: scoring buffers for %zu tokens failed\n", cap);
+            return false;  // score_cap_ stays 0: the next call frees what was allocated and retries
+        }
+        score_cap_ = cap;
+    }
+    if (T > 1 && !score_tile_ && hipMalloc(&score_tile_, (size_t)kScoreRows * m_->n_vocab * 4 + 64) != hipSuccess) {
+        score_tile_ = nullptr;
+        (void)hipGetLastError();
+        fprintf(stderr, "rwkv: head tile of %d rows failed to allocate\n", kScoreRows);
+        return false;
+    }
+    return true;
+}
+
+// After the layers of tokens [done, done + n) of a score() call: x_ holds their n final residual
+// rows (n > 1), or the decode program's head has written logits_ (n == 1).
+bool Engine::score_chunk(size_t done, size_t n, bool last) {
+    const size_t C = m_->n_embed, V = m_->n_vocab;
+    const bool want_loss = score_->targets != nullptr;
+    if (want_loss)
+        HIP_OK(hipMemcpyAsync(score_targets_ + done, score_->targets + done, n * 4, hipMemcpyHostToDevice, stream_));
+    auto reduce = [&](const float * lg, size_t row0, int rows) {
+        const size_t at = done + row0;
+        if (!launch_xent(stream_, lg, rows, (int)V, want_loss ? score_targets_ + at : nullptr,
+                         want_loss ? score_loss_ + at : nullptr, score_argmax_ + at))
+            return false;
+        if (score_->logits_out) {
+            // the next tile (or step) overwrites lg: the copy has landed before it is enqueued
+            HIP_OK(hipMemcpyAsync(score_->logits_out + at * V, lg, (size_t)rows * V * 4, hipMemcpyDeviceToHost, stream_));
+            HIP_OK(hipStreamSynchronize(stream_));
+        }
+        return true;
+    };
+    if (n == 1) return reduce(logits_, 0, 1);
+    for (size_t row0 = 0; row0 < n; row0 += (size_t)kScoreRows) {
+        const int rows = (int)std::min(n - row0, (size_t)kScoreRows);
+        // the head over `rows` rows as batched decode runs it over that many contexts (mm_dispatch:
+        // k_fmm, k_mvb or k_mm, each row the bits of its one-token head); never the sequence GEMM,
+        // for which the head has no tile records (upload_mat)
+        bs_ = m_->state_len;
+        const bool ok = head_rows(x_ + row0 * C, rows, score_tile_);
+        bs_ = 0;
+        if (!ok || !reduce(score_tile_, row0, rows)) return false;
+        if (last && row0 + rows == n)
+            HIP_OK(hipMemcpyAsync(logits_, score_tile_ + (size_t)(rows - 1) * V, V * 4, hipMemcpyDeviceToDevice, stream_));
+    }
+    return true;
+}
+
+bool Engine::score(const uint32_t * tokens, size_t T, const uint32_t * targets, double * losses_out,
+                   uint32_t * argmax_out, float * logits_out) {
+    HIP_OK(hipSetDevice(m_->device));
+    if (!tokens || T == 0 || (targets != nullptr) != (losses_out != nullptr) || !score_buffers(T)) return false;
+    ScoreRun run{targets, logits_out};
+    co_retry_ = false;
+    score_ = &run;
+    const bool ok = run_tokens(tokens, T, true);
+    score_ = nullptr;
+    if (!ok) return false;
+    if (losses_out) HIP_OK(hipMemcpyAsync(losses_out, score_loss_, T * 8, hipMemcpyDeviceToHost, stream_));
+    if (argmax_out) HIP_OK(hipMemcpyAsync(argmax_out, score_argmax_, T * 4, hipMemcpyDeviceToHost, stream_));
+    HIP_OK(hipStreamSynchronize(stream_));
+    // a hand-off timeout in a one-token chunk: nothing is re-run (the state has moved on)
+    return handoff_check();
 }
 
 }  // namespace rwkvmi

@@ -146,6 +146,14 @@ class Engine : public KLaunchTimer {
     // Both need logits_valid().
     bool sample(const SamplingParams & p, uint32_t * token_out);
     bool generate(const SamplingParams & p, size_t n, uint32_t * tokens_out, float * logits_out);
+    // Scoring (rwkv_mi355x_score_sequence): eval_device(tokens, T, want_logits = true, sync = true)
+    // with the head on every token.  Each chunk's final residual rows go through the head in tiles
+    // of kScoreRows rows (LayerNorm, the batched decode's head matmul, k_xent); losses and argmaxes
+    // stay in device buffers until one copy at the end, logits_out (host [T][n_vocab], may be NULL)
+    // receives each tile.  targets / losses_out: both NULL or both set; argmax_out may be NULL.
+    bool score(const uint32_t * tokens, size_t T, const uint32_t * targets, double * losses_out, uint32_t * argmax_out,
+               float * logits_out);
+    static constexpr int kScoreRows = 128;  // a multiple of 64 (k_fmm's token tile); <= kBatchMax (k_mvb)
     // the device logits follow the device state: set by an evaluation that ran the head, cleared by
     // one that did not and by every state upload
     bool logits_valid() const { return logits_valid_; }
@@ -208,6 +216,21 @@ class Engine : public KLaunchTimer {
     bool run_tokens(const uint32_t * tokens, size_t T, bool want_logits);
     bool run_tokens_impl(const uint32_t * tokens, size_t T, bool want_logits);
     bool sampler_buffers(const SamplingParams & p, size_t n, SampleArgs & a);
+    // final LayerNorm + head over `rows` residual rows at x into out [rows][n_vocab]
+    bool head_rows(const float * x, int rows, float * out);
+    // score(): what run_tokens_impl does after the layers of each chunk while score_ is set
+    struct ScoreRun {
+        const uint32_t * targets;
+        float * logits_out;
+    };
+    bool score_buffers(size_t T);
+    bool score_chunk(size_t done, size_t n, bool last);
+    ScoreRun * score_ = nullptr;
+    float * score_tile_ = nullptr;      // [kScoreRows][n_vocab] head tile (lazily allocated)
+    uint32_t * score_targets_ = nullptr;  // [score_cap_]
+    double * score_loss_ = nullptr;
+    uint32_t * score_argmax_ = nullptr;
+    size_t score_cap_ = 0;
     bool layer_v4(int l, int T, const float * si, float * so);
     bool wkv6(int T, int H, int S, const float * u, const float * w, int wpt, const float * sin, float * sout);
     bool layer_v5(int l, int T, const float * si, float * so);

@@ -204,6 +204,12 @@ struct SampleArgs {
 // One workgroup per row: bias, greedy or top-p / temperature sampling (rwkv_mi355x.h).
 bool launch_sample(hipStream_t st, const SampleArgs & a);
 
+// One workgroup per row of logits [rows][V] (xent.hip): loss[r] = -log softmax(row r)[targets[r]]
+// with the exponentials and their sum in fp64, argmax[r] = the lowest index of the row's maximum.
+// loss (with targets) and argmax may each be NULL; targets beyond the row are clamped to V - 1.
+bool launch_xent(hipStream_t st, const float * logits, int rows, int V, const uint32_t * targets, double * loss,
+                 uint32_t * argmax);
+
 bool launch_mv_group(hipStream_t st, MVGroup & g);
 int mva_rows();
 

@@ -639,6 +639,29 @@ RWKV_API bool rwkv_mi355x_generate(struct rwkv_context * ctx, const struct rwkv_
     return true;
 }
 
+RWKV_API bool rwkv_mi355x_score_sequence(struct rwkv_context * ctx, const uint32_t * tokens, size_t T,
+                                         const uint32_t * targets, double * losses_out, uint32_t * argmax_out,
+                                         float * logits_out) {
+    if (!ctx || !ctx->engine) return false;
+    ctx->last_error = RWKV_ERROR_NONE;
+    const DeviceModel & dm = ctx->model->dm;
+    CTX_CHECK(ctx, RWKV_ERROR_CTX | RWKV_ERROR_UNSUPPORTED, false, ctx->pipe == nullptr,
+              "Scoring is not supported on a pipeline context");
+    CTX_CHECK(ctx, RWKV_ERROR_CTX | RWKV_ERROR_UNSUPPORTED, false, !dm.partial(),
+              "This context holds layers [%u, %u) only (a pipeline stage)", dm.layer_lo, dm.layer_hi);
+    CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, T > 0 && tokens != nullptr, "Sequence length is 0");
+    CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, (targets != nullptr) == (losses_out != nullptr),
+              "targets and losses_out go together (both NULL or both set)");
+    for (size_t i = 0; i < T; i++) CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, tokens[i] < dm.n_vocab, "Token out of range");
+    for (size_t i = 0; targets && i < T; i++)
+        CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, targets[i] < dm.n_vocab, "Target at index %zu (%" PRIu32 ") is out of range", i,
+                  targets[i]);
+    use_device(ctx);
+    CTX_CHECK(ctx, RWKV_ERROR_CTX, false, ctx->engine->score(tokens, T, targets, losses_out, argmax_out, logits_out),
+              "GPU scoring failed");
+    return true;
+}
+
 static bool eval_layers(struct rwkv_context * ctx, const uint32_t * tokens, size_t T, uint32_t layer_begin,
                         uint32_t layer_end, float * x_dev, float * vfirst_dev, bool compute_logits, float * logits_out,
                         bool sync) {

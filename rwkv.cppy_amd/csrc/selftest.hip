@@ -232,3 +232,28 @@ extern "C" RWKV_API bool rwkv_mi355x_selftest_sample(const float * logits, int r
     if (cutoff && hipMemcpy(cutoff, a.cutoff, (size_t)rows * 4, hipMemcpyDeviceToHost) != hipSuccess) return false;
     return true;
 }
+
+// The scoring kernel (xent.hip) on host operands: what rwkv_mi355x_score_sequence launches per head
+// tile, one workgroup per row.  Targets beyond the row are refused here (the kernel clamps them).
+extern "C" RWKV_API bool rwkv_mi355x_selftest_xent(const float * logits, int rows, int V, const uint32_t * targets,
+                                                   double * losses, uint32_t * argmax) {
+    if (!logits || rows < 1 || V < 1 || (losses && !targets)) return false;
+    if (targets)
+        for (int r = 0; r < rows; r++)
+            if (targets[r] >= (uint32_t)V) return false;
+    const size_t n = (size_t)rows * V;
+    DevBufs b;
+    float * dl = (float *)b.alloc(n * 4);
+    uint32_t * dt = (uint32_t *)b.alloc((size_t)rows * 4);
+    double * dloss = (double *)b.alloc((size_t)rows * 8);
+    uint32_t * da = (uint32_t *)b.alloc((size_t)rows * 4);
+    if (!dl || !dt || !dloss || !da) return false;
+    if (hipMemcpy(dl, logits, n * 4, hipMemcpyHostToDevice) != hipSuccess) return false;
+    if (targets && hipMemcpy(dt, targets, (size_t)rows * 4, hipMemcpyHostToDevice) != hipSuccess) return false;
+    if (!launch_xent(nullptr, dl, rows, V, targets ? dt : nullptr, losses ? dloss : nullptr, da) ||
+        hipDeviceSynchronize() != hipSuccess)
+        return false;
+    if (losses && hipMemcpy(losses, dloss, (size_t)rows * 8, hipMemcpyDeviceToHost) != hipSuccess) return false;
+    if (argmax && hipMemcpy(argmax, da, (size_t)rows * 4, hipMemcpyDeviceToHost) != hipSuccess) return false;
+    return true;
+}

@@ -183,6 +183,25 @@ class RWKVModel:
             out += tokens
         return out
 
+    def reset_state(self) -> None:
+        """MI355X extension (rwkv_mi355x_state_upload with NULL): the device-resident state becomes the
+        fresh state, as before the first token."""
+        if not self._valid:
+            raise ValueError('Model was freed')
+        if not self._library.library.rwkv_mi355x_state_upload(self._ctx.ptr, None):
+            raise ValueError('rwkv_mi355x_state_upload failed, check stderr')
+
+    def score(self, tokens: List[int], targets: Optional[List[int]] = None, want_logits: bool = False):
+        """MI355X extension (rwkv_mi355x_score_sequence): evaluates the tokens on the device-resident
+        state (continuing from wherever the last evaluation on this model left it) with the head on
+        every token.  Returns (losses, argmax, logits): losses float64 [T], the cross-entropy of
+        targets[t] under the logits following tokens[t] (None without targets); argmax uint32 [T];
+        logits float32 [T, n_vocab] when want_logits, else None.  Only the losses and argmaxes cross
+        PCIe unless the logits are asked for.  sample / generate continue from the last token."""
+        if not self._valid:
+            raise ValueError('Model was freed')
+        return self._library.rwkv_mi355x_score_sequence(self._ctx, tokens, targets, want_logits)
+
     def free(self) -> None:
         if not self._valid:
             raise ValueError('Already freed')

@@ -157,6 +157,11 @@ class RWKVSharedLibrary:
         L.rwkv_mi355x_selftest_sample.argtypes = [P_FLOAT, ctypes.c_int, ctypes.c_int, P_SAMPLING, P_FLOAT, P_U32, P_U32,
                                                   P_FLOAT]
         L.rwkv_mi355x_selftest_sample.restype = ctypes.c_bool
+        P_DOUBLE = ctypes.POINTER(ctypes.c_double)
+        L.rwkv_mi355x_score_sequence.argtypes = [vp, P_U32, sz, P_U32, P_DOUBLE, P_U32, P_FLOAT]
+        L.rwkv_mi355x_score_sequence.restype = ctypes.c_bool
+        L.rwkv_mi355x_selftest_xent.argtypes = [P_FLOAT, ctypes.c_int, ctypes.c_int, P_U32, P_DOUBLE, P_U32]
+        L.rwkv_mi355x_selftest_xent.restype = ctypes.c_bool
 
         self.nullptr = ctypes.cast(0, ctypes.c_void_p)
 
@@ -286,6 +291,47 @@ class RWKVSharedLibrary:
                 tokens.ctypes.data_as(P_U32), kept.ctypes.data_as(P_U32), cutoff.ctypes.data_as(P_FLOAT)):
             raise ValueError('rwkv_mi355x_selftest_sample failed')
         return tokens, kept, cutoff
+
+    # ---- additive: scoring a sequence on the device ------------------------------------------
+    def rwkv_mi355x_score_sequence(self, ctx: RWKVContext, tokens, targets=None, want_logits: bool = False):
+        """Evaluates the tokens on the device-resident state with the head on every token.  Returns
+        (losses float64 [T] or None without targets, argmax uint32 [T], logits float32 [T, n_vocab] or
+        None): losses[t] = -log softmax(logits[t])[targets[t]]."""
+        import numpy as np
+        tokens = np.ascontiguousarray(tokens, dtype=np.uint32)
+        T = int(tokens.size)
+        P_U32, P_DOUBLE = ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_double)
+        losses = None
+        if targets is not None:
+            targets = np.ascontiguousarray(targets, dtype=np.uint32)
+            if targets.shape != tokens.shape:
+                raise ValueError(f'{targets.size} targets for {T} tokens')
+            losses = np.zeros(T, np.float64)
+        argmax = np.zeros(T, np.uint32)
+        logits = np.zeros((T, self.rwkv_get_n_vocab(ctx)), np.float32) if want_logits else None
+        if not self.library.rwkv_mi355x_score_sequence(
+                ctx.ptr, tokens.ctypes.data_as(P_U32), T,
+                targets.ctypes.data_as(P_U32) if targets is not None else None,
+                losses.ctypes.data_as(P_DOUBLE) if losses is not None else None,
+                argmax.ctypes.data_as(P_U32), logits.ctypes.data_as(P_FLOAT) if want_logits else None):
+            raise ValueError('rwkv_mi355x_score_sequence failed, check stderr')
+        return losses, argmax, logits
+
+    def rwkv_mi355x_selftest_xent(self, logits, targets):
+        """The scoring kernel on host logits [rows][V] (float32 numpy) and targets [rows].  Returns
+        (losses float64 [rows], argmax uint32 [rows])."""
+        import numpy as np
+        logits = np.ascontiguousarray(logits, dtype=np.float32)
+        rows, V = logits.shape
+        targets = np.ascontiguousarray(targets, dtype=np.uint32)
+        assert targets.shape == (rows,)
+        losses, argmax = np.zeros(rows, np.float64), np.zeros(rows, np.uint32)
+        P_U32 = ctypes.POINTER(ctypes.c_uint32)
+        if not self.library.rwkv_mi355x_selftest_xent(
+                logits.ctypes.data_as(P_FLOAT), rows, V, targets.ctypes.data_as(P_U32),
+                losses.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), argmax.ctypes.data_as(P_U32)):
+            raise ValueError('rwkv_mi355x_selftest_xent failed')
+        return losses, argmax
 
     def rwkv_get_system_info_string(self) -> str:
         return self.library.rwkv_get_system_info_string().decode('utf-8')
