@@ -217,6 +217,33 @@ RWKV_API bool rwkv_mi355x_write_synthetic_model(const char * path, int arch, uin
                                                 uint32_t n_embed, uint32_t n_layer, uint32_t ffn,
                                                 const char * fmt, uint64_t seed);
 
+/* Options of rwkv_mi355x_write_synthetic_model_ex (test infrastructure: data the plain writer never
+ * produces).  All zero = the plain writer.
+ *   norms       nonzero: the weights of ln0 / ln1 / ln2 / ln_out / att.ln_x are U(0.5, 1.5) with every
+ *               17th channel (c % 17 == 16) negated, the biases U(-0.5, 0.5), each tensor from its own
+ *               seed (the plain writer stores ones and zeros: every norm the identity).
+ *   wide_decay  nonzero: v6 time_decay and v7 w0 are U(-8, 2); v5 time_decay is exp(-exp(U(-8, 2)));
+ *               v4 time_first is U(-4, 4) and time_decay -exp(U(-3, 3)).
+ *   maa_d, decay_d            v6 LoRA widths (time_maa_w1 is C x 5 maa_d, time_decay_w1 C x decay_d)
+ *   w_d, a_d, v_d, g_d        v7 LoRA widths (w1 / a1 / v1 / g1 are C x width)
+ *               0 keeps the plain writer's width.  A width whose matrix the file format quantizes
+ *               (v6 time_decay_w2, K = decay_d) must be a multiple of 32 there; the call fails otherwise.
+ *               The writer stores any other width; rwkv_init_from_file refuses maa_d > 64 and decay /
+ *               v7 widths that are no multiple of 32 (the CPU oracle of tests/ takes them all). */
+struct rwkv_mi355x_synth_opts {
+    uint32_t norms;
+    uint32_t wide_decay;
+    uint32_t maa_d, decay_d;
+    uint32_t w_d, a_d, v_d, g_d;
+};
+
+/* rwkv_mi355x_write_synthetic_model with options; opts == NULL writes the same bytes as the plain
+ * entry, which calls this one. */
+RWKV_API bool rwkv_mi355x_write_synthetic_model_ex(const char * path, int arch, uint32_t n_vocab,
+                                                   uint32_t n_embed, uint32_t n_layer, uint32_t ffn,
+                                                   const char * fmt, uint64_t seed,
+                                                   const struct rwkv_mi355x_synth_opts * opts);
+
 /* Kernel timing: while on, every matmul launch on the context stream is bracketed by hipEvents
  * (decode runs eagerly, not from the captured graph) and accumulated per kernel class -- the
  * template instantiation name rocprofv3 reports, e.g. "k_mm<2, 2, 1>" (weight type, rows per
@@ -273,6 +300,18 @@ RWKV_API bool rwkv_mi355x_selftest_sample(const float * logits, int rows, int V,
 /* k_xent on host operands (tests): logits [rows][V], targets [rows]; losses / argmax may be NULL */
 RWKV_API bool rwkv_mi355x_selftest_xent(const float * logits, int rows, int V, const uint32_t * targets,
                                         double * losses, uint32_t * argmax);
+
+/* k_groupnorm (the sequence path's per-head norm after WKV) on host operands, fp32 output:
+ * out = ((y - mean_head) / sqrt(var_head + eps) * w + b [+ v * bonus, mode 2]) [* g, modes 1 and 2].
+ * y, g, v, out: [T][H*S]; w, b: [H*S]; bonus: [T][H].  S: a power of two <= 64; H*S % 32 == 0.
+ * g is unused in mode 0, v and bonus unless mode 2 (may be NULL then). */
+RWKV_API bool rwkv_mi355x_selftest_groupnorm(int T, int H, int S, float eps, int mode, const float * y,
+                                             const float * w, const float * b, const float * g, const float * v,
+                                             const float * bonus, float * out);
+
+/* k_ln_emit (the LayerNorm in front of the head, eps 1e-5) on host operands, fp32 output:
+ * x, out: [rows][C]; w, b: [C]; C % 64 == 0. */
+RWKV_API bool rwkv_mi355x_selftest_ln(int C, int rows, const float * x, const float * w, const float * b, float * out);
 
 #if defined(__cplusplus)
 }

@@ -1557,7 +1557,9 @@ __global__ __launch_bounds__(1024) void k_groupnorm(int T, int H, int S, float e
     // channel block of 256 (4 heads of 64) per grid.y: one channel per thread
     {
         const int c0 = (int)blockIdx.y * 256, c = c0 + tid;
-        if (c0 + (tid & ~63) >= C) return;  // whole wave out of range
+        // whole half-waves out of range (C % 32 == 0; a head of S = 64 makes C % 64 == 0, narrower heads
+        // sum inside their own S <= 32 lanes): at C % 64 == 32 the last wave's upper half owns no channel
+        if (c0 + (tid & ~31) >= C) return;
         const size_t i = (size_t)t * C + c;
         const float x = y[i];
         const double s = group_tree_sum_d((double)x, S);

@@ -224,6 +224,9 @@ static bool check_shapes(const ModelFile & mf) {
         DW = mf.find("blocks.0.att.time_decay_w1")->ne[1];
         RWKV_CHECK(RWKV_ERROR_MODEL_PARAMS | RWKV_ERROR_SHAPE, false, D5 % 5 == 0 && D5 / 5 <= 64 && DW >= 1,
                    "Unsupported v6 LoRA widths (maa %u, decay %u)", D5, DW);
+        // the second LoRA stage is a matvec over K = the width, in whole 32-element blocks for every type
+        RWKV_CHECK(RWKV_ERROR_MODEL_PARAMS | RWKV_ERROR_UNSUPPORTED, false, DW % 32 == 0,
+                   "v6 decay LoRA width %u is not a multiple of 32", DW);
     }
     if (mf.arch_major == 7) {
         DW7 = mf.find("blocks.0.att.w1")->ne[1];
@@ -231,6 +234,10 @@ static bool check_shapes(const ModelFile & mf) {
         DG7 = mf.find("blocks.0.att.g1")->ne[1];
         const HostTensor * v1 = mf.header.n_layer > 1 ? mf.find("blocks.1.att.v1") : nullptr;
         DV7 = v1 ? v1->ne[1] : 0;
+        // w2 / a2 / v2 / g2 are matvecs over K = the width, in whole 32-element blocks for every type
+        RWKV_CHECK(RWKV_ERROR_MODEL_PARAMS | RWKV_ERROR_UNSUPPORTED, false,
+                   DW7 % 32 == 0 && DA7 % 32 == 0 && DG7 % 32 == 0 && DV7 % 32 == 0,
+                   "v7 LoRA widths must be multiples of 32 (w %u, a %u, v %u, g %u)", DW7, DA7, DV7, DG7);
     }
     for (uint32_t i = 0; ok && i < mf.header.n_layer; i++) {
         const std::string p = "blocks." + std::to_string(i) + ".";

@@ -222,9 +222,9 @@ struct Rng {
 struct SynthTensor {
     std::string name;
     std::vector<uint32_t> ne;  // ggml order
-    enum Kind { MAT, ONES, ZEROS, UNIF, CUSTOM } kind;
+    enum Kind { MAT, ONES, ZEROS, UNIF, CUSTOM, NORMW } kind;
     float lo = 0, hi = 1;      // UNIF range
-    int custom = 0;            // 1: v4 decay  2: v5.2 decay
+    int custom = 0;            // 1: v4 decay  2: v5.2 decay  3: v4 wide decay  4: v5.2 wide decay
 };
 
 static uint64_t nel(const std::vector<uint32_t> & ne) {
@@ -257,9 +257,16 @@ static void fill_tensor(const SynthTensor & t, float * x, uint64_t seed) {
             case SynthTensor::ONES: x[i] = 1.0f; break;
             case SynthTensor::ZEROS: x[i] = 0.0f; break;
             case SynthTensor::UNIF: x[i] = t.lo + (t.hi - t.lo) * g.uniform(); break;
+            case SynthTensor::NORMW: {  // a norm weight away from 1: U(0.5, 1.5), every 17th channel negated
+                const float u = 0.5f + g.uniform();
+                x[i] = (i % 17 == 16) ? -u : u;
+                break;
+            }
             default: {
                 const float u = g.uniform();
                 if (t.custom == 1) x[i] = -expf(-1.0f + 2.0f * u);               // v4: -exp(w)
+                else if (t.custom == 3) x[i] = -expf(-3.0f + 6.0f * u);          // v4, wide: -exp(U(-3, 3))
+                else if (t.custom == 4) x[i] = expf(-expf(-8.0f + 10.0f * u));   // v5.2, wide: exp(-exp(U(-8, 2)))
                 else x[i] = expf(-expf(-6.0f + 5.0f * u));                       // v5.2: exp(-exp(w))
             }
         }
@@ -267,8 +274,9 @@ static void fill_tensor(const SynthTensor & t, float * x, uint64_t seed) {
 }
 
 static bool write_synthetic(const char * path, int arch, uint32_t V, uint32_t C, uint32_t L, uint32_t F,
-                            const char * fmt, uint64_t seed) {
-    const int ftype = type_from_name(fmt);
+                            const char * fmt, uint64_t seed, const rwkv_mi355x_synth_opts * opts) {
+    const rwkv_mi355x_synth_opts o = opts ? *opts : rwkv_mi355x_synth_opts{};
+    const int ftype = type_from_name(fmt ? fmt : "");
     if (ftype < 0 || !type_supported((uint32_t)ftype) || C % 64 || arch < 4 || arch > 7) return false;
     const uint32_t S = 64, H = arch >= 5 ? C / S : 0;
     if (F == 0) F = (arch == 4 || arch == 7) ? 4 * C : (C * 7) / 2;
@@ -282,26 +290,39 @@ static bool write_synthetic(const char * path, int arch, uint32_t V, uint32_t C,
         t.custom = cu;
         ts.push_back(t);
     };
+    // a norm's weight and bias: the identity, or (opts.norms) seeded values; every tensor of the file
+    // draws from its own seed, so no two norms are equal
+    auto norm = [&](const std::string & n) {
+        if (o.norms) {
+            vec(n + ".weight", {C}, SynthTensor::NORMW);
+            vec(n + ".bias", {C}, SynthTensor::UNIF, -0.5f, 0.5f);
+        } else {
+            vec(n + ".weight", {C}, SynthTensor::ONES);
+            vec(n + ".bias", {C}, SynthTensor::ZEROS);
+        }
+    };
+    auto width = [](uint32_t asked, uint32_t dflt) { return asked ? asked : dflt; };
+    const float dlo = o.wide_decay ? -8.0f : -6.0f, dhi = o.wide_decay ? 2.0f : -1.0f;  // v6 time_decay, v7 w0
     mat("emb.weight", C, V);
-    vec("blocks.0.ln0.weight", {C}, SynthTensor::ONES);
-    vec("blocks.0.ln0.bias", {C}, SynthTensor::ZEROS);
-    const uint32_t DW7 = C >= 4096 ? 128 : 96, DA7 = DW7, DV7 = 64, DG7 = C >= 4096 ? 480 : 320;
+    norm("blocks.0.ln0");
+    const uint32_t DM6 = width(o.maa_d, 32), DD6 = width(o.decay_d, 64);
+    const uint32_t DW7 = width(o.w_d, C >= 4096 ? 128 : 96), DA7 = width(o.a_d, C >= 4096 ? 128 : 96),
+                   DV7 = width(o.v_d, 64), DG7 = width(o.g_d, C >= 4096 ? 480 : 320);
     for (uint32_t i = 0; i < L; i++) {
         const std::string p = "blocks." + std::to_string(i) + ".";
-        vec(p + "ln1.weight", {C}, SynthTensor::ONES);
-        vec(p + "ln1.bias", {C}, SynthTensor::ZEROS);
-        vec(p + "ln2.weight", {C}, SynthTensor::ONES);
-        vec(p + "ln2.bias", {C}, SynthTensor::ZEROS);
+        norm(p + "ln1");
+        norm(p + "ln2");
         if (arch == 4 || arch == 5) {
             vec(p + "att.time_mix_k", {C}, SynthTensor::UNIF);
             vec(p + "att.time_mix_v", {C}, SynthTensor::UNIF);
             vec(p + "att.time_mix_r", {C}, SynthTensor::UNIF);
             if (arch == 4) {
-                vec(p + "att.time_first", {C}, SynthTensor::UNIF, -1, 1);
-                vec(p + "att.time_decay", {C}, SynthTensor::CUSTOM, 0, 0, 1);
+                if (o.wide_decay) vec(p + "att.time_first", {C}, SynthTensor::UNIF, -4, 4);
+                else vec(p + "att.time_first", {C}, SynthTensor::UNIF, -1, 1);
+                vec(p + "att.time_decay", {C}, SynthTensor::CUSTOM, 0, 0, o.wide_decay ? 3 : 1);
             } else {
                 vec(p + "att.time_mix_g", {C}, SynthTensor::UNIF);
-                vec(p + "att.time_decay", {1, S, H}, SynthTensor::CUSTOM, 0, 0, 2);
+                vec(p + "att.time_decay", {1, S, H}, SynthTensor::CUSTOM, 0, 0, o.wide_decay ? 4 : 2);
                 vec(p + "att.time_faaaa", {1, S, H}, SynthTensor::UNIF, -1, 1);
             }
             mat(p + "att.key.weight", C, C);
@@ -310,8 +331,7 @@ static bool write_synthetic(const char * path, int arch, uint32_t V, uint32_t C,
             mat(p + "att.output.weight", C, C);
             if (arch == 5) {
                 mat(p + "att.gate.weight", C, C);
-                vec(p + "att.ln_x.weight", {C}, SynthTensor::ONES);
-                vec(p + "att.ln_x.bias", {C}, SynthTensor::ZEROS);
+                norm(p + "att.ln_x");
             }
             vec(p + "ffn.time_mix_k", {C}, SynthTensor::UNIF);
             vec(p + "ffn.time_mix_r", {C}, SynthTensor::UNIF);
@@ -320,19 +340,18 @@ static bool write_synthetic(const char * path, int arch, uint32_t V, uint32_t C,
             mat(p + "ffn.receptance.weight", C, C);
         } else if (arch == 6) {
             for (const char * s : {"x", "w", "k", "v", "r", "g"}) vec(p + "att.time_maa_" + s, {C}, SynthTensor::UNIF);
-            mat(p + "att.time_maa_w1", C, 160);
-            vec(p + "att.time_maa_w2", {32, C, 5}, SynthTensor::UNIF, -0.1f, 0.1f);
-            vec(p + "att.time_decay", {1, S, H}, SynthTensor::UNIF, -6, -1);
-            mat(p + "att.time_decay_w1", C, 64);
-            mat(p + "att.time_decay_w2", 64, C);
+            mat(p + "att.time_maa_w1", C, 5 * DM6);
+            vec(p + "att.time_maa_w2", {DM6, C, 5}, SynthTensor::UNIF, -0.1f, 0.1f);
+            vec(p + "att.time_decay", {1, S, H}, SynthTensor::UNIF, dlo, dhi);
+            mat(p + "att.time_decay_w1", C, DD6);
+            mat(p + "att.time_decay_w2", DD6, C);
             vec(p + "att.time_faaaa", {1, S, H}, SynthTensor::UNIF, -1, 1);
             mat(p + "att.receptance.weight", C, C);
             mat(p + "att.key.weight", C, C);
             mat(p + "att.value.weight", C, C);
             mat(p + "att.output.weight", C, C);
             mat(p + "att.gate.weight", C, C);
-            vec(p + "att.ln_x.weight", {C}, SynthTensor::ONES);
-            vec(p + "att.ln_x.bias", {C}, SynthTensor::ZEROS);
+            norm(p + "att.ln_x");
             vec(p + "ffn.time_maa_k", {C}, SynthTensor::UNIF);
             vec(p + "ffn.time_maa_r", {C}, SynthTensor::UNIF);
             mat(p + "ffn.key.weight", C, F);
@@ -340,7 +359,7 @@ static bool write_synthetic(const char * path, int arch, uint32_t V, uint32_t C,
             mat(p + "ffn.value.weight", F, C);
         } else {
             vec(p + "att.x_rwkvag", {C, 1, 6}, SynthTensor::UNIF);
-            vec(p + "att.w0", {C, 1, 1}, SynthTensor::UNIF, -6, -1);
+            vec(p + "att.w0", {C, 1, 1}, SynthTensor::UNIF, dlo, dhi);
             mat(p + "att.w1", C, DW7);
             mat(p + "att.w2", DW7, C);
             vec(p + "att.a0", {C, 1, 1}, SynthTensor::UNIF, -1, 1);
@@ -360,16 +379,18 @@ static bool write_synthetic(const char * path, int arch, uint32_t V, uint32_t C,
             mat(p + "att.key.weight", C, C);
             mat(p + "att.value.weight", C, C);
             mat(p + "att.output.weight", C, C);
-            vec(p + "att.ln_x.weight", {C}, SynthTensor::ONES);
-            vec(p + "att.ln_x.bias", {C}, SynthTensor::ZEROS);
+            norm(p + "att.ln_x");
             vec(p + "ffn.x_k", {C, 1, 1}, SynthTensor::UNIF);
             mat(p + "ffn.key.weight", C, F);
             mat(p + "ffn.value.weight", F, C);
         }
     }
-    vec("ln_out.weight", {C}, SynthTensor::ONES);
-    vec("ln_out.bias", {C}, SynthTensor::ZEROS);
+    norm("ln_out");
     mat("head.weight", C, V);
+    // a matrix this format stores in 32-element blocks needs whole blocks per row
+    if (type_quantized((uint32_t)ftype))
+        for (const auto & t : ts)
+            if (t.ne.size() == 2 && tensor_needs_quant(t.name) && t.ne[0] % 32) return false;
 
     FILE * f = fopen(path, "wb");
     if (!f) return false;
@@ -429,5 +450,16 @@ extern "C" RWKV_API bool rwkv_quantize_model_file(const char * in, const char * 
 extern "C" RWKV_API bool rwkv_mi355x_write_synthetic_model(const char * path, int arch, uint32_t n_vocab,
                                                            uint32_t n_embed, uint32_t n_layer, uint32_t ffn,
                                                            const char * fmt, uint64_t seed) {
-    return rwkvmi::write_synthetic(path, arch, n_vocab, n_embed, n_layer, ffn, fmt, seed);
+    return rwkv_mi355x_write_synthetic_model_ex(path, arch, n_vocab, n_embed, n_layer, ffn, fmt, seed, nullptr);
+}
+
+extern "C" RWKV_API bool rwkv_mi355x_write_synthetic_model_ex(const char * path, int arch, uint32_t n_vocab,
+                                                              uint32_t n_embed, uint32_t n_layer, uint32_t ffn,
+                                                              const char * fmt, uint64_t seed,
+                                                              const struct rwkv_mi355x_synth_opts * opts) {
+    try {
+        return rwkvmi::write_synthetic(path, arch, n_vocab, n_embed, n_layer, ffn, fmt, seed, opts);
+    } catch (const std::exception &) {
+        return false;
+    }
 }

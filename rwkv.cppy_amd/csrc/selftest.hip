@@ -257,3 +257,56 @@ extern "C" RWKV_API bool rwkv_mi355x_selftest_xent(const float * logits, int row
     if (argmax && hipMemcpy(argmax, da, (size_t)rows * 4, hipMemcpyDeviceToHost) != hipSuccess) return false;
     return true;
 }
+
+// k_groupnorm (the sequence path's per-head norm after WKV) on host operands with an fp32 output:
+// out[t][c] = ((y - mean_h) / sqrt(var_h + eps) * w[c] + b[c] (+ v * bonus[t][h], mode 2)) (* g, modes 1, 2).
+// y, g, v, out: [T][H*S]; w, b: [H*S]; bonus: [T][H].  S a power of two <= 64, H*S a multiple of 32.
+extern "C" RWKV_API bool rwkv_mi355x_selftest_groupnorm(int T, int H, int S, float eps, int mode, const float * y,
+                                                       const float * w, const float * b, const float * g,
+                                                       const float * v, const float * bonus, float * out) {
+    if (T < 1 || H < 1 || S < 1 || mode < 0 || mode > 2 || !y || !w || !b || !out) return false;
+    if ((mode >= 1 && !g) || (mode == 2 && (!v || !bonus)) || (H * S) % 32) return false;
+    const size_t C = (size_t)H * S, TC = (size_t)T * C;
+    DevBufs bf;
+    ActBuf o;
+    memset(&o, 0, sizeof(o));
+    o.fmt = A_F32;
+    o.K = (int)C;
+    float *dy = (float *)bf.alloc(TC * 4), *dw = (float *)bf.alloc(C * 4), *db = (float *)bf.alloc(C * 4),
+          *dg = (float *)bf.alloc(TC * 4), *dv = (float *)bf.alloc(TC * 4), *dbo = (float *)bf.alloc((size_t)T * H * 4);
+    o.f = (float *)bf.alloc(TC * 4);
+    if (!dy || !dw || !db || !dg || !dv || !dbo || !o.f) return false;
+    if (hipMemcpy(dy, y, TC * 4, hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemcpy(dw, w, C * 4, hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemcpy(db, b, C * 4, hipMemcpyHostToDevice) != hipSuccess)
+        return false;
+    if (mode >= 1 && hipMemcpy(dg, g, TC * 4, hipMemcpyHostToDevice) != hipSuccess) return false;
+    if (mode == 2 && (hipMemcpy(dv, v, TC * 4, hipMemcpyHostToDevice) != hipSuccess ||
+                      hipMemcpy(dbo, bonus, (size_t)T * H * 4, hipMemcpyHostToDevice) != hipSuccess))
+        return false;
+    if (!launch_groupnorm(nullptr, T, H, S, eps, dy, dw, db, mode, dg, dv, dbo, o) || hipDeviceSynchronize() != hipSuccess)
+        return false;
+    return hipMemcpy(out, o.f, TC * 4, hipMemcpyDeviceToHost) == hipSuccess;
+}
+
+// k_ln_emit (the LayerNorm in front of the head) on host operands with an fp32 output:
+// out[r] = LN(x[r]) * w + b, eps 1e-5.  x, out: [rows][C]; w, b: [C]; C a multiple of 64.
+extern "C" RWKV_API bool rwkv_mi355x_selftest_ln(int C, int rows, const float * x, const float * w, const float * b,
+                                                float * out) {
+    if (C < 64 || C % 64 || rows < 1 || !x || !w || !b || !out) return false;
+    const size_t n = (size_t)rows * C;
+    DevBufs bf;
+    ActBuf o;
+    memset(&o, 0, sizeof(o));
+    o.fmt = A_F32;
+    o.K = C;
+    float *dx = (float *)bf.alloc(n * 4), *dw = (float *)bf.alloc((size_t)C * 4), *db = (float *)bf.alloc((size_t)C * 4);
+    o.f = (float *)bf.alloc(n * 4);
+    if (!dx || !dw || !db || !o.f) return false;
+    if (hipMemcpy(dx, x, n * 4, hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemcpy(dw, w, (size_t)C * 4, hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemcpy(db, b, (size_t)C * 4, hipMemcpyHostToDevice) != hipSuccess)
+        return false;
+    if (!launch_ln_emit(nullptr, C, dx, dw, db, o, rows) || hipDeviceSynchronize() != hipSuccess) return false;
+    return hipMemcpy(out, o.f, n * 4, hipMemcpyDeviceToHost) == hipSuccess;
+}

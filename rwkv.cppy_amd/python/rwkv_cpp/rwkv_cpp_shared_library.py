@@ -31,6 +31,11 @@ class RWKVSampling(ctypes.Structure):
                 ('seed', ctypes.c_uint64), ('offset', ctypes.c_uint64)]
 
 
+class RWKVSynthOpts(ctypes.Structure):
+    """struct rwkv_mi355x_synth_opts (include/rwkv_mi355x.h); all zero = the plain synthetic writer."""
+    _fields_ = [(n, ctypes.c_uint32) for n in ('norms', 'wide_decay', 'maa_d', 'decay_d', 'w_d', 'a_d', 'v_d', 'g_d')]
+
+
 def make_sampling(temperature: float = 1.0, top_p: float = 0.8, logit_bias=None, seed: int = 0,
                   offset: int = 0) -> RWKVSampling:
     """Fills an RWKVSampling; logit_bias: {token id: value}.  The bias arrays stay referenced by the
@@ -119,6 +124,15 @@ class RWKVSharedLibrary:
         L.rwkv_mi355x_write_synthetic_model.argtypes = [ctypes.c_char_p, ctypes.c_int, u32, u32, u32, u32,
                                                         ctypes.c_char_p, ctypes.c_uint64]
         L.rwkv_mi355x_write_synthetic_model.restype = ctypes.c_bool
+        L.rwkv_mi355x_write_synthetic_model_ex.argtypes = [ctypes.c_char_p, ctypes.c_int, u32, u32, u32, u32,
+                                                           ctypes.c_char_p, ctypes.c_uint64,
+                                                           ctypes.POINTER(RWKVSynthOpts)]
+        L.rwkv_mi355x_write_synthetic_model_ex.restype = ctypes.c_bool
+        L.rwkv_mi355x_selftest_groupnorm.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_float,
+                                                     ctypes.c_int] + [P_FLOAT] * 7
+        L.rwkv_mi355x_selftest_groupnorm.restype = ctypes.c_bool
+        L.rwkv_mi355x_selftest_ln.argtypes = [ctypes.c_int, ctypes.c_int] + [P_FLOAT] * 4
+        L.rwkv_mi355x_selftest_ln.restype = ctypes.c_bool
         L.rwkv_mi355x_eval_batch.argtypes = [vp, vp, sz, vp, vp, vp]
         L.rwkv_mi355x_eval_batch.restype = ctypes.c_bool
         L.rwkv_mi355x_eval_batch_device.argtypes = [vp, vp, sz, vp, vp, vp]

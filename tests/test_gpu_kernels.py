@@ -166,3 +166,51 @@ def test_mfma_gemm_split_k_bit_exact(fmt, M, K, T, split):
     assert L.rwkv_mi355x_selftest_gemm_split(TYPE_IDS[fmt], wb.ctypes.data, K, M, x.ctypes.data, T, y_g.ctypes.data,
                                              split)
     assert np.array_equal(y_g.view(np.uint32), y_mm.view(np.uint32)), float(np.abs(y_g - y_mm).max())
+
+
+ODD_M = [1, 3, 5, 33, 50277]
+ODD_CASES = [(fmt, K, M, T) for fmt, K in (('Q8_0', 96), ('FP16', 768), ('FP32', 64), ('Q4_1', 2048)) for M in ODD_M
+             for T in (1, 5, 16, 130) if M < 50277 or K <= 768]
+_odd_weights = {}
+
+
+def odd_weights(fmt, K, M):
+    """(block bytes, float64 |W|) of the seeded [M, K] matrix, built once per shape."""
+    if (fmt, K, M) not in _odd_weights:
+        w = (np.random.default_rng(M + K).standard_normal((M, K)) / np.sqrt(K)).astype(np.float32)
+        wb = quantize_rows(fmt, w)
+        _odd_weights[(fmt, K, M)] = (wb, np.abs(dequantize(fmt, wb, K, M).astype(np.float64)))
+    return _odd_weights[(fmt, K, M)]
+
+
+@pytest.mark.parametrize('fmt,K,M,T', ODD_CASES)
+def test_matmul_odd_row_counts(fmt, K, M, T):
+    """Row counts that fill no wave's row group (1, 3, 5), one past a 32-row tile (33) and the RWKV-4
+    vocabulary 50277 (odd: y rows of T > 1 are only 4-byte aligned), at T = 1 (k_mv), 5 (the token
+    pass), 16 (the f32 MFMA's first T) and 130 (two tokens past a 128-token tile): bit-exact against
+    the GPU-association oracle and within 1e-5 * |W| |x| + 1e-6 of the ggml-order one.
+
+    rwkv_mi355x_selftest_gemm at M = 33 and 50277: it returns false for the float formats and for
+    T = 1 (its contract: quantized weights, T >= 2); for Q8_0 and Q4_1 at T = 5, 16, 130 it runs and
+    equals the matmul bit for bit."""
+    wb, absw = odd_weights(fmt, K, M)
+    x = np.random.default_rng(K * 3 + T).standard_normal((T, K)).astype(np.float32)
+    y = np.full((T, M), np.nan, np.float32)
+    L = lib()
+    assert L.rwkv_mi355x_selftest_matmul(TYPE_IDS[fmt], wb.ctypes.data, K, M, x.ctypes.data, T, y.ctypes.data)
+    set_variant(VARIANT_GPU)
+    try:
+        ref8 = oracle_matmul(fmt, wb, K, M, x)
+    finally:
+        set_variant(0)
+    assert_bits_equal(y, ref8, f'{fmt} K {K} M {M} T {T} vs GPU-association oracle')
+    ref = oracle_matmul(fmt, wb, K, M, x)
+    bound = np.abs(x.astype(np.float64)) @ absw.T
+    err = np.abs(y.astype(np.float64) - ref)
+    assert np.all(err <= 1e-5 * bound + 1e-6), float((err / (bound + 1e-12)).max())
+    if M in (33, 50277):
+        yg = np.full((T, M), np.nan, np.float32)
+        ran = L.rwkv_mi355x_selftest_gemm(TYPE_IDS[fmt], wb.ctypes.data, K, M, x.ctypes.data, T, yg.ctypes.data)
+        assert ran == (fmt in ('Q8_0', 'Q4_1') and T >= 2)
+        if ran:
+            assert_bits_equal(yg, y, f'{fmt} K {K} M {M} T {T} GEMM vs matmul')
