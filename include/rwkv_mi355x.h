@@ -92,6 +92,65 @@ RWKV_API bool rwkv_mi355x_sample(struct rwkv_context * ctx, const struct rwkv_mi
 RWKV_API bool rwkv_mi355x_generate(struct rwkv_context * ctx, const struct rwkv_mi355x_sampling * params, size_t n,
                                    uint32_t * tokens_out, float * logits_out);
 
+/* Batched generation on the device: up to 256 sequences of one context sample, are penalised, stop
+ * and decode together, one pass over the weights per step, nothing but the tokens crossing PCIe.
+ *
+ * Slots.  rwkv_mi355x_batch_reserve gives the context n_slots <= 256 generation slots (each a state
+ * and its logits in HBM, apart from the context's own state; 0 frees them) and invalidates every
+ * slot it had.  rwkv_mi355x_batch_store copies the context's device state and device logits into a
+ * slot, device to device (the logits must follow the state, as for rwkv_mi355x_sample), and starts a
+ * new sequence there: its token counts are zero and it is not finished.  rwkv_mi355x_batch_load is
+ * the reverse: the context continues from the slot (rwkv_mi355x_sample / _generate /
+ * _score_sequence / _eval_device).  A slot >= n_slots, a store without valid device logits and a load
+ * of a slot that was never stored fail with RWKV_ERROR_ARGS.
+ *
+ * rwkv_mi355x_generate_batch runs rows = slots [0, B) for up to n steps.  Step i of a live row r:
+ *   l = logits_r; for every token t with c = counts_r[t] > 0, in float32 and in this order,
+ *     l_t = l_t - (presence[r] + (float)c * frequency[r])       (one multiply, one add, one subtract,
+ *   none fused: rwkv_cpp.sampling.penalize restates it bit for bit.  The reference's chat loop,
+ *   chat_with_bot.py:245-274, forms the penalty in double, so its l_t can differ by one rounding);
+ *   l += bias; the draw of rwkv_mi355x_sample with temperature[r], top_p[r] and
+ *   u = uniform(seed[r], offset[r] + i); counts_r[token] += 1.
+ * If the token is one of stop_tokens the row is finished: the stop token is the last of its tokens
+ * and is not evaluated.  Otherwise the token is evaluated (one batched decode step for all rows,
+ * bit-identical to rwkv_mi355x_eval_device per row).  On return tokens_out[r][0 .. lengths_out[r]) are
+ * the tokens row r drew in this call and the entries after them are 0xFFFFFFFF.  Slot r holds, for a
+ * finished row, the state that has consumed every token before the stop token and the logits that
+ * produced the stop token; for a row that never stopped (lengths_out[r] == n) the state that has
+ * consumed all n tokens and the logits after the last, as rwkv_mi355x_generate leaves a context.
+ * keep_counts != 0 continues the previous call on these slots: the counts go on, rows that finished
+ * stay finished (lengths_out[r] == 0, slot unchanged), and with offset[r] + n the draws continue the
+ * same streams, so two calls of n equal one of 2 n.  keep_counts == 0 starts every row afresh.
+ * check_every = k > 0: every k steps the host reads the number of live rows (4 bytes, one
+ * synchronisation) and leaves the loop when it is 0; the results do not depend on it.  steps_out
+ * (may be NULL) receives the number of decode steps that ran.
+ * Errors, all before anything is enqueued (RWKV_ERROR_ARGS; state and slots untouched): B == 0 or
+ * B > the reserved slots, a slot in [0, B) never stored, n == 0 or n > 65536, a NULL required
+ * pointer, a temperature < 0 or NaN, a top_p outside [0, 1], a NaN penalty, n_bias > 256, a bias id
+ * >= n_vocab, n_stop > 16, a stop id >= n_vocab.  A pipeline context or a stage context fails with
+ * RWKV_ERROR_CTX | RWKV_ERROR_UNSUPPORTED.  An in-launch hand-off timeout fails the call with
+ * RWKV_ERROR_CTX and leaves slots [0, B) invalid (store them again). */
+RWKV_API bool rwkv_mi355x_batch_reserve(struct rwkv_context * ctx, size_t n_slots);
+RWKV_API size_t rwkv_mi355x_batch_slots(const struct rwkv_context * ctx);
+RWKV_API bool rwkv_mi355x_batch_store(struct rwkv_context * ctx, size_t slot);
+RWKV_API bool rwkv_mi355x_batch_load(struct rwkv_context * ctx, size_t slot);
+struct rwkv_mi355x_batch_sampling {
+    const float * temperature, * top_p;  /* host [B] */
+    const float * presence, * frequency; /* host [B], or NULL: 0 */
+    const uint64_t * seed, * offset;     /* host [B]; row r draw i: uniform(seed[r], offset[r] + i) */
+    uint32_t n_bias;                     /* shared by the rows, <= 256 */
+    const uint32_t * bias_ids;
+    const float * bias_values;
+    uint32_t n_stop;                     /* <= 16, each < n_vocab */
+    const uint32_t * stop_tokens;
+    uint32_t keep_counts;                /* 0: counts and finished rows start from zero; else continue the last call's */
+    uint32_t check_every;                /* 0: never look; k: the host looks every k steps and leaves when no row is live */
+};
+RWKV_API bool rwkv_mi355x_generate_batch(struct rwkv_context * ctx, size_t B,
+                                         const struct rwkv_mi355x_batch_sampling * params, size_t n,
+                                         uint32_t * tokens_out /* [B][n] */, uint32_t * lengths_out /* [B] */,
+                                         uint32_t * steps_out);
+
 /* Scoring: rwkv_mi355x_eval_device over T >= 1 tokens with the head on EVERY token.  Position t's
  * logits row (the logits serial rwkv_eval of tokens[0..t] gives, bit for bit) is reduced on the device
  * to losses_out[t] = -log softmax(row t)[targets[t]] (the exponentials and their sum in fp64) and
@@ -296,6 +355,19 @@ RWKV_API bool rwkv_mi355x_selftest_wkv7(int T, int H, int chunked, const float *
 RWKV_API bool rwkv_mi355x_selftest_sample(const float * logits, int rows, int V,
                                           const struct rwkv_mi355x_sampling * params, const float * u,
                                           uint32_t * tokens, uint32_t * kept, float * cutoff);
+
+/* The sampler kernel of rwkv_mi355x_generate_batch (k_sample_rows) on host operands, as step `step`
+ * of a call: logits [rows][V]; params' temperature, top_p, presence, frequency (host [rows]; the
+ * penalties may be NULL), bias and stop tokens (seed, offset, keep_counts, check_every unused); one
+ * draw u[r] per row.  counts [rows][V] (may be NULL: no penalties) and done [rows] are read and
+ * written.  tokens, decode_tokens (what the decode step would embed), kept, cutoff, lengths [rows]
+ * and active (one word) are uploaded first and downloaded afterwards, so an entry the kernel does
+ * not write keeps the caller's value; none of them may be NULL. */
+RWKV_API bool rwkv_mi355x_selftest_sample_rows(const float * logits, int rows, int V,
+                                               const struct rwkv_mi355x_batch_sampling * params, const float * u,
+                                               uint32_t step, uint32_t * counts, uint32_t * done, uint32_t * tokens,
+                                               uint32_t * decode_tokens, uint32_t * kept, float * cutoff,
+                                               uint32_t * lengths, uint32_t * active);
 
 /* k_xent on host operands (tests): logits [rows][V], targets [rows]; losses / argmax may be NULL */
 RWKV_API bool rwkv_mi355x_selftest_xent(const float * logits, int rows, int V, const uint32_t * targets,

@@ -372,6 +372,8 @@ Engine::~Engine() {
     for (float * p : bstate_)
         if (p) (void)hipFree(p);
     if (blogits_) (void)hipFree(blogits_);
+    free_slots();
+    if (gtokens_) (void)hipFree(gtokens_);
     if (gy_) (void)hipFree(gy_);
     if (part_) (void)hipFree(part_);
     if (m2_) (void)hipFree(m2_);
@@ -1655,7 +1657,10 @@ bool Engine::eval_batch(const uint32_t * tokens, size_t B, const float * state_i
     }
     if (!ensure_workspace((int)B)) return false;
     const size_t n = m_->state_len, V = m_->n_vocab;
-    if (B > bcap_) {
+    // tokens == NULL (generate_batch): the tokens are already in dtokens_[0 .. B) (the sampler wrote
+    // them), every buffer is the caller's device memory and nothing is staged
+    if (!tokens && !(dev && state_in && state_out && logits_out)) return false;
+    if (tokens && B > bcap_) {
         HIP_OK(hipStreamSynchronize(stream_));
         drop_batch_graphs();
         for (float *& p : bstate_) {
@@ -1684,10 +1689,12 @@ bool Engine::eval_batch(const uint32_t * tokens, size_t B, const float * state_i
         bcap_ = cap;
     }
     // tokens: pinned copy in stream order (the previous call's copy may still read it)
-    HIP_OK(hipEventSynchronize(tok_event_));
-    memcpy(htokens_, tokens, B * 4);
-    HIP_OK(hipMemcpyAsync(dtokens_, htokens_, B * 4, hipMemcpyHostToDevice, stream_));
-    HIP_OK(hipEventRecord(tok_event_, stream_));
+    if (tokens) {
+        HIP_OK(hipEventSynchronize(tok_event_));
+        memcpy(htokens_, tokens, B * 4);
+        HIP_OK(hipMemcpyAsync(dtokens_, htokens_, B * 4, hipMemcpyHostToDevice, stream_));
+        HIP_OK(hipEventRecord(tok_event_, stream_));
+    }
     // input states: device pointer as given, else staged into bstate_[0] (NULL = fresh states)
     const float * sin = state_in;
     if (!state_in) {
@@ -1852,6 +1859,193 @@ bool Engine::generate(const SamplingParams & p, size_t n, uint32_t * tokens_out,
         logits_valid_ = false;
     }
     return ok;
+}
+
+// ---------------------------------------------------------------- batched generation
+// Slots [0, B) of the context generate together: per step one k_sample_rows launch over the slots'
+// logits (per-row parameters, penalties, stops), k_gen_snapshot of the rows that just stopped, and
+// one batched decode step (eval_batch, tokens already in dtokens_) from gstate_[p] to gstate_[p ^ 1].
+// A finished row keeps being decoded on token 0 -- the batched kernels take row t's state at
+// t * state_len, so leaving a row out would need a per-row offset through every one of them -- and
+// its live state and logits are garbage from then on; what the caller sees is the snapshot, which
+// k_gen_restore puts back into gstate_[0] / glogits_ at the end of the call.
+void Engine::free_slots() {
+    for (void * p : {(void *)gstate_[0], (void *)gstate_[1], (void *)glogits_, (void *)gsnap_state_, (void *)gsnap_logits_,
+                     (void *)gcounts_, (void *)gparams_, (void *)gstreams_, (void *)gwords_})
+        if (p) (void)hipFree(p);
+    gstate_[0] = gstate_[1] = glogits_ = gsnap_state_ = gsnap_logits_ = gparams_ = nullptr;
+    gcounts_ = nullptr;
+    gstreams_ = nullptr;
+    gwords_ = nullptr;
+    gslots_ = 0;
+    gvalid_.clear();
+}
+
+bool Engine::batch_reserve(size_t n_slots) {
+    HIP_OK(hipSetDevice(m_->device));
+    if (n_slots > (size_t)kBatchMax) return false;
+    HIP_OK(hipStreamSynchronize(stream_));
+    drop_batch_graphs();  // they hold the old slots' addresses
+    free_slots();
+    if (n_slots == 0) return true;
+    const size_t n = m_->state_len, V = m_->n_vocab;
+    bool ok = true;
+    auto A = [&](auto *& p, size_t bytes) { ok = ok && hipMalloc((void **)&p, bytes + 64) == hipSuccess; };
+    A(gstate_[0], n_slots * n * 4);
+    A(gstate_[1], n_slots * n * 4);
+    A(gsnap_state_, n_slots * n * 4);
+    A(glogits_, n_slots * V * 4);
+    A(gsnap_logits_, n_slots * V * 4);
+    A(gcounts_, n_slots * V * 4);
+    A(gparams_, 4 * (size_t)kBatchMax * 4);
+    A(gstreams_, 2 * (size_t)kBatchMax * 8);
+    A(gwords_, (3 * (size_t)kBatchMax + 1) * 4);
+    ok = ok && hipMemsetAsync(gwords_, 0, (3 * (size_t)kBatchMax + 1) * 4, stream_) == hipSuccess;
+    if (!ok) {
+        (void)hipGetLastError();
+        free_slots();
+        fprintf(stderr, "rwkv: allocation of %zu generation slots failed\n", n_slots);
+        return false;
+    }
+    gslots_ = n_slots;
+    gvalid_.assign(n_slots, 0);
+    return true;
+}
+
+bool Engine::batch_store(size_t slot) {
+    HIP_OK(hipSetDevice(m_->device));
+    if (slot >= gslots_ || !logits_valid_) return false;
+    const size_t n = m_->state_len, V = m_->n_vocab;
+    gvalid_[slot] = 0;
+    HIP_OK(hipMemcpyAsync(gstate_[0] + slot * n, dstate_[cur_], n * 4, hipMemcpyDeviceToDevice, stream_));
+    HIP_OK(hipMemcpyAsync(glogits_ + slot * V, logits_, V * 4, hipMemcpyDeviceToDevice, stream_));
+    // a new sequence in the slot: no token counted yet, not finished
+    HIP_OK(hipMemsetAsync(gcounts_ + slot * V, 0, V * 4, stream_));
+    HIP_OK(hipMemsetAsync(gwords_ + slot, 0, 4, stream_));
+    gvalid_[slot] = 1;
+    return true;
+}
+
+bool Engine::batch_load(size_t slot) {
+    HIP_OK(hipSetDevice(m_->device));
+    if (!batch_slot_valid(slot)) return false;
+    const size_t n = m_->state_len, V = m_->n_vocab;
+    logits_valid_ = false;
+    HIP_OK(hipMemcpyAsync(dstate_[cur_], gstate_[0] + slot * n, n * 4, hipMemcpyDeviceToDevice, stream_));
+    HIP_OK(hipMemcpyAsync(logits_, glogits_ + slot * V, V * 4, hipMemcpyDeviceToDevice, stream_));
+    logits_valid_ = true;
+    return true;
+}
+
+bool Engine::generate_batch(size_t B, const BatchSamplingParams & p, size_t n, uint32_t * tokens_out,
+                            uint32_t * lengths_out, uint32_t * steps_out) {
+    HIP_OK(hipSetDevice(m_->device));
+    if (B == 0 || B > gslots_ || n == 0 || !tokens_out || !lengths_out || !p.temperature || !p.top_p || !p.seed ||
+        !p.offset || p.n_bias > (uint32_t)SAMPLE_MAX_BIAS || p.n_stop > (uint32_t)SAMPLE_MAX_STOP)
+        return false;
+    for (size_t r = 0; r < B; r++)
+        if (!gvalid_[r]) return false;
+    const size_t S = m_->state_len, V = m_->n_vocab, K = (size_t)kBatchMax;
+    // everything that allocates, before anything is enqueued: dtokens_ moves when the workspace
+    // grows (and the batch graphs are dropped with it), the token buffer grows with B * n
+    if (!ensure_workspace((int)B)) return false;
+    if (B * n > gtokens_cap_) {
+        HIP_OK(hipStreamSynchronize(stream_));
+        if (gtokens_) (void)hipFree(gtokens_);
+        gtokens_ = nullptr;
+        gtokens_cap_ = 0;
+        size_t cap = 1024;
+        while (cap < B * n) cap *= 2;
+        HIP_OK(hipMalloc(&gtokens_, cap * 4));
+        gtokens_cap_ = cap;
+    }
+    if (!bias_ids_) HIP_OK(hipMalloc(&bias_ids_, SAMPLE_MAX_BIAS * 4));
+    if (!bias_vals_) HIP_OK(hipMalloc(&bias_vals_, SAMPLE_MAX_BIAS * 4));
+    // from here on a failure leaves the slots of the call undefined
+    auto fail = [&] {
+        (void)hipStreamSynchronize(stream_);
+        (void)handoff_check();
+        for (size_t r = 0; r < B; r++) gvalid_[r] = 0;
+        return false;
+    };
+    gparams_h_.assign(4 * K, 0.0f);
+    gstreams_h_.assign(2 * K, 0);
+    for (size_t r = 0; r < B; r++) {
+        gparams_h_[r] = p.temperature[r];
+        gparams_h_[K + r] = p.top_p[r];
+        gparams_h_[2 * K + r] = p.presence ? p.presence[r] : 0.0f;
+        gparams_h_[3 * K + r] = p.frequency ? p.frequency[r] : 0.0f;
+        gstreams_h_[r] = p.seed[r];
+        gstreams_h_[K + r] = p.offset[r];
+    }
+    bool ok = hipMemcpyAsync(gparams_, gparams_h_.data(), 4 * K * 4, hipMemcpyHostToDevice, stream_) == hipSuccess &&
+              hipMemcpyAsync(gstreams_, gstreams_h_.data(), 2 * K * 8, hipMemcpyHostToDevice, stream_) == hipSuccess;
+    if (ok && p.n_bias)
+        ok = hipMemcpyAsync(bias_ids_, p.bias_ids, p.n_bias * 4, hipMemcpyHostToDevice, stream_) == hipSuccess &&
+             hipMemcpyAsync(bias_vals_, p.bias_values, p.n_bias * 4, hipMemcpyHostToDevice, stream_) == hipSuccess;
+    ok = ok && hipMemsetAsync(gtokens_, 0xff, B * n * 4, stream_) == hipSuccess;
+    if (ok && !p.keep_counts) ok = hipMemsetAsync(gcounts_, 0, B * V * 4, stream_) == hipSuccess;
+    uint32_t *done = gwords_, *length = gwords_ + K, *fin = gwords_ + 2 * K, *active = gwords_ + 3 * K;
+    ok = ok && launch_gen_begin(stream_, (int)B, p.keep_counts ? 1 : 0, done, length, fin, active);
+    if (!ok) return fail();
+
+    SampleArgs a;
+    memset(&a, 0, sizeof(a));
+    a.logits = glogits_;
+    a.rows = (int)B;
+    a.V = (int)V;
+    a.n_bias = (int)p.n_bias;
+    a.bias_ids = bias_ids_;
+    a.bias_vals = bias_vals_;
+    a.temperature_r = gparams_;
+    a.top_p_r = gparams_ + K;
+    a.presence_r = gparams_ + 2 * K;
+    a.frequency_r = gparams_ + 3 * K;
+    a.counts = gcounts_;
+    a.seed_r = gstreams_;
+    a.counter_r = gstreams_ + K;
+    a.n_stop = (int)p.n_stop;
+    for (uint32_t j = 0; j < p.n_stop; j++) a.stop[j] = p.stop_tokens[j];
+    a.done = done;
+    a.length = length;
+    a.fin_step = fin;
+    a.active = active;
+    a.tok = gtokens_;
+    a.tok_stride = (uint32_t)n;
+    a.tok2 = dtokens_;
+    GenRows g{(int)B, S, V, done, fin};
+
+    size_t steps = 0;
+    uint32_t live = 1;
+    for (size_t i = 0; ok && i < n && live; i++) {
+        // the step is a kernel argument of eager launches between the decode graph's replays
+        a.counter = i;
+        a.step = (uint32_t)i;
+        if (timing_) g_klt = this;
+        ok = launch_sample(stream_, a) && launch_gen_snapshot(stream_, g, (uint32_t)i, gstate_[steps & 1], glogits_,
+                                                              gsnap_state_, gsnap_logits_);
+        g_klt = nullptr;
+        ok = ok && eval_batch(nullptr, B, gstate_[steps & 1], gstate_[(steps & 1) ^ 1], glogits_, true);
+        if (!ok) break;
+        steps++;
+        if (p.check_every && (i + 1) % p.check_every == 0 && i + 1 < n) {
+            ok = hipMemcpyAsync(&live, active, 4, hipMemcpyDeviceToHost, stream_) == hipSuccess &&
+                 hipStreamSynchronize(stream_) == hipSuccess;
+        }
+    }
+    if (!ok) return fail();
+    ok = launch_gen_restore(stream_, g, gsnap_state_, gsnap_logits_, gstate_[steps & 1], gstate_[0], glogits_);
+    // [B][n] tokens with the rows n apart, as the caller's
+    ok = ok && hipMemcpyAsync(tokens_out, gtokens_, B * n * 4, hipMemcpyDeviceToHost, stream_) == hipSuccess &&
+         hipMemcpyAsync(lengths_out, length, B * 4, hipMemcpyDeviceToHost, stream_) == hipSuccess;
+    if (!ok) return fail();
+    if (hipStreamSynchronize(stream_) != hipSuccess) return fail();
+    if (!handoff_check()) {
+        for (size_t r = 0; r < B; r++) gvalid_[r] = 0;
+        return false;
+    }
+    if (steps_out) *steps_out = (uint32_t)steps;
+    return true;
 }
 
 // ---------------------------------------------------------------- scoring

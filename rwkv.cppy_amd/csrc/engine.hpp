@@ -123,6 +123,20 @@ struct SamplingParams {
     uint64_t seed = 0, offset = 0;
 };
 
+// rwkv_mi355x_batch_sampling, checked by the caller (include/rwkv_mi355x.h): host arrays of B rows
+struct BatchSamplingParams {
+    const float *temperature = nullptr, *top_p = nullptr;
+    const float *presence = nullptr, *frequency = nullptr;  // may be NULL: 0
+    const uint64_t *seed = nullptr, *offset = nullptr;
+    uint32_t n_bias = 0;
+    const uint32_t * bias_ids = nullptr;
+    const float * bias_values = nullptr;
+    uint32_t n_stop = 0;
+    const uint32_t * stop_tokens = nullptr;
+    bool keep_counts = false;
+    uint32_t check_every = 0;
+};
+
 class Engine : public KLaunchTimer {
   public:
     explicit Engine(DeviceModel * m) : m_(m) {}
@@ -161,6 +175,21 @@ class Engine : public KLaunchTimer {
     bool eval_batch(const uint32_t * tokens, size_t B, const float * state_in, float * state_out, float * logits_out,
                     bool dev);
     static constexpr int kBatchMax = 256;
+    // Batched generation (rwkv_mi355x_generate_batch).  A context owns n_slots <= kBatchMax slots,
+    // each a state and its logits, apart from the context's own state and from eval_batch's staging.
+    // reserve: (re)allocates the slots, all of them invalid afterwards; 0 frees.  store / load: the
+    // context's device state and logits to / from a slot, device to device on the context's stream.
+    // generate_batch over slots [0, B): n times { k_sample_rows on the slots' logits, k_gen_snapshot
+    // of the rows that stopped, one batched decode step of the drawn tokens }, nothing crossing PCIe
+    // but `active` every check_every steps; a finished row's slot ends with the state before its stop
+    // token and the logits that produced it.  A failed call leaves slots [0, B) invalid.
+    bool batch_reserve(size_t n_slots);
+    size_t batch_slots() const { return gslots_; }
+    bool batch_slot_valid(size_t slot) const { return slot < gslots_ && gvalid_[slot]; }
+    bool batch_store(size_t slot);
+    bool batch_load(size_t slot);
+    bool generate_batch(size_t B, const BatchSamplingParams & p, size_t n, uint32_t * tokens_out, uint32_t * lengths_out,
+                        uint32_t * steps_out);
     float * device_logits() const { return logits_; }
     bool state_upload(const float * state);
     bool state_download(float * state);
@@ -355,6 +384,24 @@ class Engine : public KLaunchTimer {
     };
     std::vector<BatchGraph> bgraphs_;
     void drop_batch_graphs();
+    // generation slots (batch_reserve): the live states [2][gslots_][state_len] (slots are stored
+    // in and loaded from gstate_[0]; the batched step alternates the two), the live logits
+    // [gslots_][n_vocab], the finished rows' snapshots of both, the penalty counts
+    // [gslots_][n_vocab], the per-row parameters and the words done / length / fin_step [kBatchMax]
+    // each + active
+    size_t gslots_ = 0;
+    std::vector<char> gvalid_;
+    float * gstate_[2] = {nullptr, nullptr};
+    float *glogits_ = nullptr, *gsnap_state_ = nullptr, *gsnap_logits_ = nullptr;
+    uint32_t * gcounts_ = nullptr;
+    float * gparams_ = nullptr;      // temperature, top_p, presence, frequency: [4][kBatchMax]
+    uint64_t * gstreams_ = nullptr;  // seed, offset: [2][kBatchMax]
+    uint32_t * gwords_ = nullptr;    // done, length, fin_step: [3][kBatchMax], active
+    uint32_t * gtokens_ = nullptr;   // the drawn tokens [B][n] of a call
+    size_t gtokens_cap_ = 0;
+    std::vector<float> gparams_h_;   // the host copies the uploads read
+    std::vector<uint64_t> gstreams_h_;
+    void free_slots();
     // rwkv_eval with host state buffers: the decode as io_chunk_-layer graphs with the state
     // copies of other chunks overlapped (eval_host_chunked)
     bool io_pipeline_ = true;

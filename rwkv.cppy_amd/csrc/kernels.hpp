@@ -200,9 +200,56 @@ struct SampleArgs {
     uint32_t * tok2;             // optional second copy of the tokens (the decode step's input)
     uint32_t * kept;             // optional [rows]: tokens that passed the top-p filter
     float * cutoff;              // optional [rows]: the smallest kept probability
+    // ---- rows with their own parameters (k_sample_rows; launch_sample picks it when any of these
+    // is set, and k_sample, which reads none of them, otherwise).  All device, all optional.
+    const float * temperature_r; // [rows]: replaces temperature
+    const float * top_p_r;       // [rows]: replaces top_p
+    const uint64_t * seed_r;     // [rows] with counter_r: row r draws sample_uniform(seed_r[r],
+    const uint64_t * counter_r;  //        counter_r[r] + counter) -- its own stream, not counter + r
+    // Penalties over the tokens drawn so far (the reference's chat loop: logits[n] -= presence +
+    // counts[n] * frequency before the bias).  For c = counts[r][i] > 0, in float32 and in this
+    // order: l_i = (logit_i - (presence + (float)c * frequency)) + bias_i -- one multiply, one add,
+    // one subtract, none contracted; c == 0 leaves the element alone.  A row whose two penalties are
+    // 0 does not read its counts row.  The drawn token's entry grows by one (whenever counts is set).
+    const float * presence_r;    // [rows]
+    const float * frequency_r;   // [rows]
+    uint32_t * counts;           // [rows][V]
+    // Stops and finished rows.  done[r] != 0: the workgroup writes token 0 to tok2[r] and nothing
+    // else.  A live row writes its token to tok[r * tok_stride + step] and tok2[r], length[r] =
+    // step + 1, and, when the token is one of stop[0 .. n_stop): done[r] = 1, fin_step[r] = step and
+    // *active -= 1 (an integer atomic).
+    int n_stop;                  // <= SAMPLE_MAX_STOP
+    uint32_t stop[16];
+    uint32_t * done;             // [rows]
+    uint32_t * length;           // [rows]
+    uint32_t * fin_step;         // [rows]
+    uint32_t * active;           // one word: the live rows
+    uint32_t step;
+    uint32_t tok_stride;         // 0: tok[r]
 };
+constexpr int SAMPLE_MAX_STOP = 16;
 // One workgroup per row: bias, greedy or top-p / temperature sampling (rwkv_mi355x.h).
 bool launch_sample(hipStream_t st, const SampleArgs & a);
+
+// Batched generation (Engine::generate_batch; sample.hip).  Row r of a [rows][n] buffer is at r * n.
+struct GenRows {
+    int rows;
+    size_t state_len, V;
+    const uint32_t * done;       // [rows]
+    const uint32_t * fin_step;   // [rows]
+};
+// Rows with done[r] != 0 and fin_step[r] == step: state [state_len] and logits [V] of the row are
+// copied from the live buffers into the row's snapshot area.
+bool launch_gen_snapshot(hipStream_t st, const GenRows & g, uint32_t step, const float * state, const float * logits,
+                         float * snap_state, float * snap_logits);
+// The end of a call: a finished row's snapshot goes to state_final / logits; a live row's state is
+// copied from state_live when that is another buffer than state_final (an odd number of steps).
+bool launch_gen_restore(hipStream_t st, const GenRows & g, const float * snap_state, const float * snap_logits,
+                        const float * state_live, float * state_final, float * logits);
+// The start of a call over rows [0, rows): keep == 0 zeroes done; length = 0, fin_step = ~0,
+// *active = the rows with done == 0.
+bool launch_gen_begin(hipStream_t st, int rows, int keep, uint32_t * done, uint32_t * length, uint32_t * fin_step,
+                      uint32_t * active);
 
 // One workgroup per row of logits [rows][V] (xent.hip): loss[r] = -log softmax(row r)[targets[r]]
 // with the exponentials and their sum in fp64, argmax[r] = the lowest index of the row's maximum.

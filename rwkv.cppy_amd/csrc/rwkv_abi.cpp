@@ -639,6 +639,105 @@ RWKV_API bool rwkv_mi355x_generate(struct rwkv_context * ctx, const struct rwkv_
     return true;
 }
 
+// ---- batched generation: every check returns before any GPU call
+static bool batch_ctx_ok(struct rwkv_context * ctx) {
+    CTX_CHECK(ctx, RWKV_ERROR_CTX | RWKV_ERROR_UNSUPPORTED, false, ctx->pipe == nullptr && !ctx->model->dm.partial(),
+              "Batched generation is not supported on a pipeline context");
+    CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, ctx->model->dm.n_vocab <= (uint32_t)SAMPLE_MAX_VOCAB,
+              "The sampler takes vocabularies up to %d tokens", SAMPLE_MAX_VOCAB);
+    return true;
+}
+
+RWKV_API bool rwkv_mi355x_batch_reserve(struct rwkv_context * ctx, size_t n_slots) {
+    if (!ctx || !ctx->engine) return false;
+    ctx->last_error = RWKV_ERROR_NONE;
+    if (!batch_ctx_ok(ctx)) return false;
+    CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, n_slots <= (size_t)Engine::kBatchMax, "%zu generation slots (at most %d)",
+              n_slots, Engine::kBatchMax);
+    use_device(ctx);
+    CTX_CHECK(ctx, RWKV_ERROR_CTX | RWKV_ERROR_ALLOC, false, ctx->engine->batch_reserve(n_slots), "Generation slot allocation failed");
+    return true;
+}
+
+RWKV_API size_t rwkv_mi355x_batch_slots(const struct rwkv_context * ctx) {
+    return ctx && ctx->engine ? ctx->engine->batch_slots() : 0;
+}
+
+RWKV_API bool rwkv_mi355x_batch_store(struct rwkv_context * ctx, size_t slot) {
+    if (!ctx || !ctx->engine) return false;
+    ctx->last_error = RWKV_ERROR_NONE;
+    if (!batch_ctx_ok(ctx)) return false;
+    CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, slot < ctx->engine->batch_slots(), "Slot %zu of %zu reserved", slot,
+              ctx->engine->batch_slots());
+    CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, ctx->engine->logits_valid(),
+              "The device logits do not follow the device state (evaluate with logits first)");
+    use_device(ctx);
+    CTX_CHECK(ctx, RWKV_ERROR_CTX, false, ctx->engine->batch_store(slot), "Storing the slot failed");
+    return true;
+}
+
+RWKV_API bool rwkv_mi355x_batch_load(struct rwkv_context * ctx, size_t slot) {
+    if (!ctx || !ctx->engine) return false;
+    ctx->last_error = RWKV_ERROR_NONE;
+    if (!batch_ctx_ok(ctx)) return false;
+    CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, ctx->engine->batch_slot_valid(slot), "Slot %zu holds nothing", slot);
+    use_device(ctx);
+    CTX_CHECK(ctx, RWKV_ERROR_CTX, false, ctx->engine->batch_load(slot), "Loading the slot failed");
+    return true;
+}
+
+RWKV_API bool rwkv_mi355x_generate_batch(struct rwkv_context * ctx, size_t B, const struct rwkv_mi355x_batch_sampling * p,
+                                         size_t n, uint32_t * tokens_out, uint32_t * lengths_out, uint32_t * steps_out) {
+    if (!ctx || !ctx->engine) return false;
+    ctx->last_error = RWKV_ERROR_NONE;
+    if (!batch_ctx_ok(ctx)) return false;
+    const uint32_t V = ctx->model->dm.n_vocab;
+    CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, B > 0 && B <= ctx->engine->batch_slots(), "Batch of %zu rows with %zu slots reserved",
+              B, ctx->engine->batch_slots());
+    for (size_t r = 0; r < B; r++)
+        CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, ctx->engine->batch_slot_valid(r), "Slot %zu holds nothing", r);
+    CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, n > 0 && n <= 65536, "Token count %zu is outside [1, 65536]", n);
+    CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, p != nullptr, "NULL sampling parameters");
+    CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, tokens_out != nullptr && lengths_out != nullptr, "NULL tokens_out or lengths_out");
+    CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, p->temperature && p->top_p && p->seed && p->offset,
+              "NULL temperature, top_p, seed or offset array");
+    for (size_t r = 0; r < B; r++) {
+        CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, p->temperature[r] >= 0.0f, "Row %zu: temperature %f is negative or NaN", r,
+                  p->temperature[r]);
+        CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, p->top_p[r] >= 0.0f && p->top_p[r] <= 1.0f, "Row %zu: top_p %f is outside [0, 1]",
+                  r, p->top_p[r]);
+        CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, !p->presence || p->presence[r] == p->presence[r], "Row %zu: presence penalty is NaN", r);
+        CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, !p->frequency || p->frequency[r] == p->frequency[r], "Row %zu: frequency penalty is NaN", r);
+    }
+    CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, p->n_bias <= (uint32_t)SAMPLE_MAX_BIAS, "More than %d logit biases", SAMPLE_MAX_BIAS);
+    CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, p->n_bias == 0 || (p->bias_ids != nullptr && p->bias_values != nullptr),
+              "NULL logit bias arrays");
+    for (uint32_t i = 0; i < p->n_bias; i++)
+        CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, p->bias_ids[i] < V, "Logit bias token %u out of range", p->bias_ids[i]);
+    CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, p->n_stop <= (uint32_t)SAMPLE_MAX_STOP, "More than %d stop tokens", SAMPLE_MAX_STOP);
+    CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, p->n_stop == 0 || p->stop_tokens != nullptr, "NULL stop token array");
+    for (uint32_t i = 0; i < p->n_stop; i++)
+        CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, p->stop_tokens[i] < V, "Stop token %u out of range", p->stop_tokens[i]);
+    BatchSamplingParams bp;
+    bp.temperature = p->temperature;
+    bp.top_p = p->top_p;
+    bp.presence = p->presence;
+    bp.frequency = p->frequency;
+    bp.seed = p->seed;
+    bp.offset = p->offset;
+    bp.n_bias = p->n_bias;
+    bp.bias_ids = p->bias_ids;
+    bp.bias_values = p->bias_values;
+    bp.n_stop = p->n_stop;
+    bp.stop_tokens = p->stop_tokens;
+    bp.keep_counts = p->keep_counts != 0;
+    bp.check_every = p->check_every;
+    use_device(ctx);
+    CTX_CHECK(ctx, RWKV_ERROR_CTX, false, ctx->engine->generate_batch(B, bp, n, tokens_out, lengths_out, steps_out),
+              "GPU batched generation failed");
+    return true;
+}
+
 RWKV_API bool rwkv_mi355x_score_sequence(struct rwkv_context * ctx, const uint32_t * tokens, size_t T,
                                          const uint32_t * targets, double * losses_out, uint32_t * argmax_out,
                                          float * logits_out) {

@@ -18,6 +18,12 @@
 // call is a pure function of its inputs.  Chains: 64 serial adds per thread, 6 DPP levels per wave,
 // a 4-level tree over the 16 waves (sums); 6 DPP levels, 6 scan levels, 15 wave offsets (the cdf).
 // Non-finite logits cannot hang or fault it: every loop has a fixed bound and the token is clamped.
+//
+// k_sample_rows is the same arithmetic for a batch of rows that each have their own parameters
+// (rwkv_mi355x_generate_batch): per-row temperature, top_p and draw stream, presence / frequency
+// penalties over a count table, stop tokens and finished rows (SampleArgs in kernels.hpp).
+// k_gen_snapshot / k_gen_restore / k_gen_begin keep the finished rows' states (engine.hip,
+// generate_batch).
 #include "device_common.hpp"
 #include "kernels.hpp"
 
@@ -58,14 +64,68 @@ __device__ __forceinline__ float sm_block_sum(float part, SampleShared & sh, int
     return t[0];
 }
 
-__global__ __launch_bounds__(SM_THREADS) void k_sample(const SampleArgs a) {
-    __shared__ SampleShared sh;
+// The sampler of one row.  ROWS = false is k_sample: one set of parameters for every row.  ROWS =
+// true is k_sample_rows: per-row parameters, penalties, stops and finished rows (SampleArgs); every
+// addition is behind `if constexpr (ROWS)`, so the two kernels share one copy of the arithmetic and
+// k_sample keeps the registers, LDS and occupancy it had before its sibling existed.
+template <bool ROWS>
+__device__ __forceinline__ void sample_row(const SampleArgs & a, SampleShared & sh) {
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int V = a.V, nb = a.n_bias;
     const int nrows = (V + SM_THREADS - 1) / SM_THREADS;  // <= SM_MAX_ROWS (launch_sample)
     const float * lg = a.logits + (size_t)blockIdx.x * (size_t)V;
     const float NEG_INF = __int_as_float(0xff800000);
     int phase = 0;
+    float temperature = a.temperature, top_p = a.top_p;
+    // penalties: pen is uniform over the workgroup
+    bool pen = false;
+    float presence = 0.0f, frequency = 0.0f;
+    const uint32_t * cnt_row = nullptr;
+    if constexpr (ROWS) {
+        const int r = blockIdx.x;
+        if (a.done && a.done[r] != 0) {
+            // a finished row: the decode step still embeds tok2[r], so it gets an id < V
+            if (tid == 0 && a.tok2) a.tok2[r] = 0;
+            return;
+        }
+        if (a.temperature_r) temperature = a.temperature_r[r];
+        if (a.top_p_r) top_p = a.top_p_r[r];
+        if (a.counts) {
+            if (a.presence_r) presence = a.presence_r[r];
+            if (a.frequency_r) frequency = a.frequency_r[r];
+            pen = presence != 0.0f || frequency != 0.0f;
+            cnt_row = a.counts + (size_t)r * (size_t)V;
+        }
+    }
+    // the one thread that holds the drawn token publishes it
+    auto emit = [&](uint32_t t) {
+        if constexpr (!ROWS) {
+            a.tok[blockIdx.x] = t;
+            if (a.tok2) a.tok2[blockIdx.x] = t;
+        } else {
+            const int r = blockIdx.x;
+            a.tok[a.tok_stride ? (size_t)r * a.tok_stride + a.step : (size_t)r] = t;
+            if (a.tok2) a.tok2[r] = t;
+            if (a.length) a.length[r] = a.step + 1u;
+            if (a.counts) {
+                uint32_t * c = a.counts + (size_t)r * (size_t)V + t;
+                *c = *c + 1u;  // no other workgroup touches row r
+            }
+            bool stop = false;
+#pragma unroll
+            for (int j = 0; j < SAMPLE_MAX_STOP; j++) stop = stop || (j < a.n_stop && a.stop[j] == t);
+            if (stop && a.done) {
+                a.done[r] = 1u;
+                if (a.fin_step) a.fin_step[r] = a.step;
+                if (a.active) atomicSub(a.active, 1u);
+            }
+        }
+    };
+    // the penalty of SampleArgs::counts: exactly one multiply, one add, one subtract in float32
+    auto penalized = [&](float x, int i) -> float {
+        const uint32_t c = cnt_row[i];
+        return c > 0u ? __fsub_rn(x, __fadd_rn(presence, __fmul_rn((float)c, frequency))) : x;
+    };
 
     for (int j = tid; j < nb; j += SM_THREADS) {
         sh.bid[j] = a.bias_ids[j];
@@ -78,6 +138,9 @@ __global__ __launch_bounds__(SM_THREADS) void k_sample(const SampleArgs a) {
     // the same additions in the same order as the register copy below
     auto biased = [&](int i) -> float {
         float x = lg[i];
+        if constexpr (ROWS) {
+            if (pen) x = penalized(x, i);
+        }
         for (int j = 0; j < nb; j++)
             if (sh.bid[j] == (uint32_t)i) x += sh.bval[j];
         return x;
@@ -89,6 +152,15 @@ __global__ __launch_bounds__(SM_THREADS) void k_sample(const SampleArgs a) {
         const int i = k * SM_THREADS + tid;
         const float x = lg[min(i, V - 1)];  // a clamped load and a select: no branch per element
         v[k] = i < V ? x : NEG_INF;
+    }
+    if constexpr (ROWS) {
+        if (pen) {
+#pragma unroll
+            for (int k = 0; k < SM_REGS; k++) {
+                const int i = k * SM_THREADS + tid;
+                if (i < V) v[k] = penalized(v[k], i);
+            }
+        }
     }
     for (int j = 0; j < nb; j++) {
         const uint32_t id = sh.bid[j];
@@ -128,11 +200,10 @@ __global__ __launch_bounds__(SM_THREADS) void k_sample(const SampleArgs a) {
         if (ov > bv || (ov == bv && oi < bi)) bv = ov, bi = oi;
     }
     const float m = bv;
-    if (a.temperature == 0.0f) {
+    if (temperature == 0.0f) {
         if (tid == 0) {
             const uint32_t t = (uint32_t)min(max(bi == 0x7fffffff ? 0 : bi, 0), V - 1);
-            a.tok[blockIdx.x] = t;
-            if (a.tok2) a.tok2[blockIdx.x] = t;
+            emit(t);
             if (a.kept) a.kept[blockIdx.x] = 1;
             if (a.cutoff) a.cutoff[blockIdx.x] = 0.0f;
         }
@@ -171,8 +242,8 @@ __global__ __launch_bounds__(SM_THREADS) void k_sample(const SampleArgs a) {
     // fixed-association sum of non-negative terms, so it is monotone in cb and the search is exact;
     // the result is the bit pattern of an element (mass only changes there).
     uint32_t cb = 0u;
-    if (a.top_p > 0.0f && a.top_p < 1.0f) {
-        const float target = a.top_p * S;
+    if (top_p > 0.0f && top_p < 1.0f) {
+        const float target = top_p * S;
         uint32_t lo = 0u, hi = 0x3f800001u;  // e <= 1: mass(hi) = 0
         for (int it = 0; it < 31 && hi - lo > 1u; it++) {
             const uint32_t mid = lo + ((hi - lo) >> 1);
@@ -184,7 +255,7 @@ __global__ __launch_bounds__(SM_THREADS) void k_sample(const SampleArgs a) {
     }
 
     // ---- 4. weights of the kept elements; their count and the largest kept index
-    const bool t1 = a.temperature == 1.0f;
+    const bool t1 = temperature == 1.0f;
     int cnt = 0, last = -1;
 #pragma unroll
     for (int k = 0; k < SM_REGS; k++) {
@@ -193,7 +264,7 @@ __global__ __launch_bounds__(SM_THREADS) void k_sample(const SampleArgs a) {
         if (i < V && __float_as_uint(v[k]) >= cb) {
             cnt++;
             last = i;
-            w = t1 ? v[k] : expf((biased(i) - m) / a.temperature);
+            w = t1 ? v[k] : expf((biased(i) - m) / temperature);
         }
         v[k] = w;
     }
@@ -202,7 +273,7 @@ __global__ __launch_bounds__(SM_THREADS) void k_sample(const SampleArgs a) {
         const float d = biased(i) - m, e = expf(d);
         if (__float_as_uint(e) < cb) return 0.0f;
         if (count) cnt++, last = i;
-        return t1 ? e : expf(d / a.temperature);
+        return t1 ? e : expf(d / temperature);
     };
     // (row, wave) totals in vocabulary order: entry k * 16 + wave covers indices k * 1024 + wave * 64 + lane
 #pragma unroll
@@ -251,7 +322,10 @@ __global__ __launch_bounds__(SM_THREADS) void k_sample(const SampleArgs a) {
     const float Z = carry;
 
     // ---- 5. the draw
-    const float u = a.u ? a.u[blockIdx.x] : sample_uniform(a.seed, a.counter + blockIdx.x);
+    float u;
+    if (a.u) u = a.u[blockIdx.x];
+    else if (ROWS && a.seed_r && a.counter_r) u = sample_uniform(a.seed_r[blockIdx.x], a.counter_r[blockIdx.x] + a.counter);
+    else u = sample_uniform(a.seed, a.counter + blockIdx.x);
     const float target = u * Z;
     for (int e = tid; e < E; e += SM_THREADS)
         if (sh.tab[e] > target) atomicMin(&sh.sel, e);
@@ -287,9 +361,76 @@ __global__ __launch_bounds__(SM_THREADS) void k_sample(const SampleArgs a) {
     } else if (tid != 0) {
         return;
     }
-    const uint32_t t = (uint32_t)min(max(token, 0), V - 1);
-    a.tok[blockIdx.x] = t;
-    if (a.tok2) a.tok2[blockIdx.x] = t;
+    emit((uint32_t)min(max(token, 0), V - 1));
+}
+
+__global__ __launch_bounds__(SM_THREADS) void k_sample(const SampleArgs a) {
+    __shared__ SampleShared sh;
+    sample_row<false>(a, sh);
+}
+
+__global__ __launch_bounds__(SM_THREADS) void k_sample_rows(const SampleArgs a) {
+    __shared__ SampleShared sh;
+    sample_row<true>(a, sh);
+}
+
+// ---- batched generation: the rows' snapshots ------------------------------------------------
+// Copies n floats from src to dst with 16-byte loads and stores; the workgroup takes part `part` of
+// `parts`.  src and dst are at the same offset from 16-byte aligned buffers (row r of [rows][n]
+// arrays), so one scalar head aligns both; n need not be a multiple of 4 (odd vocabularies).
+__device__ __forceinline__ void gen_copy_row(float * dst, const float * src, size_t n, int part, int parts) {
+    const size_t head = min(n, (size_t)((4 - (((uintptr_t)src >> 2) & 3)) & 3));
+    const size_t nvec = (n - head) / 4, tail = head + nvec * 4;
+    if (part == 0) {
+        for (size_t i = threadIdx.x; i < head; i += blockDim.x) dst[i] = src[i];
+        for (size_t i = tail + threadIdx.x; i < n; i += blockDim.x) dst[i] = src[i];
+    }
+    const float4 * s4 = (const float4 *)(src + head);
+    float4 * d4 = (float4 *)(dst + head);
+    for (size_t i = (size_t)part * blockDim.x + threadIdx.x; i < nvec; i += (size_t)parts * blockDim.x) d4[i] = s4[i];
+}
+
+constexpr int GEN_THREADS = 256;
+
+// grid (parts, rows)
+__global__ __launch_bounds__(GEN_THREADS) void k_gen_snapshot(const GenRows g, uint32_t step, const float * state,
+                                                              const float * logits, float * snap_state,
+                                                              float * snap_logits) {
+    const int r = blockIdx.y;
+    if (g.done[r] == 0 || g.fin_step[r] != step) return;
+    gen_copy_row(snap_state + (size_t)r * g.state_len, state + (size_t)r * g.state_len, g.state_len, blockIdx.x, gridDim.x);
+    gen_copy_row(snap_logits + (size_t)r * g.V, logits + (size_t)r * g.V, g.V, blockIdx.x, gridDim.x);
+}
+
+__global__ __launch_bounds__(GEN_THREADS) void k_gen_restore(const GenRows g, const float * snap_state,
+                                                             const float * snap_logits, const float * state_live,
+                                                             float * state_final, float * logits) {
+    const int r = blockIdx.y;
+    if (g.done[r] != 0) {
+        gen_copy_row(state_final + (size_t)r * g.state_len, snap_state + (size_t)r * g.state_len, g.state_len, blockIdx.x,
+                     gridDim.x);
+        gen_copy_row(logits + (size_t)r * g.V, snap_logits + (size_t)r * g.V, g.V, blockIdx.x, gridDim.x);
+    } else if (state_live != state_final) {
+        gen_copy_row(state_final + (size_t)r * g.state_len, state_live + (size_t)r * g.state_len, g.state_len, blockIdx.x,
+                     gridDim.x);
+    }
+}
+
+// one workgroup of GEN_THREADS >= rows threads
+__global__ __launch_bounds__(GEN_THREADS) void k_gen_begin(int rows, int keep, uint32_t * done, uint32_t * length,
+                                                           uint32_t * fin_step, uint32_t * active) {
+    __shared__ unsigned live;
+    const int r = threadIdx.x;
+    if (r == 0) live = 0u;
+    __syncthreads();
+    if (r < rows) {
+        if (!keep) done[r] = 0u;
+        length[r] = 0u;
+        fin_step[r] = 0xffffffffu;
+        if (keep == 0 || done[r] == 0u) atomicAdd(&live, 1u);
+    }
+    __syncthreads();
+    if (r == 0) *active = live;
 }
 
 }  // namespace
@@ -297,7 +438,51 @@ __global__ __launch_bounds__(SM_THREADS) void k_sample(const SampleArgs a) {
 bool launch_sample(hipStream_t st, const SampleArgs & a) {
     if (!a.logits || !a.tok || a.rows < 1 || a.V < 1 || a.V > SAMPLE_MAX_VOCAB) return false;
     if (a.n_bias < 0 || a.n_bias > SAMPLE_MAX_BIAS || (a.n_bias && (!a.bias_ids || !a.bias_vals))) return false;
-    RK_LAUNCH(k_sample, dim3((unsigned)a.rows), dim3(SM_THREADS), 0, st, a);
+    if (a.n_stop < 0 || a.n_stop > SAMPLE_MAX_STOP) return false;
+    const bool rows = a.temperature_r || a.top_p_r || a.seed_r || a.counter_r || a.presence_r || a.frequency_r ||
+                      a.counts || a.n_stop || a.done || a.length || a.fin_step || a.active || a.tok_stride;
+    if (rows) {
+        if ((a.seed_r == nullptr) != (a.counter_r == nullptr)) return false;
+        RK_LAUNCH(k_sample_rows, dim3((unsigned)a.rows), dim3(SM_THREADS), 0, st, a);
+    } else {
+        RK_LAUNCH(k_sample, dim3((unsigned)a.rows), dim3(SM_THREADS), 0, st, a);
+    }
+    HIP_OK(hipGetLastError());
+    return true;
+}
+
+// parts of a row: about 8 vectors a thread, at most 32 workgroups
+static unsigned gen_parts(const GenRows & g) {
+    const size_t vec = (g.state_len + g.V) / 4 + 1;
+    return (unsigned)std::min<size_t>(32, std::max<size_t>(1, vec / (GEN_THREADS * 8)));
+}
+
+static bool gen_rows_ok(const GenRows & g) {
+    return g.rows >= 1 && g.rows <= 65535 && g.done && g.fin_step && g.state_len >= 1 && g.V >= 1;
+}
+
+bool launch_gen_snapshot(hipStream_t st, const GenRows & g, uint32_t step, const float * state, const float * logits,
+                         float * snap_state, float * snap_logits) {
+    if (!gen_rows_ok(g) || !state || !logits || !snap_state || !snap_logits) return false;
+    RK_LAUNCH(k_gen_snapshot, dim3(gen_parts(g), (unsigned)g.rows), dim3(GEN_THREADS), 0, st, g, step, state, logits,
+              snap_state, snap_logits);
+    HIP_OK(hipGetLastError());
+    return true;
+}
+
+bool launch_gen_restore(hipStream_t st, const GenRows & g, const float * snap_state, const float * snap_logits,
+                        const float * state_live, float * state_final, float * logits) {
+    if (!gen_rows_ok(g) || !snap_state || !snap_logits || !state_live || !state_final || !logits) return false;
+    RK_LAUNCH(k_gen_restore, dim3(gen_parts(g), (unsigned)g.rows), dim3(GEN_THREADS), 0, st, g, snap_state, snap_logits,
+              state_live, state_final, logits);
+    HIP_OK(hipGetLastError());
+    return true;
+}
+
+bool launch_gen_begin(hipStream_t st, int rows, int keep, uint32_t * done, uint32_t * length, uint32_t * fin_step,
+                      uint32_t * active) {
+    if (rows < 1 || rows > GEN_THREADS || !done || !length || !fin_step || !active) return false;
+    RK_LAUNCH(k_gen_begin, dim3(1), dim3(GEN_THREADS), 0, st, rows, keep, done, length, fin_step, active);
     HIP_OK(hipGetLastError());
     return true;
 }

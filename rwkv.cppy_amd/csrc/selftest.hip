@@ -233,6 +233,68 @@ extern "C" RWKV_API bool rwkv_mi355x_selftest_sample(const float * logits, int r
     return true;
 }
 
+// The batched sampler kernel (sample.hip, k_sample_rows) on host operands: what
+// rwkv_mi355x_generate_batch launches per step, with the uniform draws given.
+extern "C" RWKV_API bool rwkv_mi355x_selftest_sample_rows(const float * logits, int rows, int V,
+                                                         const struct rwkv_mi355x_batch_sampling * p, const float * u,
+                                                         uint32_t step, uint32_t * counts, uint32_t * done,
+                                                         uint32_t * tokens, uint32_t * decode_tokens, uint32_t * kept,
+                                                         float * cutoff, uint32_t * lengths, uint32_t * active) {
+    if (!logits || !p || !u || !done || !tokens || !decode_tokens || !kept || !cutoff || !lengths || !active) return false;
+    if (rows < 1 || V < 1 || V > SAMPLE_MAX_VOCAB || !p->temperature || !p->top_p) return false;
+    if (p->n_bias > (uint32_t)SAMPLE_MAX_BIAS || (p->n_bias && (!p->bias_ids || !p->bias_values))) return false;
+    if (p->n_stop > (uint32_t)SAMPLE_MAX_STOP || (p->n_stop && !p->stop_tokens)) return false;
+    for (int r = 0; r < rows; r++)
+        if (!(p->temperature[r] >= 0.0f) || !(p->top_p[r] >= 0.0f && p->top_p[r] <= 1.0f)) return false;
+    for (uint32_t i = 0; i < p->n_bias; i++)
+        if (p->bias_ids[i] >= (uint32_t)V) return false;
+    for (uint32_t i = 0; i < p->n_stop; i++)
+        if (p->stop_tokens[i] >= (uint32_t)V) return false;
+    const size_t n = (size_t)rows * V, R = (size_t)rows * 4;
+    DevBufs b;
+    SampleArgs a;
+    memset(&a, 0, sizeof(a));
+    // a device copy of a host array of `bytes` bytes (NULL stays NULL)
+    bool ok = true;
+    auto up = [&](const void * h, size_t bytes) -> void * {
+        if (!h) return nullptr;
+        void * d = b.alloc(bytes);
+        ok = ok && d && hipMemcpy(d, h, bytes, hipMemcpyHostToDevice) == hipSuccess;
+        return d;
+    };
+    a.logits = (const float *)up(logits, n * 4);
+    a.u = (const float *)up(u, R);
+    a.temperature_r = (const float *)up(p->temperature, R);
+    a.top_p_r = (const float *)up(p->top_p, R);
+    a.presence_r = (const float *)up(p->presence, R);
+    a.frequency_r = (const float *)up(p->frequency, R);
+    a.counts = (uint32_t *)up(counts, n * 4);
+    a.done = (uint32_t *)up(done, R);
+    a.tok = (uint32_t *)up(tokens, R);
+    a.tok2 = (uint32_t *)up(decode_tokens, R);
+    a.kept = (uint32_t *)up(kept, R);
+    a.cutoff = (float *)up(cutoff, R);
+    a.length = (uint32_t *)up(lengths, R);
+    a.active = (uint32_t *)up(active, 4);
+    a.fin_step = (uint32_t *)b.alloc(R);
+    a.bias_ids = (const uint32_t *)up(p->n_bias ? p->bias_ids : nullptr, p->n_bias * 4);
+    a.bias_vals = (const float *)up(p->n_bias ? p->bias_values : nullptr, p->n_bias * 4);
+    if (!ok || !a.fin_step) return false;
+    a.rows = rows;
+    a.V = V;
+    a.n_bias = (int)p->n_bias;
+    a.n_stop = (int)p->n_stop;
+    for (uint32_t i = 0; i < p->n_stop; i++) a.stop[i] = p->stop_tokens[i];
+    a.step = step;
+    if (!launch_sample(nullptr, a) || hipDeviceSynchronize() != hipSuccess) return false;
+    const std::pair<void *, const void *> down[] = {{done, a.done},     {tokens, a.tok},     {decode_tokens, a.tok2},
+                                                    {kept, a.kept},     {cutoff, a.cutoff}, {lengths, a.length}};
+    for (const auto & d : down)
+        if (hipMemcpy(d.first, d.second, R, hipMemcpyDeviceToHost) != hipSuccess) return false;
+    if (counts && hipMemcpy(counts, a.counts, n * 4, hipMemcpyDeviceToHost) != hipSuccess) return false;
+    return hipMemcpy(active, a.active, 4, hipMemcpyDeviceToHost) == hipSuccess;
+}
+
 // The scoring kernel (xent.hip) on host operands: what rwkv_mi355x_score_sequence launches per head
 // tile, one workgroup per row.  Targets beyond the row are refused here (the kernel clamps them).
 extern "C" RWKV_API bool rwkv_mi355x_selftest_xent(const float * logits, int rows, int V, const uint32_t * targets,

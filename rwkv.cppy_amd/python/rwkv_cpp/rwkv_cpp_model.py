@@ -183,6 +183,60 @@ class RWKVModel:
             out += tokens
         return out
 
+    # ---- batched generation (rwkv_mi355x_generate_batch) --------------------------------------
+    def batch_reserve(self, n_slots: int) -> None:
+        """MI355X extension: gives the model n_slots <= 256 generation slots (0 frees them).  Every
+        slot is empty afterwards."""
+        if not self._valid:
+            raise ValueError('Model was freed')
+        self._library.rwkv_mi355x_batch_reserve(self._ctx, n_slots)
+
+    def batch_store(self, slot: int) -> None:
+        """MI355X extension: the device state and logits of the last evaluation on this model go into
+        the slot, on the device.  The slot starts a new sequence (no token counted, not finished)."""
+        if not self._valid:
+            raise ValueError('Model was freed')
+        self._library.rwkv_mi355x_batch_store(self._ctx, slot)
+
+    def batch_load(self, slot: int) -> None:
+        """MI355X extension: the model continues from the slot's state and logits; score, sample and
+        generate go on from there."""
+        if not self._valid:
+            raise ValueError('Model was freed')
+        self._library.rwkv_mi355x_batch_load(self._ctx, slot)
+
+    def generate_batch(self, prompts: List[List[int]], n: int, temperature=1.0, top_p=0.8, presence_penalty=0.0,
+                       frequency_penalty=0.0, logit_bias=None, seeds=None, stop_tokens=(),
+                       check_every: int = 16) -> List[List[int]]:
+        """MI355X extension (rwkv_mi355x_generate_batch): generates up to n tokens for every prompt, all
+        rows together on the device: sampling, penalties over the tokens a row has drawn, exact stops
+        and one batched decode step per token, with only the tokens coming back.  temperature, top_p,
+        the penalties and seeds are scalars or one value per prompt (seeds None: row r uses seed r);
+        logit_bias and stop_tokens are shared.  Each prompt is evaluated from a fresh state on the
+        device and stored into slot i (slots are reserved as needed).  Returns one token list per
+        prompt; a list that ends early ends with a stop token, which is not evaluated: slot i then
+        holds the state before it, and batch_load(i) continues from there."""
+        if not self._valid:
+            raise ValueError('Model was freed')
+        rows = len(prompts)
+        if not 0 < rows <= 256:
+            raise ValueError(f'{rows} prompts (1 to 256)')
+        if not n > 0:
+            raise ValueError('n must be > 0')
+        if any(len(p) == 0 for p in prompts):
+            raise ValueError('empty prompt')
+        params = rwkv_cpp_shared_library.make_batch_sampling(
+            rows, temperature, top_p, presence_penalty, frequency_penalty, logit_bias, seeds, 0, stop_tokens,
+            False, check_every)
+        if self._library.rwkv_mi355x_batch_slots(self._ctx) < rows:
+            self._library.rwkv_mi355x_batch_reserve(self._ctx, rows)
+        for slot, prompt in enumerate(prompts):
+            self.reset_state()
+            self._library.rwkv_mi355x_eval_device(self._ctx, list(prompt))
+            self._library.rwkv_mi355x_batch_store(self._ctx, slot)
+        tokens, lengths, _ = self._library.rwkv_mi355x_generate_batch(self._ctx, rows, n, params)
+        return [[int(t) for t in tokens[r][:int(lengths[r])]] for r in range(rows)]
+
     def reset_state(self) -> None:
         """MI355X extension (rwkv_mi355x_state_upload with NULL): the device-resident state becomes the
         fresh state, as before the first token."""

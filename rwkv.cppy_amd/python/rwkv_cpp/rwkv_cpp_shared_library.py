@@ -49,6 +49,63 @@ def make_sampling(temperature: float = 1.0, top_p: float = 0.8, logit_bias=None,
     return p
 
 
+class RWKVBatchSampling(ctypes.Structure):
+    """struct rwkv_mi355x_batch_sampling (include/rwkv_mi355x.h)."""
+    _fields_ = [('temperature', P_FLOAT), ('top_p', P_FLOAT), ('presence', P_FLOAT), ('frequency', P_FLOAT),
+                ('seed', ctypes.POINTER(ctypes.c_uint64)), ('offset', ctypes.POINTER(ctypes.c_uint64)),
+                ('n_bias', ctypes.c_uint32), ('bias_ids', ctypes.POINTER(ctypes.c_uint32)), ('bias_values', P_FLOAT),
+                ('n_stop', ctypes.c_uint32), ('stop_tokens', ctypes.POINTER(ctypes.c_uint32)),
+                ('keep_counts', ctypes.c_uint32), ('check_every', ctypes.c_uint32)]
+
+
+def _per_row(value, rows: int, name: str) -> list:
+    """A scalar repeated for every row, or a sequence of exactly `rows` values."""
+    if hasattr(value, '__len__'):
+        if len(value) != rows:
+            raise ValueError(f'{name}: {len(value)} values for {rows} rows')
+        return list(value)
+    return [value] * rows
+
+
+def make_batch_sampling(rows: int, temperature=1.0, top_p=0.8, presence=None, frequency=None, logit_bias=None,
+                        seeds=None, offsets=0, stop_tokens=(), keep_counts: bool = False,
+                        check_every: int = 0) -> RWKVBatchSampling:
+    """Fills an RWKVBatchSampling for `rows` rows.  temperature, top_p, presence, frequency, seeds and
+    offsets are scalars (the same for every row) or sequences of `rows` values; presence / frequency
+    None leave the structure's pointer NULL (no penalty); seeds None gives row r the seed r.
+    logit_bias: {token id: value}, shared by the rows.  The arrays stay referenced by the returned
+    structure."""
+    if not rows > 0:
+        raise ValueError('rows must be > 0')
+    P_U32, P_U64 = ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_uint64)
+    keep = []
+
+    def floats(value, name):
+        if value is None:
+            return ctypes.cast(None, P_FLOAT)
+        arr = (ctypes.c_float * rows)(*[float(v) for v in _per_row(value, rows, name)])
+        keep.append(arr)
+        return ctypes.cast(arr, P_FLOAT)
+
+    def words(value, name):
+        arr = (ctypes.c_uint64 * rows)(*[int(v) & 0xFFFFFFFFFFFFFFFF for v in _per_row(value, rows, name)])
+        keep.append(arr)
+        return ctypes.cast(arr, P_U64)
+
+    bias = dict(logit_bias or {})
+    ids = (ctypes.c_uint32 * max(1, len(bias)))(*bias.keys())
+    values = (ctypes.c_float * max(1, len(bias)))(*bias.values())
+    stops = list(stop_tokens)
+    stop_arr = (ctypes.c_uint32 * max(1, len(stops)))(*stops)
+    keep += [ids, values, stop_arr]
+    p = RWKVBatchSampling(floats(temperature, 'temperature'), floats(top_p, 'top_p'), floats(presence, 'presence'),
+                          floats(frequency, 'frequency'), words(range(rows) if seeds is None else seeds, 'seeds'),
+                          words(offsets, 'offsets'), len(bias), ctypes.cast(ids, P_U32), ctypes.cast(values, P_FLOAT),
+                          len(stops), ctypes.cast(stop_arr, P_U32), 1 if keep_counts else 0, int(check_every))
+    p._keep = keep
+    return p
+
+
 class RWKVSharedLibrary:
     """Python wrapper around librwkv.so."""
 
@@ -171,6 +228,20 @@ class RWKVSharedLibrary:
         L.rwkv_mi355x_selftest_sample.argtypes = [P_FLOAT, ctypes.c_int, ctypes.c_int, P_SAMPLING, P_FLOAT, P_U32, P_U32,
                                                   P_FLOAT]
         L.rwkv_mi355x_selftest_sample.restype = ctypes.c_bool
+        P_BATCH = ctypes.POINTER(RWKVBatchSampling)
+        L.rwkv_mi355x_batch_reserve.argtypes = [vp, sz]
+        L.rwkv_mi355x_batch_reserve.restype = ctypes.c_bool
+        L.rwkv_mi355x_batch_slots.argtypes = [vp]
+        L.rwkv_mi355x_batch_slots.restype = sz
+        L.rwkv_mi355x_batch_store.argtypes = [vp, sz]
+        L.rwkv_mi355x_batch_store.restype = ctypes.c_bool
+        L.rwkv_mi355x_batch_load.argtypes = [vp, sz]
+        L.rwkv_mi355x_batch_load.restype = ctypes.c_bool
+        L.rwkv_mi355x_generate_batch.argtypes = [vp, sz, P_BATCH, sz, P_U32, P_U32, P_U32]
+        L.rwkv_mi355x_generate_batch.restype = ctypes.c_bool
+        L.rwkv_mi355x_selftest_sample_rows.argtypes = [P_FLOAT, ctypes.c_int, ctypes.c_int, P_BATCH, P_FLOAT, u32, P_U32,
+                                                       P_U32, P_U32, P_U32, P_U32, P_FLOAT, P_U32, P_U32]
+        L.rwkv_mi355x_selftest_sample_rows.restype = ctypes.c_bool
         P_DOUBLE = ctypes.POINTER(ctypes.c_double)
         L.rwkv_mi355x_score_sequence.argtypes = [vp, P_U32, sz, P_U32, P_DOUBLE, P_U32, P_FLOAT]
         L.rwkv_mi355x_score_sequence.restype = ctypes.c_bool
@@ -305,6 +376,80 @@ class RWKVSharedLibrary:
                 tokens.ctypes.data_as(P_U32), kept.ctypes.data_as(P_U32), cutoff.ctypes.data_as(P_FLOAT)):
             raise ValueError('rwkv_mi355x_selftest_sample failed')
         return tokens, kept, cutoff
+
+    def rwkv_mi355x_eval_device(self, ctx: RWKVContext, tokens: List[int], compute_logits: bool = True) -> None:
+        """Evaluates the tokens on the device-resident state (the logits stay on the device);
+        synchronous."""
+        arr = (ctypes.c_int32 * len(tokens))(*tokens)
+        if not self.library.rwkv_mi355x_eval_device(ctx.ptr, ctypes.cast(arr, P_INT), len(tokens), compute_logits,
+                                                    None, True):
+            raise ValueError('rwkv_mi355x_eval_device failed, check stderr')
+
+    # ---- additive: batched generation on the device ------------------------------------------
+    def rwkv_mi355x_batch_reserve(self, ctx: RWKVContext, n_slots: int) -> None:
+        """Gives the context n_slots <= 256 generation slots (0 frees them); every slot is empty."""
+        if not self.library.rwkv_mi355x_batch_reserve(ctx.ptr, n_slots):
+            raise ValueError('rwkv_mi355x_batch_reserve failed, check stderr')
+
+    def rwkv_mi355x_batch_slots(self, ctx: RWKVContext) -> int:
+        return self.library.rwkv_mi355x_batch_slots(ctx.ptr)
+
+    def rwkv_mi355x_batch_store(self, ctx: RWKVContext, slot: int) -> None:
+        """The context's device state and logits go into the slot, which starts a new sequence."""
+        if not self.library.rwkv_mi355x_batch_store(ctx.ptr, slot):
+            raise ValueError('rwkv_mi355x_batch_store failed, check stderr')
+
+    def rwkv_mi355x_batch_load(self, ctx: RWKVContext, slot: int) -> None:
+        """The context continues from the slot's state and logits."""
+        if not self.library.rwkv_mi355x_batch_load(ctx.ptr, slot):
+            raise ValueError('rwkv_mi355x_batch_load failed, check stderr')
+
+    def rwkv_mi355x_generate_batch(self, ctx: RWKVContext, rows: int, n: int, params: RWKVBatchSampling):
+        """Up to n tokens for each of slots [0, rows) (make_batch_sampling).  Returns (tokens uint32
+        [rows, n], 0xFFFFFFFF after a row's last token; lengths uint32 [rows]; the decode steps run)."""
+        import numpy as np
+        tokens = np.zeros((rows, max(1, n)), np.uint32)
+        lengths = np.zeros(rows, np.uint32)
+        steps = ctypes.c_uint32(0)
+        P_U32 = ctypes.POINTER(ctypes.c_uint32)
+        if not self.library.rwkv_mi355x_generate_batch(ctx.ptr, rows, ctypes.byref(params), n,
+                                                       tokens.ctypes.data_as(P_U32), lengths.ctypes.data_as(P_U32),
+                                                       ctypes.byref(steps)):
+            raise ValueError('rwkv_mi355x_generate_batch failed, check stderr')
+        return tokens[:, :n], lengths, steps.value
+
+    def rwkv_mi355x_selftest_sample_rows(self, logits, u, temperature, top_p, presence=None, frequency=None,
+                                         counts=None, done=None, logit_bias=None, stop_tokens=(), step: int = 0,
+                                         fill: int = 0xFFFFFFFF, active: Optional[int] = None):
+        """The batched sampler kernel on host logits [rows][V] with the draws u [rows] given and
+        per-row parameters (scalars or [rows]).  counts (uint32 [rows][V]) and done (uint32 [rows]) are
+        updated in place when given.  Every output starts as `fill` (cutoff: its bits), so an entry
+        the kernel does not write keeps it.  Returns a dict: tokens, decode_tokens, kept, cutoff,
+        lengths, done [rows] and active (the live rows, starting from `active`, default rows)."""
+        import numpy as np
+        logits = np.ascontiguousarray(logits, dtype=np.float32)
+        rows, V = logits.shape
+        u = np.ascontiguousarray(np.broadcast_to(np.asarray(u, dtype=np.float32), (rows,)))
+        p = make_batch_sampling(rows, temperature, top_p, presence, frequency, logit_bias, stop_tokens=stop_tokens)
+        if counts is not None:
+            assert counts.dtype == np.uint32 and counts.shape == (rows, V) and counts.flags['C_CONTIGUOUS']
+        if done is None:
+            done = np.zeros(rows, np.uint32)
+        assert done.dtype == np.uint32 and done.shape == (rows,)
+        out = {k: np.full(rows, fill, np.uint32) for k in ('tokens', 'decode_tokens', 'kept', 'cutoff', 'lengths')}
+        act = np.array([rows if active is None else active], np.uint32)
+        P_U32 = ctypes.POINTER(ctypes.c_uint32)
+        if not self.library.rwkv_mi355x_selftest_sample_rows(
+                logits.ctypes.data_as(P_FLOAT), rows, V, ctypes.byref(p), u.ctypes.data_as(P_FLOAT), step,
+                counts.ctypes.data_as(P_U32) if counts is not None else None, done.ctypes.data_as(P_U32),
+                out['tokens'].ctypes.data_as(P_U32), out['decode_tokens'].ctypes.data_as(P_U32),
+                out['kept'].ctypes.data_as(P_U32), out['cutoff'].ctypes.data_as(P_FLOAT),
+                out['lengths'].ctypes.data_as(P_U32), act.ctypes.data_as(P_U32)):
+            raise ValueError('rwkv_mi355x_selftest_sample_rows failed')
+        out['cutoff'] = out['cutoff'].view(np.float32)
+        out['done'] = done
+        out['active'] = int(act[0])
+        return out
 
     # ---- additive: scoring a sequence on the device ------------------------------------------
     def rwkv_mi355x_score_sequence(self, ctx: RWKVContext, tokens, targets=None, want_logits: bool = False):

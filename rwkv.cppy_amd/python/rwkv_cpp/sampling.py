@@ -63,6 +63,24 @@ def splitmix64(seed: int, counter: int) -> int:
     return z ^ (z >> 31)
 
 
+def penalize(logits, counts, presence: float, frequency: float) -> np.ndarray:
+    """The presence / frequency penalty of librwkv.so's batched sampler (rwkv_mi355x_generate_batch),
+    bit for bit: for every token with counts > 0, in float32 and in this order,
+    logits - (presence + float32(counts) * frequency) -- one multiply, one add, one subtract, each
+    rounded to float32; tokens never drawn are untouched.  Returns a new float32 array.  (The
+    reference's chat loop, chat_with_bot.py:245-274, forms the penalty in double precision: its
+    result can differ from this one by one float32 rounding of the logit.)"""
+    l = np.array(logits, dtype=np.float32, copy=True)
+    c = np.asarray(counts)
+    if c.shape != l.shape:
+        raise ValueError(f'counts {c.shape} for logits {l.shape}')
+    hit = c > 0
+    product = np.multiply(c[hit].astype(np.float32), np.float32(frequency), dtype=np.float32)
+    penalty = np.add(np.float32(presence), product, dtype=np.float32)
+    l[hit] = np.subtract(l[hit], penalty, dtype=np.float32)
+    return l
+
+
 def sample_probs_u(probs: np.ndarray, u: float, temperature: float = 1.0, top_p: float = 0.8,
                    logit_bias: Optional[Dict[int, float]] = None) -> int:
     """sample_probs with the uniform draw u in [0, 1) given instead of an rng: the same bias, top-p
