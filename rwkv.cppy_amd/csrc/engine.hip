@@ -1,5 +1,7 @@
-// engine.hip -- device model upload, the per-version sequence / batched forward programs and the
-// evaluation entry points (the single-token decode program: engine_decode.hip).
+// engine.hip -- the engine core: lifetime, workspace, the per-version sequence / batched forward
+// programs, the state I/O and the evaluation entry points on host or device state.  The
+// single-token decode program: engine_decode.hip; batched decode and generation: engine_batch.hip;
+// sampling, generation and scoring: engine_generate.hip; the weights: model_upload.hip.
 //
 // A token step is a fixed sequence of launches on the context's stream.  The T == 1 step
 // is captured once into a hipGraph per (state parity, logits) and replayed, so decode pays
@@ -37,8 +39,11 @@ static StampCtl g_host_stamp = {nullptr, nullptr};
 static void stamp_init() {
     if (g_host_stamp.buf) return;
     const size_t bytes = (size_t)kStampCUs * kStampRing * 64;
-    if (hipMalloc(&g_host_stamp.buf, bytes) != hipSuccess || hipMalloc(&g_host_stamp.ctr, kStampCUs * 4) != hipSuccess)
-        return;
+    // the process's rings, never freed (static destructors run after the HIP runtime's)
+    static auto & buf = *new DevBuf<unsigned long long>;
+    static auto & ctr = *new DevBuf<unsigned>;
+    if (!buf.alloc(bytes / 8) || !ctr.alloc(kStampCUs)) return;
+    g_host_stamp = {buf, ctr};
     (void)hipMemset(g_host_stamp.buf, 0, bytes);
     (void)hipMemset(g_host_stamp.ctr, 0, kStampCUs * 4);
     for (auto f : stamp_setters()) f(g_host_stamp);
@@ -61,289 +66,6 @@ static void stamp_dump() {
 static void stamp_init() {}
 static void stamp_dump() {}
 #endif
-
-// ------------------------------------------------------------------------- upload
-
-template <typename T>
-static T * dalloc(DeviceModel & dm, size_t n) {
-    void * p = nullptr;
-    if (hipMalloc(&p, n * sizeof(T) + 16) != hipSuccess) return nullptr;
-    dm.allocs.push_back(p);
-    return (T *)p;
-}
-
-static float * upload_vec(DeviceModel & dm, const HostTensor * t) {
-    if (!t) return nullptr;
-    const uint64_t n = t->nel();
-    std::vector<float> v(n);
-    if (t->type == W_F32) {
-        memcpy(v.data(), t->data.data(), n * 4);
-    } else if (t->type == W_F16) {
-        for (uint64_t i = 0; i < n; i++) {
-            uint16_t h;
-            memcpy(&h, t->data.data() + 2 * i, 2);
-            v[i] = f16_to_f32(h);
-        }
-    } else {
-        fprintf(stderr, "rwkv: parameter %s must be FP32/FP16\n", t->name.c_str());
-        return nullptr;
-    }
-    float * d = dalloc<float>(dm, n);
-    if (!d || hipMemcpy(d, v.data(), n * 4, hipMemcpyHostToDevice) != hipSuccess) return nullptr;
-    dm.small_param_bytes += (double)n * 4;
-    return d;
-}
-
-static float * upload_host_floats(DeviceModel & dm, const std::vector<float> & v) {
-    float * d = dalloc<float>(dm, v.size());
-    if (!d || hipMemcpy(d, v.data(), v.size() * 4, hipMemcpyHostToDevice) != hipSuccess) return nullptr;
-    dm.small_param_bytes += (double)v.size() * 4;
-    return d;
-}
-
-// Repack one ggml-order matrix ne=[K, M] into the device layout of common.hpp.
-bool upload_mat(DeviceModel & dm, const HostTensor * t, DMat & out, bool count_bytes, bool is_head) {
-    if (!t) return true;
-    if (t->ndim != 2) {
-        fprintf(stderr, "rwkv: %s: matrix expected\n", t->name.c_str());
-        return false;
-    }
-    out.type = (int)t->type;
-    out.gt = nullptr;
-    out.mt = nullptr;
-    out.K = (int)t->ne[0];
-    out.M = (int)t->ne[1];
-    const size_t M = out.M, K = out.K;
-    if (t->type == W_F32 || t->type == W_F16) {
-        const size_t bytes = t->data.size();
-        uint8_t * d = dalloc<uint8_t>(dm, bytes);
-        if (!d || hipMemcpy(d, t->data.data(), bytes, hipMemcpyHostToDevice) != hipSuccess) return false;
-        out.qs = d;
-    } else {
-        if (K % 32) {
-            fprintf(stderr, "rwkv: %s: K=%zu not a multiple of 32\n", t->name.c_str(), K);
-            return false;
-        }
-        const size_t nb = K / 32, nblk = M * nb, bb = type_block_bytes(t->type);
-        const size_t qbytes = (t->type == W_Q8_0) ? 32 : 16;
-        std::vector<uint8_t> qs(nblk * qbytes);
-        std::vector<uint32_t> qh;
-        std::vector<uint16_t> sc16;
-        std::vector<uint32_t> sc32;
-        const bool q5 = t->type == W_Q5_0 || t->type == W_Q5_1;
-        const bool one = t->type == W_Q4_1 || t->type == W_Q5_1;
-        if (q5) qh.resize(nblk);
-        if (one) sc32.resize(nblk); else sc16.resize(nblk);
-        const uint8_t * src = t->data.data();
-        for (size_t i = 0; i < nblk; i++) {
-            const uint8_t * b = src + i * bb;
-            uint16_t d, mm;
-            memcpy(&d, b, 2);
-            switch (t->type) {
-                case W_Q4_0: sc16[i] = d; memcpy(&qs[i * 16], b + 2, 16); break;
-                case W_Q4_1: memcpy(&mm, b + 2, 2); sc32[i] = (uint32_t)d | ((uint32_t)mm << 16); memcpy(&qs[i * 16], b + 4, 16); break;
-                case W_Q5_0: sc16[i] = d; memcpy(&qh[i], b + 2, 4); memcpy(&qs[i * 16], b + 6, 16); break;
-                case W_Q5_1: memcpy(&mm, b + 2, 2); sc32[i] = (uint32_t)d | ((uint32_t)mm << 16); memcpy(&qh[i], b + 4, 4); memcpy(&qs[i * 16], b + 8, 16); break;
-                case W_Q8_0: sc16[i] = d; memcpy(&qs[i * 32], b + 2, 32); break;
-                default: return false;
-            }
-        }
-        uint8_t * dq = dalloc<uint8_t>(dm, qs.size());
-        if (!dq || hipMemcpy(dq, qs.data(), qs.size(), hipMemcpyHostToDevice) != hipSuccess) return false;
-        out.qs = dq;
-        if (q5) {
-            uint32_t * dh = dalloc<uint32_t>(dm, qh.size());
-            if (!dh || hipMemcpy(dh, qh.data(), qh.size() * 4, hipMemcpyHostToDevice) != hipSuccess) return false;
-            out.qh = dh;
-        }
-        if (one) {
-            uint32_t * ds = dalloc<uint32_t>(dm, sc32.size());
-            if (!ds || hipMemcpy(ds, sc32.data(), sc32.size() * 4, hipMemcpyHostToDevice) != hipSuccess) return false;
-            out.sc = ds;
-        } else {
-            uint16_t * ds = dalloc<uint16_t>(dm, sc16.size());
-            if (!ds || hipMemcpy(ds, sc16.data(), sc16.size() * 2, hipMemcpyHostToDevice) != hipSuccess) return false;
-            out.sc = ds;
-        }
-        // the same blocks again as sequence-GEMM tile records (common.hpp qg_*); the head never
-        // takes that GEMM: it runs on one token, or over rows through the batched decode's forms
-        // (eval_batch, score_chunk)
-        if (!is_head) {
-            const int wt = (int)t->type, R = qg_rows(wt);
-            const size_t tiles = (M + R - 1) / R, rb = qg_w_bytes(wt);
-            std::vector<uint8_t> gt(tiles * nb * rb, 0);
-            for (size_t rt = 0; rt < tiles; rt++)
-                for (size_t b = 0; b < nb; b++) {
-                    uint8_t * rec = &gt[(rt * nb + b) * rb];
-                    for (int r = 0; r < R && rt * R + r < M; r++) {
-                        const size_t i = (rt * R + r) * nb + b;
-                        int8_t * w8 = (int8_t *)rec;
-                        for (int j = 0; j < 32; j++) {
-                            int v;
-                            if (wt == W_Q8_0) {
-                                v = (int8_t)qs[i * 32 + j];
-                            } else {
-                                const uint8_t byte = qs[i * 16 + (j & 15)];
-                                v = j < 16 ? (byte & 0xF) : (byte >> 4);
-                                if (q5) v |= (int)((qh[i] >> j) & 1u) << 4;
-                                if (wt == W_Q4_0) v -= 8;
-                                if (wt == W_Q5_0) v -= 16;
-                            }
-                            w8[qg_w_off(r, j)] = (int8_t)v;
-                        }
-                        const float d = f16_to_f32(one ? (uint16_t)(sc32[i] & 0xFFFFu) : sc16[i]);
-                        memcpy(rec + qg_w_d(wt) + r * 4, &d, 4);
-                    }
-                }
-            uint8_t * dg = dalloc<uint8_t>(dm, gt.size());
-            if (!dg || hipMemcpy(dg, gt.data(), gt.size(), hipMemcpyHostToDevice) != hipSuccess) return false;
-            out.gt = dg;
-            if (one) {  // the mins, block-major, for the m*s chain kernel
-                const size_t MS = qm_stride((int)M);  // rows padded to k_qg_msum's 8-row loads
-                std::vector<float> mt(nb * MS, 0.0f);
-                for (size_t r = 0; r < M; r++)
-                    for (size_t b = 0; b < nb; b++) mt[b * MS + r] = f16_to_f32((uint16_t)(sc32[r * nb + b] >> 16));
-                float * dmt = dalloc<float>(dm, mt.size());
-                if (!dmt || hipMemcpy(dmt, mt.data(), mt.size() * 4, hipMemcpyHostToDevice) != hipSuccess) return false;
-                out.mt = dmt;
-            }
-        }
-    }
-    if (count_bytes) {
-        const double bytes = (double)type_nbytes(t->type, t->nel());
-        const double flops = 2.0 * (double)M * (double)K;
-        if (is_head) {
-            dm.head_weight_bytes += bytes;
-            dm.head_flops += flops;
-        } else {
-            dm.layer_weight_bytes += bytes;
-            dm.layer_flops += flops;
-        }
-    }
-    if (out.K > dm.kmax) dm.kmax = out.K;
-    return true;
-}
-
-bool upload_model(const ModelFile & mf, DeviceModel & dm, uint32_t layer_begin, uint32_t layer_end) {
-    dm.n_vocab = mf.header.n_vocab;
-    dm.n_embed = mf.header.n_embed;
-    dm.n_layer = mf.header.n_layer;
-    dm.layer_lo = std::min(layer_begin, dm.n_layer);
-    dm.layer_hi = std::min(layer_end, dm.n_layer);
-    if (dm.layer_lo >= dm.layer_hi) {
-        fprintf(stderr, "rwkv: empty layer range [%u, %u)\n", layer_begin, layer_end);
-        return false;
-    }
-    const bool first = dm.layer_lo == 0, last = dm.layer_hi == dm.n_layer;
-    dm.major = mf.arch_major;
-    dm.minor = mf.arch_minor;
-    dm.H = mf.head_count;
-    dm.S = mf.head_size;
-    const size_t C = dm.n_embed;
-    dm.state_len = dm.major >= 5 ? C * (2 + (size_t)dm.S) * dm.n_layer : C * 5 * dm.n_layer;
-    if (C % 64) {
-        fprintf(stderr, "rwkv: n_embed %zu must be a multiple of 64\n", C);
-        return false;
-    }
-    auto T = [&](const std::string & n) { return mf.find(n); };
-    // a pipeline stage holds only its layers (+ embedding on the first, head on the last)
-    if (first && (!upload_mat(dm, T("emb.weight"), dm.emb, false, false) ||
-                  !(dm.ln0_w = upload_vec(dm, T("blocks.0.ln0.weight"))) ||
-                  !(dm.ln0_b = upload_vec(dm, T("blocks.0.ln0.bias")))))
-        return false;
-    if (last && (!upload_mat(dm, T("head.weight"), dm.head, true, true) ||
-                 !(dm.lnout_w = upload_vec(dm, T("ln_out.weight"))) || !(dm.lnout_b = upload_vec(dm, T("ln_out.bias")))))
-        return false;
-    dm.layers.resize(dm.n_layer);
-    for (uint32_t i = dm.layer_lo; i < dm.layer_hi; i++) {
-        DLayer & L = dm.layers[i];
-        const std::string p = "blocks." + std::to_string(i) + ".";
-        auto V = [&](const char * n) { return upload_vec(dm, T(p + n)); };
-        auto Mt = [&](const char * n, DMat & d) { return upload_mat(dm, T(p + n), d, true, false); };
-        bool ok = (L.ln1_w = V("ln1.weight")) && (L.ln1_b = V("ln1.bias")) && (L.ln2_w = V("ln2.weight")) &&
-                  (L.ln2_b = V("ln2.bias"));
-        ok = ok && Mt("att.key.weight", L.att_k) && Mt("att.value.weight", L.att_v) &&
-             Mt("att.receptance.weight", L.att_r) && Mt("att.output.weight", L.att_o) &&
-             Mt("ffn.key.weight", L.ffn_k) && Mt("ffn.value.weight", L.ffn_v);
-        if (!ok) return false;
-        dm.F = L.ffn_k.M;
-        if (dm.major != 7 && !Mt("ffn.receptance.weight", L.ffn_r)) return false;
-        if (dm.major == 4 || dm.major == 5) {
-            ok = (L.att_mix_k = V("att.time_mix_k")) && (L.att_mix_v = V("att.time_mix_v")) &&
-                 (L.att_mix_r = V("att.time_mix_r")) && (L.ffn_mix_k = V("ffn.time_mix_k")) &&
-                 (L.ffn_mix_r = V("ffn.time_mix_r"));
-            if (!ok) return false;
-        }
-        if (dm.major == 4) {
-            if (!(L.att_first = V("att.time_first")) || !(L.att_decay = V("att.time_decay"))) return false;
-        }
-        if (dm.major >= 5) {
-            if (!(L.att_lnx_w = V("att.ln_x.weight")) || !(L.att_lnx_b = V("att.ln_x.bias"))) return false;
-        }
-        if (dm.major == 5) {
-            // wkv6 operands u and w expanded to [C] (5.1 repeats per head, rwkv_graph.inc:256-273)
-            const HostTensor * dec = T(p + "att.time_decay");
-            const HostTensor * fu = dm.minor >= 2 ? T(p + "att.time_faaaa") : T(p + "att.time_first");
-            std::vector<float> u(C), w(C);
-            const float * dd = (const float *)dec->data.data();
-            const float * ff = (const float *)fu->data.data();
-            if (dec->type != W_F32 || fu->type != W_F32) return false;
-            for (int64_t h = 0; h < dm.H; h++)
-                for (int64_t j = 0; j < dm.S; j++) {
-                    u[h * dm.S + j] = dm.minor >= 2 ? ff[h * dm.S + j] : ff[h];
-                    w[h * dm.S + j] = dm.minor >= 2 ? dd[h * dm.S + j] : dd[h];
-                }
-            if (!(L.att_u = upload_host_floats(dm, u)) || !(L.att_w = upload_host_floats(dm, w))) return false;
-            if (dm.minor >= 2) {
-                if (!(L.att_mix_g = V("att.time_mix_g")) || !Mt("att.gate.weight", L.att_g)) return false;
-            }
-        }
-        if (dm.major == 6) {
-            ok = (L.maa_x = V("att.time_maa_x")) && (L.maa[0] = V("att.time_maa_w")) && (L.maa[1] = V("att.time_maa_k")) &&
-                 (L.maa[2] = V("att.time_maa_v")) && (L.maa[3] = V("att.time_maa_r")) && (L.maa[4] = V("att.time_maa_g")) &&
-                 (L.maa_w2 = V("att.time_maa_w2")) && (L.att_u = V("att.time_faaaa")) && (L.decay6 = V("att.time_decay")) &&
-                 (L.ffn_maa_k = V("ffn.time_maa_k")) && (L.ffn_maa_r = V("ffn.time_maa_r"));
-            ok = ok && Mt("att.time_maa_w1", L.maa_w1) && Mt("att.time_decay_w1", L.decay_w1) &&
-                 Mt("att.time_decay_w2", L.decay_w2) && Mt("att.gate.weight", L.att_g);
-            if (!ok) return false;
-            dm.maa_D = (int)T(p + "att.time_maa_w2")->ne[0];
-            {
-                const HostTensor * w2 = T(p + "att.time_maa_w2");
-                if (w2->type != W_F32) return false;
-                const size_t D = w2->ne[0], Cc = w2->ne[1];
-                const float * src = (const float *)w2->data.data();
-                std::vector<float> t(5 * D * Cc);
-                for (size_t n = 0; n < 5; n++)
-                    for (size_t c = 0; c < Cc; c++)
-                        for (size_t i = 0; i < D; i++) t[(n * D + i) * Cc + c] = src[(n * Cc + c) * D + i];
-                if (!(L.maa_w2t = upload_host_floats(dm, t))) return false;
-                dm.small_param_bytes -= (double)t.size() * 4;  // same bytes as maa_w2, counted once
-            }
-            if (L.maa_w1.M != 5 * dm.maa_D) {
-                fprintf(stderr, "rwkv: unexpected time_maa_w1 shape\n");
-                return false;
-            }
-        }
-        if (dm.major == 7) {
-            ok = (L.x_rwkvag = V("att.x_rwkvag")) && (L.w0 = V("att.w0")) && (L.a0 = V("att.a0")) &&
-                 (L.k_k = V("att.k_k")) && (L.k_a = V("att.k_a")) && (L.r_k = V("att.r_k")) && (L.ffn_x_k = V("ffn.x_k"));
-            ok = ok && Mt("att.w1", L.w1) && Mt("att.w2", L.w2) && Mt("att.a1", L.a1) && Mt("att.a2", L.a2) &&
-                 Mt("att.g1", L.g1) && Mt("att.g2", L.g2);
-            if (ok && i != 0) ok = (L.v0 = V("att.v0")) && Mt("att.v1", L.v1) && Mt("att.v2", L.v2);
-            if (!ok) return false;
-        }
-    }
-    if (dm.H && dm.S > 64) {
-        fprintf(stderr, "rwkv: head size %lld > 64 unsupported\n", (long long)dm.S);
-        return false;
-    }
-    return hipDeviceSynchronize() == hipSuccess;
-}
-
-void free_model(DeviceModel & dm) {
-    for (void * p : dm.allocs) (void)hipFree(p);
-    dm.allocs.clear();
-}
 
 // ------------------------------------------------------------------------- engine
 
@@ -369,21 +91,7 @@ Engine::~Engine() {
     for (hipEvent_t e : io_ev_) (void)hipEventDestroy(e);
     if (io_entry_ev_) (void)hipEventDestroy(io_entry_ev_);
     drop_batch_graphs();
-    for (float * p : bstate_)
-        if (p) (void)hipFree(p);
-    if (blogits_) (void)hipFree(blogits_);
-    free_slots();
-    if (gtokens_) (void)hipFree(gtokens_);
-    if (gy_) (void)hipFree(gy_);
-    if (part_) (void)hipFree(part_);
-    if (m2_) (void)hipFree(m2_);
-    if (wkvc_) (void)hipFree(wkvc_);
-    if (gen_tokens_) (void)hipFree(gen_tokens_);
-    if (bias_ids_) (void)hipFree(bias_ids_);
-    if (bias_vals_) (void)hipFree(bias_vals_);
-    for (void * p : {(void *)score_tile_, (void *)score_targets_, (void *)score_loss_, (void *)score_argmax_})
-        if (p) (void)hipFree(p);
-    for (void * p : ws_allocs_) (void)hipFree(p);
+    // (device memory: the DevBuf members free themselves)
     if (htokens_) (void)hipHostFree(htokens_);
     if (herr_h_) (void)hipHostFree(herr_h_);
     collect_timing();
@@ -392,15 +100,13 @@ Engine::~Engine() {
     if (stream_) (void)hipStreamDestroy(stream_);
 }
 
-bool GranuleMem::alloc(size_t C, size_t F, std::vector<void *> & allocs) {
-    cleared_n = 6 * C;  // 4 C + H D (D <= 128, H = C / 64)
+bool GranuleMem::alloc(size_t C, size_t F) {
     const size_t kg = (size_t)KG_STRIDE * (F / 32);
-    tagged_n = C + kg + C + C;
-    for (auto [p, n] : {std::pair{&cleared, cleared_n}, std::pair{&y, tagged_n}}) {
-        HIP_OK(hipMalloc(p, n * 8));
-        allocs.push_back(*p);
-        HIP_OK(hipMemset(*p, 0, n * 8));
-    }
+    // cleared: 4 C + H D (D <= 128, H = C / 64)
+    if (!cleared.alloc(6 * C) || !tagged.alloc(C + kg + C + C)) return false;
+    HIP_OK(hipMemset(cleared, 0, cleared.size() * 8));
+    HIP_OK(hipMemset(tagged, 0, tagged.size() * 8));
+    y = tagged;
     k = y + C;
     r = k + kg;
     x = r + C;
@@ -418,18 +124,16 @@ bool Engine::init() {
     HIP_OK(hipStreamCreateWithFlags(&stream_, hipStreamNonBlocking));
     HIP_OK(hipEventCreateWithFlags(&tok_event_, hipEventDisableTiming));
     HIP_OK(hipEventRecord(tok_event_, stream_));
-    for (int i = 0; i < 2; i++) {
-        HIP_OK(hipMalloc(&dstate_[i], m_->state_len * sizeof(float) + 16));
-        ws_allocs_.push_back(dstate_[i]);
+    if (!dstate_[0].alloc(m_->state_len) || !dstate_[1].alloc(m_->state_len) || !logits_.alloc(m_->n_vocab)) {
+        fprintf(stderr, "rwkv: device state and logits allocation failed\n");
+        return false;
     }
-    HIP_OK(hipMalloc(&logits_, (size_t)m_->n_vocab * sizeof(float) + 16));
-    ws_allocs_.push_back(logits_);
     // in-launch hand-offs (handoff.hpp): the timeout flag is a host-mapped word, so checking it
     // costs the host one load after a sync
     HIP_OK(hipHostMalloc((void **)&herr_h_, 64, hipHostMallocMapped | hipHostMallocCoherent));
     *(volatile unsigned *)herr_h_ = 0;
     HIP_OK(hipHostGetDevicePointer((void **)&herr_d_, herr_h_, 0));
-    if (!gran_.alloc(m_->n_embed, (size_t)std::max(m_->F, 32), ws_allocs_)) return false;
+    if (!gran_.alloc(m_->n_embed, (size_t)std::max(m_->F, 32))) return false;
     // Per-context switches read when the context is created (each arm tested):
     const char * io = getenv("RWKV_MI355X_STATE_PIPELINE");  // 0: host state copied whole
     io_pipeline_ = !(io && io[0] == '0');
@@ -487,87 +191,67 @@ bool Engine::choose_co() {
     return co;
 }
 
-bool Engine::ensure_workspace(int T) {
-    if (T <= tcap_) return true;
+bool Engine::settle(unsigned graphs) {
     HIP_OK(hipStreamSynchronize(stream_));
-    drop_graphs();
-    drop_batch_graphs();
-    drop_io_graphs();
-    // keep state and logits, drop the rest; until every allocation below has succeeded the
-    // workspace counts as absent (tcap_ = 0, pointers null), so a failed grow can never leave a
-    // capacity that points at freed or missing buffers
-    std::vector<void *> keep = {dstate_[0], dstate_[1], logits_, gran_.cleared, gran_.y};
-    for (void * p : ws_allocs_) {
-        bool k = false;
-        for (void * q : keep) k |= (p == q);
-        if (!k) (void)hipFree(p);
+    if (graphs & GRAPHS_DECODE) drop_graphs();
+    if (graphs & GRAPHS_IO) drop_io_graphs();
+    if (graphs & GRAPHS_BATCH) drop_batch_graphs();
+    return true;
+}
+
+bool Workspace::alloc(size_t cap, size_t C, size_t kmax, size_t H) {
+    bool ok = true;
+    for (auto * b : {&x_, &xa_, &sx_, &r_, &k_, &v_, &g_, &w_, &y_, &a_, &nb_, &bb_, &vfirst_, &fr_})
+        ok = ok && b->alloc(cap * C);
+    ok = ok && lora_.alloc(cap * kmax) && bonus_.alloc(cap * H);
+    for (auto & b : dsmall_) ok = ok && b.alloc(kmax);
+    ok = ok && dtokens_.alloc(cap);
+    for (auto & s : slots_) {
+        const size_t n = cap * kmax, nbk = n / 32 + 1;
+        // sequence-GEMM token tiles: whole QG_TOK-token tiles, records of up to qg_a_bytes(true)
+        const size_t ttiles = (cap + QG_TOK - 1) / QG_TOK;
+        ok = ok && s.q.alloc(n) && s.d.alloc(nbk) && s.s.alloc(nbk) && s.qsum.alloc(nbk) && s.h.alloc(n) && s.f.alloc(n) &&
+             s.tq.alloc(ttiles * (kmax / 32 + 1) * qg_a_bytes(true));
     }
-    ws_allocs_ = keep;
-    tcap_ = 0;
-    float ** fbufs[] = {&x_, &xa_, &sx_, &r_, &k_, &v_, &g_, &w_, &y_, &a_, &nb_, &bb_, &vfirst_, &fr_, &lora_, &bonus_};
-    for (float ** b : fbufs) *b = nullptr;
-    for (auto & p : dsmall_) p = nullptr;
-    dtokens_ = nullptr;
-    for (auto & s : slots_) s = ActSlot{};
+    return ok;
+}
+
+bool Engine::ensure_workspace(int T) {
+    if ((size_t)T <= dtokens_.size()) return true;
+    if (!settle(GRAPHS_ALL)) return false;
+    // until every allocation below has succeeded the workspace counts as absent (empty buffers),
+    // so a failed grow can never leave a capacity that points at freed or missing buffers
+    static_cast<Workspace &>(*this) = Workspace{};
     HIP_OK(hipEventSynchronize(tok_event_));
     if (htokens_) {
         (void)hipHostFree(htokens_);
         htokens_ = nullptr;
     }
-    int cap = 1;
-    while (cap < T) cap *= 2;
-    const size_t C = m_->n_embed, TC = (size_t)cap * C;
-    bool ok = true;
-    auto A = [&](size_t bytes) -> void * {
-        void * p = nullptr;
-        if (!ok || hipMalloc(&p, bytes + 64) != hipSuccess) {
-            ok = false;
-            return nullptr;
-        }
-        ws_allocs_.push_back(p);
-        return p;
-    };
-    float *x = nullptr, *xa = nullptr, *sx = nullptr, *r = nullptr, *k = nullptr, *v = nullptr, *g = nullptr,
-          *w = nullptr, *y = nullptr, *a = nullptr, *nb = nullptr, *bb = nullptr, *vf = nullptr, *fr = nullptr;
-    float ** locals[] = {&x, &xa, &sx, &r, &k, &v, &g, &w, &y, &a, &nb, &bb, &vf, &fr};
-    for (float ** b : locals) *b = (float *)A(TC * 4);
-    const size_t kmax = std::max<size_t>((size_t)m_->kmax, C);
-    float * lora = (float *)A((size_t)cap * kmax * 4);
-    float * bonus = (float *)A((size_t)cap * std::max<int64_t>(1, m_->H) * 4);
-    float * dsmall[4];
-    for (auto & p : dsmall) p = (float *)A(kmax * 4);
-    uint32_t * dtok = (uint32_t *)A((size_t)cap * 4);
-    ActSlot slots[kSlots];
-    for (auto & s : slots) {
-        const size_t n = (size_t)cap * kmax, nbk = n / 32 + 1;
-        s.q = (int8_t *)A(n);
-        s.d = (float *)A(nbk * 4);
-        s.s = (float *)A(nbk * 4);
-        s.qsum = (int *)A(nbk * 4);
-        s.h = (__half *)A(n * 2);
-        s.f = (float *)A(n * 4);
-        // sequence-GEMM token tiles: whole QG_TOK-token tiles, records of up to qg_a_bytes(true)
-        const size_t ttiles = ((size_t)cap + QG_TOK - 1) / QG_TOK;
-        s.tq = (uint8_t *)A(ttiles * (kmax / 32 + 1) * qg_a_bytes(true));
-    }
+    const size_t cap = doubled(1, (size_t)T), C = m_->n_embed;
+    Workspace ws;
     uint32_t * htok = nullptr;
-    if (ok && hipHostMalloc((void **)&htok, (size_t)cap * 4, hipHostMallocDefault) != hipSuccess) {
-        htok = nullptr;
-        ok = false;
-    }
-    if (!ok) {
+    if (!ws.alloc(cap, C, std::max<size_t>((size_t)m_->kmax, C), (size_t)std::max<int64_t>(1, m_->H)) ||
+        hipHostMalloc((void **)&htok, cap * 4, hipHostMallocDefault) != hipSuccess) {
         (void)hipGetLastError();  // clear the sticky out-of-memory status: later launches check it
-        fprintf(stderr, "rwkv: device workspace allocation for %d tokens failed\n", cap);
-        return false;  // tcap_ stays 0: the next call retries the allocation
+        fprintf(stderr, "rwkv: device workspace allocation for %zu tokens failed\n", cap);
+        return false;  // the workspace stays absent: the next call retries the allocation
     }
-    for (size_t i = 0; i < sizeof(locals) / sizeof(*locals); i++) *fbufs[i] = *locals[i];
-    lora_ = lora;
-    bonus_ = bonus;
-    for (int i = 0; i < 4; i++) dsmall_[i] = dsmall[i];
-    dtokens_ = dtok;
-    for (int i = 0; i < kSlots; i++) slots_[i] = slots[i];
+    static_cast<Workspace &>(*this) = std::move(ws);
     htokens_ = htok;
-    tcap_ = cap;
+    return true;
+}
+
+// the pinned token buffer may still feed the previous (async) call's copy
+bool Engine::stage_tokens(const uint32_t * tokens, size_t n) {
+    HIP_OK(hipEventSynchronize(tok_event_));
+    memcpy(htokens_, tokens, n * 4);
+    HIP_OK(hipMemcpyAsync(dtokens_, htokens_, n * 4, hipMemcpyHostToDevice, stream_));
+    HIP_OK(hipEventRecord(tok_event_, stream_));
+    return true;
+}
+
+bool Engine::copy_logits(float * host_out) {
+    HIP_OK(hipMemcpyAsync(host_out, logits_, (size_t)m_->n_vocab * 4, hipMemcpyDeviceToHost, stream_));
     return true;
 }
 
@@ -645,23 +329,6 @@ void Engine::set_timing(bool on) {
     if (on) stats_.clear();
 }
 
-// Split-K partial scratch of at least n floats (grows; captured batched graphs point at the old one)
-bool Engine::ensure_part(size_t n) {
-    if (n <= part_cap_) return true;
-    HIP_OK(hipStreamSynchronize(stream_));
-    drop_batch_graphs();
-    if (part_) (void)hipFree(part_);
-    part_ = nullptr;
-    part_cap_ = 0;
-    if (hipMalloc(&part_, n * 4 + 64) != hipSuccess) {
-        part_ = nullptr;
-        (void)hipGetLastError();
-        return false;
-    }
-    part_cap_ = n;
-    return true;
-}
-
 // Sequence matmuls on quantized weights go to the int8-MFMA GEMM; entries that only emit get
 // a scratch y, and emission is a separate quantization pass (same bits as k_mm's epilogue).
 bool Engine::mm_dispatch(MMGroup & g, int wtype) {
@@ -681,9 +348,10 @@ bool Engine::mm_dispatch(MMGroup & g, int wtype) {
         }
         if (splittable && blocks < 2 * kQgCUs) {
             const size_t split = (size_t)blocks * 4 >= (size_t)2 * kQgCUs ? 4 : 8;
-            if (!ensure_part(split * g.T * msum)) return false;
+            const size_t pneed = split * g.T * msum;
+            if (!grow(part_, pneed, pneed, GRAPHS_BATCH)) return false;
             g.part = part_;
-            g.part_floats = part_cap_;
+            g.part_floats = part_.size();
         }
     }
     if (bs_ && !(tile_acts_ && wtype_quantized(wtype))) {
@@ -699,19 +367,7 @@ bool Engine::mm_dispatch(MMGroup & g, int wtype) {
     size_t need = 0;
     for (int i = 0; i < g.n; i++)
         if (!g.e[i].y) need += (size_t)g.T * g.e[i].W.M;
-    if (need > gy_cap_) {
-        HIP_OK(hipStreamSynchronize(stream_));
-        drop_batch_graphs();  // captured batched steps point at the old scratch
-        if (gy_) (void)hipFree(gy_);
-        gy_ = nullptr;
-        gy_cap_ = 0;
-        if (hipMalloc(&gy_, need * 4 + 64) != hipSuccess) {
-            gy_ = nullptr;
-            (void)hipGetLastError();
-            return false;
-        }
-        gy_cap_ = need;
-    }
+    if (!grow(gy_, need, need, GRAPHS_BATCH)) return false;
     // split-K partials (launch_qgemm splits groups with few tiles: small T or small M)
     {
         const int rows = qg_rows(wtype), tilesT = (g.T + QG_TOK - 1) / QG_TOK;
@@ -721,27 +377,16 @@ bool Engine::mm_dispatch(MMGroup & g, int wtype) {
             tiles += (size_t)(g.e[i].W.M + rows - 1) / rows * tilesT;
         }
         if (tiles < 1024) {
-            if (!ensure_part((size_t)8 * g.T * msum)) return false;
+            const size_t pneed = (size_t)8 * g.T * msum;
+            if (!grow(part_, pneed, pneed, GRAPHS_BATCH)) return false;
             g.part = part_;
-            g.part_floats = part_cap_;
+            g.part_floats = part_.size();
         }
         if (qg_one(wtype)) {
             const size_t mneed = (size_t)g.T * msum;
-            if (mneed > m2_cap_) {
-                HIP_OK(hipStreamSynchronize(stream_));
-                drop_batch_graphs();
-                if (m2_) (void)hipFree(m2_);
-                m2_ = nullptr;
-                m2_cap_ = 0;
-                if (hipMalloc(&m2_, mneed * 4 + 64) != hipSuccess) {
-                    m2_ = nullptr;
-                    (void)hipGetLastError();
-                    return false;
-                }
-                m2_cap_ = mneed;
-            }
+            if (!grow(m2_, mneed, mneed, GRAPHS_BATCH)) return false;
             g.m2 = m2_;
-            g.m2_floats = m2_cap_;
+            g.m2_floats = m2_.size();
         }
     }
     size_t off = 0;
@@ -928,29 +573,13 @@ bool Engine::layer_v4(int l, int T, const float * si, float * so) {
     return ffn(l, T, si, so);
 }
 
-// The chunked WKV scratch (wkv_chunk.hip, wkv7_chunk.hip), grown on demand.
-bool Engine::ensure_wkvc(size_t need) {
-    if (need <= wkvc_cap_) return true;
-    HIP_OK(hipStreamSynchronize(stream_));
-    if (wkvc_) (void)hipFree(wkvc_);
-    wkvc_ = nullptr;
-    wkvc_cap_ = 0;
-    if (hipMalloc(&wkvc_, need * 4 + 64) != hipSuccess) {
-        wkvc_ = nullptr;
-        (void)hipGetLastError();
-        fprintf(stderr, "rwkv: chunked wkv scratch (%zu MB) allocation failed\n", need * 4 >> 20);
-        return false;
-    }
-    wkvc_cap_ = need;
-    return true;
-}
-
 // v5/v6 sequence wkv: the serial recurrence (k_wkv6_s64, bit-exact with decode), or behind the
 // wkv_chunk_ switch the chunk-parallel form (RA / KB in the v7-only nb_ / bb_ buffers, free during a
 // v5/v6 layer; the chunk matrices and states in wkvc_, grown on demand)
 bool Engine::wkv6(int T, int H, int S, const float * u, const float * w, int wpt, const float * sin, float * sout) {
     if (wkv_chunk_ && wkv6_chunked_supported(T, S, (int)bs_)) {
-        if (!ensure_wkvc(wkv6_chunked_scratch_floats(T, H))) return false;
+        const size_t need = wkv6_chunked_scratch_floats(T, H);
+        if (!grow(wkvc_, need, need, GRAPHS_NONE)) return false;
         return launch_wkv6_chunked(stream_, T, H, k_, v_, r_, u, w, wpt, sin, sout, y_, nb_, bb_, wkvc_);
     }
     return launch_wkv6(stream_, T, H, S, k_, v_, r_, u, w, wpt, sin, sout, y_, (int)bs_);
@@ -1106,7 +735,8 @@ bool Engine::layer_v7(int l, int T, const float * si, float * so) {
     // the serial recurrence (bit-exact with decode), or behind the wkv_chunk_ switch the chunk-parallel
     // form (wkv7_chunk.hip; scratch in wkvc_)
     if (wkv_chunk_ && wkv7_chunked_supported(T, S, (int)bs_)) {
-        if (!ensure_wkvc(wkv7_chunked_scratch_floats(T, H))) return false;
+        const size_t need = wkv7_chunked_scratch_floats(T, H);
+        if (!grow(wkvc_, need, need, GRAPHS_NONE)) return false;
         if (!launch_wkv7_chunked(stream_, T, H, r_, w_, k_, v_, nb_, bb_, si + 2 * C, so + 2 * C, y_, wkvc_)) return false;
     } else if (!launch_wkv7(stream_, T, H, S, r_, w_, k_, v_, nb_, bb_, si + 2 * C, so + 2 * C, y_, (int)bs_)) {
         return false;
@@ -1200,23 +830,6 @@ void Engine::end(const char * kernel) {
     kt_bytes_ = kt_flops_ = 0;
 }
 
-// Captures what build() enqueues on stream_ and instantiates it as ge.  A failed build still ends
-// the capture (the stream has to leave capture mode) before its graph is dropped.
-template <class F>
-bool Engine::capture(hipGraphExec_t & ge, F && build) {
-    hipGraph_t g = nullptr;
-    HIP_OK(hipStreamBeginCapture(stream_, hipStreamCaptureModeThreadLocal));
-    const bool ok = build();
-    HIP_OK(hipStreamEndCapture(stream_, &g));
-    if (!ok) {
-        (void)hipGraphDestroy(g);
-        return false;
-    }
-    HIP_OK(hipGraphInstantiate(&ge, g, nullptr, nullptr, 0));
-    (void)hipGraphDestroy(g);
-    return true;
-}
-
 // Runs T tokens from dstate_[cur_] (ping-pong), chunked by the workspace capacity.
 bool Engine::run_tokens(const uint32_t * tokens, size_t T, bool want_logits) {
     // a failed call restores the ping-pong parity it started with, so the next state upload
@@ -1248,12 +861,8 @@ bool Engine::run_tokens_impl(const uint32_t * tokens, size_t T, bool want_logits
         } else if (n == 1) {
             // one token: a CP write packet in stream order (no blit kernel, no pinned buffer)
             HIP_OK(hipStreamWriteValue32(stream_, dtokens_, tokens[done], 0));
-        } else {
-            // the pinned token buffer may still feed the previous (async) call's copy
-            HIP_OK(hipEventSynchronize(tok_event_));
-            memcpy(htokens_, tokens + done, n * 4);
-            HIP_OK(hipMemcpyAsync(dtokens_, htokens_, n * 4, hipMemcpyHostToDevice, stream_));
-            HIP_OK(hipEventRecord(tok_event_, stream_));
+        } else if (!stage_tokens(tokens + done, n)) {
+            return false;
         }
         // scoring: a one-token chunk's step writes logits_ (score_chunk reads it), longer chunks get
         // their head from score_chunk
@@ -1499,8 +1108,7 @@ bool Engine::eval_host_chunked(uint32_t token, const float * state_in, float * s
         for (uint32_t c = NC >= 2 ? NC - 2 : 0; state_out && c < NC; c++)
             if (!download(c)) return false;
     }
-    if (logits_out)
-        HIP_OK(hipMemcpyAsync(logits_out, logits_, (size_t)m_->n_vocab * 4, hipMemcpyDeviceToHost, stream_));
+    if (logits_out && !copy_logits(logits_out)) return false;
     HIP_OK(hipStreamSynchronize(io_stream_[1]));
     HIP_OK(hipStreamSynchronize(io_stream_[0]));
     HIP_OK(hipStreamSynchronize(stream_));
@@ -1546,8 +1154,7 @@ bool Engine::eval_once(const uint32_t * tokens, size_t T, const float * state_in
     if (!state_upload(state_in)) return false;
     const int cur0 = cur_;
     if (!run_tokens(tokens, T, logits_out != nullptr)) return false;
-    if (logits_out)
-        HIP_OK(hipMemcpyAsync(logits_out, logits_, (size_t)m_->n_vocab * 4, hipMemcpyDeviceToHost, stream_));
+    if (logits_out && !copy_logits(logits_out)) return false;
     if (state_out) {
         HIP_OK(hipMemcpyAsync(state_out, dstate_[cur_], m_->state_len * 4, hipMemcpyDeviceToHost, stream_));
         io_d2h_ += m_->state_len * 4.0;
@@ -1570,10 +1177,7 @@ bool Engine::eval_layers(const uint32_t * tokens, size_t T, uint32_t l0, uint32_
     if (!ensure_workspace((int)T)) return false;
     const size_t bytes = T * (size_t)m_->n_embed * 4;
     if (l0 == 0) {
-        HIP_OK(hipEventSynchronize(tok_event_));
-        memcpy(htokens_, tokens, T * 4);
-        HIP_OK(hipMemcpyAsync(dtokens_, htokens_, T * 4, hipMemcpyHostToDevice, stream_));
-        HIP_OK(hipEventRecord(tok_event_, stream_));
+        if (!stage_tokens(tokens, T)) return false;
     } else {
         HIP_OK(hipMemcpyAsync(x_, x_io, bytes, hipMemcpyDeviceToDevice, stream_));
         if (m_->major == 7) HIP_OK(hipMemcpyAsync(vfirst_, vfirst_io, bytes, hipMemcpyDeviceToDevice, stream_));
@@ -1588,8 +1192,7 @@ bool Engine::eval_layers(const uint32_t * tokens, size_t T, uint32_t l0, uint32_
                           (size_t)(l1 - l0) * per_layer * 4, hipMemcpyDeviceToDevice, stream_));
     if (x_io) HIP_OK(hipMemcpyAsync(x_io, x_, bytes, hipMemcpyDeviceToDevice, stream_));
     if (vfirst_io && m_->major == 7) HIP_OK(hipMemcpyAsync(vfirst_io, vfirst_, bytes, hipMemcpyDeviceToDevice, stream_));
-    if (lg && logits_out)
-        HIP_OK(hipMemcpyAsync(logits_out, logits_, (size_t)m_->n_vocab * 4, hipMemcpyDeviceToHost, stream_));
+    if (lg && logits_out && !copy_logits(logits_out)) return false;
     logits_valid_ = lg;
     if (sync) {
         HIP_OK(hipStreamSynchronize(stream_));
@@ -1605,159 +1208,33 @@ long long Engine::debug_copy(const char * name, void * out, size_t bytes) {
     const std::string n(name);
     const void * src = nullptr;
     size_t cap_bytes = 0;
-    const size_t cap = (size_t)tcap_, C = m_->n_embed;
-    const size_t kmax = std::max<size_t>((size_t)m_->kmax, C);
-    const std::pair<const char *, float *> fb[] = {{"x", x_}, {"xa", xa_}, {"sx", sx_}, {"r", r_}, {"k", k_},
-        {"v", v_}, {"g", g_}, {"w", w_}, {"y", y_}, {"a", a_}, {"nb", nb_}, {"bb", bb_}, {"vfirst", vfirst_},
-        {"fr", fr_}};
+    auto pick = [&](const auto & b) { src = b.get(), cap_bytes = b.size() * sizeof(*b.get()); };
+    const std::pair<const char *, const DevBuf<float> *> fb[] = {{"x", &x_}, {"xa", &xa_}, {"sx", &sx_}, {"r", &r_},
+        {"k", &k_}, {"v", &v_}, {"g", &g_}, {"w", &w_}, {"y", &y_}, {"a", &a_}, {"nb", &nb_}, {"bb", &bb_},
+        {"vfirst", &vfirst_}, {"fr", &fr_}, {"lora", &lora_}, {"bonus", &bonus_}, {"logits", &logits_}};
     for (const auto & p : fb)
-        if (n == p.first) src = p.second, cap_bytes = cap * C * 4;
+        if (n == p.first) pick(*p.second);
     // the fused v7 decode (k_att7_lora) keeps w, a, g and the mixed v in LDS: those buffers hold
     // another evaluation's values, so they are refused rather than returned stale
     if (last_decode_ && v7_fused_lora_ && (n == "w" || n == "a" || n == "g" || n == "v")) return -1;
-    if (n == "lora") src = lora_, cap_bytes = cap * kmax * 4;
-    if (n == "bonus") src = bonus_, cap_bytes = cap * (size_t)std::max<int64_t>(1, m_->H) * 4;
-    if (n == "logits") src = logits_, cap_bytes = (size_t)m_->n_vocab * 4;
-    if (n == "granules") src = gran_.cleared, cap_bytes = gran_.cleared_n * 8;  // the fused v6 attention's
+    if (n == "granules") pick(gran_.cleared);  // the fused v6 attention's
     if (!src && n.rfind("slot", 0) == 0) {
         const size_t dot = n.find('.');
         const int i = atoi(n.c_str() + 4);
         if (dot == std::string::npos || i < 0 || i >= kSlots) return -1;
         const std::string f = n.substr(dot + 1);
         const ActSlot & s = slots_[i];
-        const size_t el = cap * kmax, nbk = el / 32 + 1;
-        if (f == "q") src = s.q, cap_bytes = el;
-        else if (f == "d") src = s.d, cap_bytes = nbk * 4;
-        else if (f == "s") src = s.s, cap_bytes = nbk * 4;
-        else if (f == "qsum") src = s.qsum, cap_bytes = nbk * 4;
-        else if (f == "h") src = s.h, cap_bytes = el * 2;
-        else if (f == "f") src = s.f, cap_bytes = el * 4;
+        if (f == "q") pick(s.q);
+        else if (f == "d") pick(s.d);
+        else if (f == "s") pick(s.s);
+        else if (f == "qsum") pick(s.qsum);
+        else if (f == "h") pick(s.h);
+        else if (f == "f") pick(s.f);
     }
     if (!src || bytes > cap_bytes) return -1;
     if (hipStreamSynchronize(stream_) != hipSuccess || hipMemcpy(out, src, bytes, hipMemcpyDeviceToHost) != hipSuccess)
         return -1;
     return (long long)bytes;
-}
-
-// ---------------------------------------------------------------- batched decode
-// B independent contexts of this model advance one token each in one pass: the layer matmuls
-// run the decode matvec kernel (k_mm) over the B activation rows, so every weight byte is read
-// once per step for all B contexts, and each context's arithmetic is exactly its single-token
-// decode (same lane/block association, same kernels' per-token math); token shift and the wkv
-// recurrences take context t's state at t * state_len (LnMixArgs::bs, launch_wkv* bs).
-// states: [B][state_len] contiguous.  dev: pointers are device memory (else host).
-bool Engine::eval_batch(const uint32_t * tokens, size_t B, const float * state_in, float * state_out,
-                        float * logits_out, bool dev) {
-    HIP_OK(hipSetDevice(m_->device));
-    co_ = false;  // batched decode: the ordered layouts only
-    if (B == 0) return true;
-    if (B > (size_t)kBatchMax) {
-        fprintf(stderr, "rwkv: batched decode takes at most %d contexts (got %zu)\n", kBatchMax, B);
-        return false;
-    }
-    if (!ensure_workspace((int)B)) return false;
-    const size_t n = m_->state_len, V = m_->n_vocab;
-    // tokens == NULL (generate_batch): the tokens are already in dtokens_[0 .. B) (the sampler wrote
-    // them), every buffer is the caller's device memory and nothing is staged
-    if (!tokens && !(dev && state_in && state_out && logits_out)) return false;
-    if (tokens && B > bcap_) {
-        HIP_OK(hipStreamSynchronize(stream_));
-        drop_batch_graphs();
-        for (float *& p : bstate_) {
-            if (p) (void)hipFree(p);
-            p = nullptr;
-        }
-        if (blogits_) (void)hipFree(blogits_);
-        blogits_ = nullptr;
-        bcap_ = 0;
-        size_t cap = 1;
-        while (cap < B) cap *= 2;
-        bool ok = true;
-        for (float *& p : bstate_) ok = ok && hipMalloc(&p, cap * n * 4 + 64) == hipSuccess;
-        ok = ok && hipMalloc(&blogits_, cap * V * 4 + 64) == hipSuccess;
-        if (!ok) {
-            (void)hipGetLastError();
-            for (float *& p : bstate_) {
-                if (p) (void)hipFree(p);
-                p = nullptr;
-            }
-            if (blogits_) (void)hipFree(blogits_);
-            blogits_ = nullptr;
-            fprintf(stderr, "rwkv: batched decode state allocation for %zu contexts failed\n", B);
-            return false;
-        }
-        bcap_ = cap;
-    }
-    // tokens: pinned copy in stream order (the previous call's copy may still read it)
-    if (tokens) {
-        HIP_OK(hipEventSynchronize(tok_event_));
-        memcpy(htokens_, tokens, B * 4);
-        HIP_OK(hipMemcpyAsync(dtokens_, htokens_, B * 4, hipMemcpyHostToDevice, stream_));
-        HIP_OK(hipEventRecord(tok_event_, stream_));
-    }
-    // input states: device pointer as given, else staged into bstate_[0] (NULL = fresh states)
-    const float * sin = state_in;
-    if (!state_in) {
-        RK_LAUNCH(k_init_state, dim3((unsigned)((B * n + 255) / 256)), dim3(256), 0, stream_, bstate_[0],
-                           B * n, (int)m_->n_embed, m_->major == 4 ? 1 : 0);
-        HIP_OK(hipGetLastError());
-        sin = bstate_[0];
-    } else if (!dev) {
-        HIP_OK(hipMemcpyAsync(bstate_[0], state_in, B * n * 4, hipMemcpyHostToDevice, stream_));
-        sin = bstate_[0];
-    }
-    float * sout = (dev && state_out) ? state_out : bstate_[1];
-    float * lout = (dev && logits_out) ? logits_out : blogits_;
-    const bool lg = logits_out != nullptr;
-    // the batched forward: bs_ / head_out_ are set only while it is being enqueued
-    auto step = [&] {
-        bs_ = n;
-        head_out_ = lout;
-        const bool ok = forward_range((int)B, sin, sout, 0, m_->n_layer, lg);
-        bs_ = 0;
-        head_out_ = nullptr;
-        return ok;
-    };
-    bool ok;
-    if (use_graphs_ && !timing_) {
-        // one graph per (B, state pointers, logits pointer): a decode loop alternating two state
-        // buffers replays two graphs
-        hipGraphExec_t ge = nullptr;
-        for (const BatchGraph & g : bgraphs_)
-            if (g.B == B && g.sin == sin && g.sout == sout && g.lout == (lg ? lout : nullptr)) ge = g.ge;
-        if (!ge) {
-            // first step with these buffers: run it eagerly (lazy GEMM scratch allocations happen
-            // here, outside any capture), then capture the graph the next steps replay
-            if (!step()) {
-                (void)hipStreamSynchronize(stream_);
-                return false;
-            }
-            if (bgraphs_.size() >= 8) drop_batch_graphs();
-            if (!capture(ge, step)) return false;
-            bgraphs_.push_back(BatchGraph{B, sin, sout, lg ? lout : nullptr, ge});
-        } else {
-            HIP_OK(hipGraphLaunch(ge, stream_));
-        }
-        ok = true;
-    } else {
-        ok = step();
-    }
-    if (!ok) {
-        (void)hipStreamSynchronize(stream_);
-        return false;
-    }
-    if (!dev) {
-        if (logits_out) HIP_OK(hipMemcpyAsync(logits_out, lout, B * V * 4, hipMemcpyDeviceToHost, stream_));
-        if (state_out) HIP_OK(hipMemcpyAsync(state_out, sout, B * n * 4, hipMemcpyDeviceToHost, stream_));
-        HIP_OK(hipStreamSynchronize(stream_));
-        return handoff_check();
-    }
-    return true;
-}
-
-void Engine::drop_batch_graphs() {
-    for (BatchGraph & g : bgraphs_) (void)hipGraphExecDestroy(g.ge);
-    bgraphs_.clear();
 }
 
 bool Engine::eval_device(const uint32_t * tokens, size_t T, bool want_logits, float * logits_out, bool sync_after) {
@@ -1766,8 +1243,7 @@ bool Engine::eval_device(const uint32_t * tokens, size_t T, bool want_logits, fl
     co_retry_ = false;
     for (int attempt = 0;; attempt++) {
         if (!run_tokens(tokens, T, want_logits || logits_out != nullptr)) return false;
-        if (logits_out)
-            HIP_OK(hipMemcpyAsync(logits_out, logits_, (size_t)m_->n_vocab * 4, hipMemcpyDeviceToHost, stream_));
+        if (logits_out && !copy_logits(logits_out)) return false;
         if (!(sync_after || logits_out)) return true;
         HIP_OK(hipStreamSynchronize(stream_));
         if (handoff_check()) return true;
@@ -1778,357 +1254,6 @@ bool Engine::eval_device(const uint32_t * tokens, size_t T, bool want_logits, fl
         co_retry_ = false;
         cur_ = cur0;
     }
-}
-
-// ---------------------------------------------------------------- sampling / generation
-// The sampler's device buffers, allocated or grown before anything is enqueued (never inside the
-// loop): n token slots and the bias arrays, which are uploaded in stream order.
-bool Engine::sampler_buffers(const SamplingParams & p, size_t n, SampleArgs & a) {
-    if (p.n_bias > (uint32_t)SAMPLE_MAX_BIAS) return false;
-    if (n > gen_cap_) {
-        HIP_OK(hipStreamSynchronize(stream_));
-        if (gen_tokens_) (void)hipFree(gen_tokens_);
-        gen_tokens_ = nullptr;
-        gen_cap_ = 0;
-        size_t cap = 64;
-        while (cap < n) cap *= 2;
-        HIP_OK(hipMalloc(&gen_tokens_, cap * 4));
-        gen_cap_ = cap;
-    }
-    if (!bias_ids_) HIP_OK(hipMalloc(&bias_ids_, SAMPLE_MAX_BIAS * 4));
-    if (!bias_vals_) HIP_OK(hipMalloc(&bias_vals_, SAMPLE_MAX_BIAS * 4));
-    if (p.n_bias) {
-        HIP_OK(hipMemcpyAsync(bias_ids_, p.bias_ids, p.n_bias * 4, hipMemcpyHostToDevice, stream_));
-        HIP_OK(hipMemcpyAsync(bias_vals_, p.bias_values, p.n_bias * 4, hipMemcpyHostToDevice, stream_));
-    }
-    memset(&a, 0, sizeof(a));
-    a.logits = logits_;
-    a.rows = 1;
-    a.V = (int)m_->n_vocab;
-    a.temperature = p.temperature;
-    a.top_p = p.top_p;
-    a.n_bias = (int)p.n_bias;
-    a.bias_ids = bias_ids_;
-    a.bias_vals = bias_vals_;
-    a.seed = p.seed;
-    a.counter = p.offset;
-    a.tok = gen_tokens_;
-    return true;
-}
-
-bool Engine::sample(const SamplingParams & p, uint32_t * token_out) {
-    HIP_OK(hipSetDevice(m_->device));
-    if (!logits_valid_ || !token_out) return false;
-    SampleArgs a;
-    if (!sampler_buffers(p, 1, a) || !launch_sample(stream_, a)) return false;
-    HIP_OK(hipMemcpyAsync(token_out, gen_tokens_, 4, hipMemcpyDeviceToHost, stream_));
-    HIP_OK(hipStreamSynchronize(stream_));
-    return handoff_check();
-}
-
-bool Engine::generate(const SamplingParams & p, size_t n, uint32_t * tokens_out, float * logits_out) {
-    HIP_OK(hipSetDevice(m_->device));
-    if (!logits_valid_ || !tokens_out || n == 0) return false;
-    SampleArgs a;
-    // dtokens_ moves when the workspace grows (the graphs are dropped with it): settle it first
-    if (!ensure_workspace(1) || !sampler_buffers(p, n, a)) return false;
-    const int cur0 = cur_;
-    co_retry_ = false;
-    bool ok = true;
-    for (size_t i = 0; ok && i < n; i++) {
-        // the counter is a kernel argument of an eager launch between the decode graphs' replays:
-        // nothing per step is baked into a captured node
-        a.counter = p.offset + i;
-        a.tok = gen_tokens_ + i;
-        a.tok2 = dtokens_;
-        if (timing_) g_klt = this;
-        ok = launch_sample(stream_, a);
-        g_klt = nullptr;
-        ok = ok && run_tokens(nullptr, 1, true);
-    }
-    if (ok) {
-        ok = hipMemcpyAsync(tokens_out, gen_tokens_, n * 4, hipMemcpyDeviceToHost, stream_) == hipSuccess;
-        if (ok && logits_out)
-            ok = hipMemcpyAsync(logits_out, logits_, (size_t)m_->n_vocab * 4, hipMemcpyDeviceToHost, stream_) == hipSuccess;
-    }
-    ok = (hipStreamSynchronize(stream_) == hipSuccess) && ok;
-    ok = handoff_check() && ok;
-    if (!ok) {
-        // as run_tokens: the parity the call started with; state and logits are unspecified
-        cur_ = cur0;
-        logits_valid_ = false;
-    }
-    return ok;
-}
-
-// ---------------------------------------------------------------- batched generation
-// Slots [0, B) of the context generate together: per step one k_sample_rows launch over the slots'
-// logits (per-row parameters, penalties, stops), k_gen_snapshot of the rows that just stopped, and
-// one batched decode step (eval_batch, tokens already in dtokens_) from gstate_[p] to gstate_[p ^ 1].
-// A finished row keeps being decoded on token 0 -- the batched kernels take row t's state at
-// t * state_len, so leaving a row out would need a per-row offset through every one of them -- and
-// its live state and logits are garbage from then on; what the caller sees is the snapshot, which
-// k_gen_restore puts back into gstate_[0] / glogits_ at the end of the call.
-void Engine::free_slots() {
-    for (void * p : {(void *)gstate_[0], (void *)gstate_[1], (void *)glogits_, (void *)gsnap_state_, (void *)gsnap_logits_,
-                     (void *)gcounts_, (void *)gparams_, (void *)gstreams_, (void *)gwords_})
-        if (p) (void)hipFree(p);
-    gstate_[0] = gstate_[1] = glogits_ = gsnap_state_ = gsnap_logits_ = gparams_ = nullptr;
-    gcounts_ = nullptr;
-    gstreams_ = nullptr;
-    gwords_ = nullptr;
-    gslots_ = 0;
-    gvalid_.clear();
-}
-
-bool Engine::batch_reserve(size_t n_slots) {
-    HIP_OK(hipSetDevice(m_->device));
-    if (n_slots > (size_t)kBatchMax) return false;
-    HIP_OK(hipStreamSynchronize(stream_));
-    drop_batch_graphs();  // they hold the old slots' addresses
-    free_slots();
-    if (n_slots == 0) return true;
-    const size_t n = m_->state_len, V = m_->n_vocab;
-    bool ok = true;
-    auto A = [&](auto *& p, size_t bytes) { ok = ok && hipMalloc((void **)&p, bytes + 64) == hipSuccess; };
-    A(gstate_[0], n_slots * n * 4);
-    A(gstate_[1], n_slots * n * 4);
-    A(gsnap_state_, n_slots * n * 4);
-    A(glogits_, n_slots * V * 4);
-    A(gsnap_logits_, n_slots * V * 4);
-    A(gcounts_, n_slots * V * 4);
-    A(gparams_, 4 * (size_t)kBatchMax * 4);
-    A(gstreams_, 2 * (size_t)kBatchMax * 8);
-    A(gwords_, (3 * (size_t)kBatchMax + 1) * 4);
-    ok = ok && hipMemsetAsync(gwords_, 0, (3 * (size_t)kBatchMax + 1) * 4, stream_) == hipSuccess;
-    if (!ok) {
-        (void)hipGetLastError();
-        free_slots();
-        fprintf(stderr, "rwkv: allocation of %zu generation slots failed\n", n_slots);
-        return false;
-    }
-    gslots_ = n_slots;
-    gvalid_.assign(n_slots, 0);
-    return true;
-}
-
-bool Engine::batch_store(size_t slot) {
-    HIP_OK(hipSetDevice(m_->device));
-    if (slot >= gslots_ || !logits_valid_) return false;
-    const size_t n = m_->state_len, V = m_->n_vocab;
-    gvalid_[slot] = 0;
-    HIP_OK(hipMemcpyAsync(gstate_[0] + slot * n, dstate_[cur_], n * 4, hipMemcpyDeviceToDevice, stream_));
-    HIP_OK(hipMemcpyAsync(glogits_ + slot * V, logits_, V * 4, hipMemcpyDeviceToDevice, stream_));
-    // a new sequence in the slot: no token counted yet, not finished
-    HIP_OK(hipMemsetAsync(gcounts_ + slot * V, 0, V * 4, stream_));
-    HIP_OK(hipMemsetAsync(gwords_ + slot, 0, 4, stream_));
-    gvalid_[slot] = 1;
-    return true;
-}
-
-bool Engine::batch_load(size_t slot) {
-    HIP_OK(hipSetDevice(m_->device));
-    if (!batch_slot_valid(slot)) return false;
-    const size_t n = m_->state_len, V = m_->n_vocab;
-    logits_valid_ = false;
-    HIP_OK(hipMemcpyAsync(dstate_[cur_], gstate_[0] + slot * n, n * 4, hipMemcpyDeviceToDevice, stream_));
-    HIP_OK(hipMemcpyAsync(logits_, glogits_ + slot * V, V * 4, hipMemcpyDeviceToDevice, stream_));
-    logits_valid_ = true;
-    return true;
-}
-
-bool Engine::generate_batch(size_t B, const BatchSamplingParams & p, size_t n, uint32_t * tokens_out,
-                            uint32_t * lengths_out, uint32_t * steps_out) {
-    HIP_OK(hipSetDevice(m_->device));
-    if (B == 0 || B > gslots_ || n == 0 || !tokens_out || !lengths_out || !p.temperature || !p.top_p || !p.seed ||
-        !p.offset || p.n_bias > (uint32_t)SAMPLE_MAX_BIAS || p.n_stop > (uint32_t)SAMPLE_MAX_STOP)
-        return false;
-    for (size_t r = 0; r < B; r++)
-        if (!gvalid_[r]) return false;
-    const size_t S = m_->state_len, V = m_->n_vocab, K = (size_t)kBatchMax;
-    // everything that allocates, before anything is enqueued: dtokens_ moves when the workspace
-    // grows (and the batch graphs are dropped with it), the token buffer grows with B * n
-    if (!ensure_workspace((int)B)) return false;
-    if (B * n > gtokens_cap_) {
-        HIP_OK(hipStreamSynchronize(stream_));
-        if (gtokens_) (void)hipFree(gtokens_);
-        gtokens_ = nullptr;
-        gtokens_cap_ = 0;
-        size_t cap = 1024;
-        while (cap < B * n) cap *= 2;
-        HIP_OK(hipMalloc(&gtokens_, cap * 4));
-        gtokens_cap_ = cap;
-    }
-    if (!bias_ids_) HIP_OK(hipMalloc(&bias_ids_, SAMPLE_MAX_BIAS * 4));
-    if (!bias_vals_) HIP_OK(hipMalloc(&bias_vals_, SAMPLE_MAX_BIAS * 4));
-    // from here on a failure leaves the slots of the call undefined
-    auto fail = [&] {
-        (void)hipStreamSynchronize(stream_);
-        (void)handoff_check();
-        for (size_t r = 0; r < B; r++) gvalid_[r] = 0;
-        return false;
-    };
-    gparams_h_.assign(4 * K, 0.0f);
-    gstreams_h_.assign(2 * K, 0);
-    for (size_t r = 0; r < B; r++) {
-        gparams_h_[r] = p.temperature[r];
-        gparams_h_[K + r] = p.top_p[r];
-        gparams_h_[2 * K + r] = p.presence ? p.presence[r] : 0.0f;
-        gparams_h_[3 * K + r] = p.frequency ? p.frequency[r] : 0.0f;
-        gstreams_h_[r] = p.seed[r];
-        gstreams_h_[K + r] = p.offset[r];
-    }
-    bool ok = hipMemcpyAsync(gparams_, gparams_h_.data(), 4 * K * 4, hipMemcpyHostToDevice, stream_) == hipSuccess &&
-              hipMemcpyAsync(gstreams_, gstreams_h_.data(), 2 * K * 8, hipMemcpyHostToDevice, stream_) == hipSuccess;
-    if (ok && p.n_bias)
-        ok = hipMemcpyAsync(bias_ids_, p.bias_ids, p.n_bias * 4, hipMemcpyHostToDevice, stream_) == hipSuccess &&
-             hipMemcpyAsync(bias_vals_, p.bias_values, p.n_bias * 4, hipMemcpyHostToDevice, stream_) == hipSuccess;
-    ok = ok && hipMemsetAsync(gtokens_, 0xff, B * n * 4, stream_) == hipSuccess;
-    if (ok && !p.keep_counts) ok = hipMemsetAsync(gcounts_, 0, B * V * 4, stream_) == hipSuccess;
-    uint32_t *done = gwords_, *length = gwords_ + K, *fin = gwords_ + 2 * K, *active = gwords_ + 3 * K;
-    ok = ok && launch_gen_begin(stream_, (int)B, p.keep_counts ? 1 : 0, done, length, fin, active);
-    if (!ok) return fail();
-
-    SampleArgs a;
-    memset(&a, 0, sizeof(a));
-    a.logits = glogits_;
-    a.rows = (int)B;
-    a.V = (int)V;
-    a.n_bias = (int)p.n_bias;
-    a.bias_ids = bias_ids_;
-    a.bias_vals = bias_vals_;
-    a.temperature_r = gparams_;
-    a.top_p_r = gparams_ + K;
-    a.presence_r = gparams_ + 2 * K;
-    a.frequency_r = gparams_ + 3 * K;
-    a.counts = gcounts_;
-    a.seed_r = gstreams_;
-    a.counter_r = gstreams_ + K;
-    a.n_stop = (int)p.n_stop;
-    for (uint32_t j = 0; j < p.n_stop; j++) a.stop[j] = p.stop_tokens[j];
-    a.done = done;
-    a.length = length;
-    a.fin_step = fin;
-    a.active = active;
-    a.tok = gtokens_;
-    a.tok_stride = (uint32_t)n;
-    a.tok2 = dtokens_;
-    GenRows g{(int)B, S, V, done, fin};
-
-    size_t steps = 0;
-    uint32_t live = 1;
-    for (size_t i = 0; ok && i < n && live; i++) {
-        // the step is a kernel argument of eager launches between the decode graph's replays
-        a.counter = i;
-        a.step = (uint32_t)i;
-        if (timing_) g_klt = this;
-        ok = launch_sample(stream_, a) && launch_gen_snapshot(stream_, g, (uint32_t)i, gstate_[steps & 1], glogits_,
-                                                              gsnap_state_, gsnap_logits_);
-        g_klt = nullptr;
-        ok = ok && eval_batch(nullptr, B, gstate_[steps & 1], gstate_[(steps & 1) ^ 1], glogits_, true);
-        if (!ok) break;
-        steps++;
-        if (p.check_every && (i + 1) % p.check_every == 0 && i + 1 < n) {
-            ok = hipMemcpyAsync(&live, active, 4, hipMemcpyDeviceToHost, stream_) == hipSuccess &&
-                 hipStreamSynchronize(stream_) == hipSuccess;
-        }
-    }
-    if (!ok) return fail();
-    ok = launch_gen_restore(stream_, g, gsnap_state_, gsnap_logits_, gstate_[steps & 1], gstate_[0], glogits_);
-    // [B][n] tokens with the rows n apart, as the caller's
-    ok = ok && hipMemcpyAsync(tokens_out, gtokens_, B * n * 4, hipMemcpyDeviceToHost, stream_) == hipSuccess &&
-         hipMemcpyAsync(lengths_out, length, B * 4, hipMemcpyDeviceToHost, stream_) == hipSuccess;
-    if (!ok) return fail();
-    if (hipStreamSynchronize(stream_) != hipSuccess) return fail();
-    if (!handoff_check()) {
-        for (size_t r = 0; r < B; r++) gvalid_[r] = 0;
-        return false;
-    }
-    if (steps_out) *steps_out = (uint32_t)steps;
-    return true;
-}
-
-// ---------------------------------------------------------------- scoring
-// The scorer's device buffers, allocated or grown before anything is enqueued: T targets, losses
-// and argmaxes, and (T > 1: some chunk has more than one token) the head tile.
-bool Engine::score_buffers(size_t T) {
-    if (T > score_cap_) {
-        HIP_OK(hipStreamSynchronize(stream_));
-        for (void * p : {(void *)score_targets_, (void *)score_loss_, (void *)score_argmax_})
-            if (p) (void)hipFree(p);
-        score_targets_ = score_argmax_ = nullptr;
-        score_loss_ = nullptr;
-        score_cap_ = 0;
-        size_t cap = 1024;
-        while (cap < T) cap *= 2;
-        const bool ok = hipMalloc(&score_targets_, cap * 4) == hipSuccess && hipMalloc(&score_loss_, cap * 8) == hipSuccess &&
-                        hipMalloc(&score_argmax_, cap * 4) == hipSuccess;
-        if (!ok) {
-            (void)hipGetLastError();
-            fprintf(stderr, "rwkv: scoring buffers for %zu tokens failed\n", cap);
-            return false;  // score_cap_ stays 0: the next call frees what was allocated and retries
-        }
-        score_cap_ = cap;
-    }
-    if (T > 1 && !score_tile_ && hipMalloc(&score_tile_, (size_t)kScoreRows * m_->n_vocab * 4 + 64) != hipSuccess) {
-        score_tile_ = nullptr;
-        (void)hipGetLastError();
-        fprintf(stderr, "rwkv: head tile of %d rows failed to allocate\n", kScoreRows);
-        return false;
-    }
-    return true;
-}
-
-// After the layers of tokens [done, done + n) of a score() call: x_ holds their n final residual
-// rows (n > 1), or the decode program's head has written logits_ (n == 1).
-bool Engine::score_chunk(size_t done, size_t n, bool last) {
-    const size_t C = m_->n_embed, V = m_->n_vocab;
-    const bool want_loss = score_->targets != nullptr;
-    if (want_loss)
-        HIP_OK(hipMemcpyAsync(score_targets_ + done, score_->targets + done, n * 4, hipMemcpyHostToDevice, stream_));
-    auto reduce = [&](const float * lg, size_t row0, int rows) {
-        const size_t at = done + row0;
-        if (!launch_xent(stream_, lg, rows, (int)V, want_loss ? score_targets_ + at : nullptr,
-                         want_loss ? score_loss_ + at : nullptr, score_argmax_ + at))
-            return false;
-        if (score_->logits_out) {
-            // the next tile (or step) overwrites lg: the copy has landed before it is enqueued
-            HIP_OK(hipMemcpyAsync(score_->logits_out + at * V, lg, (size_t)rows * V * 4, hipMemcpyDeviceToHost, stream_));
-            HIP_OK(hipStreamSynchronize(stream_));
-        }
-        return true;
-    };
-    if (n == 1) return reduce(logits_, 0, 1);
-    for (size_t row0 = 0; row0 < n; row0 += (size_t)kScoreRows) {
-        const int rows = (int)std::min(n - row0, (size_t)kScoreRows);
-        // the head over `rows` rows as batched decode runs it over that many contexts (mm_dispatch:
-        // k_fmm, k_mvb or k_mm, each row the bits of its one-token head); never the sequence GEMM,
-        // for which the head has no tile records (upload_mat)
-        bs_ = m_->state_len;
-        const bool ok = head_rows(x_ + row0 * C, rows, score_tile_);
-        bs_ = 0;
-        if (!ok || !reduce(score_tile_, row0, rows)) return false;
-        if (last && row0 + rows == n)
-            HIP_OK(hipMemcpyAsync(logits_, score_tile_ + (size_t)(rows - 1) * V, V * 4, hipMemcpyDeviceToDevice, stream_));
-    }
-    return true;
-}
-
-bool Engine::score(const uint32_t * tokens, size_t T, const uint32_t * targets, double * losses_out,
-                   uint32_t * argmax_out, float * logits_out) {
-    HIP_OK(hipSetDevice(m_->device));
-    if (!tokens || T == 0 || (targets != nullptr) != (losses_out != nullptr) || !score_buffers(T)) return false;
-    ScoreRun run{targets, logits_out};
-    co_retry_ = false;
-    score_ = &run;
-    const bool ok = run_tokens(tokens, T, true);
-    score_ = nullptr;
-    if (!ok) return false;
-    if (losses_out) HIP_OK(hipMemcpyAsync(losses_out, score_loss_, T * 8, hipMemcpyDeviceToHost, stream_));
-    if (argmax_out) HIP_OK(hipMemcpyAsync(argmax_out, score_argmax_, T * 4, hipMemcpyDeviceToHost, stream_));
-    HIP_OK(hipStreamSynchronize(stream_));
-    // a hand-off timeout in a one-token chunk: nothing is re-run (the state has moved on)
-    return handoff_check();
 }
 
 }  // namespace rwkvmi

@@ -1,10 +1,13 @@
 // engine.hpp -- device-resident RWKV model and the per-version forward programs.
 #pragma once
 
+#include <stdio.h>
+
 #include <string>
 #include <vector>
 
 #include "common.hpp"
+#include "devbuf.hpp"
 #include "kernels.hpp"
 #include "model_file.hpp"
 
@@ -58,36 +61,60 @@ bool upload_mat(DeviceModel & dm, const HostTensor * t, DMat & out, bool count_b
 void free_model(DeviceModel & dm);
 
 struct ActSlot {
-    int8_t * q = nullptr;
-    float * d = nullptr;
-    float * s = nullptr;
-    int * qsum = nullptr;
-    __half * h = nullptr;
-    float * f = nullptr;
-    uint8_t * tq = nullptr;  // sequence-GEMM token-tile records
+    DevBuf<int8_t> q;
+    DevBuf<float> d, s;
+    DevBuf<int> qsum;
+    DevBuf<__half> h;
+    DevBuf<float> f;
+    DevBuf<uint8_t> tq;  // sequence-GEMM token-tile records
+};
+
+// The buffers sized by the token capacity.  Engine::ensure_workspace builds a fresh one and moves
+// it into the engine (its private base, so the members keep their names) once it is complete.
+struct Workspace {
+    static constexpr int kSlots = 12;
+    DevBuf<float> x_, xa_, sx_, r_, k_, v_, g_, w_, y_, a_, nb_, bb_, vfirst_, fr_;  // [cap][C]
+    DevBuf<float> lora_, bonus_;  // [cap][kmax], [cap][H]
+    DevBuf<float> dsmall_[4];     // decode LoRA intermediates [kmax]
+    DevBuf<uint32_t> dtokens_;    // [cap]
+    ActSlot slots_[kSlots];
+    bool alloc(size_t cap, size_t C, size_t kmax, size_t H);
+};
+
+// The generation slots' buffers (Engine::batch_reserve), replaced as a whole in the same way: the
+// live states [2][slots][state_len] (slots are stored in and loaded from gstate_[0]; the batched step
+// alternates the two), the live logits [slots][n_vocab], the finished rows' snapshots of both, the
+// penalty counts [slots][n_vocab], the per-row parameters and the words
+struct GenSlots {
+    DevBuf<float> gstate_[2], glogits_, gsnap_state_, gsnap_logits_;
+    DevBuf<uint32_t> gcounts_;
+    DevBuf<float> gparams_;      // temperature, top_p, presence, frequency: [4][kBatchMax]
+    DevBuf<uint64_t> gstreams_;  // seed, offset: [2][kBatchMax]
+    DevBuf<uint32_t> gwords_;    // done, length, fin_step: [3][kBatchMax], active
+    bool alloc(size_t n_slots, size_t state_len, size_t n_vocab, size_t batch_max);
 };
 
 // The granule memory of the in-launch hand-offs (handoff.hpp; DESIGN.md "The hand-off protocol").
 struct GranuleMem {
     // cleared granules (tag 1, zeroed here and re-armed by their one reader): the fused v6
     // attention's r, k, v, g [4 C] and decay-LoRA values [H D]
-    unsigned long long * cleared = nullptr;
+    DevBuf<unsigned long long> cleared;
     // tagged granules (Engine::handoff_tag, never cleared by their readers), one allocation: y [C]
     // head / channel outputs -> fused Wo rows; k [KG_STRIDE F / 32] FFN key blocks and r [C]
     // receptance rows -> fused FFN value rows; x [C] v6 x rows -> the next layer's maa (k_sig_maa)
+    DevBuf<unsigned long long> tagged;
     unsigned long long *y = nullptr, *k = nullptr, *r = nullptr, *x = nullptr;
-    size_t cleared_n = 0, tagged_n = 0;
-    bool alloc(size_t C, size_t F, std::vector<void *> & allocs);
+    bool alloc(size_t C, size_t F);
     // A tag names a layer and a state parity, so a step that flips the parity without running the
     // fused decode (a sequence chunk, the generic decode, a decode program without the hand-off
     // after a debug knob changed) leaves the granules of the decode before it in place: the next
     // decode runs at that decode's parity again and could take a stale value for its own (one-layer
     // engines: the same layer tag).  So does a failed call that is replayed at the parity it started
     // with.  Every such step clears the tagged granules in stream order.
-    hipError_t clear_tagged(hipStream_t st) const { return hipMemsetAsync(y, 0, tagged_n * 8, st); }
+    hipError_t clear_tagged(hipStream_t st) const { return hipMemsetAsync(tagged, 0, tagged.size() * 8, st); }
     // after a timeout: a producer that arrived late left its granule set, cleared or tagged
     void clear_all(hipStream_t st) const {
-        (void)hipMemsetAsync(cleared, 0, cleared_n * 8, st);
+        (void)hipMemsetAsync(cleared, 0, cleared.size() * 8, st);
         (void)clear_tagged(st);
     }
 };
@@ -137,7 +164,7 @@ struct BatchSamplingParams {
     uint32_t check_every = 0;
 };
 
-class Engine : public KLaunchTimer {
+class Engine : public KLaunchTimer, private Workspace, private GenSlots {
   public:
     explicit Engine(DeviceModel * m) : m_(m) {}
     ~Engine();
@@ -217,7 +244,30 @@ class Engine : public KLaunchTimer {
     bool handoff_check();
 
   private:
+    // Device memory.  Every device allocation of an engine is a DevBuf member (devbuf.hpp), freed
+    // with the engine; the weights belong to the DeviceModel.  A buffer is replaced in one place,
+    // grow(): nothing happens while b holds `need` elements; otherwise the stream is drained, the
+    // graph caches named in `graphs` are dropped and b is reallocated with `cap` >= need elements
+    // (empty after a failure).  The rule for `graphs`: every cache whose graphs may hold the old
+    // address -- the decode graphs (graphs_, io_graphs_) capture the workspace, state, logits and
+    // granules; the batched graphs (bgraphs_) the workspace, the GEMM scratch (gy_, part_, m2_),
+    // eval_batch's staging and the generation slots; nothing captures a buffer that only eager
+    // launches and copies touch (tokens drawn, scores, bias, wkvc_).  Never called while a capture
+    // is open: whatever a captured step may grow has been grown by an eager step before it.
+    enum : unsigned { GRAPHS_NONE = 0, GRAPHS_DECODE = 1, GRAPHS_IO = 2, GRAPHS_BATCH = 4, GRAPHS_ALL = 7 };
+    bool settle(unsigned graphs);  // drains stream_ and drops those caches
+    template <class T>
+    bool grow(DevBuf<T> & b, size_t need, size_t cap, unsigned graphs);
+    static size_t doubled(size_t floor, size_t n) {  // floor * 2^k >= n
+        while (floor < n) floor *= 2;
+        return floor;
+    }
     bool ensure_workspace(int T);
+    // the pinned staging copy of n tokens into dtokens_, in stream order
+    bool stage_tokens(const uint32_t * tokens, size_t n);
+    bool copy_logits(float * host_out);  // logits_ to the host on stream_
+    // the sampler's logit bias, (allocated and) uploaded in stream order
+    bool upload_bias(uint32_t n_bias, const uint32_t * ids, const float * values);
     bool init_state(float * st, size_t n = 0);
     bool forward(int T, const float * sin, float * sout, bool logits);
     bool forward_range(int T, const float * sin, float * sout, uint32_t l0, uint32_t l1, bool logits);
@@ -255,11 +305,10 @@ class Engine : public KLaunchTimer {
     bool score_buffers(size_t T);
     bool score_chunk(size_t done, size_t n, bool last);
     ScoreRun * score_ = nullptr;
-    float * score_tile_ = nullptr;      // [kScoreRows][n_vocab] head tile (lazily allocated)
-    uint32_t * score_targets_ = nullptr;  // [score_cap_]
-    double * score_loss_ = nullptr;
-    uint32_t * score_argmax_ = nullptr;
-    size_t score_cap_ = 0;
+    DevBuf<float> score_tile_;         // [kScoreRows][n_vocab] head tile (lazily allocated)
+    DevBuf<uint32_t> score_targets_;   // one element per token of the longest call so far
+    DevBuf<double> score_loss_;
+    DevBuf<uint32_t> score_argmax_;
     bool layer_v4(int l, int T, const float * si, float * so);
     bool wkv6(int T, int H, int S, const float * u, const float * w, int wpt, const float * sin, float * sout);
     bool layer_v5(int l, int T, const float * si, float * so);
@@ -272,22 +321,13 @@ class Engine : public KLaunchTimer {
     DeviceModel * m_;
     hipStream_t stream_ = nullptr;
     double io_h2d_ = 0, io_d2h_ = 0;
-    int tcap_ = 0;
-    std::vector<void *> ws_allocs_;
-    float *x_ = nullptr, *xa_ = nullptr, *sx_ = nullptr, *r_ = nullptr, *k_ = nullptr, *v_ = nullptr, *g_ = nullptr;
-    float *w_ = nullptr, *y_ = nullptr, *a_ = nullptr, *nb_ = nullptr, *bb_ = nullptr, *vfirst_ = nullptr;
-    float *fr_ = nullptr, *lora_ = nullptr, *bonus_ = nullptr, *logits_ = nullptr;
-    float *dsmall_[4] = {nullptr, nullptr, nullptr, nullptr};  // decode LoRA intermediates [kmax]
-    uint32_t * dtokens_ = nullptr;
-    uint32_t * htokens_ = nullptr;  // pinned
+    DevBuf<float> logits_;
+    uint32_t * htokens_ = nullptr;  // pinned, as many tokens as the Workspace's dtokens_
     bool logits_valid_ = false;
-    uint32_t * gen_tokens_ = nullptr;  // generate: the drawn tokens [gen_cap_]
-    size_t gen_cap_ = 0;
-    uint32_t * bias_ids_ = nullptr;    // the sampler's logit bias [SAMPLE_MAX_BIAS]
-    float * bias_vals_ = nullptr;
-    static constexpr int kSlots = 12;
-    ActSlot slots_[kSlots];
-    float * dstate_[2] = {nullptr, nullptr};
+    DevBuf<uint32_t> gen_tokens_;   // generate: the drawn tokens
+    DevBuf<uint32_t> bias_ids_;     // the sampler's logit bias [SAMPLE_MAX_BIAS]
+    DevBuf<float> bias_vals_;
+    DevBuf<float> dstate_[2];
     int cur_ = 0;
     unsigned * herr_h_ = nullptr;  // hand-off timeout flag, host-mapped (herr_d_ = its device address)
     unsigned * herr_d_ = nullptr;
@@ -297,9 +337,7 @@ class Engine : public KLaunchTimer {
     // chunk-parallel wkv6 for sequences (wkv_chunk.hip; re-associated, not bit-exact): 0 = serial
     // k_wkv6_s64 (default); RWKV_MI355X_WKV_CHUNK=1 or rwkv_mi355x_debug_set(ctx, "wkv_chunk", 1)
     bool wkv_chunk_ = false;
-    float * wkvc_ = nullptr;  // its chunk matrices / chunk states
-    bool ensure_wkvc(size_t need);
-    size_t wkvc_cap_ = 0;
+    DevBuf<float> wkvc_;  // its chunk matrices / chunk states, grown on demand
     hipGraphExec_t graphs_[2][2][2] = {};  // [co-resident layout][cur][logits]
     bool use_graphs_ = true;
     bool split_maa_ = false;       // RWKV_MI355X_SPLIT_MAA=1: v6 decode W1 + mix as two launches
@@ -358,13 +396,10 @@ class Engine : public KLaunchTimer {
     double kt_bytes_ = 0, kt_flops_ = 0;  // algorithmic work of the next timed launch
     hipEvent_t kt_a_ = nullptr, kt_b_ = nullptr;
     bool mm_dispatch(MMGroup & g, int wtype);
-    bool ensure_part(size_t n);
-    float * gy_ = nullptr;     // scratch y of emit-only GEMM entries
-    size_t gy_cap_ = 0;
-    float * part_ = nullptr;   // split-K partials (launch_qgemm, k_fmm)
-    size_t part_cap_ = 0;
-    float * m2_ = nullptr;     // _1 formats: m*s chain totals (launch_qgemm, k_qg_msum)
-    size_t m2_cap_ = 0;
+    // the GEMM scratch, grown to the exact size a group needs (captured batched graphs point at it)
+    DevBuf<float> gy_;    // scratch y of emit-only GEMM entries
+    DevBuf<float> part_;  // split-K partials (launch_qgemm, k_fmm)
+    DevBuf<float> m2_;    // _1 formats: m*s chain totals (launch_qgemm, k_qg_msum)
     bool use_mm_ = false;
     bool tile_acts_ = false;  // Aview: Q8 activations in sequence-GEMM tiles (forward, T >= 2)
     // batched decode (eval_batch): state floats per context while a batched forward is built
@@ -372,9 +407,7 @@ class Engine : public KLaunchTimer {
     size_t bs_ = 0;
     int batch_gemm_min_ = 16;
     float * head_out_ = nullptr;
-    float * bstate_[2] = {nullptr, nullptr};
-    float * blogits_ = nullptr;
-    size_t bcap_ = 0;
+    DevBuf<float> bstate_[2], blogits_;  // staging of host states / logits: a power of two >= B rows
     struct BatchGraph {
         size_t B;
         const float * sin;
@@ -384,21 +417,10 @@ class Engine : public KLaunchTimer {
     };
     std::vector<BatchGraph> bgraphs_;
     void drop_batch_graphs();
-    // generation slots (batch_reserve): the live states [2][gslots_][state_len] (slots are stored
-    // in and loaded from gstate_[0]; the batched step alternates the two), the live logits
-    // [gslots_][n_vocab], the finished rows' snapshots of both, the penalty counts
-    // [gslots_][n_vocab], the per-row parameters and the words done / length / fin_step [kBatchMax]
-    // each + active
+    // generation slots (batch_reserve; their buffers: GenSlots)
     size_t gslots_ = 0;
     std::vector<char> gvalid_;
-    float * gstate_[2] = {nullptr, nullptr};
-    float *glogits_ = nullptr, *gsnap_state_ = nullptr, *gsnap_logits_ = nullptr;
-    uint32_t * gcounts_ = nullptr;
-    float * gparams_ = nullptr;      // temperature, top_p, presence, frequency: [4][kBatchMax]
-    uint64_t * gstreams_ = nullptr;  // seed, offset: [2][kBatchMax]
-    uint32_t * gwords_ = nullptr;    // done, length, fin_step: [3][kBatchMax], active
-    uint32_t * gtokens_ = nullptr;   // the drawn tokens [B][n] of a call
-    size_t gtokens_cap_ = 0;
+    DevBuf<uint32_t> gtokens_;  // the drawn tokens [B][n] of a call
     std::vector<float> gparams_h_;   // the host copies the uploads read
     std::vector<uint64_t> gstreams_h_;
     void free_slots();
@@ -419,5 +441,31 @@ class Engine : public KLaunchTimer {
     std::vector<KernelStat> stats_;
     void collect_timing();
 };
+
+template <class T>
+bool Engine::grow(DevBuf<T> & b, size_t need, size_t cap, unsigned graphs) {
+    if (need <= b.size()) return true;
+    if (!settle(graphs)) return false;
+    if (b.alloc(cap)) return true;
+    fprintf(stderr, "rwkv: device allocation of %zu bytes failed\n", cap * sizeof(T));
+    return false;
+}
+
+// Captures what build() enqueues on stream_ and instantiates it as ge.  A failed build still ends
+// the capture (the stream has to leave capture mode) before its graph is dropped.
+template <class F>
+bool Engine::capture(hipGraphExec_t & ge, F && build) {
+    hipGraph_t g = nullptr;
+    HIP_OK(hipStreamBeginCapture(stream_, hipStreamCaptureModeThreadLocal));
+    const bool ok = build();
+    HIP_OK(hipStreamEndCapture(stream_, &g));
+    if (!ok) {
+        (void)hipGraphDestroy(g);
+        return false;
+    }
+    HIP_OK(hipGraphInstantiate(&ge, g, nullptr, nullptr, 0));
+    (void)hipGraphDestroy(g);
+    return true;
+}
 
 }  // namespace rwkvmi

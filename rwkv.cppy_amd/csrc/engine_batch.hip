@@ -1,0 +1,262 @@
+// engine_batch.hip -- batched decode (eval_batch), the generation slots and batched generation.
+#include <stdio.h>
+#include <string.h>
+
+#include "engine.hpp"
+#include "kernels.hpp"
+
+namespace rwkvmi {
+
+// B independent contexts of this model advance one token each in one pass: the layer matmuls
+// run the decode matvec kernel (k_mm) over the B activation rows, so every weight byte is read
+// once per step for all B contexts, and each context's arithmetic is exactly its single-token
+// decode (same lane/block association, same kernels' per-token math); token shift and the wkv
+// recurrences take context t's state at t * state_len (LnMixArgs::bs, launch_wkv* bs).
+// states: [B][state_len] contiguous.  dev: pointers are device memory (else host).
+bool Engine::eval_batch(const uint32_t * tokens, size_t B, const float * state_in, float * state_out,
+                        float * logits_out, bool dev) {
+    HIP_OK(hipSetDevice(m_->device));
+    co_ = false;  // batched decode: the ordered layouts only
+    if (B == 0) return true;
+    if (B > (size_t)kBatchMax) {
+        fprintf(stderr, "rwkv: batched decode takes at most %d contexts (got %zu)\n", kBatchMax, B);
+        return false;
+    }
+    if (!ensure_workspace((int)B)) return false;
+    const size_t n = m_->state_len, V = m_->n_vocab;
+    // tokens == NULL (generate_batch): the tokens are already in dtokens_[0 .. B) (the sampler wrote
+    // them), every buffer is the caller's device memory and nothing is staged
+    if (!tokens && !(dev && state_in && state_out && logits_out)) return false;
+    if (tokens) {
+        const size_t cap = doubled(1, B);
+        if (!grow(bstate_[0], B * n, cap * n, GRAPHS_BATCH) || !grow(bstate_[1], B * n, cap * n, GRAPHS_BATCH) ||
+            !grow(blogits_, B * V, cap * V, GRAPHS_BATCH))
+            return false;
+    }
+    if (tokens && !stage_tokens(tokens, B)) return false;
+    // input states: device pointer as given, else staged into bstate_[0] (NULL = fresh states)
+    const float * sin = state_in;
+    if (!state_in) {
+        if (!init_state(bstate_[0], B * n)) return false;
+        sin = bstate_[0];
+    } else if (!dev) {
+        HIP_OK(hipMemcpyAsync(bstate_[0], state_in, B * n * 4, hipMemcpyHostToDevice, stream_));
+        sin = bstate_[0];
+    }
+    float * sout = (dev && state_out) ? state_out : bstate_[1].get();
+    float * lout = (dev && logits_out) ? logits_out : blogits_.get();
+    const bool lg = logits_out != nullptr;
+    // the batched forward: bs_ / head_out_ are set only while it is being enqueued
+    auto step = [&] {
+        bs_ = n;
+        head_out_ = lout;
+        const bool ok = forward_range((int)B, sin, sout, 0, m_->n_layer, lg);
+        bs_ = 0;
+        head_out_ = nullptr;
+        return ok;
+    };
+    bool ok;
+    if (use_graphs_ && !timing_) {
+        // one graph per (B, state pointers, logits pointer): a decode loop alternating two state
+        // buffers replays two graphs
+        hipGraphExec_t ge = nullptr;
+        for (const BatchGraph & g : bgraphs_)
+            if (g.B == B && g.sin == sin && g.sout == sout && g.lout == (lg ? lout : nullptr)) ge = g.ge;
+        if (!ge) {
+            // first step with these buffers: run it eagerly (lazy GEMM scratch allocations happen
+            // here, outside any capture), then capture the graph the next steps replay
+            if (!step()) {
+                (void)hipStreamSynchronize(stream_);
+                return false;
+            }
+            if (bgraphs_.size() >= 8) drop_batch_graphs();
+            if (!capture(ge, step)) return false;
+            bgraphs_.push_back(BatchGraph{B, sin, sout, lg ? lout : nullptr, ge});
+        } else {
+            HIP_OK(hipGraphLaunch(ge, stream_));
+        }
+        ok = true;
+    } else {
+        ok = step();
+    }
+    if (!ok) {
+        (void)hipStreamSynchronize(stream_);
+        return false;
+    }
+    if (!dev) {
+        if (logits_out) HIP_OK(hipMemcpyAsync(logits_out, lout, B * V * 4, hipMemcpyDeviceToHost, stream_));
+        if (state_out) HIP_OK(hipMemcpyAsync(state_out, sout, B * n * 4, hipMemcpyDeviceToHost, stream_));
+        HIP_OK(hipStreamSynchronize(stream_));
+        return handoff_check();
+    }
+    return true;
+}
+
+void Engine::drop_batch_graphs() {
+    for (BatchGraph & g : bgraphs_) (void)hipGraphExecDestroy(g.ge);
+    bgraphs_.clear();
+}
+
+// Slots [0, B) of the context generate together: per step one k_sample_rows launch over the slots'
+// logits (per-row parameters, penalties, stops), k_gen_snapshot of the rows that just stopped, and
+// one batched decode step (eval_batch, tokens already in dtokens_) from gstate_[p] to gstate_[p ^ 1].
+// A finished row keeps being decoded on token 0 -- the batched kernels take row t's state at
+// t * state_len, so leaving a row out would need a per-row offset through every one of them -- and
+// its live state and logits are garbage from then on; what the caller sees is the snapshot, which
+// k_gen_restore puts back into gstate_[0] / glogits_ at the end of the call.
+void Engine::free_slots() {
+    static_cast<GenSlots &>(*this) = GenSlots{};
+    gslots_ = 0;
+    gvalid_.clear();
+}
+
+bool GenSlots::alloc(size_t n_slots, size_t state_len, size_t n_vocab, size_t batch_max) {
+    return gstate_[0].alloc(n_slots * state_len) && gstate_[1].alloc(n_slots * state_len) &&
+           gsnap_state_.alloc(n_slots * state_len) && glogits_.alloc(n_slots * n_vocab) &&
+           gsnap_logits_.alloc(n_slots * n_vocab) && gcounts_.alloc(n_slots * n_vocab) && gparams_.alloc(4 * batch_max) &&
+           gstreams_.alloc(2 * batch_max) && gwords_.alloc(3 * batch_max + 1);
+}
+
+bool Engine::batch_reserve(size_t n_slots) {
+    HIP_OK(hipSetDevice(m_->device));
+    if (n_slots > (size_t)kBatchMax) return false;
+    if (!settle(GRAPHS_BATCH)) return false;  // they hold the old slots' addresses
+    free_slots();
+    if (n_slots == 0) return true;
+    GenSlots gs;
+    if (!gs.alloc(n_slots, m_->state_len, m_->n_vocab, (size_t)kBatchMax) ||
+        hipMemsetAsync(gs.gwords_, 0, gs.gwords_.size() * 4, stream_) != hipSuccess) {
+        (void)hipGetLastError();
+        fprintf(stderr, "rwkv: allocation of %zu generation slots failed\n", n_slots);
+        return false;
+    }
+    static_cast<GenSlots &>(*this) = std::move(gs);
+    gslots_ = n_slots;
+    gvalid_.assign(n_slots, 0);
+    return true;
+}
+
+bool Engine::batch_store(size_t slot) {
+    HIP_OK(hipSetDevice(m_->device));
+    if (slot >= gslots_ || !logits_valid_) return false;
+    const size_t n = m_->state_len, V = m_->n_vocab;
+    gvalid_[slot] = 0;
+    HIP_OK(hipMemcpyAsync(gstate_[0] + slot * n, dstate_[cur_], n * 4, hipMemcpyDeviceToDevice, stream_));
+    HIP_OK(hipMemcpyAsync(glogits_ + slot * V, logits_, V * 4, hipMemcpyDeviceToDevice, stream_));
+    // a new sequence in the slot: no token counted yet, not finished
+    HIP_OK(hipMemsetAsync(gcounts_ + slot * V, 0, V * 4, stream_));
+    HIP_OK(hipMemsetAsync(gwords_ + slot, 0, 4, stream_));
+    gvalid_[slot] = 1;
+    return true;
+}
+
+bool Engine::batch_load(size_t slot) {
+    HIP_OK(hipSetDevice(m_->device));
+    if (!batch_slot_valid(slot)) return false;
+    const size_t n = m_->state_len, V = m_->n_vocab;
+    logits_valid_ = false;
+    HIP_OK(hipMemcpyAsync(dstate_[cur_], gstate_[0] + slot * n, n * 4, hipMemcpyDeviceToDevice, stream_));
+    HIP_OK(hipMemcpyAsync(logits_, glogits_ + slot * V, V * 4, hipMemcpyDeviceToDevice, stream_));
+    logits_valid_ = true;
+    return true;
+}
+
+bool Engine::generate_batch(size_t B, const BatchSamplingParams & p, size_t n, uint32_t * tokens_out,
+                            uint32_t * lengths_out, uint32_t * steps_out) {
+    HIP_OK(hipSetDevice(m_->device));
+    if (B == 0 || B > gslots_ || n == 0 || !tokens_out || !lengths_out || !p.temperature || !p.top_p || !p.seed ||
+        !p.offset || p.n_bias > (uint32_t)SAMPLE_MAX_BIAS || p.n_stop > (uint32_t)SAMPLE_MAX_STOP)
+        return false;
+    for (size_t r = 0; r < B; r++)
+        if (!gvalid_[r]) return false;
+    const size_t S = m_->state_len, V = m_->n_vocab, K = (size_t)kBatchMax;
+    // everything that allocates, before anything is enqueued: dtokens_ moves when the workspace
+    // grows (and the batch graphs are dropped with it), the token buffer grows with B * n
+    if (!ensure_workspace((int)B)) return false;
+    if (!grow(gtokens_, B * n, doubled(1024, B * n), GRAPHS_NONE) || !upload_bias(p.n_bias, p.bias_ids, p.bias_values))
+        return false;
+    // from here on a failure leaves the slots of the call undefined
+    auto fail = [&] {
+        (void)hipStreamSynchronize(stream_);
+        (void)handoff_check();
+        for (size_t r = 0; r < B; r++) gvalid_[r] = 0;
+        return false;
+    };
+    gparams_h_.assign(4 * K, 0.0f);
+    gstreams_h_.assign(2 * K, 0);
+    for (size_t r = 0; r < B; r++) {
+        gparams_h_[r] = p.temperature[r];
+        gparams_h_[K + r] = p.top_p[r];
+        gparams_h_[2 * K + r] = p.presence ? p.presence[r] : 0.0f;
+        gparams_h_[3 * K + r] = p.frequency ? p.frequency[r] : 0.0f;
+        gstreams_h_[r] = p.seed[r];
+        gstreams_h_[K + r] = p.offset[r];
+    }
+    bool ok = hipMemcpyAsync(gparams_, gparams_h_.data(), 4 * K * 4, hipMemcpyHostToDevice, stream_) == hipSuccess &&
+              hipMemcpyAsync(gstreams_, gstreams_h_.data(), 2 * K * 8, hipMemcpyHostToDevice, stream_) == hipSuccess;
+    ok = ok && hipMemsetAsync(gtokens_, 0xff, B * n * 4, stream_) == hipSuccess;
+    if (ok && !p.keep_counts) ok = hipMemsetAsync(gcounts_, 0, B * V * 4, stream_) == hipSuccess;
+    uint32_t *done = gwords_, *length = gwords_ + K, *fin = gwords_ + 2 * K, *active = gwords_ + 3 * K;
+    ok = ok && launch_gen_begin(stream_, (int)B, p.keep_counts ? 1 : 0, done, length, fin, active);
+    if (!ok) return fail();
+
+    SampleArgs a;
+    memset(&a, 0, sizeof(a));
+    a.logits = glogits_;
+    a.rows = (int)B;
+    a.V = (int)V;
+    a.n_bias = (int)p.n_bias;
+    a.bias_ids = bias_ids_;
+    a.bias_vals = bias_vals_;
+    a.temperature_r = gparams_;
+    a.top_p_r = gparams_ + K;
+    a.presence_r = gparams_ + 2 * K;
+    a.frequency_r = gparams_ + 3 * K;
+    a.counts = gcounts_;
+    a.seed_r = gstreams_;
+    a.counter_r = gstreams_ + K;
+    a.n_stop = (int)p.n_stop;
+    for (uint32_t j = 0; j < p.n_stop; j++) a.stop[j] = p.stop_tokens[j];
+    a.done = done;
+    a.length = length;
+    a.fin_step = fin;
+    a.active = active;
+    a.tok = gtokens_;
+    a.tok_stride = (uint32_t)n;
+    a.tok2 = dtokens_;
+    GenRows g{(int)B, S, V, done, fin};
+
+    size_t steps = 0;
+    uint32_t live = 1;
+    for (size_t i = 0; ok && i < n && live; i++) {
+        // the step is a kernel argument of eager launches between the decode graph's replays
+        a.counter = i;
+        a.step = (uint32_t)i;
+        if (timing_) g_klt = this;
+        ok = launch_sample(stream_, a) && launch_gen_snapshot(stream_, g, (uint32_t)i, gstate_[steps & 1], glogits_,
+                                                              gsnap_state_, gsnap_logits_);
+        g_klt = nullptr;
+        ok = ok && eval_batch(nullptr, B, gstate_[steps & 1], gstate_[(steps & 1) ^ 1], glogits_, true);
+        if (!ok) break;
+        steps++;
+        if (p.check_every && (i + 1) % p.check_every == 0 && i + 1 < n) {
+            ok = hipMemcpyAsync(&live, active, 4, hipMemcpyDeviceToHost, stream_) == hipSuccess &&
+                 hipStreamSynchronize(stream_) == hipSuccess;
+        }
+    }
+    if (!ok) return fail();
+    ok = launch_gen_restore(stream_, g, gsnap_state_, gsnap_logits_, gstate_[steps & 1], gstate_[0], glogits_);
+    // [B][n] tokens with the rows n apart, as the caller's
+    ok = ok && hipMemcpyAsync(tokens_out, gtokens_, B * n * 4, hipMemcpyDeviceToHost, stream_) == hipSuccess &&
+         hipMemcpyAsync(lengths_out, length, B * 4, hipMemcpyDeviceToHost, stream_) == hipSuccess;
+    if (!ok) return fail();
+    if (hipStreamSynchronize(stream_) != hipSuccess) return fail();
+    if (!handoff_check()) {
+        for (size_t r = 0; r < B; r++) gvalid_[r] = 0;
+        return false;
+    }
+    if (steps_out) *steps_out = (uint32_t)steps;
+    return true;
+}
+
+}  // namespace rwkvmi

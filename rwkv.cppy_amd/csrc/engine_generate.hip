@@ -1,0 +1,151 @@
+// engine_generate.hip -- token sampling, the device-resident generation loop and sequence scoring
+// on the context's own state.
+#include <stdio.h>
+#include <string.h>
+
+#include "engine.hpp"
+#include "kernels.hpp"
+
+namespace rwkvmi {
+
+// The sampler's device buffers, allocated or grown before anything is enqueued (never inside the
+// loop): n token slots and the bias arrays, which are uploaded in stream order.
+bool Engine::sampler_buffers(const SamplingParams & p, size_t n, SampleArgs & a) {
+    if (p.n_bias > (uint32_t)SAMPLE_MAX_BIAS) return false;
+    if (!grow(gen_tokens_, n, doubled(64, n), GRAPHS_NONE) || !upload_bias(p.n_bias, p.bias_ids, p.bias_values))
+        return false;
+    memset(&a, 0, sizeof(a));
+    a.logits = logits_;
+    a.rows = 1;
+    a.V = (int)m_->n_vocab;
+    a.temperature = p.temperature;
+    a.top_p = p.top_p;
+    a.n_bias = (int)p.n_bias;
+    a.bias_ids = bias_ids_;
+    a.bias_vals = bias_vals_;
+    a.seed = p.seed;
+    a.counter = p.offset;
+    a.tok = gen_tokens_;
+    return true;
+}
+
+bool Engine::upload_bias(uint32_t n_bias, const uint32_t * ids, const float * values) {
+    if (!grow(bias_ids_, SAMPLE_MAX_BIAS, SAMPLE_MAX_BIAS, GRAPHS_NONE) ||
+        !grow(bias_vals_, SAMPLE_MAX_BIAS, SAMPLE_MAX_BIAS, GRAPHS_NONE))
+        return false;
+    if (n_bias) {
+        HIP_OK(hipMemcpyAsync(bias_ids_, ids, n_bias * 4, hipMemcpyHostToDevice, stream_));
+        HIP_OK(hipMemcpyAsync(bias_vals_, values, n_bias * 4, hipMemcpyHostToDevice, stream_));
+    }
+    return true;
+}
+
+bool Engine::sample(const SamplingParams & p, uint32_t * token_out) {
+    HIP_OK(hipSetDevice(m_->device));
+    if (!logits_valid_ || !token_out) return false;
+    SampleArgs a;
+    if (!sampler_buffers(p, 1, a) || !launch_sample(stream_, a)) return false;
+    HIP_OK(hipMemcpyAsync(token_out, gen_tokens_, 4, hipMemcpyDeviceToHost, stream_));
+    HIP_OK(hipStreamSynchronize(stream_));
+    return handoff_check();
+}
+
+bool Engine::generate(const SamplingParams & p, size_t n, uint32_t * tokens_out, float * logits_out) {
+    HIP_OK(hipSetDevice(m_->device));
+    if (!logits_valid_ || !tokens_out || n == 0) return false;
+    SampleArgs a;
+    // dtokens_ moves when the workspace grows (the graphs are dropped with it): settle it first
+    if (!ensure_workspace(1) || !sampler_buffers(p, n, a)) return false;
+    const int cur0 = cur_;
+    co_retry_ = false;
+    bool ok = true;
+    for (size_t i = 0; ok && i < n; i++) {
+        // the counter is a kernel argument of an eager launch between the decode graphs' replays:
+        // nothing per step is baked into a captured node
+        a.counter = p.offset + i;
+        a.tok = gen_tokens_ + i;
+        a.tok2 = dtokens_;
+        if (timing_) g_klt = this;
+        ok = launch_sample(stream_, a);
+        g_klt = nullptr;
+        ok = ok && run_tokens(nullptr, 1, true);
+    }
+    if (ok) {
+        ok = hipMemcpyAsync(tokens_out, gen_tokens_, n * 4, hipMemcpyDeviceToHost, stream_) == hipSuccess;
+        if (ok && logits_out) ok = copy_logits(logits_out);
+    }
+    ok = (hipStreamSynchronize(stream_) == hipSuccess) && ok;
+    ok = handoff_check() && ok;
+    if (!ok) {
+        // as run_tokens: the parity the call started with; state and logits are unspecified
+        cur_ = cur0;
+        logits_valid_ = false;
+    }
+    return ok;
+}
+
+// The scorer's device buffers, allocated or grown before anything is enqueued: T targets, losses
+// and argmaxes, and (T > 1: some chunk has more than one token) the head tile.
+bool Engine::score_buffers(size_t T) {
+    const size_t cap = doubled(1024, T);
+    if (!grow(score_targets_, T, cap, GRAPHS_NONE) || !grow(score_loss_, T, cap, GRAPHS_NONE) ||
+        !grow(score_argmax_, T, cap, GRAPHS_NONE))
+        return false;
+    const size_t tile = (size_t)kScoreRows * m_->n_vocab;
+    if (T > 1 && !grow(score_tile_, tile, tile, GRAPHS_NONE)) return false;
+    return true;
+}
+
+// After the layers of tokens [done, done + n) of a score() call: x_ holds their n final residual
+// rows (n > 1), or the decode program's head has written logits_ (n == 1).
+bool Engine::score_chunk(size_t done, size_t n, bool last) {
+    const size_t C = m_->n_embed, V = m_->n_vocab;
+    const bool want_loss = score_->targets != nullptr;
+    if (want_loss)
+        HIP_OK(hipMemcpyAsync(score_targets_ + done, score_->targets + done, n * 4, hipMemcpyHostToDevice, stream_));
+    auto reduce = [&](const float * lg, size_t row0, int rows) {
+        const size_t at = done + row0;
+        if (!launch_xent(stream_, lg, rows, (int)V, want_loss ? score_targets_ + at : nullptr,
+                         want_loss ? score_loss_ + at : nullptr, score_argmax_ + at))
+            return false;
+        if (score_->logits_out) {
+            // the next tile (or step) overwrites lg: the copy has landed before it is enqueued
+            HIP_OK(hipMemcpyAsync(score_->logits_out + at * V, lg, (size_t)rows * V * 4, hipMemcpyDeviceToHost, stream_));
+            HIP_OK(hipStreamSynchronize(stream_));
+        }
+        return true;
+    };
+    if (n == 1) return reduce(logits_, 0, 1);
+    for (size_t row0 = 0; row0 < n; row0 += (size_t)kScoreRows) {
+        const int rows = (int)std::min(n - row0, (size_t)kScoreRows);
+        // the head over `rows` rows as batched decode runs it over that many contexts (mm_dispatch:
+        // k_fmm, k_mvb or k_mm, each row the bits of its one-token head); never the sequence GEMM,
+        // for which the head has no tile records (upload_mat)
+        bs_ = m_->state_len;
+        const bool ok = head_rows(x_ + row0 * C, rows, score_tile_);
+        bs_ = 0;
+        if (!ok || !reduce(score_tile_, row0, rows)) return false;
+        if (last && row0 + rows == n)
+            HIP_OK(hipMemcpyAsync(logits_, score_tile_ + (size_t)(rows - 1) * V, V * 4, hipMemcpyDeviceToDevice, stream_));
+    }
+    return true;
+}
+
+bool Engine::score(const uint32_t * tokens, size_t T, const uint32_t * targets, double * losses_out,
+                   uint32_t * argmax_out, float * logits_out) {
+    HIP_OK(hipSetDevice(m_->device));
+    if (!tokens || T == 0 || (targets != nullptr) != (losses_out != nullptr) || !score_buffers(T)) return false;
+    ScoreRun run{targets, logits_out};
+    co_retry_ = false;
+    score_ = &run;
+    const bool ok = run_tokens(tokens, T, true);
+    score_ = nullptr;
+    if (!ok) return false;
+    if (losses_out) HIP_OK(hipMemcpyAsync(losses_out, score_loss_, T * 8, hipMemcpyDeviceToHost, stream_));
+    if (argmax_out) HIP_OK(hipMemcpyAsync(argmax_out, score_argmax_, T * 4, hipMemcpyDeviceToHost, stream_));
+    HIP_OK(hipStreamSynchronize(stream_));
+    // a hand-off timeout in a one-token chunk: nothing is re-run (the state has moved on)
+    return handoff_check();
+}
+
+}  // namespace rwkvmi

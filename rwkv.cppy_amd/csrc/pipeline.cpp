@@ -24,8 +24,8 @@ LayerPipeline::~LayerPipeline() {
         (void)hipSetDevice(s.device);
         if (s.eng) (void)hipStreamSynchronize(s.eng->stream());
         for (int b = 0; b < 2; b++) {
-            if (s.xb[b]) (void)hipFree(s.xb[b]);
-            if (s.vb[b]) (void)hipFree(s.vb[b]);
+            s.xb[b].reset();  // on the stage's device, its stream drained
+            s.vb[b].reset();
             if (s.ready[b]) (void)hipEventDestroy(s.ready[b]);
             if (s.consumed[b]) (void)hipEventDestroy(s.consumed[b]);
         }
@@ -41,7 +41,7 @@ bool LayerPipeline::init(const std::vector<StageSpec> & specs, size_t n_embed, b
         s.device = sp.device;
         s.l0 = sp.l0;
         s.l1 = sp.l1;
-        st_.push_back(s);
+        st_.push_back(std::move(s));
     }
     for (Stage & s : st_) {
         HIP_OK(hipSetDevice(s.device));
@@ -95,17 +95,18 @@ bool LayerPipeline::ensure_buffers(size_t chunk) {
         HIP_OK(hipSetDevice(s.device));
         HIP_OK(hipStreamSynchronize(s.eng->stream()));
         for (int b = 0; b < 2; b++) {
-            if (s.xb[b]) (void)hipFree(s.xb[b]);
-            if (s.vb[b]) (void)hipFree(s.vb[b]);
-            s.xb[b] = s.vb[b] = nullptr;
+            s.xb[b].reset();
+            s.vb[b].reset();
         }
     }
     cap_ = 0;
     for (Stage & s : st_) {
         HIP_OK(hipSetDevice(s.device));
         for (int b = 0; b < 2; b++) {
-            HIP_OK(hipMalloc(&s.xb[b], chunk * C_ * 4 + 64));
-            if (v7_) HIP_OK(hipMalloc(&s.vb[b], chunk * C_ * 4 + 64));
+            if (!s.xb[b].alloc(chunk * C_) || (v7_ && !s.vb[b].alloc(chunk * C_))) {
+                fprintf(stderr, "rwkv: layer pipeline: staging buffers for %zu tokens failed to allocate\n", chunk);
+                return false;
+            }
         }
     }
     cap_ = chunk;
@@ -158,7 +159,7 @@ bool LayerPipeline::eval_impl(const uint32_t * tokens, size_t T, const float * s
             hipStream_t sst = s.eng->stream();
             if (i > 0) HIP_OK(hipStreamWaitEvent(sst, st_[i - 1].ready[b], 0));  // chunk c's input landed
             const bool last = i + 1 == P && c + 1 == nc;
-            if (!s.eng->eval_layers(tokens + a, n, s.l0, s.l1, s.xb[b], v7_ ? s.vb[b] : nullptr, last && logits_out,
+            if (!s.eng->eval_layers(tokens + a, n, s.l0, s.l1, s.xb[b], v7_ ? s.vb[b].get() : nullptr, last && logits_out,
                                     last ? logits_out : nullptr, false))
                 return false;
             if (i + 1 < P) {

@@ -30,8 +30,8 @@ class LayerPipeline {
         Engine * eng = nullptr;
         int device = 0;
         uint32_t l0 = 0, l1 = 0;
-        float * xb[2] = {nullptr, nullptr};  // x of a chunk entering / leaving this stage
-        float * vb[2] = {nullptr, nullptr};  // v7 v_first
+        DevBuf<float> xb[2];  // x of a chunk entering / leaving this stage
+        DevBuf<float> vb[2];  // v7 v_first
         hipEvent_t ready[2] = {nullptr, nullptr};     // chunk forwarded to the next stage
         hipEvent_t consumed[2] = {nullptr, nullptr};  // this stage is done with buffer b
     };

@@ -22,7 +22,7 @@
 // k_sample_rows is the same arithmetic for a batch of rows that each have their own parameters
 // (rwkv_mi355x_generate_batch): per-row temperature, top_p and draw stream, presence / frequency
 // penalties over a count table, stop tokens and finished rows (SampleArgs in kernels.hpp).
-// k_gen_snapshot / k_gen_restore / k_gen_begin keep the finished rows' states (engine.hip,
+// k_gen_snapshot / k_gen_restore / k_gen_begin keep the finished rows' states (engine_batch.hip,
 // generate_batch).
 #include "device_common.hpp"
 #include "kernels.hpp"
