@@ -151,6 +151,27 @@ RWKV_API bool rwkv_mi355x_generate_batch(struct rwkv_context * ctx, size_t B,
                                          uint32_t * tokens_out /* [B][n] */, uint32_t * lengths_out /* [B] */,
                                          uint32_t * steps_out);
 
+/* Batched prefill: n_rows prompts, concatenated in `tokens` (lengths[i] >= 1 tokens each), are
+ * evaluated together in packed sequence passes and land in slots[i] (distinct, each < the reserved
+ * slots).  cont == NULL or cont[i] == 0: row i starts from the fresh state (the slot need not have
+ * been stored); cont[i] != 0: it continues from the slot's state (the slot must be valid).  The head
+ * runs on each row's last token.  On return slot slots[i] is what state_upload(NULL) [or batch_load],
+ * rwkv_mi355x_eval_device(row i, logits) and rwkv_mi355x_batch_store(slots[i]) leave there, bit for
+ * bit: state, logits, zero counts, not finished.  Other slots, the context's device state and its
+ * device logits are untouched.  Synchronous; only the tokens cross PCIe.
+ *
+ * The rows are packed, in order, into passes of at most 1024 tokens; a row that crosses a pass is
+ * split and its next piece continues from the state the previous one wrote, so the packing never
+ * shows in the results.  The weights are read once per pass instead of once per prompt.
+ *
+ * n_rows == 0 or above the reserved slots, a NULL slots / tokens / lengths, a slot at or above the
+ * reserved count or named twice, a zero length, a token >= n_vocab and cont[i] != 0 on a slot that
+ * was never stored fail with RWKV_ERROR_ARGS before anything is enqueued: every slot is as it was.
+ * A failure after that (RWKV_ERROR_CTX) leaves the slots of the call invalid.  A pipeline or stage
+ * context fails with RWKV_ERROR_CTX | RWKV_ERROR_UNSUPPORTED. */
+RWKV_API bool rwkv_mi355x_prefill_batch(struct rwkv_context * ctx, size_t n_rows, const uint32_t * slots,
+                                        const uint32_t * tokens, const size_t * lengths, const uint8_t * cont);
+
 /* Scoring: rwkv_mi355x_eval_device over T >= 1 tokens with the head on EVERY token.  Position t's
  * logits row (the logits serial rwkv_eval of tokens[0..t] gives, bit for bit) is reduced on the device
  * to losses_out[t] = -log softmax(row t)[targets[t]] (the exponentials and their sum in fp64) and
@@ -368,6 +389,14 @@ RWKV_API bool rwkv_mi355x_selftest_sample_rows(const float * logits, int rows, i
                                                uint32_t step, uint32_t * counts, uint32_t * done, uint32_t * tokens,
                                                uint32_t * decode_tokens, uint32_t * kept, float * cutoff,
                                                uint32_t * lengths, uint32_t * active);
+
+/* The host planner of rwkv_mi355x_prefill_batch (no GPU call): packs n_rows rows of lengths[i] >= 1
+ * tokens, in order, into chunks of at most cap tokens.  Segment j is seg_len[j] tokens of row
+ * seg_row[j], from token seg_begin[j] of chunk seg_chunk[j] on.  Returns the number of segments, -1
+ * when max_segs is too small (nothing past it is written), -2 for n_rows == 0, cap == 0 or a zero length. */
+RWKV_API long long rwkv_mi355x_selftest_prefill_plan(const size_t * lengths, size_t n_rows, size_t cap, uint32_t * seg_row,
+                                                     uint32_t * seg_begin, uint32_t * seg_len, uint32_t * seg_chunk,
+                                                     size_t max_segs);
 
 /* k_xent on host operands (tests): logits [rows][V], targets [rows]; losses / argmax may be NULL */
 RWKV_API bool rwkv_mi355x_selftest_xent(const float * logits, int rows, int V, const uint32_t * targets,

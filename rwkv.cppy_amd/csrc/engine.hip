@@ -502,7 +502,7 @@ bool Engine::ffn(int l, int T, const float * si, float * so) {
         a.n_out = 1;
         a.mu[0] = L.ffn_x_k;
         a.out[0] = A(0, L.ffn_k);
-        if (!launch_ln_mix(stream_, a)) return false;
+        if (!launch_ln_mix(stream_, a, seg_)) return false;
         ActBuf kin = A(1, L.ffn_v);
         b.add(L.ffn_k, A(0, L.ffn_k), nullptr, 0, EPI_RELU_SQ, nullptr, nullptr, &kin);
         if (!b.run(*this, T)) return false;
@@ -516,7 +516,7 @@ bool Engine::ffn(int l, int T, const float * si, float * so) {
     a.mu[1] = m_->major == 6 ? L.ffn_maa_r : L.ffn_mix_r;
     a.out[0] = A(0, L.ffn_k);
     a.out[1] = A(1, L.ffn_r);
-    if (!launch_ln_mix(stream_, a)) return false;
+    if (!launch_ln_mix(stream_, a, seg_)) return false;
     ActBuf kin = A(2, L.ffn_v);
     b.add(L.ffn_r, A(1, L.ffn_r), fr_, C, EPI_STORE);
     b.add(L.ffn_k, A(0, L.ffn_k), nullptr, 0, EPI_RELU_SQ, nullptr, nullptr, &kin);
@@ -560,29 +560,29 @@ bool Engine::layer_v4(int l, int T, const float * si, float * so) {
     a.out[0] = A(0, L.att_k);
     a.out[1] = A(1, L.att_v);
     a.out[2] = A(2, L.att_r);
-    if (!launch_ln_mix(stream_, a)) return false;
+    if (!launch_ln_mix(stream_, a, seg_)) return false;
     MMBatch b;
     b.add(L.att_r, A(2, L.att_r), r_, C, EPI_SIGMOID);
     b.add(L.att_k, A(0, L.att_k), k_, C, EPI_STORE);
     b.add(L.att_v, A(1, L.att_v), v_, C, EPI_STORE);
     if (!b.run(*this, T)) return false;
     ActBuf o = A(3, L.att_o);
-    if (!launch_wkv4(stream_, T, C, r_, k_, v_, L.att_first, L.att_decay, si, so, o, (int)bs_)) return false;
+    if (!launch_wkv4(stream_, T, C, r_, k_, v_, L.att_first, L.att_decay, si, so, o, (int)bs_, seg_)) return false;
     b.add(L.att_o, o, x_, C, EPI_ADD);
     if (!b.run(*this, T)) return false;
     return ffn(l, T, si, so);
 }
 
-// v5/v6 sequence wkv: the serial recurrence (k_wkv6_s64, bit-exact with decode), or behind the
-// wkv_chunk_ switch the chunk-parallel form (RA / KB in the v7-only nb_ / bb_ buffers, free during a
+// v5/v6 sequence wkv: the serial recurrence (k_wkv6_s64, bit-exact with decode; a prefill's packed
+// chunk always: its segmented form), or behind the wkv_chunk_ switch the chunk-parallel form (RA / KB in the v7-only nb_ / bb_ buffers, free during a
 // v5/v6 layer; the chunk matrices and states in wkvc_, grown on demand)
 bool Engine::wkv6(int T, int H, int S, const float * u, const float * w, int wpt, const float * sin, float * sout) {
-    if (wkv_chunk_ && wkv6_chunked_supported(T, S, (int)bs_)) {
+    if (wkv_chunk_ && !seg_ && wkv6_chunked_supported(T, S, (int)bs_)) {
         const size_t need = wkv6_chunked_scratch_floats(T, H);
         if (!grow(wkvc_, need, need, GRAPHS_NONE)) return false;
         return launch_wkv6_chunked(stream_, T, H, k_, v_, r_, u, w, wpt, sin, sout, y_, nb_, bb_, wkvc_);
     }
-    return launch_wkv6(stream_, T, H, S, k_, v_, r_, u, w, wpt, sin, sout, y_, (int)bs_);
+    return launch_wkv6(stream_, T, H, S, k_, v_, r_, u, w, wpt, sin, sout, y_, (int)bs_, seg_);
 }
 
 bool Engine::layer_v5(int l, int T, const float * si, float * so) {
@@ -602,7 +602,7 @@ bool Engine::layer_v5(int l, int T, const float * si, float * so) {
         a.mu[3] = L.att_mix_g;
         a.out[3] = A(3, L.att_g);
     }
-    if (!launch_ln_mix(stream_, a)) return false;
+    if (!launch_ln_mix(stream_, a, seg_)) return false;
     MMBatch b;
     b.add(L.att_r, A(2, L.att_r), r_, C, EPI_STORE);
     b.add(L.att_k, A(0, L.att_k), k_, C, EPI_STORE);
@@ -629,7 +629,7 @@ bool Engine::layer_v6(int l, int T, const float * si, float * so) {
     a.out[0] = A(0, L.maa_w1);
     a.out_xa = xa_;
     a.out_sx = sx_;
-    if (!launch_ln_mix(stream_, a)) return false;
+    if (!launch_ln_mix(stream_, a, seg_)) return false;
     MMBatch b;
     b.add(L.maa_w1, A(0, L.maa_w1), lora_, 5 * D, EPI_TANH);
     if (!b.run(*this, T)) return false;
@@ -704,10 +704,10 @@ bool Engine::layer_v7(int l, int T, const float * si, float * so) {
             a2.mu[0] = a.mu[3];
             a2.out[0] = xv1;
             a2.carry_out = nullptr;
-            if (!launch_ln_mix(stream_, a2)) return false;
+            if (!launch_ln_mix(stream_, a2, seg_)) return false;
         }
     }
-    if (!launch_ln_mix(stream_, a)) return false;
+    if (!launch_ln_mix(stream_, a, seg_)) return false;
     MMBatch b;
     ActBuf lw = A(6, L.w2), la = A(7, L.a2), lg = A(8, L.g2);
     b.add(L.att_r, a.out[0], r_, C, EPI_STORE);
@@ -734,11 +734,11 @@ bool Engine::layer_v7(int l, int T, const float * si, float * so) {
     if (!launch_v7_prep(stream_, T, H, S, k_, a_, r_, L.k_k, L.k_a, L.r_k, nb_, bb_, bonus_)) return false;
     // the serial recurrence (bit-exact with decode), or behind the wkv_chunk_ switch the chunk-parallel
     // form (wkv7_chunk.hip; scratch in wkvc_)
-    if (wkv_chunk_ && wkv7_chunked_supported(T, S, (int)bs_)) {
+    if (wkv_chunk_ && !seg_ && wkv7_chunked_supported(T, S, (int)bs_)) {
         const size_t need = wkv7_chunked_scratch_floats(T, H);
         if (!grow(wkvc_, need, need, GRAPHS_NONE)) return false;
         if (!launch_wkv7_chunked(stream_, T, H, r_, w_, k_, v_, nb_, bb_, si + 2 * C, so + 2 * C, y_, wkvc_)) return false;
-    } else if (!launch_wkv7(stream_, T, H, S, r_, w_, k_, v_, nb_, bb_, si + 2 * C, so + 2 * C, y_, (int)bs_)) {
+    } else if (!launch_wkv7(stream_, T, H, S, r_, w_, k_, v_, nb_, bb_, si + 2 * C, so + 2 * C, y_, (int)bs_, seg_)) {
         return false;
     }
     ActBuf o = A(0, L.att_o);
@@ -850,7 +850,6 @@ bool Engine::run_tokens(const uint32_t * tokens, size_t T, bool want_logits) {
 }
 
 bool Engine::run_tokens_impl(const uint32_t * tokens, size_t T, bool want_logits) {
-    const size_t kChunkMax = 1024;
     size_t done = 0;
     while (done < T) {
         const size_t n = std::min(T - done, kChunkMax);
@@ -980,6 +979,8 @@ bool Engine::debug_set(const char * name, long long value) {
     else if (n == "wkv_chunk") wkv_chunk_ = value != 0;
     else if (n == "generic_decode") generic_decode_ = value != 0 || m_->n_embed > 4096;
     else if (n == "graphs") use_graphs_ = value != 0;
+    // the packing cap of prefill_batch in tokens (tests reach row splits at small shapes); <= 0: the default
+    else if (n == "prefill_chunk" && value <= (long long)kChunkMax) prefill_chunk_ = value <= 0 ? kChunkMax : (size_t)value;
     else if (n == "co_mode" && value >= -1 && value <= 1) co_knob_ = (int)value;
     else if (n == "decode_fusion")  // -1: the default for this model
         fuse_ = value < 0 ? FUSE_DEFAULT | (m_->major == 4 ? FUSE_FFNCO : 0u) : (unsigned)value & FUSE_ALL;

@@ -83,10 +83,13 @@ struct Workspace {
 
 // The generation slots' buffers (Engine::batch_reserve), replaced as a whole in the same way: the
 // live states [2][slots][state_len] (slots are stored in and loaded from gstate_[0]; the batched step
-// alternates the two), the live logits [slots][n_vocab], the finished rows' snapshots of both, the
+// alternates the two) and one fresh state behind them, all one allocation, so that a prefill's segment
+// table names any of them by its float offset from gstates_ (state_off); the live logits [slots][n_vocab], the finished rows' snapshots of both, the
 // penalty counts [slots][n_vocab], the per-row parameters and the words
 struct GenSlots {
-    DevBuf<float> gstate_[2], glogits_, gsnap_state_, gsnap_logits_;
+    DevBuf<float> gstates_, glogits_, gsnap_state_, gsnap_logits_;
+    float * gstate_[2] = {nullptr, nullptr};  // views of gstates_
+    float * gfresh_ = nullptr;                // the fresh state (Engine::batch_reserve fills it)
     DevBuf<uint32_t> gcounts_;
     DevBuf<float> gparams_;      // temperature, top_p, presence, frequency: [4][kBatchMax]
     DevBuf<uint64_t> gstreams_;  // seed, offset: [2][kBatchMax]
@@ -217,6 +220,16 @@ class Engine : public KLaunchTimer, private Workspace, private GenSlots {
     bool batch_load(size_t slot);
     bool generate_batch(size_t B, const BatchSamplingParams & p, size_t n, uint32_t * tokens_out, uint32_t * lengths_out,
                         uint32_t * steps_out);
+    // Batched prefill (rwkv_mi355x_prefill_batch; engine_prefill.hip): n_rows prompts, concatenated in
+    // tokens, are packed into chunks of at most prefill_chunk_ tokens (prefill_plan.hpp) and each chunk
+    // runs as one sequence pass whose token shift and WKV kernels follow a segment table (SegTab);
+    // the head runs once, over the residual rows that end the prompts.  Row i lands in slots[i] as
+    // batch_store leaves a slot.  The caller has checked the arguments (distinct slots below
+    // batch_slots(), lengths >= 1, tokens in range, cont rows valid).  A failure after the first launch
+    // leaves the call's slots invalid.  Never captured into a graph.
+    bool prefill_batch(size_t n_rows, const uint32_t * slots, const uint32_t * tokens, const size_t * lengths,
+                       const uint8_t * cont);
+    static constexpr size_t kChunkMax = 1024;  // tokens per sequence pass (run_tokens_impl, prefill_batch)
     float * device_logits() const { return logits_; }
     bool state_upload(const float * state);
     bool state_download(float * state);
@@ -237,7 +250,8 @@ class Engine : public KLaunchTimer, private Workspace, private GenSlots {
     // debugging aid (rwkv_mi355x_debug_buffer): copies a workspace buffer of the last evaluation
     long long debug_copy(const char * name, void * out, size_t bytes);
     // test hooks (rwkv_mi355x_debug_set): "skip_granule" = producer workgroup of k_v6_att_fused that
-    // publishes nothing (-1 off), "spin_max" = the hand-off sweep bound; returns false for unknown names
+    // publishes nothing (-1 off), "spin_max" = the hand-off sweep bound, "prefill_chunk" = the packing
+    // cap of prefill_batch in tokens (1 .. kChunkMax; <= 0 the default); returns false for unknown names
     bool debug_set(const char * name, long long value);
     // false when an in-launch hand-off of the work completed so far timed out: reports it, clears the
     // granules and the flag (the caller fails the evaluation with RWKV_ERROR_CTX)
@@ -405,6 +419,13 @@ class Engine : public KLaunchTimer, private Workspace, private GenSlots {
     // batched decode (eval_batch): state floats per context while a batched forward is built
     // (0 otherwise), the head's output rows, and the engine-owned staging buffers / graphs
     size_t bs_ = 0;
+    // batched prefill: the segment table of the packed chunk while its forward is being enqueued (NULL
+    // otherwise) -- the third mode of the layer functions beside bs_ == 0 and bs_ > 0
+    const SegTab * seg_ = nullptr;
+    size_t prefill_chunk_ = kChunkMax;  // debug knob "prefill_chunk": the packing cap in tokens
+    DevBuf<uint32_t> ptokens_;          // a prefill's tokens
+    DevBuf<uint64_t> ptab_;             // its segment tables and row lists
+    DevBuf<float> pend_x_;              // [kBatchMax][C] the residual rows that end its prompts
     int batch_gemm_min_ = 16;
     float * head_out_ = nullptr;
     DevBuf<float> bstate_[2], blogits_;  // staging of host states / logits: a power of two >= B rows

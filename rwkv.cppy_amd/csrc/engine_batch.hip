@@ -111,8 +111,11 @@ void Engine::free_slots() {
 }
 
 bool GenSlots::alloc(size_t n_slots, size_t state_len, size_t n_vocab, size_t batch_max) {
-    return gstate_[0].alloc(n_slots * state_len) && gstate_[1].alloc(n_slots * state_len) &&
-           gsnap_state_.alloc(n_slots * state_len) && glogits_.alloc(n_slots * n_vocab) &&
+    if (!gstates_.alloc((2 * n_slots + 1) * state_len)) return false;
+    gstate_[0] = gstates_;
+    gstate_[1] = gstates_ + n_slots * state_len;
+    gfresh_ = gstates_ + 2 * n_slots * state_len;
+    return gsnap_state_.alloc(n_slots * state_len) && glogits_.alloc(n_slots * n_vocab) &&
            gsnap_logits_.alloc(n_slots * n_vocab) && gcounts_.alloc(n_slots * n_vocab) && gparams_.alloc(4 * batch_max) &&
            gstreams_.alloc(2 * batch_max) && gwords_.alloc(3 * batch_max + 1);
 }
@@ -125,7 +128,7 @@ bool Engine::batch_reserve(size_t n_slots) {
     if (n_slots == 0) return true;
     GenSlots gs;
     if (!gs.alloc(n_slots, m_->state_len, m_->n_vocab, (size_t)kBatchMax) ||
-        hipMemsetAsync(gs.gwords_, 0, gs.gwords_.size() * 4, stream_) != hipSuccess) {
+        hipMemsetAsync(gs.gwords_, 0, gs.gwords_.size() * 4, stream_) != hipSuccess || !init_state(gs.gfresh_)) {
         (void)hipGetLastError();
         fprintf(stderr, "rwkv: allocation of %zu generation slots failed\n", n_slots);
         return false;

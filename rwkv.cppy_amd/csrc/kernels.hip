@@ -511,8 +511,11 @@ static int tile_q(const ActBuf * outs, int n, int K) {
 }
 
 // rwkv_carry_x (rwkv_graph.inc:56-82) + the token-shift mixes of each version.
-template <int TQ>
-__global__ __launch_bounds__(1024) void k_ln_mix(LnMixArgs a) {
+// SEG (batched prefill): the T tokens are a packed chunk cut into segments (SegTab); a segment's first
+// token is shifted against the segment's input carry, its last token writes the output carry.  The
+// statistics and the per-token arithmetic are the unsegmented form's.
+template <int TQ, bool SEG>
+__device__ __forceinline__ void ln_mix_body(const LnMixArgs & a, const SegTab & sg) {
     // LayerNorm statistics of the workgroup's TOKS_PER_WG + 1 rows (its tokens and the one before),
     // one wave per row (the canonical one-wave association), shared through LDS
     __shared__ float s_mean[TOKS_PER_WG + 1], s_scale[TOKS_PER_WG + 1];
@@ -533,7 +536,18 @@ __global__ __launch_bounds__(1024) void k_ln_mix(LnMixArgs a) {
     if (t >= a.T) return;  // whole 256-thread token groups
     const float * xt = a.x + (size_t)t * C;
     const float mean = s_mean[tg + 1], scale = s_scale[tg + 1];
-    const float pmean = t > 0 ? s_mean[tg] : 0.0f, pscale = t > 0 ? s_scale[tg] : 0.0f;
+    // the token opens a sequence (its shift partner is a carry) / closes one (it writes the carry)
+    bool first = t == 0, last = t == a.T - 1;
+    const float * cin = a.carry_in;
+    float * cout = a.carry_out;
+    if constexpr (SEG) {
+        const uint32_t s = sg.seg_of[t], b = sg.begin[s];
+        first = (uint32_t)t == b;
+        last = (uint32_t)t == b + sg.len[s] - 1;
+        cin += sg.sin_off[s];
+        if (cout) cout += sg.sout_off[s];
+    }
+    const float pmean = !first ? s_mean[tg] : 0.0f, pscale = !first ? s_scale[tg] : 0.0f;
     // channel blocks of 256 split over grid.y (short sequences / batched decode: more workgroups);
     // LNM_CB blocks at a time: all their loads are issued before the first store
     constexpr int LNM_CB = TQ > 0 ? 4 : 2;  // (4 spills in the runtime-format emit)
@@ -548,7 +562,8 @@ __global__ __launch_bounds__(1024) void k_ln_mix(LnMixArgs a) {
             wv[j] = a.lnw[c];
             bv[j] = a.lnb[c];
             // batch (a.bs > 0): every token is its own context, shifted against its own carry
-            pv[j] = a.bs ? a.carry_in[(size_t)t * a.bs + c] : (t > 0) ? xt[c - C] : a.carry_in[c];
+            if constexpr (SEG) pv[j] = first ? cin[c] : xt[c - C];
+            else pv[j] = a.bs ? a.carry_in[(size_t)t * a.bs + c] : (t > 0) ? xt[c - C] : a.carry_in[c];
 #pragma unroll
             for (int n = 0; n < 6; n++) muv[j][n] = n < nmu ? a.mu[n][c] : 0.0f;
         }
@@ -557,9 +572,13 @@ __global__ __launch_bounds__(1024) void k_ln_mix(LnMixArgs a) {
             const int c0 = cb0 + j * cstride, c = c0 + tid;
             if (c0 + (tid & ~63) >= C) continue;  // whole wave out of range (C % 64 == 0)
             const float xa = ln_apply(xv[j], mean, scale, wv[j], bv[j]);
-            const float xp = (a.bs || t == 0) ? pv[j] : ln_apply(pv[j], pmean, pscale, wv[j], bv[j]);
-            if (a.bs && a.carry_out) a.carry_out[(size_t)t * a.bs + c] = xa;
-            else if (t == a.T - 1 && a.carry_out) a.carry_out[c] = xa;
+            const float xp = ((!SEG && a.bs) || first) ? pv[j] : ln_apply(pv[j], pmean, pscale, wv[j], bv[j]);
+            if constexpr (SEG) {
+                if (last && cout) cout[c] = xa;
+            } else {
+                if (a.bs && a.carry_out) a.carry_out[(size_t)t * a.bs + c] = xa;
+                else if (last && a.carry_out) a.carry_out[c] = xa;
+            }
             if (a.out_xa) a.out_xa[(size_t)t * C + c] = xa;
             if (a.out_sx) a.out_sx[(size_t)t * C + c] = xp - xa;
 #pragma unroll
@@ -579,7 +598,17 @@ __global__ __launch_bounds__(1024) void k_ln_mix(LnMixArgs a) {
     }
 }
 
-bool launch_ln_mix(hipStream_t st, const LnMixArgs & a) {
+template <int TQ>
+__global__ __launch_bounds__(1024) void k_ln_mix(LnMixArgs a) {
+    ln_mix_body<TQ, false>(a, SegTab{});
+}
+
+template <int TQ>
+__global__ __launch_bounds__(1024) void k_ln_mix_seg(LnMixArgs a, SegTab sg) {
+    ln_mix_body<TQ, true>(a, sg);
+}
+
+bool launch_ln_mix(hipStream_t st, const LnMixArgs & a, const SegTab * seg) {
     // long sequences: one channel block row (grid.y = 1; each workgroup computes its rows' LayerNorm
     // statistics itself, so splitting the channels repeats that work: y = 2 / 4 / 8 measured slower)
     // fewer token groups than ~2 per CU (short sequences, batched decode): the channel blocks over
@@ -588,6 +617,14 @@ bool launch_ln_mix(hipStream_t st, const LnMixArgs & a) {
     const int gy = a.T <= 64 ? cbs : tgs < 256 ? std::min(cbs, (512 + tgs - 1) / tgs) : 1;
     const dim3 grid((a.T + TOKS_PER_WG - 1) / TOKS_PER_WG, gy), block(256 * TOKS_PER_WG);
     const int tq = tile_q(a.out, a.n_out, a.C);
+    if (seg) {
+        if (a.bs) return false;  // segments or contexts, not both
+        if (tq == 1) RK_LAUNCH(k_ln_mix_seg<1>, grid, block, 0, st, a, *seg);
+        else if (tq == 2) RK_LAUNCH(k_ln_mix_seg<2>, grid, block, 0, st, a, *seg);
+        else RK_LAUNCH(k_ln_mix_seg<0>, grid, block, 0, st, a, *seg);
+        HIP_OK(hipGetLastError());
+        return true;
+    }
     if (tq == 1) RK_LAUNCH(k_ln_mix<1>, grid, block, 0, st, a);
     else if (tq == 2) RK_LAUNCH(k_ln_mix<2>, grid, block, 0, st, a);
     else RK_LAUNCH(k_ln_mix<0>, grid, block, 0, st, a);
@@ -871,9 +908,10 @@ bool launch_v6_mix5(hipStream_t st, int T, int C, int D, const float * lora, con
 }
 
 // --------------------------------------------------------------------------- v4 wkv
-__global__ __launch_bounds__(256) void k_wkv4(int T, int C, const float * r, const float * k, const float * v,
-                                              const float * first, const float * decay, const float * sin,
-                                              float * sout, ActBuf out, int bs) {
+// tb (every WKV-4 form): the output row of token 0 -- a segment's first row in the packed chunk
+__device__ __forceinline__ void wkv4_body(int T, int C, const float * r, const float * k, const float * v,
+                                          const float * first, const float * decay, const float * sin, float * sout,
+                                          const ActBuf & out, int bs, int tb) {
     const int c = blockIdx.x * blockDim.x + threadIdx.x;
     if ((int)(blockIdx.x * blockDim.x + (threadIdx.x & ~63)) >= C) return;
     // batch (bs > 0): token blockIdx.y is its own context with its state at blockIdx.y * bs
@@ -897,11 +935,30 @@ __global__ __launch_bounds__(256) void k_wkv4(int T, int C, const float * r, con
         aa = e1 * aa + e2 * vt;
         bb = e1 * bb + e2;
         pp = qq;
-        emit32(out, t, c, r[i] * (an / bn));
+        emit32(out, tb + t, c, r[i] * (an / bn));
     }
     sout[2 * C + c] = aa;
     sout[3 * C + c] = bb;
     sout[4 * C + c] = pp;
+}
+
+__global__ __launch_bounds__(256) void k_wkv4(int T, int C, const float * r, const float * k, const float * v,
+                                              const float * first, const float * decay, const float * sin,
+                                              float * sout, ActBuf out, int bs) {
+    wkv4_body(T, C, r, k, v, first, decay, sin, sout, out, bs, 0);
+}
+
+// Segmented forms of the WKV kernels (batched prefill): workgroup (.., .., s) runs segment s of the
+// packed chunk alone -- its len[s] tokens from row begin[s] on, its state read at sin_off[s] and
+// written at sout_off[s] -- so the look-ahead clamps stay inside the segment and its result is bit
+// for bit the unsegmented kernel's on that segment.
+__global__ __launch_bounds__(256) void k_wkv4_seg(SegTab sg, int C, const float * r, const float * k, const float * v,
+                                                  const float * first, const float * decay, const float * sin,
+                                                  float * sout, ActBuf out) {
+    const uint32_t s = blockIdx.z, b = sg.begin[s];
+    const size_t o = (size_t)b * C;
+    wkv4_body((int)sg.len[s], C, r + o, k + o, v + o, first, decay, sin + sg.sin_off[s], sout + sg.sout_off[s], out, 0,
+              (int)b);
 }
 
 // Sequence form (T > 1, one context): the same per-channel recurrence, one wave per 64 channels.
@@ -910,9 +967,9 @@ __global__ __launch_bounds__(256) void k_wkv4(int T, int C, const float * r, con
 // outputs of a chunk are emitted after its recurrence steps, off the chain.  Per channel and
 // token the operations are k_wkv4's, in its order, so decode and sequence stay bit-identical.
 constexpr int WKV4_TT = 16;
-__global__ __launch_bounds__(64) void k_wkv4_seq(int T, int C, const float * r, const float * k, const float * v,
-                                                 const float * first, const float * decay, const float * sin,
-                                                 float * sout, ActBuf out) {
+__device__ __forceinline__ void wkv4_seq_body(int T, int C, const float * r, const float * k, const float * v,
+                                              const float * first, const float * decay, const float * sin,
+                                              float * sout, const ActBuf & out, int tb) {
     const int c = blockIdx.x * 64 + threadIdx.x;
     const int cl = min(c, C - 1);
     float aa = sin[2 * C + cl], bb = sin[3 * C + cl], pp = sin[4 * C + cl];
@@ -956,7 +1013,7 @@ __global__ __launch_bounds__(64) void k_wkv4_seq(int T, int C, const float * r, 
         }
 #pragma unroll
         for (int tt = 0; tt < WKV4_TT; tt++)
-            if (tt < n) emit32(out, t0 + tt, c, y[tt]);
+            if (tt < n) emit32(out, tb + t0 + tt, c, y[tt]);
     }
     if (c < C) {
         sout[2 * C + c] = aa;
@@ -965,9 +1022,37 @@ __global__ __launch_bounds__(64) void k_wkv4_seq(int T, int C, const float * r, 
     }
 }
 
+__global__ __launch_bounds__(64) void k_wkv4_seq(int T, int C, const float * r, const float * k, const float * v,
+                                                 const float * first, const float * decay, const float * sin,
+                                                 float * sout, ActBuf out) {
+    wkv4_seq_body(T, C, r, k, v, first, decay, sin, sout, out, 0);
+}
+
+__global__ __launch_bounds__(64) void k_wkv4_seq_seg(SegTab sg, int C, const float * r, const float * k,
+                                                     const float * v, const float * first, const float * decay,
+                                                     const float * sin, float * sout, ActBuf out) {
+    const uint32_t s = blockIdx.z, b = sg.begin[s];
+    const size_t o = (size_t)b * C;
+    wkv4_seq_body((int)sg.len[s], C, r + o, k + o, v + o, first, decay, sin + sg.sin_off[s], sout + sg.sout_off[s], out,
+                  (int)b);
+}
+
 bool launch_wkv4(hipStream_t st, int T, int C, const float * r, const float * k, const float * v,
                  const float * first, const float * decay, const float * state_in, float * state_out,
-                 const ActBuf & out, int bs) {
+                 const ActBuf & out, int bs, const SegTab * seg) {
+    if (seg) {
+        // the unsegmented rule for the kernel (a segment of one token takes k_wkv4_seq too: per
+        // channel and token the two are the same operations)
+        if (bs) return false;
+        if (C % 64 == 0)
+            RK_LAUNCH(k_wkv4_seq_seg, dim3((C + 63) / 64, 1, seg->n), dim3(64), 0, st, *seg, C, r, k, v, first, decay,
+                      state_in, state_out, out);
+        else
+            RK_LAUNCH(k_wkv4_seg, dim3((C + 255) / 256, 1, seg->n), dim3(256), 0, st, *seg, C, r, k, v, first, decay,
+                      state_in, state_out, out);
+        HIP_OK(hipGetLastError());
+        return true;
+    }
     if (T > 1 && !bs && C % 64 == 0) {  // whole waves of channels
         RK_LAUNCH(k_wkv4_seq, dim3((C + 63) / 64), dim3(64), 0, st, T, C, r, k, v, first, decay, state_in,
                            state_out, out);
@@ -984,9 +1069,9 @@ bool launch_wkv4(hipStream_t st, int T, int C, const float * r, const float * k,
 // One workgroup per head; lane group (j, g): j = value index, g splits the key index i.
 // The state column S[i][j] for the lane's IPG keys lives in registers across all T tokens.
 template <int IPG>
-__global__ void k_wkv6(int T, int H, int S, int G, const float * k, const float * v, const float * r,
-                       const float * u, const float * w, int w_per_token, const float * sin, float * sout,
-                       float * y, int bs) {
+__device__ __forceinline__ void wkv6_body(int T, int H, int S, int G, const float * k, const float * v, const float * r,
+                                          const float * u, const float * w, int w_per_token, const float * sin,
+                                          float * sout, float * y, int bs) {
     const int h = blockIdx.x;
     const int j = threadIdx.x / G, g = threadIdx.x % G;
     const int C = H * S;
@@ -1024,6 +1109,23 @@ __global__ void k_wkv6(int T, int H, int S, int G, const float * k, const float 
     }
 #pragma unroll
     for (int ii = 0; ii < IPG; ii++) sout[hb + (size_t)(g * IPG + ii) * S + j] = st[ii];
+}
+
+template <int IPG>
+__global__ void k_wkv6(int T, int H, int S, int G, const float * k, const float * v, const float * r,
+                       const float * u, const float * w, int w_per_token, const float * sin, float * sout,
+                       float * y, int bs) {
+    wkv6_body<IPG>(T, H, S, G, k, v, r, u, w, w_per_token, sin, sout, y, bs);
+}
+
+template <int IPG>
+__global__ void k_wkv6_seg(SegTab sg, int H, int S, int G, const float * k, const float * v, const float * r,
+                           const float * u, const float * w, int w_per_token, const float * sin, float * sout,
+                           float * y) {
+    const uint32_t s = blockIdx.z;
+    const size_t o = (size_t)sg.begin[s] * H * S;
+    wkv6_body<IPG>((int)sg.len[s], H, S, G, k + o, v + o, r + o, u, w_per_token ? w + o : w, w_per_token,
+                   sin + sg.sin_off[s], sout + sg.sout_off[s], y + o, 0);
 }
 
 static int pick_groups(int S) {
@@ -1077,9 +1179,9 @@ constexpr int WKV6_TC = 64;
 constexpr int WKV6_PAD = 8;  // >= 2 * the token group
 
 template <bool WPT, int NWV>
-__global__ __launch_bounds__(64 * NWV) void k_wkv6_s64(int T, int H, const float * k, const float * v, const float * r,
-                                                       const float * u, const float * w, const float * sin, float * sout,
-                                                       float * y, int bs) {
+__device__ __forceinline__ void wkv6_s64_body(int T, int H, const float * k, const float * v, const float * r,
+                                              const float * u, const float * w, const float * sin, float * sout,
+                                              float * y, int bs) {
     constexpr int S = 64;
     if (bs) {  // batch: context blockIdx.z, one token
         const size_t o = (size_t)blockIdx.z * H * S;
@@ -1267,12 +1369,46 @@ __global__ __launch_bounds__(64 * NWV) void k_wkv6_s64(int T, int H, const float
     }
 }
 
+template <bool WPT, int NWV>
+__global__ __launch_bounds__(64 * NWV) void k_wkv6_s64(int T, int H, const float * k, const float * v, const float * r,
+                                                       const float * u, const float * w, const float * sin, float * sout,
+                                                       float * y, int bs) {
+    wkv6_s64_body<WPT, NWV>(T, H, k, v, r, u, w, sin, sout, y, bs);
+}
+
+template <bool WPT, int NWV>
+__global__ __launch_bounds__(64 * NWV) void k_wkv6_s64_seg(SegTab sg, int H, const float * k, const float * v,
+                                                           const float * r, const float * u, const float * w,
+                                                           const float * sin, float * sout, float * y) {
+    const uint32_t s = blockIdx.z;
+    const size_t o = (size_t)sg.begin[s] * H * 64;
+    wkv6_s64_body<WPT, NWV>((int)sg.len[s], H, k + o, v + o, r + o, u, WPT ? w + o : w, sin + sg.sin_off[s],
+                            sout + sg.sout_off[s], y + o, 0);
+}
+
 int g_wkv6_nwv = 4;  // waves per workgroup of k_wkv6_s64 (tools/wkv_probe.hip varies it)
 
 bool launch_wkv6(hipStream_t st, int T, int H, int S, const float * k, const float * v, const float * r,
                  const float * u, const float * w, int w_per_token, const float * state_in, float * state_out,
-                 float * y, int bs) {
-    const int nz = bs ? T : 1;
+                 float * y, int bs, const SegTab * seg) {
+    if (seg && bs) return false;
+    const int nz = seg ? seg->n : bs ? T : 1;
+    if (seg && S == 64) {
+#define WKV6_L(P, N) RK_LAUNCH((k_wkv6_s64_seg<P, N>), dim3(H, 16 / (N), nz), dim3(64 * (N)), 0, st, *seg, H, k, v, r, u, w, state_in, state_out, y)
+        const int nwv = g_wkv6_nwv;
+        if (w_per_token) {
+            if (nwv == 1) WKV6_L(true, 1);
+            else if (nwv == 2) WKV6_L(true, 2);
+            else WKV6_L(true, 4);
+        } else {
+            if (nwv == 1) WKV6_L(false, 1);
+            else if (nwv == 2) WKV6_L(false, 2);
+            else WKV6_L(false, 4);
+        }
+#undef WKV6_L
+        HIP_OK(hipGetLastError());
+        return true;
+    }
     if (S == 64) {
 #define WKV6_L(P, N) RK_LAUNCH((k_wkv6_s64<P, N>), dim3(H, 16 / (N), nz), dim3(64 * (N)), 0, st, T, H, k, v, r, u, w, state_in, state_out, y, bs)
         const int nwv = g_wkv6_nwv;
@@ -1291,6 +1427,21 @@ bool launch_wkv6(hipStream_t st, int T, int H, int S, const float * k, const flo
     }
     const int G = pick_groups(S), IPG = S / G;
     dim3 grid(H, 1, nz), block(S * G);
+    if (seg) {
+#define WKV6_G(N) case N: RK_LAUNCH(k_wkv6_seg<N>, grid, block, 0, st, *seg, H, S, G, k, v, r, u, w, w_per_token, state_in, state_out, y); break
+        switch (IPG) {
+            WKV6_G(1);
+            WKV6_G(2);
+            WKV6_G(4);
+            WKV6_G(8);
+            WKV6_G(16);
+            WKV6_G(32);
+            default: fprintf(stderr, "rwkv: unsupported head size %d\n", S); return false;
+        }
+#undef WKV6_G
+        HIP_OK(hipGetLastError());
+        return true;
+    }
     switch (IPG) {
         case 1: RK_LAUNCH(k_wkv6<1>, grid, block, 0, st, T, H, S, G, k, v, r, u, w, w_per_token, state_in, state_out, y, bs); break;
         case 2: RK_LAUNCH(k_wkv6<2>, grid, block, 0, st, T, H, S, G, k, v, r, u, w, w_per_token, state_in, state_out, y, bs); break;
@@ -1345,9 +1496,9 @@ bool launch_v7_prep(hipStream_t st, int T, int H, int S, float * k, const float 
 
 // state [h][i(value)][j(key)]; lane group (i, g): g splits j.
 template <int JPG>
-__global__ void k_wkv7(int T, int H, int S, int G, const float * r, const float * w, const float * k,
-                       const float * v, const float * a, const float * b, const float * sin, float * sout,
-                       float * y, int bs) {
+__device__ __forceinline__ void wkv7_body(int T, int H, int S, int G, const float * r, const float * w, const float * k,
+                                          const float * v, const float * a, const float * b, const float * sin,
+                                          float * sout, float * y, int bs) {
     const int h = blockIdx.x;
     const int i = threadIdx.x / G, g = threadIdx.x % G;
     const int C = H * S;
@@ -1384,6 +1535,23 @@ __global__ void k_wkv7(int T, int H, int S, int G, const float * r, const float 
     for (int jj = 0; jj < JPG; jj++) sout[hb + jj] = st[jj];
 }
 
+template <int JPG>
+__global__ void k_wkv7(int T, int H, int S, int G, const float * r, const float * w, const float * k,
+                       const float * v, const float * a, const float * b, const float * sin, float * sout,
+                       float * y, int bs) {
+    wkv7_body<JPG>(T, H, S, G, r, w, k, v, a, b, sin, sout, y, bs);
+}
+
+template <int JPG>
+__global__ void k_wkv7_seg(SegTab sg, int H, int S, int G, const float * r, const float * w, const float * k,
+                           const float * v, const float * a, const float * b, const float * sin, float * sout,
+                           float * y) {
+    const uint32_t s = blockIdx.z;
+    const size_t o = (size_t)sg.begin[s] * H * S;
+    wkv7_body<JPG>((int)sg.len[s], H, S, G, r + o, w + o, k + o, v + o, a + o, b + o, sin + sg.sin_off[s],
+                   sout + sg.sout_off[s], y + o, 0);
+}
+
 // Head size 64: keys in 16 groups of 4 (k_att7_dec's split for S = 64, G = 16).  Workgroup = 4
 // waves over 16 value rows of one head, grid (H, 4); lane (g = lane & 15, il = 4 wv + (lane >> 4))
 // owns row i = 16 blockIdx.y + il, keys j = 4g .. 4g + 3.  Per token: sa = sum_j a_j s_ij (4 terms
@@ -1402,9 +1570,9 @@ __device__ __forceinline__ float row_bfly16(float v) {
     return v;
 }
 
-__global__ __launch_bounds__(256) void k_wkv7_s64(int T, int H, const float * r, const float * w, const float * k,
-                                                  const float * v, const float * a, const float * b,
-                                                  const float * sin, float * sout, float * y, int bs) {
+__device__ __forceinline__ void wkv7_s64_body(int T, int H, const float * r, const float * w, const float * k,
+                                              const float * v, const float * a, const float * b, const float * sin,
+                                              float * sout, float * y, int bs) {
     constexpr int S = 64;
     if (bs) {  // batch: context blockIdx.z, one token
         const size_t o = (size_t)blockIdx.z * H * S;
@@ -1522,10 +1690,31 @@ __global__ __launch_bounds__(256) void k_wkv7_s64(int T, int H, const float * r,
     for (int e = 0; e < 4; e++) sout[hb + e] = st[e];
 }
 
+__global__ __launch_bounds__(256) void k_wkv7_s64(int T, int H, const float * r, const float * w, const float * k,
+                                                  const float * v, const float * a, const float * b,
+                                                  const float * sin, float * sout, float * y, int bs) {
+    wkv7_s64_body(T, H, r, w, k, v, a, b, sin, sout, y, bs);
+}
+
+__global__ __launch_bounds__(256) void k_wkv7_s64_seg(SegTab sg, int H, const float * r, const float * w,
+                                                      const float * k, const float * v, const float * a,
+                                                      const float * b, const float * sin, float * sout, float * y) {
+    const uint32_t s = blockIdx.z;
+    const size_t o = (size_t)sg.begin[s] * H * 64;
+    wkv7_s64_body((int)sg.len[s], H, r + o, w + o, k + o, v + o, a + o, b + o, sin + sg.sin_off[s],
+                  sout + sg.sout_off[s], y + o, 0);
+}
+
 bool launch_wkv7(hipStream_t st, int T, int H, int S, const float * r, const float * w, const float * k,
                  const float * v, const float * a, const float * b, const float * state_in, float * state_out,
-                 float * y, int bs) {
-    const int nz = bs ? T : 1;
+                 float * y, int bs, const SegTab * seg) {
+    if (seg && bs) return false;
+    const int nz = seg ? seg->n : bs ? T : 1;
+    if (seg && S == 64) {
+        RK_LAUNCH(k_wkv7_s64_seg, dim3(H, 4, nz), dim3(256), 0, st, *seg, H, r, w, k, v, a, b, state_in, state_out, y);
+        HIP_OK(hipGetLastError());
+        return true;
+    }
     if (S == 64) {
         RK_LAUNCH(k_wkv7_s64, dim3(H, 4, nz), dim3(256), 0, st, T, H, r, w, k, v, a, b, state_in, state_out, y,
                            bs);
@@ -1534,6 +1723,21 @@ bool launch_wkv7(hipStream_t st, int T, int H, int S, const float * r, const flo
     }
     const int G = pick_groups(S), JPG = S / G;
     dim3 grid(H, 1, nz), block(S * G);
+    if (seg) {
+#define WKV7_G(N) case N: RK_LAUNCH(k_wkv7_seg<N>, grid, block, 0, st, *seg, H, S, G, r, w, k, v, a, b, state_in, state_out, y); break
+        switch (JPG) {
+            WKV7_G(1);
+            WKV7_G(2);
+            WKV7_G(4);
+            WKV7_G(8);
+            WKV7_G(16);
+            WKV7_G(32);
+            default: fprintf(stderr, "rwkv: unsupported head size %d\n", S); return false;
+        }
+#undef WKV7_G
+        HIP_OK(hipGetLastError());
+        return true;
+    }
     switch (JPG) {
         case 1: RK_LAUNCH(k_wkv7<1>, grid, block, 0, st, T, H, S, G, r, w, k, v, a, b, state_in, state_out, y, bs); break;
         case 2: RK_LAUNCH(k_wkv7<2>, grid, block, 0, st, T, H, S, G, r, w, k, v, a, b, state_in, state_out, y, bs); break;
@@ -1597,6 +1801,23 @@ bool launch_groupnorm(hipStream_t st, int T, int H, int S, float eps, const floa
 __global__ void k_fill(float * p, size_t n, float value) {
     const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n) p[i] = value;
+}
+
+__global__ __launch_bounds__(256) void k_copy_rows(const float * src, const uint32_t * src_idx, float * dst,
+                                                   const uint32_t * dst_idx, size_t len) {
+    const size_t i = blockIdx.y;
+    const float * s = src + (src_idx ? (size_t)src_idx[i] : i) * len;
+    float * d = dst + (dst_idx ? (size_t)dst_idx[i] : i) * len;
+    for (size_t e = (size_t)blockIdx.x * 256 + threadIdx.x; e < len; e += (size_t)gridDim.x * 256) d[e] = s[e];
+}
+
+bool launch_copy_rows(hipStream_t st, const float * src, const uint32_t * src_idx, float * dst, const uint32_t * dst_idx,
+                      int n, size_t len) {
+    if (n <= 0 || len == 0) return true;
+    const unsigned gx = (unsigned)std::min<size_t>((len + 255) / 256, 1024);
+    RK_LAUNCH(k_copy_rows, dim3(gx, (unsigned)n), dim3(256), 0, st, src, src_idx, dst, dst_idx, len);
+    HIP_OK(hipGetLastError());
+    return true;
 }
 
 bool launch_fill(hipStream_t st, float * p, size_t n, float value) {

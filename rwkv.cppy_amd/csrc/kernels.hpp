@@ -39,7 +39,20 @@ struct LnMixArgs {
     size_t bs;                  // 0: one sequence; > 0: batched decode -- token t is context t, its
                                 // carries at carry_in/out + t * bs (state floats per context)
 };
-bool launch_ln_mix(hipStream_t st, const LnMixArgs & a);
+// A packed chunk of T tokens cut into segments (batched prefill, Engine::prefill_batch): segment s is
+// the tokens [begin[s], begin[s] + len[s]) (len >= 1; the segments tile [0, T) in order) of one row,
+// with a state of its own, read at sin_off[s] and written at sout_off[s] -- float offsets from the
+// state pointers a launch takes, which differ for every segment (a segment's first token reads what
+// another workgroup's last token would otherwise be writing).  seg_of[t]: the segment of token t.
+// Device pointers; every entry is validated on the host before a launch reads it.
+struct SegTab {
+    int n;
+    const uint32_t * begin, * len;
+    const uint64_t * sin_off, * sout_off;
+    const uint32_t * seg_of;
+};
+// seg (launch_ln_mix and every wkv launcher): the segmented form over the packed chunk (bs == 0)
+bool launch_ln_mix(hipStream_t st, const LnMixArgs & a, const SegTab * seg = nullptr);
 
 // v6: xs[n] = (W2[n] . lora_n + maa[n]) * sx + xa, n = w,k,v,r,g   (rwkv_graph.inc:313-346)
 bool launch_v6_mix5(hipStream_t st, int T, int C, int D, const float * lora, const float * w2,
@@ -48,14 +61,14 @@ bool launch_v6_mix5(hipStream_t st, int T, int C, int D, const float * lora, con
 // v4 wkv with aa/bb/pp state (rwkv_graph.inc:119-161); emits r*wkv into `out`.
 bool launch_wkv4(hipStream_t st, int T, int C, const float * r, const float * k, const float * v,
                  const float * first, const float * decay, const float * state_in, float * state_out,
-                 const ActBuf & out, int bs = 0);
+                 const ActBuf & out, int bs = 0, const SegTab * seg = nullptr);
 
 // ggml_rwkv_wkv6 semantics (v5/v6): y[T][C]; w_per_token selects v6 (w [T][C]) vs v5 (w [C]).
 // bs > 0 (every wkv launcher): batched decode -- the T tokens are T contexts, one token each,
 // context t's state at state_in/out + t * bs.
 bool launch_wkv6(hipStream_t st, int T, int H, int S, const float * k, const float * v, const float * r,
                  const float * u, const float * w, int w_per_token, const float * state_in,
-                 float * state_out, float * y, int bs = 0);
+                 float * state_out, float * y, int bs = 0, const SegTab * seg = nullptr);
 
 // Chunk-parallel wkv6 (wkv_chunk.hip, head size 64, T >= 2, no batch): the same recurrence with the
 // sums re-associated (not bit-exact with launch_wkv6).  RA / KB: [T][C] scratch; scratch:
@@ -82,7 +95,7 @@ bool launch_v7_prep(hipStream_t st, int T, int H, int S, float * k, const float 
 // rwkv_operators_wkv_v7.inc:37-107
 bool launch_wkv7(hipStream_t st, int T, int H, int S, const float * r, const float * w, const float * k,
                  const float * v, const float * a, const float * b, const float * state_in,
-                 float * state_out, float * y, int bs = 0);
+                 float * state_out, float * y, int bs = 0, const SegTab * seg = nullptr);
 
 // GroupNorm over heads + ln_x (+ v7 bonus) (+ gate), emitted as the output projection's input.
 // mode 0: none, 1: *g, 2: + v*bonus then *g
@@ -93,6 +106,12 @@ bool launch_groupnorm(hipStream_t st, int T, int H, int S, float eps, const floa
 // LN of rows x[0..rows) emitted into rows 0..rows of an ActBuf (head input).
 bool launch_ln_emit(hipStream_t st, int C, const float * x, const float * w, const float * b, const ActBuf & out,
                     int rows = 1);
+
+// Row i of n: dst[(dst_idx ? dst_idx[i] : i) * len ..] = src[(src_idx ? src_idx[i] : i) * len ..], len
+// floats, in one launch (batched prefill: the residual rows that end a prompt, the logits rows into
+// their slots, states between the two slot buffers).  The index arrays are device memory.
+bool launch_copy_rows(hipStream_t st, const float * src, const uint32_t * src_idx, float * dst, const uint32_t * dst_idx,
+                      int n, size_t len);
 
 // v4 state init value helper: fills n floats with value
 bool launch_fill(hipStream_t st, float * p, size_t n, float value);

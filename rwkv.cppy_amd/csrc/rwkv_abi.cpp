@@ -19,6 +19,7 @@
 #include "engine.hpp"
 #include "model_file.hpp"
 #include "pipeline.hpp"
+#include "prefill_plan.hpp"
 
 using namespace rwkvmi;
 
@@ -736,6 +737,45 @@ RWKV_API bool rwkv_mi355x_generate_batch(struct rwkv_context * ctx, size_t B, co
     CTX_CHECK(ctx, RWKV_ERROR_CTX, false, ctx->engine->generate_batch(B, bp, n, tokens_out, lengths_out, steps_out),
               "GPU batched generation failed");
     return true;
+}
+
+RWKV_API bool rwkv_mi355x_prefill_batch(struct rwkv_context * ctx, size_t n_rows, const uint32_t * slots,
+                                        const uint32_t * tokens, const size_t * lengths, const uint8_t * cont) {
+    if (!ctx || !ctx->engine) return false;
+    ctx->last_error = RWKV_ERROR_NONE;
+    if (!batch_ctx_ok(ctx)) return false;
+    const uint32_t V = ctx->model->dm.n_vocab;
+    const size_t reserved = ctx->engine->batch_slots();
+    CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, n_rows > 0 && n_rows <= reserved, "Prefill of %zu rows with %zu slots reserved",
+              n_rows, reserved);
+    CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, slots != nullptr && tokens != nullptr && lengths != nullptr,
+              "NULL slots, tokens or lengths");
+    bool seen[Engine::kBatchMax] = {};
+    size_t at = 0;
+    for (size_t i = 0; i < n_rows; i++) {
+        CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, slots[i] < reserved, "Row %zu: slot %" PRIu32 " of %zu reserved", i, slots[i],
+                  reserved);
+        CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, !seen[slots[i]], "Row %zu: slot %" PRIu32 " is named twice", i, slots[i]);
+        seen[slots[i]] = true;
+        CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, lengths[i] > 0, "Row %zu is empty", i);
+        CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, lengths[i] <= ((size_t)1 << 31) - at, "Row %zu: too many tokens", i);
+        CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, !cont || !cont[i] || ctx->engine->batch_slot_valid(slots[i]),
+                  "Row %zu continues slot %" PRIu32 ", which holds nothing", i, slots[i]);
+        for (size_t t = 0; t < lengths[i]; t++)
+            CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, tokens[at + t] < V, "Row %zu: token at index %zu (%" PRIu32 ") is out of range",
+                      i, t, tokens[at + t]);
+        at += lengths[i];
+    }
+    use_device(ctx);
+    CTX_CHECK(ctx, RWKV_ERROR_CTX, false, ctx->engine->prefill_batch(n_rows, slots, tokens, lengths, cont),
+              "GPU batched prefill failed");
+    return true;
+}
+
+RWKV_API long long rwkv_mi355x_selftest_prefill_plan(const size_t * lengths, size_t n_rows, size_t cap, uint32_t * seg_row,
+                                                     uint32_t * seg_begin, uint32_t * seg_len, uint32_t * seg_chunk,
+                                                     size_t max_segs) {
+    return prefill_plan(lengths, n_rows, cap, seg_row, seg_begin, seg_len, seg_chunk, max_segs);
 }
 
 RWKV_API bool rwkv_mi355x_score_sequence(struct rwkv_context * ctx, const uint32_t * tokens, size_t T,

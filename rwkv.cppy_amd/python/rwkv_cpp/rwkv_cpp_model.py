@@ -205,15 +205,45 @@ class RWKVModel:
             raise ValueError('Model was freed')
         self._library.rwkv_mi355x_batch_load(self._ctx, slot)
 
+    def prefill_batch(self, prompts: List[List[int]], slots=None, cont=False) -> None:
+        """MI355X extension (rwkv_mi355x_prefill_batch): evaluates the prompts together, packed into
+        sequence passes of up to 1024 tokens, so the weights are read once per pass instead of once per
+        prompt.  Prompt i lands in slots[i] (None: slot i; slots are reserved when there are too few)
+        exactly as reset_state / eval / batch_store would leave it.  cont: a bool or one per prompt;
+        true continues from the slot's state instead of a fresh one.  The model's own state and logits
+        are untouched."""
+        if not self._valid:
+            raise ValueError('Model was freed')
+        rows = len(prompts)
+        if not 0 < rows <= 256:
+            raise ValueError(f'{rows} prompts (1 to 256)')
+        if any(len(p) == 0 for p in prompts):
+            raise ValueError('empty prompt')
+        slots = list(range(rows)) if slots is None else [int(s) for s in slots]
+        if len(slots) != rows:
+            raise ValueError(f'{len(slots)} slots for {rows} prompts')
+        if len(set(slots)) != rows or any(not 0 <= s < 256 for s in slots):
+            raise ValueError('slots must be distinct and in [0, 256)')
+        cont = [bool(cont)] * rows if isinstance(cont, (bool, int)) else [bool(c) for c in cont]
+        if len(cont) != rows:
+            raise ValueError(f'{len(cont)} cont flags for {rows} prompts')
+        need = max(slots) + 1
+        if self._library.rwkv_mi355x_batch_slots(self._ctx) < need:
+            if any(cont):
+                raise ValueError(f'slot {need - 1} is not reserved: nothing to continue from')
+            self._library.rwkv_mi355x_batch_reserve(self._ctx, need)
+        self._library.rwkv_mi355x_prefill_batch(self._ctx, [list(p) for p in prompts], slots, cont)
+
     def generate_batch(self, prompts: List[List[int]], n: int, temperature=1.0, top_p=0.8, presence_penalty=0.0,
                        frequency_penalty=0.0, logit_bias=None, seeds=None, stop_tokens=(),
-                       check_every: int = 16) -> List[List[int]]:
+                       check_every: int = 16, batched_prefill: bool = False) -> List[List[int]]:
         """MI355X extension (rwkv_mi355x_generate_batch): generates up to n tokens for every prompt, all
         rows together on the device: sampling, penalties over the tokens a row has drawn, exact stops
         and one batched decode step per token, with only the tokens coming back.  temperature, top_p,
         the penalties and seeds are scalars or one value per prompt (seeds None: row r uses seed r);
         logit_bias and stop_tokens are shared.  Each prompt is evaluated from a fresh state on the
-        device and stored into slot i (slots are reserved as needed).  Returns one token list per
+        device and stored into slot i (slots are reserved as needed); batched_prefill evaluates the
+        prompts together (prefill_batch) instead of one after the other, with the same bits.  Returns one token list per
         prompt; a list that ends early ends with a stop token, which is not evaluated: slot i then
         holds the state before it, and batch_load(i) continues from there."""
         if not self._valid:
@@ -230,7 +260,9 @@ class RWKVModel:
             False, check_every)
         if self._library.rwkv_mi355x_batch_slots(self._ctx) < rows:
             self._library.rwkv_mi355x_batch_reserve(self._ctx, rows)
-        for slot, prompt in enumerate(prompts):
+        if batched_prefill:
+            self._library.rwkv_mi355x_prefill_batch(self._ctx, [list(p) for p in prompts], list(range(rows)), None)
+        for slot, prompt in ([] if batched_prefill else enumerate(prompts)):
             self.reset_state()
             self._library.rwkv_mi355x_eval_device(self._ctx, list(prompt))
             self._library.rwkv_mi355x_batch_store(self._ctx, slot)

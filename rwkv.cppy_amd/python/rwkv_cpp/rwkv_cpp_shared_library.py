@@ -239,6 +239,11 @@ class RWKVSharedLibrary:
         L.rwkv_mi355x_batch_load.restype = ctypes.c_bool
         L.rwkv_mi355x_generate_batch.argtypes = [vp, sz, P_BATCH, sz, P_U32, P_U32, P_U32]
         L.rwkv_mi355x_generate_batch.restype = ctypes.c_bool
+        P_SIZE = ctypes.POINTER(sz)
+        L.rwkv_mi355x_prefill_batch.argtypes = [vp, sz, P_U32, P_U32, P_SIZE, ctypes.POINTER(ctypes.c_uint8)]
+        L.rwkv_mi355x_prefill_batch.restype = ctypes.c_bool
+        L.rwkv_mi355x_selftest_prefill_plan.argtypes = [P_SIZE, sz, sz, P_U32, P_U32, P_U32, P_U32, sz]
+        L.rwkv_mi355x_selftest_prefill_plan.restype = ctypes.c_longlong
         L.rwkv_mi355x_selftest_sample_rows.argtypes = [P_FLOAT, ctypes.c_int, ctypes.c_int, P_BATCH, P_FLOAT, u32, P_U32,
                                                        P_U32, P_U32, P_U32, P_U32, P_FLOAT, P_U32, P_U32]
         L.rwkv_mi355x_selftest_sample_rows.restype = ctypes.c_bool
@@ -417,6 +422,35 @@ class RWKVSharedLibrary:
                                                        ctypes.byref(steps)):
             raise ValueError('rwkv_mi355x_generate_batch failed, check stderr')
         return tokens[:, :n], lengths, steps.value
+
+    def rwkv_mi355x_prefill_batch(self, ctx: RWKVContext, prompts, slots, cont=None) -> None:
+        """Evaluates the prompts (token lists, none empty) together in packed sequence passes; prompt i
+        lands in slots[i] as reset / rwkv_mi355x_eval_device / rwkv_mi355x_batch_store would leave it,
+        bit for bit.  cont: None, or one flag per prompt -- true continues from the slot's state."""
+        rows = len(prompts)
+        if len(slots) != rows or (cont is not None and len(cont) != rows):
+            raise ValueError('one slot (and one cont flag) per prompt')
+        flat = [int(t) for p in prompts for t in p]
+        tokens = (ctypes.c_uint32 * max(1, len(flat)))(*flat)
+        lengths = (ctypes.c_size_t * max(1, rows))(*[len(p) for p in prompts])
+        slot_arr = (ctypes.c_uint32 * max(1, rows))(*[int(s) for s in slots])
+        cont_arr = None if cont is None else (ctypes.c_uint8 * max(1, rows))(*[1 if c else 0 for c in cont])
+        if not self.library.rwkv_mi355x_prefill_batch(ctx.ptr, rows, slot_arr, tokens, lengths, cont_arr):
+            raise ValueError('rwkv_mi355x_prefill_batch failed, check stderr')
+
+    def rwkv_mi355x_selftest_prefill_plan(self, lengths, cap: int, max_segs: Optional[int] = None):
+        """The host planner of rwkv_mi355x_prefill_batch (no GPU).  Returns (count, rows, begins, lens,
+        chunks): count as the library returns it (negative: max_segs too small, or bad arguments) and
+        the four uint32 arrays of max_segs entries, entries past count untouched (0xFFFFFFFF)."""
+        import numpy as np
+        n = len(lengths)
+        if max_segs is None:
+            max_segs = n + sum(lengths) // max(1, cap) + 1
+        arrs = [np.full(max_segs, 0xFFFFFFFF, np.uint32) for _ in range(4)]
+        larr = (ctypes.c_size_t * max(1, n))(*[int(x) for x in lengths])
+        count = self.library.rwkv_mi355x_selftest_prefill_plan(
+            larr, n, cap, *[a.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)) for a in arrs], max_segs)
+        return (int(count), *arrs)
 
     def rwkv_mi355x_selftest_sample_rows(self, logits, u, temperature, top_p, presence=None, frequency=None,
                                          counts=None, done=None, logit_bias=None, stop_tokens=(), step: int = 0,
