@@ -414,6 +414,13 @@ RWKV_API bool rwkv_mi355x_selftest_groupnorm(int T, int H, int S, float eps, int
  * x, out: [rows][C]; w, b: [C]; C % 64 == 0. */
 RWKV_API bool rwkv_mi355x_selftest_ln(int C, int rows, const float * x, const float * w, const float * b, float * out);
 
+/* The decode matvecs' multi-row wave reduction (wave_sums) against the single-row tree (wave_sum63),
+ * one wave on host operands.  n = 2, 4, ..., 64: p [64 lanes][n]; sums[l] = the result of lane l
+ * (slot l & (n - 1)); ref[j] = the single-row tree of slot j.  n = 3 / -3: the padded three-row
+ * form on p [64][6] (acc then acc2 per lane) for a plain / a _1 format; ref[j] = the per-row
+ * expression (sum + 0.0f / sum + sum2).  sums: 64 floats, ref: |n| floats. */
+RWKV_API bool rwkv_mi355x_selftest_wave_sums(int n, const float * p, float * sums, float * ref);
+
 #if defined(__cplusplus)
 }
 #endif

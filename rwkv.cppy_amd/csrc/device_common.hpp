@@ -35,6 +35,94 @@ __device__ __forceinline__ float wave_sum63(float v) {
     return v;
 }
 
+// N wave sums at once (N a power of two, 2..64): every lane holds N partials p[0..N-1]; lane l
+// returns the wave total of slot l & (N - 1), with exactly wave_sum63's bits for that slot.
+//
+// Why the bits hold: wave_sum63 is the balanced binary tree over adjacent lanes (pairs, quads, 8,
+// 16, 32, 64), and IEEE addition is commutative bit for bit (NaN payloads aside: the matvecs never
+// produce NaN), so only the tree's shape matters, not the operand order nor which lane holds a
+// node.  Here level k (xor distance D = 1, 2, 4, ...) is a butterfly: a lane keeps half of its
+// slots -- the even ones when its lane bit D is clear, the odd ones when it is set -- and adds to
+// each the same slot of lane ^ D, which holds the same slot set and keeps the other half.  Each sum
+// is therefore node (level k, lane group) of that slot's adjacent-lane tree, computed once instead
+// of in every lane, and the kept slot index gains lane bit D as its next bit.  After log2 N levels
+// one slot is left per lane (slot = lane & (N - 1)); the remaining levels are plain xor exchanges
+// x + x[lane ^ D] up to D = 32.  About 3 VALU per surviving slot and level instead of 12 per slot.
+//
+// Cross-lane forms: D = 1, 2 DPP quad_perm; D = 4, 8 two DPP row rotations under complementary bank
+// masks (a rotation by 16 - D reaches lane + D, by D lane - D); D = 16, 32 v_permlane16_swap /
+// v_permlane32_swap, which exchange the odd rows (upper half) of one register with the even rows
+// (lower half) of another -- with the even and the odd slot as the two registers, the sum of the
+// two results is the level.  (wave_sum63's mirror and broadcast controls pair lanes that hold
+// different slot sets here.)
+template <int D>
+__device__ __forceinline__ float xfold2(float x, float y, bool up) {
+    static_assert(D == 1 || D == 2 || D == 4 || D == 8 || D == 16 || D == 32, "xor distance");
+    const int xi = __builtin_bit_cast(int, x), yi = __builtin_bit_cast(int, y);
+    if constexpr (D == 1 || D == 2) {
+        const float keep = up ? y : x;
+        const int send = up ? xi : yi;
+        return keep + __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, send, D == 1 ? 0xB1 : 0x4E, 0xF, 0xF, false));
+    } else if constexpr (D == 4) {
+        int r = __builtin_amdgcn_update_dpp(0, xi, 0x12C, 0xF, 0xF, false);  // row_ror:12: x of lane + 4
+        r = __builtin_amdgcn_update_dpp(r, yi, 0x124, 0xF, 0xA, false);      // banks 1, 3: y of lane - 4
+        return (up ? y : x) + __builtin_bit_cast(float, r);
+    } else if constexpr (D == 8) {
+        int r = __builtin_amdgcn_update_dpp(0, xi, 0x128, 0xF, 0xF, false);  // row_ror:8
+        r = __builtin_amdgcn_update_dpp(r, yi, 0x128, 0xF, 0xC, false);      // banks 2, 3: y
+        return (up ? y : x) + __builtin_bit_cast(float, r);
+    } else if constexpr (D == 16) {
+        const auto p = __builtin_amdgcn_permlane16_swap(xi, yi, false, false);
+        return __builtin_bit_cast(float, (int)p[0]) + __builtin_bit_cast(float, (int)p[1]);
+    } else {
+        const auto p = __builtin_amdgcn_permlane32_swap(xi, yi, false, false);
+        return __builtin_bit_cast(float, (int)p[0]) + __builtin_bit_cast(float, (int)p[1]);
+    }
+}
+// x + x[lane ^ D] on every lane
+template <int D>
+__device__ __forceinline__ float xfold1(float x) {
+    static_assert(D == 1 || D == 2 || D == 4 || D == 8 || D == 16 || D == 32, "xor distance");
+    const int xi = __builtin_bit_cast(int, x);
+    if constexpr (D == 1) {
+        return dpp_add<0xB1, 0xF>(x);
+    } else if constexpr (D == 2) {
+        return dpp_add<0x4E, 0xF>(x);
+    } else if constexpr (D == 4) {
+        int r = __builtin_amdgcn_update_dpp(0, xi, 0x12C, 0xF, 0xF, false);
+        r = __builtin_amdgcn_update_dpp(r, xi, 0x124, 0xF, 0xA, false);
+        return x + __builtin_bit_cast(float, r);
+    } else if constexpr (D == 8) {
+        return dpp_add<0x128, 0xF>(x);
+    } else if constexpr (D == 16) {
+        const auto p = __builtin_amdgcn_permlane16_swap(xi, xi, false, false);
+        return __builtin_bit_cast(float, (int)p[0]) + __builtin_bit_cast(float, (int)p[1]);
+    } else {
+        const auto p = __builtin_amdgcn_permlane32_swap(xi, xi, false, false);
+        return __builtin_bit_cast(float, (int)p[0]) + __builtin_bit_cast(float, (int)p[1]);
+    }
+}
+template <int N, int D>
+__device__ __forceinline__ float wave_sums_level(const float (&a)[N], int lane) {
+    if constexpr (D == 64) {
+        static_assert(N == 1, "one slot per lane after the last level");
+        return a[0];
+    } else if constexpr (N == 1) {
+        const float b[1] = {xfold1<D>(a[0])};
+        return wave_sums_level<1, 2 * D>(b, lane);
+    } else {
+        float b[N / 2];
+#pragma unroll
+        for (int i = 0; i < N / 2; i++) b[i] = xfold2<D>(a[2 * i], a[2 * i + 1], (lane & D) != 0);
+        return wave_sums_level<N / 2, 2 * D>(b, lane);
+    }
+}
+template <int N>
+__device__ __forceinline__ float wave_sums(const float (&p)[N], int lane) {
+    static_assert(N >= 2 && N <= 64 && (N & (N - 1)) == 0, "N: a power of two in 2..64");
+    return wave_sums_level<N, 1>(p, lane);
+}
+
 // sum over groups of `width` adjacent lanes (width power of two <= 64); all lanes get the sum
 template <typename T>
 __device__ __forceinline__ T group_sum(T v, int width) {

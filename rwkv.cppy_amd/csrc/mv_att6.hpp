@@ -40,11 +40,7 @@ __device__ __forceinline__ float af_rows(const DMat & W, const ActBuf & x, int r
             acc2[r] = valid ? t2 : acc2[r];
         }
     }
-    constexpr bool one = WF == W_Q4_1 || WF == W_Q5_1;
-    float sr[R];
-#pragma unroll
-    for (int r = 0; r < R; r++) sr[r] = one ? wave_sum63(acc[r]) + wave_sum63(acc2[r]) : wave_sum63(acc[r]) + 0.0f;
-    const float s = lane_row_sum<R>(sr, lane);
+    const float s = row_sums<WF, R>(acc, acc2, lane);
     return epi == EPI_SILU ? siluf_(s) : epi == EPI_TANH ? rk_tanhf(s) : s;
 }
 

@@ -126,12 +126,7 @@ __global__ __launch_bounds__(320) void k_v6_att_co(Att6Fused a) {
                     acc2[j] = uv ? t2 : acc2[j];
                 }
             }
-            constexpr bool one = WF == W_Q4_1 || WF == W_Q5_1;
-            float sr_[AF_WOR];
-#pragma unroll
-            for (int j = 0; j < AF_WOR; j++)
-                sr_[j] = one ? wave_sum63(acc[j]) + wave_sum63(acc2[j]) : wave_sum63(acc[j]) + 0.0f;
-            const float s = lane_row_sum<AF_WOR>(sr_, lane);
+            const float s = row_sums<WF, AF_WOR>(acc, acc2, lane);
             const int row = gw + nwo * lane;
             if (lane < AF_WOR && row < C) a.xres[row] = xr + s;  // EPI_ADD
         }

@@ -2,7 +2,7 @@
 //
 // y[t][m] = W[m] . x[t] for the B activation rows of B contexts (MMGroup, T = B), with the decode
 // matvec's per-output arithmetic (k_mva / k_mv: lane l accumulates units l, l+64, ... with the
-// same fma chain, wave_sum63 folds the 64 lanes), so context t's outputs are bit-identical to its
+// same fma chain, wave_sum63's tree folds the 64 lanes), so context t's outputs are bit-identical to its
 // single-context decode.  What changes is the weight traffic: a wave loads its R rows' units into
 // registers ONCE (non-temporal, one HBM round trip) and streams the B activation rows past them
 // (L2-resident, each prefetched one context ahead), so a step reads every weight byte once for
@@ -59,38 +59,67 @@ __global__ __launch_bounds__(256) void k_mvb(MMGroup g) {
         for (int u = 0; u < U; u++) xb[p][u] = load_act_unit<WF, false>(a, u, lane);
     }
     constexpr bool one = WF == W_Q4_1 || WF == W_Q5_1;
+    // The row sums of G contexts of a ring round are folded together: their G * R partials (per
+    // accumulator) go through one wave_sums butterfly -- the bits of wave_sum63 per (context, row) --
+    // and lane j < G * R stores (context j / R, row j % R) to red[] in one LDS write, instead of one
+    // tree and one lane-63 store per pair.  G * R <= 32 partials per accumulator, 16 for the _1
+    // formats' two, so the held partials stay within the registers the dots leave free.  WIDE: the
+    // emitting shape with two units per lane (R = 8, U = 2) and the one-row shape (U = 8) already hold
+    // 244-256 VGPRs (the latter with AGPR copies); they keep one wave_sum63 per (context, row).
+    constexpr bool WIDE = R * U >= 16 || U >= 8;
+    constexpr int GMAX = WIDE ? 1 : (one ? 16 : 32) / R;
+    constexpr int G = PD < GMAX ? PD : GMAX;
+    static_assert(G >= 1 && PD % G == 0 && (WIDE || G * R >= 2), "contexts per reduction");
 #pragma unroll 1
     for (int t0 = 0; t0 < T; t0 += PD) {
 #pragma unroll
-        for (int p = 0; p < PD; p++) {
-            const int t = t0 + p;
-            if (t >= T) break;  // uniform
-            AUnit x[U];
+        for (int p0 = 0; p0 < PD; p0 += G) {
+            if (t0 + p0 >= T) break;  // uniform
+            float pa[G * R], pa2[G * R];
 #pragma unroll
-            for (int u = 0; u < U; u++) x[u] = xb[p][u];
-            if (t + PD < T) {
-                const ActBuf a = act_row(t + PD);
+            for (int j = 0; j < G * R; j++) pa[j] = pa2[j] = 0.0f;
 #pragma unroll
-                for (int u = 0; u < U; u++) xb[p][u] = load_act_unit<WF, false>(a, u, lane);
-            }
-            float acc[R], acc2[R];
+            for (int q = 0; q < G; q++) {
+                const int p = p0 + q, t = t0 + p;
+                if (t < T) {  // uniform
+                    AUnit x[U];
 #pragma unroll
-            for (int r = 0; r < R; r++) acc[r] = acc2[r] = 0.0f;
+                    for (int u = 0; u < U; u++) x[u] = xb[p][u];
+                    if (t + PD < T) {
+                        const ActBuf a = act_row(t + PD);
 #pragma unroll
-            for (int u = 0; u < U; u++) {
-                const bool valid = unit_valid<WF>(K, u, lane);
+                        for (int u = 0; u < U; u++) xb[p][u] = load_act_unit<WF, false>(a, u, lane);
+                    }
+                    float acc[R], acc2[R];
 #pragma unroll
-                for (int r = 0; r < R; r++) {
-                    float s = acc[r], s2 = acc2[r];
-                    dot_unit<WF>(w[r][u], x[u], s, s2);
-                    acc[r] = valid ? s : acc[r];
-                    acc2[r] = valid ? s2 : acc2[r];
+                    for (int r = 0; r < R; r++) acc[r] = acc2[r] = 0.0f;
+#pragma unroll
+                    for (int u = 0; u < U; u++) {
+                        const bool valid = unit_valid<WF>(K, u, lane);
+#pragma unroll
+                        for (int r = 0; r < R; r++) {
+                            float s = acc[r], s2 = acc2[r];
+                            dot_unit<WF>(w[r][u], x[u], s, s2);
+                            acc[r] = valid ? s : acc[r];
+                            acc2[r] = valid ? s2 : acc2[r];
+                        }
+                    }
+#pragma unroll
+                    for (int r = 0; r < R; r++) pa[q * R + r] = acc[r], pa2[q * R + r] = acc2[r];
                 }
             }
+            if constexpr (WIDE) {  // G = 1: one tree and one lane-63 store per row
 #pragma unroll
-            for (int r = 0; r < R; r++) {
-                const float s = one ? wave_sum63(acc[r]) + wave_sum63(acc2[r]) : wave_sum63(acc[r]) + 0.0f;
-                if (lane == 63) red[t * RW + wave * R + r] = s;
+                for (int r = 0; r < R; r++) {
+                    const float s = one ? wave_sum63(pa[r]) + wave_sum63(pa2[r]) : wave_sum63(pa[r]) + 0.0f;
+                    if (lane == 63) red[(t0 + p0) * RW + wave * R + r] = s;
+                }
+            } else {
+                float s;
+                if constexpr (one) s = wave_sums<G * R>(pa, lane) + wave_sums<G * R>(pa2, lane);
+                else s = wave_sums<G * R>(pa, lane) + 0.0f;
+                const int t = t0 + p0 + lane / R;
+                if (lane < G * R && t < T) red[t * RW + wave * R + lane % R] = s;
             }
         }
     }

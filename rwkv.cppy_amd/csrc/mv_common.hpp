@@ -359,6 +359,34 @@ __device__ __forceinline__ float lane_row_sum(const float (&s)[R], int lane) {
     return mine;
 }
 
+// The R row sums of a wave, lane r < R holding row r's: wave_sum63(acc[r]) + 0.0f, or for the _1
+// formats wave_sum63(acc[r]) + wave_sum63(acc2[r]) -- the same bits, by one wave_sums butterfly
+// over the R (2 R) partials instead of R (2 R) full trees and R readlanes (R = 3 pads a zero slot;
+// the _1 formats' second sums land RP lanes up and come down by one more exchange).  R = 1 keeps
+// wave_sum63.
+template <int WF, int R>
+__device__ __forceinline__ float row_sums(const float (&acc)[R], const float (&acc2)[R], int lane) {
+    constexpr bool one = WF == W_Q4_1 || WF == W_Q5_1;
+    if constexpr (R == 1) {
+        const float s[1] = {one ? wave_sum63(acc[0]) + wave_sum63(acc2[0]) : wave_sum63(acc[0]) + 0.0f};
+        return lane_row_sum<1>(s, lane);
+    } else {
+        constexpr int RP = R <= 2 ? 2 : R <= 4 ? 4 : R <= 8 ? 8 : R <= 16 ? 16 : 32;
+        static_assert(R <= RP && 2 * RP <= 64, "rows per wave");
+        if constexpr (one) {
+            float p[2 * RP];
+#pragma unroll
+            for (int r = 0; r < RP; r++) p[r] = r < R ? acc[r < R ? r : 0] : 0.0f, p[RP + r] = r < R ? acc2[r < R ? r : 0] : 0.0f;
+            return xfold1<RP>(wave_sums<2 * RP>(p, lane));
+        } else {
+            float p[RP];
+#pragma unroll
+            for (int r = 0; r < RP; r++) p[r] = r < R ? acc[r < R ? r : 0] : 0.0f;
+            return wave_sums<RP>(p, lane) + 0.0f;
+        }
+    }
+}
+
 // R rows whose U units per lane are already in registers, dotted with an LDS activation image:
 // k_mva's per-row arithmetic (lane/unit order, wave_sum63 tree; the unit count mv_units(WF, K)
 // must be <= U).  Lane r < R returns row r's sum.
@@ -379,11 +407,7 @@ __device__ __forceinline__ float rows_dot_img(const WBlk (&w)[R][U], const ActBu
             acc2[r] = uv ? t2 : acc2[r];
         }
     }
-    constexpr bool one = WF == W_Q4_1 || WF == W_Q5_1;
-    float s[R];
-#pragma unroll
-    for (int r = 0; r < R; r++) s[r] = one ? wave_sum63(acc[r]) + wave_sum63(acc2[r]) : wave_sum63(acc[r]) + 0.0f;
-    return lane_row_sum<R>(s, lane);
+    return row_sums<WF, R>(acc, acc2, lane);
 }
 
 // Epilogue operands of one output row, loaded at kernel start (not after the dots).
@@ -588,8 +612,7 @@ __device__ __forceinline__ void mv_body(const MVEntry & Ent, int wgi, int b0, in
 
     for (;;) {
         // dots (the waves with rows)
-        constexpr bool one = WF == W_Q4_1 || WF == W_Q5_1;
-        float s[RR];
+        float s = 0.0f;  // lane r < RR: row r's sum
         if (has_rows) {
             float acc[RR], acc2[RR];
 #pragma unroll
@@ -613,27 +636,21 @@ __device__ __forceinline__ void mv_body(const MVEntry & Ent, int wgi, int b0, in
                 }
             }
             // reduce
-#pragma unroll
-            for (int r = 0; r < RR; r++) s[r] = one ? wave_sum63(acc[r]) + wave_sum63(acc2[r]) : wave_sum63(acc[r]) + 0.0f;
-        } else {
-#pragma unroll
-            for (int r = 0; r < RR; r++) s[r] = 0.0f;
+            s = row_sums<WF, RR>(acc, acc2, lane);
         }
         if constexpr (!EMIT) {
 #ifdef MV_PROBE
-            if (s[0] == 1.2345f) g_probe[0] = 0;  // orders the stamp after the dots
+            if (s == 1.2345f) g_probe[0] = 0;  // orders the stamp after the dots
 #endif
             PROBE(2);
-            const float v = epi_apply(epi, lane_row_sum<RR>(s, lane), ep);
+            const float v = epi_apply(epi, s, ep);
             if (has_rows && lane < RR && row0 + lane < M) ey[row0 + lane] = v;
         } else {
             // RW rows per block (a multiple of 32): apply the epilogue and emit each 32 rows as
             // one quantization block of the next matmul's input (ggml Q8 / fp16 / fp32)
-#pragma unroll
-            for (int r = 0; r < RR; r++)
-                if (has_rows && lane == 63) red[wave * RR + r] = s[r];
+            if (has_rows && lane < RR) red[wave * RR + lane] = s;
 #ifdef RWKV_STAMP
-            if (wave == 0 && stamp_x && lane == 0) stamp_x[3] = __builtin_amdgcn_s_memrealtime() + (s[0] == 1.2345f);
+            if (wave == 0 && stamp_x && lane == 0) stamp_x[3] = __builtin_amdgcn_s_memrealtime() + (s == 1.2345f);
 #endif
             __syncthreads();
             PROBE(2);
@@ -831,7 +848,6 @@ __device__ __forceinline__ void mv_body_split(const MVEntry & Ent, int wgi, int 
         else ep = epi_load(Ent, min(wgi * RW + (tid < RW ? tid : 0), M - 1));
         __syncthreads();  // activation image ready
         for (;;) {
-            constexpr bool one = WF == W_Q4_1 || WF == W_Q5_1;
             float acc[RR], acc2[RR];
 #pragma unroll
             for (int r = 0; r < RR; r++) acc[r] = acc2[r] = 0.0f;
@@ -853,16 +869,12 @@ __device__ __forceinline__ void mv_body_split(const MVEntry & Ent, int wgi, int 
                     }
                 }
             }
-            float s[RR];
-#pragma unroll
-            for (int r = 0; r < RR; r++) s[r] = one ? wave_sum63(acc[r]) + wave_sum63(acc2[r]) : wave_sum63(acc[r]) + 0.0f;
+            const float s = row_sums<WF, RR>(acc, acc2, lane);  // lane r < RR: row r's sum
             if constexpr (!EMIT) {
-                const float v = epi_apply(epi, lane_row_sum<RR>(s, lane), ep);
+                const float v = epi_apply(epi, s, ep);
                 if (lane < RR && row0 + lane < M) ey[row0 + lane] = v;
             } else {
-#pragma unroll
-                for (int r = 0; r < RR; r++)
-                    if (lane == 63) red[wave * RR + r] = s[r];
+                if (lane < RR) red[wave * RR + lane] = s;
                 __syncthreads();
                 if (tid < RW) {
                     const int row = wgi * RW + tid;
@@ -1027,13 +1039,9 @@ __global__ __launch_bounds__(256) void k_mva(int b1, int b2, int b3, int b4, int
             acc2[r] = valid ? t2 : acc2[r];
         }
     }
-    constexpr bool one = WF == W_Q4_1 || WF == W_Q5_1;
-    float sr[R];
-#pragma unroll
-    for (int r = 0; r < R; r++) sr[r] = one ? wave_sum63(acc[r]) + wave_sum63(acc2[r]) : wave_sum63(acc[r]) + 0.0f;
     // epilogue on lane r for row r, on every lane (the operand loads stay ahead of the dots
     // instead of being sunk into the store branch: a dependent round trip at the kernel's end)
-    const float v = epi_apply(h.epi, lane_row_sum<R>(sr, lane), ep);
+    const float v = epi_apply(h.epi, row_sums<WF, R>(acc, acc2, lane), ep);
     if (lane < R && row0 + lane < M) h.y[row0 + lane] = v;
     STAMP_END(1);
 }

@@ -184,11 +184,7 @@ __device__ __forceinline__ void maa_dec4_body(const MaaDec & a, int bx, int n, c
                 }
             }
         }
-        constexpr bool one = WF == W_Q4_1 || WF == W_Q5_1;
-        float sr[R];
-#pragma unroll
-        for (int r = 0; r < R; r++) sr[r] = one ? wave_sum63(acc[r]) + wave_sum63(acc2[r]) : wave_sum63(acc[r]) + 0.0f;
-        const float t = rk_tanhf(lane_row_sum<R>(sr, lane));  // EPI_TANH, lane r for row r
+        const float t = rk_tanhf(row_sums<WF, R>(acc, acc2, lane));  // EPI_TANH, lane r for row r
         if (lane < R && wave * R + lane < D) s_lora[wave * R + lane] = t;
         __syncthreads();  // (2) lora_n ready
         // k_v6_mix5_dec's arithmetic: m = fma chain over i in order

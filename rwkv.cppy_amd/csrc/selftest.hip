@@ -8,10 +8,44 @@
 #include "../../include/rwkv_mi355x.h"
 #include "engine.hpp"
 #include "kernels.hpp"
+#include "mv_common.hpp"
 
 using namespace rwkvmi;
 
 namespace {
+
+// One wave: lane l holds p[l][0..N-1].  sums[l] = what wave_sums<N> returns in lane l; ref[j] =
+// wave_sum63 of slot j (from lane 63).
+template <int N>
+__global__ __launch_bounds__(64) void k_selftest_wave_sums(const float * p, float * sums, float * ref) {
+    const int lane = threadIdx.x;
+    float v[N];
+#pragma unroll
+    for (int j = 0; j < N; j++) v[j] = p[lane * N + j];
+    sums[lane] = wave_sums<N>(v, lane);
+#pragma unroll
+    for (int j = 0; j < N; j++) {
+        const float t = wave_sum63(v[j]);
+        if (lane == 63) ref[j] = t;
+    }
+}
+
+// The matvecs' row_sums<WF, 3> (a padded zero slot): p[l][0..2] = acc, p[l][3..5] = acc2 (read by
+// the _1 form only); sums[l] = its result in lane l; ref[j] = the per-row expression it replaces.
+template <int WF>
+__global__ __launch_bounds__(64) void k_selftest_row_sums3(const float * p, float * sums, float * ref) {
+    const int lane = threadIdx.x;
+    float a[3], a2[3];
+#pragma unroll
+    for (int j = 0; j < 3; j++) a[j] = p[lane * 6 + j], a2[j] = p[lane * 6 + 3 + j];
+    sums[lane] = row_sums<WF, 3>(a, a2, lane);
+    constexpr bool one = WF == W_Q4_1 || WF == W_Q5_1;
+#pragma unroll
+    for (int j = 0; j < 3; j++) {
+        const float t = one ? wave_sum63(a[j]) + wave_sum63(a2[j]) : wave_sum63(a[j]) + 0.0f;
+        if (lane == 63) ref[j] = t;
+    }
+}
 
 struct DevBufs {
     std::vector<void *> p;
@@ -371,4 +405,33 @@ extern "C" RWKV_API bool rwkv_mi355x_selftest_ln(int C, int rows, const float * 
         return false;
     if (!launch_ln_emit(nullptr, C, dx, dw, db, o, rows) || hipDeviceSynchronize() != hipSuccess) return false;
     return hipMemcpy(out, o.f, n * 4, hipMemcpyDeviceToHost) == hipSuccess;
+}
+
+// wave_sums<n> (device_common.hpp) against wave_sum63 on host operands, one wave.  n = 2, 4, ..., 64:
+// p [64 lanes][n]; sums[l] = the wave_sums result of lane l (slot l & (n - 1)), ref[j] = wave_sum63 of
+// slot j.  n = 3 / -3: the matvecs' padded three-row form row_sums<Q8_0 / Q4_1, 3> on p [64][6] (acc
+// then acc2 per lane); ref[j] = wave_sum63(acc_j) + 0.0f / wave_sum63(acc_j) + wave_sum63(acc2_j).
+extern "C" RWKV_API bool rwkv_mi355x_selftest_wave_sums(int n, const float * p, float * sums, float * ref) {
+    if (!p || !sums || !ref) return false;
+    const int width = (n == 3 || n == -3) ? 6 : n, slots = n < 0 ? -n : n;
+    DevBufs b;
+    float * dp = (float *)b.alloc((size_t)64 * width * 4);
+    float * ds = (float *)b.alloc(64 * 4);
+    float * dr = (float *)b.alloc(64 * 4);
+    if (!dp || !ds || !dr) return false;
+    if (hipMemcpy(dp, p, (size_t)64 * width * 4, hipMemcpyHostToDevice) != hipSuccess) return false;
+    switch (n) {
+        case 2: hipLaunchKernelGGL(k_selftest_wave_sums<2>, dim3(1), dim3(64), 0, nullptr, dp, ds, dr); break;
+        case 4: hipLaunchKernelGGL(k_selftest_wave_sums<4>, dim3(1), dim3(64), 0, nullptr, dp, ds, dr); break;
+        case 8: hipLaunchKernelGGL(k_selftest_wave_sums<8>, dim3(1), dim3(64), 0, nullptr, dp, ds, dr); break;
+        case 16: hipLaunchKernelGGL(k_selftest_wave_sums<16>, dim3(1), dim3(64), 0, nullptr, dp, ds, dr); break;
+        case 32: hipLaunchKernelGGL(k_selftest_wave_sums<32>, dim3(1), dim3(64), 0, nullptr, dp, ds, dr); break;
+        case 64: hipLaunchKernelGGL(k_selftest_wave_sums<64>, dim3(1), dim3(64), 0, nullptr, dp, ds, dr); break;
+        case 3: hipLaunchKernelGGL(k_selftest_row_sums3<W_Q8_0>, dim3(1), dim3(64), 0, nullptr, dp, ds, dr); break;
+        case -3: hipLaunchKernelGGL(k_selftest_row_sums3<W_Q4_1>, dim3(1), dim3(64), 0, nullptr, dp, ds, dr); break;
+        default: return false;
+    }
+    if (hipGetLastError() != hipSuccess || hipDeviceSynchronize() != hipSuccess) return false;
+    return hipMemcpy(sums, ds, 64 * 4, hipMemcpyDeviceToHost) == hipSuccess &&
+           hipMemcpy(ref, dr, (size_t)slots * 4, hipMemcpyDeviceToHost) == hipSuccess;
 }
