@@ -369,6 +369,19 @@ RWKV_API bool rwkv_mi355x_selftest_wkv7(int T, int H, int chunked, const float *
                                        const float * v, const float * a, const float * b, const float * state_in,
                                        float * state_out, float * y);
 
+/* The token layouts of the serial WKV kernels against each other, bit for bit.  kind 4: WKV-4 over
+ * C = H * S channels; 5 / 6: WKV-6 with a per-channel (v5) / per-token (v6) decay; 7: WKV-7 (5 - 7: H
+ * heads of S, a power of two <= 64).  The n_seg segments of lens[s] >= 1 tokens tile a packed chunk;
+ * operands and one input state per segment are drawn from the seed (sample_uniform: k, v, r, a, b
+ * and the states in [-0.5, 0.5), WKV-6 / -7 decays in [0.9, 1), WKV-4: decay in (-1, -0.9], bb in
+ * [0.5, 1.5), pp = 0).  Runs (a) one one-sequence launch per segment on its rows and state, (b) one
+ * segmented launch over the chunk, (c) for kind 4 with every length 1, the contexts form of batched
+ * decode; each form's outputs start as a poison word of its own.  out[0], out[1]: 32-bit words of the
+ * output rows / of the written output state that differ between (a) and (b); out[2], out[3]: the same
+ * between (a) and (c); out[4], out[5]: words compared for each pair (0 when (c) did not run). */
+RWKV_API bool rwkv_mi355x_selftest_wkv_layouts(int kind, int H, int S, const uint32_t * lens, int n_seg, uint64_t seed,
+                                               uint64_t * out);
+
 /* The sampler kernel of rwkv_mi355x_sample on host operands: logits [rows][V] (V <= 262144), one
  * uniform draw u[r] in [0, 1) per row, params' seed / offset unused.  tokens [rows]; kept [rows] (the
  * tokens that passed the top-p filter; 1 for greedy) and cutoff [rows] (the smallest kept

@@ -582,7 +582,7 @@ bool Engine::wkv6(int T, int H, int S, const float * u, const float * w, int wpt
         if (!grow(wkvc_, need, need, GRAPHS_NONE)) return false;
         return launch_wkv6_chunked(stream_, T, H, k_, v_, r_, u, w, wpt, sin, sout, y_, nb_, bb_, wkvc_);
     }
-    return launch_wkv6(stream_, T, H, S, k_, v_, r_, u, w, wpt, sin, sout, y_, (int)bs_, seg_);
+    return launch_wkv6(stream_, T, H, S, k_, v_, r_, u, w, wpt, sin, sout, y_, seg_);
 }
 
 bool Engine::layer_v5(int l, int T, const float * si, float * so) {
@@ -738,7 +738,7 @@ bool Engine::layer_v7(int l, int T, const float * si, float * so) {
         const size_t need = wkv7_chunked_scratch_floats(T, H);
         if (!grow(wkvc_, need, need, GRAPHS_NONE)) return false;
         if (!launch_wkv7_chunked(stream_, T, H, r_, w_, k_, v_, nb_, bb_, si + 2 * C, so + 2 * C, y_, wkvc_)) return false;
-    } else if (!launch_wkv7(stream_, T, H, S, r_, w_, k_, v_, nb_, bb_, si + 2 * C, so + 2 * C, y_, (int)bs_, seg_)) {
+    } else if (!launch_wkv7(stream_, T, H, S, r_, w_, k_, v_, nb_, bb_, si + 2 * C, so + 2 * C, y_, seg_)) {
         return false;
     }
     ActBuf o = A(0, L.att_o);

@@ -1,4 +1,4 @@
-// kernels.hpp -- host launchers for the gfx950 kernels (kernels.hip).
+// kernels.hpp -- host launchers for the gfx950 kernels (kernels.hip, wkv_serial.hip).
 #pragma once
 
 #include "common.hpp"
@@ -51,7 +51,8 @@ struct SegTab {
     const uint64_t * sin_off, * sout_off;
     const uint32_t * seg_of;
 };
-// seg (launch_ln_mix and every wkv launcher): the segmented form over the packed chunk (bs == 0)
+// seg (launch_ln_mix and every wkv launcher): the segmented form over the packed chunk (bs == 0);
+// the wkv kernels take it as a span (wkv_span.hpp)
 bool launch_ln_mix(hipStream_t st, const LnMixArgs & a, const SegTab * seg = nullptr);
 
 // v6: xs[n] = (W2[n] . lora_n + maa[n]) * sx + xa, n = w,k,v,r,g   (rwkv_graph.inc:313-346)
@@ -59,16 +60,16 @@ bool launch_v6_mix5(hipStream_t st, int T, int C, int D, const float * lora, con
                     const float * const * maa, const float * xa, const float * sx, const ActBuf * outs);
 
 // v4 wkv with aa/bb/pp state (rwkv_graph.inc:119-161); emits r*wkv into `out`.
+// bs > 0 (this wkv launcher only -- batched v5 / v6 / v7 run k_att6_dec / k_att7_dec): batched
+// decode -- the T tokens are T contexts, one token each, context t's state at state_in/out + t * bs.
 bool launch_wkv4(hipStream_t st, int T, int C, const float * r, const float * k, const float * v,
                  const float * first, const float * decay, const float * state_in, float * state_out,
                  const ActBuf & out, int bs = 0, const SegTab * seg = nullptr);
 
 // ggml_rwkv_wkv6 semantics (v5/v6): y[T][C]; w_per_token selects v6 (w [T][C]) vs v5 (w [C]).
-// bs > 0 (every wkv launcher): batched decode -- the T tokens are T contexts, one token each,
-// context t's state at state_in/out + t * bs.
 bool launch_wkv6(hipStream_t st, int T, int H, int S, const float * k, const float * v, const float * r,
                  const float * u, const float * w, int w_per_token, const float * state_in,
-                 float * state_out, float * y, int bs = 0, const SegTab * seg = nullptr);
+                 float * state_out, float * y, const SegTab * seg = nullptr);
 
 // Chunk-parallel wkv6 (wkv_chunk.hip, head size 64, T >= 2, no batch): the same recurrence with the
 // sums re-associated (not bit-exact with launch_wkv6).  RA / KB: [T][C] scratch; scratch:
@@ -95,7 +96,7 @@ bool launch_v7_prep(hipStream_t st, int T, int H, int S, float * k, const float 
 // rwkv_operators_wkv_v7.inc:37-107
 bool launch_wkv7(hipStream_t st, int T, int H, int S, const float * r, const float * w, const float * k,
                  const float * v, const float * a, const float * b, const float * state_in,
-                 float * state_out, float * y, int bs = 0, const SegTab * seg = nullptr);
+                 float * state_out, float * y, const SegTab * seg = nullptr);
 
 // GroupNorm over heads + ln_x (+ v7 bonus) (+ gate), emitted as the output projection's input.
 // mode 0: none, 1: *g, 2: + v*bonus then *g

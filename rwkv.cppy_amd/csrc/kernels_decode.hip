@@ -626,7 +626,7 @@ bool launch_att7_dec(hipStream_t st, const Att7Dec & a) {
         fprintf(stderr, "rwkv: head size %d unsupported\n", a.S);
         return false;
     }
-    // keys per lane: 4 at head size 64 (16 groups, k_wkv7_s64's split), else pick_groups' split
+    // keys per lane: 4 at head size 64 (16 groups, k_wkv7_s64's split), else with_key_groups' split
     int G = a.S == 64 ? 16 : 256 / a.S;
     if (G > a.S) G = a.S;
     const int JPG = a.S / G;

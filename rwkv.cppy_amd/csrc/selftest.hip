@@ -190,7 +190,7 @@ extern "C" RWKV_API bool rwkv_mi355x_selftest_wkv6(int T, int H, int chunked, in
         hipMemcpy(dsi, state_in, SN * 4, hipMemcpyHostToDevice) != hipSuccess)
         return false;
     const bool ok = chunked ? launch_wkv6_chunked(nullptr, T, H, dk, dv, dr, du, dw, w_per_token, dsi, dso, dy, ra, kb, sc)
-                            : launch_wkv6(nullptr, T, H, 64, dk, dv, dr, du, dw, w_per_token, dsi, dso, dy, 0);
+                            : launch_wkv6(nullptr, T, H, 64, dk, dv, dr, du, dw, w_per_token, dsi, dso, dy);
     if (!ok || hipDeviceSynchronize() != hipSuccess) return false;
     return hipMemcpy(y, dy, TC * 4, hipMemcpyDeviceToHost) == hipSuccess &&
            hipMemcpy(state_out, dso, SN * 4, hipMemcpyDeviceToHost) == hipSuccess;
@@ -216,10 +216,116 @@ extern "C" RWKV_API bool rwkv_mi355x_selftest_wkv7(int T, int H, int chunked, co
         if (hipMemcpy(p.first, p.second, TC * 4, hipMemcpyHostToDevice) != hipSuccess) return false;
     if (hipMemcpy(dsi, state_in, SN * 4, hipMemcpyHostToDevice) != hipSuccess) return false;
     const bool ok = chunked ? launch_wkv7_chunked(nullptr, T, H, dr, dw, dk, dv, da, db, dsi, dso, dy, sc)
-                            : launch_wkv7(nullptr, T, H, 64, dr, dw, dk, dv, da, db, dsi, dso, dy, 0);
+                            : launch_wkv7(nullptr, T, H, 64, dr, dw, dk, dv, da, db, dsi, dso, dy);
     if (!ok || hipDeviceSynchronize() != hipSuccess) return false;
     return hipMemcpy(y, dy, TC * 4, hipMemcpyDeviceToHost) == hipSuccess &&
            hipMemcpy(state_out, dso, SN * 4, hipMemcpyDeviceToHost) == hipSuccess;
+}
+
+// The token layouts of the serial WKV kernels (wkv_span.hpp) against each other, on operands drawn
+// here from the seed (include/rwkv_mi355x.h has the contract).  Every form's outputs start as a
+// poison word of its own, so a row or a state word that nobody wrote counts as a difference.
+extern "C" RWKV_API bool rwkv_mi355x_selftest_wkv_layouts(int kind, int H, int S, const uint32_t * lens, int n_seg,
+                                                         uint64_t seed, uint64_t * out) {
+    if (kind < 4 || kind > 7 || H < 1 || S < 1 || !lens || n_seg < 1 || !out) return false;
+    const size_t C = (size_t)H * S;
+    // state floats per segment, and the slice of it the kernel writes (WKV-4: aa, bb, pp of the
+    // layer's five rows)
+    const size_t SL = kind == 4 ? 5 * C : C * S, S0 = kind == 4 ? 2 * C : 0, SW = SL - S0;
+    std::vector<uint32_t> begin(n_seg), seg_of;
+    std::vector<uint64_t> soff(n_seg);
+    bool ones = true;
+    for (int s = 0; s < n_seg; s++) {
+        if (lens[s] < 1 || lens[s] > 4096) return false;
+        begin[s] = (uint32_t)seg_of.size();
+        soff[s] = (uint64_t)s * SL;
+        seg_of.insert(seg_of.end(), lens[s], (uint32_t)s);
+        ones = ones && lens[s] == 1;
+    }
+    const size_t T = seg_of.size(), TC = T * C, NS = (size_t)n_seg * SL;
+    DevBufs bf;
+    bool ok = true;
+    uint64_t ctr = 0;
+    // n floats lo + span * u, u the seed's next uniform draws, on the device
+    auto draw = [&](size_t n, float lo, float span) -> float * {
+        std::vector<float> h(n);
+        for (float & x : h) x = lo + span * sample_uniform(seed, ctr++);
+        float * d = (float *)bf.alloc(n * 4);
+        ok = ok && d && hipMemcpy(d, h.data(), n * 4, hipMemcpyHostToDevice) == hipSuccess;
+        return d;
+    };
+    auto up = [&](const void * h, size_t bytes) -> void * {
+        void * d = bf.alloc(bytes);
+        ok = ok && d && hipMemcpy(d, h, bytes, hipMemcpyHostToDevice) == hipSuccess;
+        return d;
+    };
+    // operands: k, v, r (and v7's a, b) in [-0.5, 0.5); WKV-6 / WKV-7 decays in [0.9, 1); WKV-4's
+    // decay is the log-space rate the models store negative, in (-1, -0.9]
+    const float * k = draw(TC, -0.5f, 1.0f), * v = draw(TC, -0.5f, 1.0f), * r = draw(TC, -0.5f, 1.0f);
+    const float * a = kind == 7 ? draw(TC, -0.5f, 1.0f) : nullptr, * b = kind == 7 ? draw(TC, -0.5f, 1.0f) : nullptr;
+    const float * w = kind == 4 ? draw(C, -0.9f, -0.1f) : draw(kind == 5 ? C : TC, 0.9f, 0.1f);
+    const float * u = kind == 7 ? nullptr : draw(C, -0.5f, 1.0f);  // WKV-4: time_first
+    // input states in [-0.5, 0.5); WKV-4: aa so, bb in [0.5, 1.5), pp = 0
+    std::vector<float> hs(NS);
+    for (float & x : hs) x = sample_uniform(seed, ctr++) - 0.5f;
+    if (kind == 4)
+        for (int s = 0; s < n_seg; s++)
+            for (size_t c = 0; c < C; c++) hs[s * SL + 3 * C + c] += 1.0f, hs[s * SL + 4 * C + c] = 0.0f;
+    const float * sin = (const float *)up(hs.data(), NS * 4);
+    SegTab sg;
+    sg.n = n_seg;
+    sg.begin = (const uint32_t *)up(begin.data(), (size_t)n_seg * 4);
+    sg.len = (const uint32_t *)up(lens, (size_t)n_seg * 4);
+    sg.sin_off = sg.sout_off = (const uint64_t *)up(soff.data(), (size_t)n_seg * 8);
+    sg.seg_of = (const uint32_t *)up(seg_of.data(), T * 4);
+    // outputs of the forms: 0 one launch per segment, 1 the segmented launch, 2 the contexts
+    float * y[3], * so[3];
+    const int poison[3] = {0xA5, 0x5A, 0xC3};
+    for (int f = 0; f < 3; f++) {
+        y[f] = (float *)bf.alloc(TC * 4);
+        so[f] = (float *)bf.alloc(NS * 4);
+        ok = ok && y[f] && so[f] && hipMemset(y[f], poison[f], TC * 4) == hipSuccess &&
+             hipMemset(so[f], poison[f], NS * 4) == hipSuccess;
+    }
+    if (!ok) return false;
+    // one launch: n tokens from row `row`, states at float offset `st`, into form f's outputs
+    auto run = [&](int f, int n, size_t row, size_t st, int bs, const SegTab * seg) {
+        const size_t o = row * C;
+        if (kind == 4) {
+            ActBuf ob;
+            memset(&ob, 0, sizeof(ob));
+            ob.fmt = A_F32;
+            ob.K = (int)C;
+            ob.f = y[f] + o;
+            return launch_wkv4(nullptr, n, (int)C, r + o, k + o, v + o, u, w, sin + st, so[f] + st, ob, bs, seg);
+        }
+        if (kind == 7) return launch_wkv7(nullptr, n, H, S, r + o, w + o, k + o, v + o, a + o, b + o, sin + st, so[f] + st, y[f] + o, seg);
+        return launch_wkv6(nullptr, n, H, S, k + o, v + o, r + o, u, kind == 6 ? w + o : w, kind == 6, sin + st, so[f] + st, y[f] + o, seg);
+    };
+    for (int s = 0; s < n_seg; s++)
+        if (!run(0, (int)lens[s], begin[s], (size_t)s * SL, 0, nullptr)) return false;
+    if (!run(1, (int)T, 0, 0, 0, &sg)) return false;
+    const bool ctx = kind == 4 && ones;
+    if (ctx && !run(2, (int)T, 0, 0, (int)SL, nullptr)) return false;
+    if (hipDeviceSynchronize() != hipSuccess) return false;
+    std::vector<uint32_t> hy[3], hso[3];
+    for (int f = 0; f < 3; f++) {
+        hy[f].resize(TC), hso[f].resize(NS);
+        if (hipMemcpy(hy[f].data(), y[f], TC * 4, hipMemcpyDeviceToHost) != hipSuccess ||
+            hipMemcpy(hso[f].data(), so[f], NS * 4, hipMemcpyDeviceToHost) != hipSuccess)
+            return false;
+    }
+    for (int f = 1; f < 3; f++) {
+        uint64_t dy = 0, ds = 0;
+        for (size_t i = 0; i < TC; i++) dy += hy[f][i] != hy[0][i];
+        for (int s = 0; s < n_seg; s++)
+            for (size_t i = S0; i < SL; i++) ds += hso[f][s * SL + i] != hso[0][s * SL + i];
+        const bool ran = f == 1 || ctx;
+        out[2 * (f - 1)] = ran ? dy : 0;
+        out[2 * (f - 1) + 1] = ran ? ds : 0;
+        out[3 + f] = ran ? TC + (uint64_t)n_seg * SW : 0;
+    }
+    return true;
 }
 
 // The sampler kernel (sample.hip) on host logits with the uniform draws given: what

@@ -252,6 +252,9 @@ class RWKVSharedLibrary:
         L.rwkv_mi355x_score_sequence.restype = ctypes.c_bool
         L.rwkv_mi355x_selftest_xent.argtypes = [P_FLOAT, ctypes.c_int, ctypes.c_int, P_U32, P_DOUBLE, P_U32]
         L.rwkv_mi355x_selftest_xent.restype = ctypes.c_bool
+        L.rwkv_mi355x_selftest_wkv_layouts.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int, P_U32, ctypes.c_int,
+                                                       ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint64)]
+        L.rwkv_mi355x_selftest_wkv_layouts.restype = ctypes.c_bool
 
         self.nullptr = ctypes.cast(0, ctypes.c_void_p)
 
@@ -525,6 +528,17 @@ class RWKVSharedLibrary:
                 losses.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), argmax.ctypes.data_as(P_U32)):
             raise ValueError('rwkv_mi355x_selftest_xent failed')
         return losses, argmax
+
+    def rwkv_mi355x_selftest_wkv_layouts(self, kind: int, H: int, S: int, lens, seed: int):
+        """The serial WKV kernels' token layouts against each other on seeded operands (kind 4, 5, 6, 7;
+        segment lengths lens).  Returns a dict of word counts: y_seg / state_seg (one launch per
+        segment vs the segmented launch), y_ctx / state_ctx (vs the contexts form; kind 4, all
+        lengths 1) and compared_seg / compared_ctx (0: that form did not run)."""
+        arr = (ctypes.c_uint32 * len(lens))(*lens)
+        out = (ctypes.c_uint64 * 6)()
+        if not self.library.rwkv_mi355x_selftest_wkv_layouts(kind, H, S, arr, len(lens), seed, out):
+            raise ValueError('rwkv_mi355x_selftest_wkv_layouts failed')
+        return dict(zip(('y_seg', 'state_seg', 'y_ctx', 'state_ctx', 'compared_seg', 'compared_ctx'), map(int, out)))
 
     def rwkv_get_system_info_string(self) -> str:
         return self.library.rwkv_get_system_info_string().decode('utf-8')

@@ -1,15 +1,14 @@
 // WKV6 sequence-kernel probe (tools/, not part of the library): times launch_wkv6 (head size 64,
-// T = 1024, H = 32, per-token decay) for each workgroup width g_wkv6_nwv and checks that the
-// variants agree bit for bit.
+// T = 1024, H = 32, per-token decay).
 // Build: hipcc -std=c++17 -O3 --offload-arch=gfx950 -ffp-contract=off -DRWKV_BUILD
 //        -Irwkv.cppy_amd/csrc -Iinclude -o tools/bin/wkv_probe tools/wkv_probe.hip
-#include "kernels.hip"
+#include "wkv_serial.hip"
 
 #include <stdlib.h>
 #include <string.h>
 #include <vector>
 
-namespace rwkvmi { extern int g_wkv6_nwv; }
+namespace rwkvmi { thread_local KLaunchTimer * g_klt = nullptr; }  // the library's is in engine.hip
 using namespace rwkvmi;
 
 #define CK(x) do { hipError_t e = (x); if (e != hipSuccess) { printf("err %s line %d\n", hipGetErrorString(e), __LINE__); exit(1); } } while (0)
@@ -35,9 +34,7 @@ int main() {
     CK(hipStreamCreate(&st));
     hipEvent_t a, b;
     CK(hipEventCreate(&a)); CK(hipEventCreate(&b));
-    std::vector<float> ref, out((size_t)T * C), sref, sout(hs.size());
-    for (int nwv : {4, 2, 1}) {
-        g_wkv6_nwv = nwv;
+    {
         for (int i = 0; i < 2; i++) launch_wkv6(st, T, H, S, k, v, r, u, w, 1, s0, s1, y);
         CK(hipEventRecord(a, st));
         const int reps = 10;
@@ -46,12 +43,7 @@ int main() {
         CK(hipEventSynchronize(b));
         float ms;
         CK(hipEventElapsedTime(&ms, a, b));
-        CK(hipMemcpy(out.data(), y, tb, hipMemcpyDeviceToHost));
-        CK(hipMemcpy(sout.data(), s1, hs.size() * 4, hipMemcpyDeviceToHost));
-        bool same = true;
-        if (ref.empty()) { ref = out; sref = sout; }
-        else same = !memcmp(ref.data(), out.data(), tb) && !memcmp(sref.data(), sout.data(), hs.size() * 4);
-        printf("wkv6 T=%d nwv=%d: %8.1f us  %s\n", T, nwv, ms * 1e3 / reps, same ? "bit-identical" : "DIFFERENT");
+        printf("wkv6 T=%d: %8.1f us\n", T, ms * 1e3 / reps);
     }
     return 0;
 }
