@@ -151,6 +151,48 @@ RWKV_API bool rwkv_mi355x_generate_batch(struct rwkv_context * ctx, size_t B,
                                          uint32_t * tokens_out /* [B][n] */, uint32_t * lengths_out /* [B] */,
                                          uint32_t * steps_out);
 
+/* Continuous batching: a queue of Q sequences over L = min(lanes, Q) decode rows ("lanes").  The
+ * sequences are slots [0, Q), filled as for rwkv_mi355x_generate_batch (batch_store or prefill_batch);
+ * every per-row array of params is [Q], indexed by sequence; sequence s wants at most max_tokens[s]
+ * tokens (host [Q], each in [1, n]; n <= 65536 is the row stride of tokens_out).  A lane whose
+ * sequence has ended is given to the next waiting sequence between two decode steps, so the L rows
+ * of a step stay full while sequences wait.  Step i = 0, 1, ...:
+ *   1. Turnover, lanes in increasing order.  A lane whose sequence s is ended -- it drew a stop token
+ *      at step i - 1, or length[s] == max_tokens[s] -- is freed.  Ended by its cap, s takes the lane's
+ *      live state and logits as its result (the state after its last token, the logits following it:
+ *      what generate_batch leaves for a row that never stopped); ended by a stop it has the state
+ *      before the stop token and the logits that produced it, as in generate_batch.  The free lanes,
+ *      in increasing order, take the waiting sequences in increasing order: state and logits from the
+ *      slot, counts zero, lane_out[s] = the lane, start_out[s] = i.  At i = 0 sequences 0 .. L-1
+ *      enter lanes 0 .. L-1.
+ *   2. If no lane holds a sequence the call is over.
+ *   3. Every busy lane samples with the parameters and counts of its sequence s and the draw
+ *      uniform(seed[s], offset[s] + length[s]); the token goes to tokens_out[s][length[s]++]; a stop
+ *      token ends s and is not evaluated.
+ *   4. One batched decode step over the L lanes (idle lanes decode token 0).
+ * Everything about sequence s -- tokens, length, slot s's state and logits on return -- equals, bit
+ * for bit, rwkv_mi355x_generate_batch with B = 1, n = max_tokens[s], s's parameters and keep_counts
+ * 0 on a slot filled the same way.  tokens_out[s] is 0xFFFFFFFF past lengths_out[s]; slot s is valid
+ * and rwkv_mi355x_batch_load(s) continues it.  lane_out / start_out (may be NULL) are the list
+ * schedule of the lengths drawn (rwkv_cpp.sampling.queue_schedule); steps_out (may be NULL) is the
+ * number of decode steps up to the one after which no lane was busy.
+ * keep_counts must be 0: a capped sequence that should go on with its counts is a job for
+ * rwkv_mi355x_generate_batch on its slot.  check_every = k > 0: every k steps the host reads the
+ * number of sequences not yet ended (4 bytes) and leaves when it is 0; with 0 it runs
+ * ceil(sum(max_tokens) / L) + max(max_tokens) steps, which list scheduling cannot exceed, the steps
+ * after the end decoding token 0 in idle lanes.  The results, steps_out included, do not depend on it.
+ * Errors before anything is enqueued (RWKV_ERROR_ARGS; slots, state and logits untouched): Q == 0 or
+ * above the reserved slots, lanes == 0 or > 256, a slot in [0, Q) never stored, n == 0 or > 65536, a
+ * NULL required pointer, a max_tokens[s] of 0 or above n, keep_counts != 0, and the parameter errors
+ * of generate_batch.  A pipeline or stage context: RWKV_ERROR_CTX | RWKV_ERROR_UNSUPPORTED.  A failure
+ * after that (RWKV_ERROR_CTX) leaves slots [0, Q) invalid. */
+RWKV_API bool rwkv_mi355x_generate_queue(struct rwkv_context * ctx, size_t Q, size_t lanes,
+                                         const struct rwkv_mi355x_batch_sampling * params,
+                                         const uint32_t * max_tokens /* host [Q] */, size_t n,
+                                         uint32_t * tokens_out /* [Q][n] */, uint32_t * lengths_out /* [Q] */,
+                                         uint32_t * lane_out /* [Q] */, uint32_t * start_out /* [Q] */,
+                                         uint32_t * steps_out);
+
 /* Batched prefill: n_rows prompts, concatenated in `tokens` (lengths[i] >= 1 tokens each), are
  * evaluated together in packed sequence passes and land in slots[i] (distinct, each < the reserved
  * slots).  cont == NULL or cont[i] == 0: row i starts from the fresh state (the slot need not have
@@ -402,6 +444,15 @@ RWKV_API bool rwkv_mi355x_selftest_sample_rows(const float * logits, int rows, i
                                                uint32_t step, uint32_t * counts, uint32_t * done, uint32_t * tokens,
                                                uint32_t * decode_tokens, uint32_t * kept, float * cutoff,
                                                uint32_t * lengths, uint32_t * active);
+
+/* The turnover kernel of rwkv_mi355x_generate_queue (k_gen_turnover) on host operands, as before step
+ * `step`: lane_seq [lanes] (a sequence id < Q or 0xFFFFFFFF: idle), done / lane / start [Q], *next
+ * (<= Q) and *active are uploaded, updated and downloaded; length and max_tokens [Q] are read;
+ * retire_to and admit_from [lanes] are uploaded, written and downloaded.  lanes in [1, 256]. */
+RWKV_API bool rwkv_mi355x_selftest_gen_turnover(int lanes, int Q, uint32_t step, uint32_t * lane_seq, uint32_t * done,
+                                                const uint32_t * length, const uint32_t * max_tokens, uint32_t * lane,
+                                                uint32_t * start, uint32_t * next, uint32_t * active,
+                                                uint32_t * retire_to, uint32_t * admit_from);
 
 /* The host planner of rwkv_mi355x_prefill_batch (no GPU call): packs n_rows rows of lengths[i] >= 1
  * tokens, in order, into chunks of at most cap tokens.  Segment j is seg_len[j] tokens of row

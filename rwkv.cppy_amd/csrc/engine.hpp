@@ -93,7 +93,10 @@ struct GenSlots {
     DevBuf<uint32_t> gcounts_;
     DevBuf<float> gparams_;      // temperature, top_p, presence, frequency: [4][kBatchMax]
     DevBuf<uint64_t> gstreams_;  // seed, offset: [2][kBatchMax]
-    DevBuf<uint32_t> gwords_;    // done, length, fin_step: [3][kBatchMax], active
+    // done, length, fin_step: [3][kBatchMax], active; then the queue's words (generate_queue):
+    // max_tokens, lane_seq, lane, start, retire_to, admit_from: [6][kBatchMax], next
+    DevBuf<uint32_t> gwords_;
+    static constexpr size_t kWordRows = 9;  // arrays of batch_max words; two single words besides
     bool alloc(size_t n_slots, size_t state_len, size_t n_vocab, size_t batch_max);
 };
 
@@ -219,6 +222,14 @@ class Engine : public KLaunchTimer, private Workspace, private GenSlots {
     bool batch_store(size_t slot);
     bool batch_load(size_t slot);
     bool generate_batch(size_t B, const BatchSamplingParams & p, size_t n, uint32_t * tokens_out, uint32_t * lengths_out,
+                        uint32_t * steps_out);
+    // A queue of Q sequences (slots [0, Q)) over L = min(lanes, Q) decode rows
+    // (rwkv_mi355x_generate_queue): per step k_gen_turnover frees the lanes of ended
+    // sequences and admits the waiting ones, k_gen_move copies a capped sequence's result out of its
+    // lane and an admitted slot in, then the sampler, the snapshot and one batched step over the L
+    // lanes as in generate_batch.  Every per-row array of p is [Q]; max_tokens[s] in [1, n].
+    bool generate_queue(size_t Q, size_t lanes, const BatchSamplingParams & p, const uint32_t * max_tokens, size_t n,
+                        uint32_t * tokens_out, uint32_t * lengths_out, uint32_t * lane_out, uint32_t * start_out,
                         uint32_t * steps_out);
     // Batched prefill (rwkv_mi355x_prefill_batch; engine_prefill.hip): n_rows prompts, concatenated in
     // tokens, are packed into chunks of at most prefill_chunk_ tokens (prefill_plan.hpp) and each chunk
@@ -444,7 +455,14 @@ class Engine : public KLaunchTimer, private Workspace, private GenSlots {
     DevBuf<uint32_t> gtokens_;  // the drawn tokens [B][n] of a call
     std::vector<float> gparams_h_;   // the host copies the uploads read
     std::vector<uint64_t> gstreams_h_;
+    std::vector<uint32_t> gqueue_h_;  // max_tokens up, start down (generate_queue)
     void free_slots();
+    // the shared pieces of generate_batch and generate_queue: the per-row arrays of `rows` rows to the
+    // device and the token buffer [rows][n] set to 0xFFFFFFFF; the sampler's arguments for them; the
+    // way out after a failure (the stream drained, slots [0, rows) invalid)
+    bool gen_upload(size_t rows, const BatchSamplingParams & p, size_t n);
+    SampleArgs gen_sample_args(size_t rows, const BatchSamplingParams & p, size_t n);
+    bool gen_fail(size_t rows);
     // rwkv_eval with host state buffers: the decode as io_chunk_-layer graphs with the state
     // copies of other chunks overlapped (eval_host_chunked)
     bool io_pipeline_ = true;

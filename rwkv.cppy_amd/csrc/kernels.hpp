@@ -246,6 +246,15 @@ struct SampleArgs {
     uint32_t * active;           // one word: the live rows
     uint32_t step;
     uint32_t tok_stride;         // 0: tok[r]
+    // A queue of sequences over the rows (rwkv_mi355x_generate_queue).  NULL: row r is sequence r,
+    // everything above.  Else row (lane) r holds sequence s = lane_seq[r]: logits and tok2 stay
+    // indexed by r; the per-row parameters, counts, done, length, fin_step and the token row are those
+    // of s; the token goes to tok[s * tok_stride + length[s]], the draw is sample_uniform(seed_r[s],
+    // counter_r[s] + length[s]) and length[s] grows by one.  A lane with lane_seq[r] == GEN_NONE is idle:
+    // a finished row.  max_tokens (with lane_seq, may be NULL): a sequence whose length reaches
+    // max_tokens[s] without a stop token takes one off *active as a stopped one does.
+    const uint32_t * lane_seq;   // [rows]
+    const uint32_t * max_tokens; // [sequences]
 };
 constexpr int SAMPLE_MAX_STOP = 16;
 // One workgroup per row: bias, greedy or top-p / temperature sampling (rwkv_mi355x.h).
@@ -257,7 +266,11 @@ struct GenRows {
     size_t state_len, V;
     const uint32_t * done;       // [rows]
     const uint32_t * fin_step;   // [rows]
+    // NULL, or the queue's table (SampleArgs::lane_seq): done, fin_step and the snapshot rows are
+    // those of sequence lane_seq[r], the live rows stay those of lane r; an idle lane has no snapshot
+    const uint32_t * lane_seq = nullptr;
 };
+constexpr uint32_t GEN_NONE = 0xffffffffu;  // no sequence (lane_seq, retire_to, admit_from)
 // Rows with done[r] != 0 and fin_step[r] == step: state [state_len] and logits [V] of the row are
 // copied from the live buffers into the row's snapshot area.
 bool launch_gen_snapshot(hipStream_t st, const GenRows & g, uint32_t step, const float * state, const float * logits,
@@ -270,6 +283,32 @@ bool launch_gen_restore(hipStream_t st, const GenRows & g, const float * snap_st
 // *active = the rows with done == 0.
 bool launch_gen_begin(hipStream_t st, int rows, int keep, uint32_t * done, uint32_t * length, uint32_t * fin_step,
                       uint32_t * active);
+
+// The queue of rwkv_mi355x_generate_queue: Q sequences over `lanes` <= 256 decode rows.
+struct GenQueue {
+    int lanes, Q;
+    uint32_t * lane_seq;          // [lanes]: the sequence in the lane, or GEN_NONE
+    uint32_t * done;              // [Q]: set for a sequence retired by its cap, as the sampler sets it at a stop
+    const uint32_t * length;      // [Q]
+    const uint32_t * max_tokens;  // [Q]
+    uint32_t * lane;              // [Q]: the lane sequence s was admitted to
+    uint32_t * start;             // [Q]: the step of its admission
+    uint32_t * retire_to;         // [lanes]: the sequence whose cap ended it in this lane, or GEN_NONE
+    uint32_t * admit_from;        // [lanes]: the sequence entering the lane, or GEN_NONE
+    uint32_t * next;              // one word: the first waiting sequence
+    uint32_t * active;            // one word: the sequences not yet ended
+};
+// The turnover before step `step`, one workgroup.  In increasing lane order: a lane whose sequence s is
+// ended (done[s] != 0, or length[s] >= max_tokens[s]) is freed, and retire_to says so when the cap
+// ended it (done[s] becomes 1: its snapshot is the move's to take); the free lanes take the waiting
+// sequences *next, *next + 1, ... < Q (admit_from, lane_seq, lane[s] = the lane, start[s] = step).
+// *active = the waiting sequences + the busy lanes.  Integers only: a ballot and a prefix count.
+bool launch_gen_turnover(hipStream_t st, const GenQueue & q, uint32_t step);
+// After a turnover, grid (parts, lanes): lane r's live state / logits row goes to the snapshot of
+// retire_to[r]; then slot admit_from[r] (row of slot_state / logits) comes into lane r of state /
+// logits (no copy where the two rows are the same memory).
+bool launch_gen_move(hipStream_t st, const GenQueue & q, size_t state_len, size_t V, float * state, float * logits,
+                     const float * slot_state, float * snap_state, float * snap_logits);
 
 // One workgroup per row of logits [rows][V] (xent.hip): loss[r] = -log softmax(row r)[targets[r]]
 // with the exponentials and their sum in fp64, argmax[r] = the lowest index of the row's maximum.

@@ -687,22 +687,14 @@ RWKV_API bool rwkv_mi355x_batch_load(struct rwkv_context * ctx, size_t slot) {
     return true;
 }
 
-RWKV_API bool rwkv_mi355x_generate_batch(struct rwkv_context * ctx, size_t B, const struct rwkv_mi355x_batch_sampling * p,
-                                         size_t n, uint32_t * tokens_out, uint32_t * lengths_out, uint32_t * steps_out) {
-    if (!ctx || !ctx->engine) return false;
-    ctx->last_error = RWKV_ERROR_NONE;
-    if (!batch_ctx_ok(ctx)) return false;
+// the per-row parameters of `rows` rows (generate_batch: the rows; generate_queue: the sequences)
+static bool batch_sampling_ok(struct rwkv_context * ctx, size_t rows, const struct rwkv_mi355x_batch_sampling * p,
+                              BatchSamplingParams & bp) {
     const uint32_t V = ctx->model->dm.n_vocab;
-    CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, B > 0 && B <= ctx->engine->batch_slots(), "Batch of %zu rows with %zu slots reserved",
-              B, ctx->engine->batch_slots());
-    for (size_t r = 0; r < B; r++)
-        CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, ctx->engine->batch_slot_valid(r), "Slot %zu holds nothing", r);
-    CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, n > 0 && n <= 65536, "Token count %zu is outside [1, 65536]", n);
     CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, p != nullptr, "NULL sampling parameters");
-    CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, tokens_out != nullptr && lengths_out != nullptr, "NULL tokens_out or lengths_out");
     CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, p->temperature && p->top_p && p->seed && p->offset,
               "NULL temperature, top_p, seed or offset array");
-    for (size_t r = 0; r < B; r++) {
+    for (size_t r = 0; r < rows; r++) {
         CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, p->temperature[r] >= 0.0f, "Row %zu: temperature %f is negative or NaN", r,
                   p->temperature[r]);
         CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, p->top_p[r] >= 0.0f && p->top_p[r] <= 1.0f, "Row %zu: top_p %f is outside [0, 1]",
@@ -719,7 +711,6 @@ RWKV_API bool rwkv_mi355x_generate_batch(struct rwkv_context * ctx, size_t B, co
     CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, p->n_stop == 0 || p->stop_tokens != nullptr, "NULL stop token array");
     for (uint32_t i = 0; i < p->n_stop; i++)
         CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, p->stop_tokens[i] < V, "Stop token %u out of range", p->stop_tokens[i]);
-    BatchSamplingParams bp;
     bp.temperature = p->temperature;
     bp.top_p = p->top_p;
     bp.presence = p->presence;
@@ -733,9 +724,56 @@ RWKV_API bool rwkv_mi355x_generate_batch(struct rwkv_context * ctx, size_t B, co
     bp.stop_tokens = p->stop_tokens;
     bp.keep_counts = p->keep_counts != 0;
     bp.check_every = p->check_every;
+    return true;
+}
+
+RWKV_API bool rwkv_mi355x_generate_batch(struct rwkv_context * ctx, size_t B, const struct rwkv_mi355x_batch_sampling * p,
+                                         size_t n, uint32_t * tokens_out, uint32_t * lengths_out, uint32_t * steps_out) {
+    if (!ctx || !ctx->engine) return false;
+    ctx->last_error = RWKV_ERROR_NONE;
+    if (!batch_ctx_ok(ctx)) return false;
+    CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, B > 0 && B <= ctx->engine->batch_slots(), "Batch of %zu rows with %zu slots reserved",
+              B, ctx->engine->batch_slots());
+    for (size_t r = 0; r < B; r++)
+        CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, ctx->engine->batch_slot_valid(r), "Slot %zu holds nothing", r);
+    CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, n > 0 && n <= 65536, "Token count %zu is outside [1, 65536]", n);
+    CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, p != nullptr, "NULL sampling parameters");
+    CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, tokens_out != nullptr && lengths_out != nullptr, "NULL tokens_out or lengths_out");
+    BatchSamplingParams bp;
+    if (!batch_sampling_ok(ctx, B, p, bp)) return false;
     use_device(ctx);
     CTX_CHECK(ctx, RWKV_ERROR_CTX, false, ctx->engine->generate_batch(B, bp, n, tokens_out, lengths_out, steps_out),
               "GPU batched generation failed");
+    return true;
+}
+
+RWKV_API bool rwkv_mi355x_generate_queue(struct rwkv_context * ctx, size_t Q, size_t lanes,
+                                         const struct rwkv_mi355x_batch_sampling * p, const uint32_t * max_tokens, size_t n,
+                                         uint32_t * tokens_out, uint32_t * lengths_out, uint32_t * lane_out,
+                                         uint32_t * start_out, uint32_t * steps_out) {
+    if (!ctx || !ctx->engine) return false;
+    ctx->last_error = RWKV_ERROR_NONE;
+    if (!batch_ctx_ok(ctx)) return false;
+    CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, Q > 0 && Q <= ctx->engine->batch_slots(), "Queue of %zu sequences with %zu slots reserved",
+              Q, ctx->engine->batch_slots());
+    CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, lanes > 0 && lanes <= (size_t)Engine::kBatchMax, "%zu lanes (1 to %d)", lanes,
+              Engine::kBatchMax);
+    for (size_t s = 0; s < Q; s++)
+        CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, ctx->engine->batch_slot_valid(s), "Slot %zu holds nothing", s);
+    CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, n > 0 && n <= 65536, "Token count %zu is outside [1, 65536]", n);
+    CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, max_tokens != nullptr && tokens_out != nullptr && lengths_out != nullptr,
+              "NULL max_tokens, tokens_out or lengths_out");
+    for (size_t s = 0; s < Q; s++)
+        CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, max_tokens[s] > 0 && max_tokens[s] <= n, "Sequence %zu: max_tokens %" PRIu32 " is outside [1, %zu]",
+                  s, max_tokens[s], n);
+    BatchSamplingParams bp;
+    if (!batch_sampling_ok(ctx, Q, p, bp)) return false;
+    CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, p->keep_counts == 0,
+              "keep_counts is not supported by the queue (continue a capped sequence with rwkv_mi355x_generate_batch)");
+    use_device(ctx);
+    CTX_CHECK(ctx, RWKV_ERROR_CTX, false,
+              ctx->engine->generate_queue(Q, lanes, bp, max_tokens, n, tokens_out, lengths_out, lane_out, start_out, steps_out),
+              "GPU queued generation failed");
     return true;
 }
 

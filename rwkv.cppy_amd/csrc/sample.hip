@@ -23,7 +23,8 @@
 // (rwkv_mi355x_generate_batch): per-row temperature, top_p and draw stream, presence / frequency
 // penalties over a count table, stop tokens and finished rows (SampleArgs in kernels.hpp).
 // k_gen_snapshot / k_gen_restore / k_gen_begin keep the finished rows' states (engine_batch.hip,
-// generate_batch).
+// generate_batch).  k_gen_turnover / k_gen_move give the rows of ended sequences to waiting ones
+// (generate_queue).
 #include "device_common.hpp"
 #include "kernels.hpp"
 
@@ -81,11 +82,19 @@ __device__ __forceinline__ void sample_row(const SampleArgs & a, SampleShared & 
     bool pen = false;
     float presence = 0.0f, frequency = 0.0f;
     const uint32_t * cnt_row = nullptr;
+    // the sequence of this row and the index of its draw (a queue: SampleArgs::lane_seq); uniform
+    uint32_t seq = blockIdx.x, at = a.step;
     if constexpr (ROWS) {
-        const int r = blockIdx.x;
-        if (a.done && a.done[r] != 0) {
-            // a finished row: the decode step still embeds tok2[r], so it gets an id < V
-            if (tid == 0 && a.tok2) a.tok2[r] = 0;
+        bool idle = false;
+        if (a.lane_seq) {
+            seq = a.lane_seq[blockIdx.x];
+            idle = seq == GEN_NONE;
+            if (!idle) at = a.length[seq];
+        }
+        const uint32_t r = seq;
+        if (idle || (a.done && a.done[r] != 0)) {
+            // a finished row: the decode step still embeds tok2[row], so it gets an id < V
+            if (tid == 0 && a.tok2) a.tok2[blockIdx.x] = 0;
             return;
         }
         if (a.temperature_r) temperature = a.temperature_r[r];
@@ -103,10 +112,10 @@ __device__ __forceinline__ void sample_row(const SampleArgs & a, SampleShared & 
             a.tok[blockIdx.x] = t;
             if (a.tok2) a.tok2[blockIdx.x] = t;
         } else {
-            const int r = blockIdx.x;
-            a.tok[a.tok_stride ? (size_t)r * a.tok_stride + a.step : (size_t)r] = t;
-            if (a.tok2) a.tok2[r] = t;
-            if (a.length) a.length[r] = a.step + 1u;
+            const uint32_t r = seq;
+            a.tok[a.tok_stride ? (size_t)r * a.tok_stride + at : (size_t)r] = t;
+            if (a.tok2) a.tok2[blockIdx.x] = t;
+            if (a.length) a.length[r] = at + 1u;
             if (a.counts) {
                 uint32_t * c = a.counts + (size_t)r * (size_t)V + t;
                 *c = *c + 1u;  // no other workgroup touches row r
@@ -118,6 +127,8 @@ __device__ __forceinline__ void sample_row(const SampleArgs & a, SampleShared & 
                 a.done[r] = 1u;
                 if (a.fin_step) a.fin_step[r] = a.step;
                 if (a.active) atomicSub(a.active, 1u);
+            } else if (a.lane_seq && a.max_tokens && a.active && at + 1u >= a.max_tokens[r]) {
+                atomicSub(a.active, 1u);  // ended by its cap: the next turnover retires it
             }
         }
     };
@@ -324,7 +335,7 @@ __device__ __forceinline__ void sample_row(const SampleArgs & a, SampleShared & 
     // ---- 5. the draw
     float u;
     if (a.u) u = a.u[blockIdx.x];
-    else if (ROWS && a.seed_r && a.counter_r) u = sample_uniform(a.seed_r[blockIdx.x], a.counter_r[blockIdx.x] + a.counter);
+    else if (ROWS && a.seed_r && a.counter_r) u = sample_uniform(a.seed_r[seq], a.counter_r[seq] + (a.lane_seq ? at : a.counter));
     else u = sample_uniform(a.seed, a.counter + blockIdx.x);
     const float target = u * Z;
     for (int e = tid; e < E; e += SM_THREADS)
@@ -390,6 +401,19 @@ __device__ __forceinline__ void gen_copy_row(float * dst, const float * src, siz
     for (size_t i = (size_t)part * blockDim.x + threadIdx.x; i < nvec; i += (size_t)parts * blockDim.x) d4[i] = s4[i];
 }
 
+// The same between rows of different indices (a queue's lane r and sequence s).  With n a multiple of
+// 4 every row of a [rows][n] array starts on 16 bytes and gen_copy_row's head and tail are empty;
+// otherwise (an odd vocabulary) the two rows need not share an alignment and the floats go one by one.
+// Either way element i of a row belongs to the same thread of the same part in every call with this
+// n, which is what lets k_gen_move read a lane's row and then write over it without a barrier.
+__device__ __forceinline__ void gen_move_row(float * dst, const float * src, size_t n, int part, int parts) {
+    if ((n & 3) == 0) {
+        gen_copy_row(dst, src, n, part, parts);
+    } else {
+        for (size_t i = (size_t)part * blockDim.x + threadIdx.x; i < n; i += (size_t)parts * blockDim.x) dst[i] = src[i];
+    }
+}
+
 constexpr int GEN_THREADS = 256;
 
 // grid (parts, rows)
@@ -397,6 +421,13 @@ __global__ __launch_bounds__(GEN_THREADS) void k_gen_snapshot(const GenRows g, u
                                                               const float * logits, float * snap_state,
                                                               float * snap_logits) {
     const int r = blockIdx.y;
+    if (g.lane_seq) {
+        const uint32_t s = g.lane_seq[r];
+        if (s == GEN_NONE || g.done[s] == 0 || g.fin_step[s] != step) return;
+        gen_move_row(snap_state + (size_t)s * g.state_len, state + (size_t)r * g.state_len, g.state_len, blockIdx.x, gridDim.x);
+        gen_move_row(snap_logits + (size_t)s * g.V, logits + (size_t)r * g.V, g.V, blockIdx.x, gridDim.x);
+        return;
+    }
     if (g.done[r] == 0 || g.fin_step[r] != step) return;
     gen_copy_row(snap_state + (size_t)r * g.state_len, state + (size_t)r * g.state_len, g.state_len, blockIdx.x, gridDim.x);
     gen_copy_row(snap_logits + (size_t)r * g.V, logits + (size_t)r * g.V, g.V, blockIdx.x, gridDim.x);
@@ -433,6 +464,74 @@ __global__ __launch_bounds__(GEN_THREADS) void k_gen_begin(int rows, int keep, u
     if (r == 0) *active = live;
 }
 
+// ---- a queue of sequences over the lanes (rwkv_mi355x_generate_queue) ---------------
+// One workgroup, thread r = lane r.  Rank of a free lane among the free lanes = a ballot's popcount
+// below the lane plus the free lanes of the waves before it; the rank-th waiting sequence enters.
+__global__ __launch_bounds__(GEN_THREADS) void k_gen_turnover(const GenQueue q, uint32_t step) {
+    __shared__ unsigned wave_free[GEN_THREADS / 64], wave_busy[GEN_THREADS / 64];
+    const int r = threadIdx.x, lane = r & 63, wave = r >> 6;
+    const bool in = r < q.lanes;
+    const uint32_t first = *q.next;  // read by every thread before the barrier, written after it
+    uint32_t s = GEN_NONE;
+    bool capped = false, ended = false;
+    if (in) s = q.lane_seq[r];
+    if (s != GEN_NONE) {
+        const bool stopped = q.done[s] != 0;
+        capped = !stopped && q.length[s] >= q.max_tokens[s];
+        ended = stopped || capped;
+    }
+    const bool is_free = in && (s == GEN_NONE || ended);
+    const unsigned long long fb = __ballot(is_free), bb = __ballot(in && !is_free);
+    if (lane == 0) wave_free[wave] = (unsigned)__popcll(fb), wave_busy[wave] = (unsigned)__popcll(bb);
+    __syncthreads();
+    unsigned rank = (unsigned)__popcll(fb & ((1ull << lane) - 1ull)), n_free = 0, n_busy = 0;
+#pragma unroll
+    for (int w = 0; w < GEN_THREADS / 64; w++) {
+        if (w < wave) rank += wave_free[w];
+        n_free += wave_free[w];
+        n_busy += wave_busy[w];
+    }
+    const uint32_t waiting = first < (uint32_t)q.Q ? (uint32_t)q.Q - first : 0u;
+    const bool admit = is_free && rank < waiting;
+    const uint32_t from = admit ? first + rank : GEN_NONE;
+    if (in) {
+        q.retire_to[r] = capped ? s : GEN_NONE;
+        q.admit_from[r] = from;
+        if (capped) q.done[s] = 1u;
+        if (is_free) q.lane_seq[r] = from;
+        if (admit) {
+            q.lane[from] = (uint32_t)r;
+            q.start[from] = step;
+        }
+    }
+    if (r == 0) {
+        const uint32_t admitted = min(n_free, waiting);
+        *q.next = first + admitted;
+        *q.active = waiting + n_busy;  // waiting - admitted still wait, n_busy + admitted are in lanes
+    }
+}
+
+// grid (parts, lanes).  Both copies of a lane give element i of its row to the same thread
+// (gen_move_row), so the admission's stores follow the retirement's loads in program order.
+__global__ __launch_bounds__(GEN_THREADS) void k_gen_move(const GenQueue q, size_t state_len, size_t V, float * state,
+                                                          float * logits, const float * slot_state, float * snap_state,
+                                                          float * snap_logits) {
+    const int r = blockIdx.y;
+    const uint32_t to = q.retire_to[r], from = q.admit_from[r];
+    float * st = state + (size_t)r * state_len;
+    float * lg = logits + (size_t)r * V;
+    if (to != GEN_NONE) {
+        gen_move_row(snap_state + (size_t)to * state_len, st, state_len, blockIdx.x, gridDim.x);
+        gen_move_row(snap_logits + (size_t)to * V, lg, V, blockIdx.x, gridDim.x);
+    }
+    if (from != GEN_NONE) {
+        const float * sst = slot_state + (size_t)from * state_len;
+        const float * slg = logits + (size_t)from * V;
+        if (sst != st) gen_move_row(st, sst, state_len, blockIdx.x, gridDim.x);
+        if (slg != lg) gen_move_row(lg, slg, V, blockIdx.x, gridDim.x);
+    }
+}
+
 }  // namespace
 
 bool launch_sample(hipStream_t st, const SampleArgs & a) {
@@ -440,9 +539,10 @@ bool launch_sample(hipStream_t st, const SampleArgs & a) {
     if (a.n_bias < 0 || a.n_bias > SAMPLE_MAX_BIAS || (a.n_bias && (!a.bias_ids || !a.bias_vals))) return false;
     if (a.n_stop < 0 || a.n_stop > SAMPLE_MAX_STOP) return false;
     const bool rows = a.temperature_r || a.top_p_r || a.seed_r || a.counter_r || a.presence_r || a.frequency_r ||
-                      a.counts || a.n_stop || a.done || a.length || a.fin_step || a.active || a.tok_stride;
+                      a.counts || a.n_stop || a.done || a.length || a.fin_step || a.active || a.tok_stride || a.lane_seq;
     if (rows) {
         if ((a.seed_r == nullptr) != (a.counter_r == nullptr)) return false;
+        if (a.lane_seq && !a.length) return false;  // a queue's draw index is the sequence's length
         RK_LAUNCH(k_sample_rows, dim3((unsigned)a.rows), dim3(SM_THREADS), 0, st, a);
     } else {
         RK_LAUNCH(k_sample, dim3((unsigned)a.rows), dim3(SM_THREADS), 0, st, a);
@@ -452,8 +552,8 @@ bool launch_sample(hipStream_t st, const SampleArgs & a) {
 }
 
 // parts of a row: about 8 vectors a thread, at most 32 workgroups
-static unsigned gen_parts(const GenRows & g) {
-    const size_t vec = (g.state_len + g.V) / 4 + 1;
+static unsigned gen_parts(size_t state_len, size_t V) {
+    const size_t vec = (state_len + V) / 4 + 1;
     return (unsigned)std::min<size_t>(32, std::max<size_t>(1, vec / (GEN_THREADS * 8)));
 }
 
@@ -464,7 +564,7 @@ static bool gen_rows_ok(const GenRows & g) {
 bool launch_gen_snapshot(hipStream_t st, const GenRows & g, uint32_t step, const float * state, const float * logits,
                          float * snap_state, float * snap_logits) {
     if (!gen_rows_ok(g) || !state || !logits || !snap_state || !snap_logits) return false;
-    RK_LAUNCH(k_gen_snapshot, dim3(gen_parts(g), (unsigned)g.rows), dim3(GEN_THREADS), 0, st, g, step, state, logits,
+    RK_LAUNCH(k_gen_snapshot, dim3(gen_parts(g.state_len, g.V), (unsigned)g.rows), dim3(GEN_THREADS), 0, st, g, step, state, logits,
               snap_state, snap_logits);
     HIP_OK(hipGetLastError());
     return true;
@@ -473,7 +573,7 @@ bool launch_gen_snapshot(hipStream_t st, const GenRows & g, uint32_t step, const
 bool launch_gen_restore(hipStream_t st, const GenRows & g, const float * snap_state, const float * snap_logits,
                         const float * state_live, float * state_final, float * logits) {
     if (!gen_rows_ok(g) || !snap_state || !snap_logits || !state_live || !state_final || !logits) return false;
-    RK_LAUNCH(k_gen_restore, dim3(gen_parts(g), (unsigned)g.rows), dim3(GEN_THREADS), 0, st, g, snap_state, snap_logits,
+    RK_LAUNCH(k_gen_restore, dim3(gen_parts(g.state_len, g.V), (unsigned)g.rows), dim3(GEN_THREADS), 0, st, g, snap_state, snap_logits,
               state_live, state_final, logits);
     HIP_OK(hipGetLastError());
     return true;
@@ -483,6 +583,28 @@ bool launch_gen_begin(hipStream_t st, int rows, int keep, uint32_t * done, uint3
                       uint32_t * active) {
     if (rows < 1 || rows > GEN_THREADS || !done || !length || !fin_step || !active) return false;
     RK_LAUNCH(k_gen_begin, dim3(1), dim3(GEN_THREADS), 0, st, rows, keep, done, length, fin_step, active);
+    HIP_OK(hipGetLastError());
+    return true;
+}
+
+static bool gen_queue_ok(const GenQueue & q) {
+    return q.lanes >= 1 && q.lanes <= GEN_THREADS && q.Q >= 1 && q.lane_seq && q.done && q.length && q.max_tokens &&
+           q.lane && q.start && q.retire_to && q.admit_from && q.next && q.active;
+}
+
+bool launch_gen_turnover(hipStream_t st, const GenQueue & q, uint32_t step) {
+    if (!gen_queue_ok(q)) return false;
+    RK_LAUNCH(k_gen_turnover, dim3(1), dim3(GEN_THREADS), 0, st, q, step);
+    HIP_OK(hipGetLastError());
+    return true;
+}
+
+bool launch_gen_move(hipStream_t st, const GenQueue & q, size_t state_len, size_t V, float * state, float * logits,
+                     const float * slot_state, float * snap_state, float * snap_logits) {
+    if (!gen_queue_ok(q) || state_len < 1 || V < 1 || !state || !logits || !slot_state || !snap_state || !snap_logits)
+        return false;
+    RK_LAUNCH(k_gen_move, dim3(gen_parts(state_len, V), (unsigned)q.lanes), dim3(GEN_THREADS), 0, st, q, state_len, V, state, logits,
+              slot_state, snap_state, snap_logits);
     HIP_OK(hipGetLastError());
     return true;
 }

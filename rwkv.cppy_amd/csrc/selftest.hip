@@ -3,6 +3,7 @@
 // name (oracle_quantize_act, oracle_matmul) without whole-model noise.
 #include <string.h>
 
+#include <tuple>
 #include <vector>
 
 #include "../../include/rwkv_mi355x.h"
@@ -433,6 +434,50 @@ extern "C" RWKV_API bool rwkv_mi355x_selftest_sample_rows(const float * logits, 
         if (hipMemcpy(d.first, d.second, R, hipMemcpyDeviceToHost) != hipSuccess) return false;
     if (counts && hipMemcpy(counts, a.counts, n * 4, hipMemcpyDeviceToHost) != hipSuccess) return false;
     return hipMemcpy(active, a.active, 4, hipMemcpyDeviceToHost) == hipSuccess;
+}
+
+// The queue's turnover kernel (sample.hip, k_gen_turnover) on host operands: what
+// rwkv_mi355x_generate_queue launches before step `step`.  lane_seq [lanes], done / lane / start [Q],
+// *next and *active are uploaded, updated and downloaded; length and max_tokens [Q] are read;
+// retire_to and admit_from [lanes] are written.
+extern "C" RWKV_API bool rwkv_mi355x_selftest_gen_turnover(int lanes, int Q, uint32_t step, uint32_t * lane_seq,
+                                                          uint32_t * done, const uint32_t * length,
+                                                          const uint32_t * max_tokens, uint32_t * lane, uint32_t * start,
+                                                          uint32_t * next, uint32_t * active, uint32_t * retire_to,
+                                                          uint32_t * admit_from) {
+    if (lanes < 1 || lanes > 256 || Q < 1 || Q > 65536 || !lane_seq || !done || !length || !max_tokens || !lane || !start ||
+        !next || !active || !retire_to || !admit_from || *next > (uint32_t)Q)
+        return false;
+    for (int r = 0; r < lanes; r++)
+        if (lane_seq[r] != GEN_NONE && lane_seq[r] >= (uint32_t)Q) return false;
+    const size_t LB = (size_t)lanes * 4, QB = (size_t)Q * 4;
+    DevBufs b;
+    bool ok = true;
+    auto up = [&](const void * h, size_t bytes) -> uint32_t * {
+        void * d = b.alloc(bytes);
+        ok = ok && d && hipMemcpy(d, h, bytes, hipMemcpyHostToDevice) == hipSuccess;
+        return (uint32_t *)d;
+    };
+    GenQueue q;
+    q.lanes = lanes;
+    q.Q = Q;
+    q.lane_seq = up(lane_seq, LB);
+    q.done = up(done, QB);
+    q.length = up(length, QB);
+    q.max_tokens = up(max_tokens, QB);
+    q.lane = up(lane, QB);
+    q.start = up(start, QB);
+    q.retire_to = up(retire_to, LB);
+    q.admit_from = up(admit_from, LB);
+    q.next = up(next, 4);
+    q.active = up(active, 4);
+    if (!ok || !launch_gen_turnover(nullptr, q, step) || hipDeviceSynchronize() != hipSuccess) return false;
+    const std::tuple<void *, const void *, size_t> down[] = {
+        {lane_seq, q.lane_seq, LB}, {done, q.done, QB}, {lane, q.lane, QB},           {start, q.start, QB},
+        {next, q.next, 4},          {active, q.active, 4}, {retire_to, q.retire_to, LB}, {admit_from, q.admit_from, LB}};
+    for (const auto & d : down)
+        if (hipMemcpy(std::get<0>(d), std::get<1>(d), std::get<2>(d), hipMemcpyDeviceToHost) != hipSuccess) return false;
+    return true;
 }
 
 // The scoring kernel (xent.hip) on host operands: what rwkv_mi355x_score_sequence launches per head

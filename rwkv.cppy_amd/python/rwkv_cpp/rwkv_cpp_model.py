@@ -269,6 +269,39 @@ class RWKVModel:
         tokens, lengths, _ = self._library.rwkv_mi355x_generate_batch(self._ctx, rows, n, params)
         return [[int(t) for t in tokens[r][:int(lengths[r])]] for r in range(rows)]
 
+    def generate_queue(self, prompts: List[List[int]], max_tokens, lanes: int = 32, temperature=1.0, top_p=0.8,
+                       presence_penalty=0.0, frequency_penalty=0.0, logit_bias=None, seeds=None, stop_tokens=(),
+                       check_every: int = 16) -> List[List[int]]:
+        """MI355X extension (rwkv_mi355x_generate_queue): continuous batching.  Up to 256 prompts are
+        evaluated together (prefill_batch) into slots 0 .. Q-1 and generated through a queue over
+        `lanes` decode rows: a row whose sequence has ended -- a stop token, or its max_tokens (a scalar
+        or one value per prompt) -- takes the next waiting prompt between two decode steps, so the rows
+        stay full.  The other parameters are those of generate_batch, per prompt.  Returns one token
+        list per prompt, each exactly what that prompt generates alone; slot i holds its final state
+        and logits, and batch_load(i) continues from there."""
+        if not self._valid:
+            raise ValueError('Model was freed')
+        rows = len(prompts)
+        if not 0 < rows <= 256:
+            raise ValueError(f'{rows} prompts (1 to 256)')
+        if any(len(p) == 0 for p in prompts):
+            raise ValueError('empty prompt')
+        if not 0 < lanes <= 256:
+            raise ValueError(f'{lanes} lanes (1 to 256)')
+        caps = [int(c) for c in rwkv_cpp_shared_library._per_row(max_tokens, rows, 'max_tokens')]
+        if any(not 0 < c <= 65536 for c in caps):
+            raise ValueError('max_tokens must be in [1, 65536]')
+        # the per-prompt parameters are checked before anything reaches the device
+        rwkv_cpp_shared_library.make_batch_sampling(rows, temperature, top_p, presence_penalty, frequency_penalty,
+                                                    logit_bias, seeds, 0, stop_tokens, False, check_every)
+        if self._library.rwkv_mi355x_batch_slots(self._ctx) < rows:
+            self._library.rwkv_mi355x_batch_reserve(self._ctx, rows)
+        self._library.rwkv_mi355x_prefill_batch(self._ctx, [list(p) for p in prompts], list(range(rows)), None)
+        out = self._library.rwkv_mi355x_generate_queue(
+            self._ctx, caps, lanes, temperature, top_p, presence_penalty, frequency_penalty, logit_bias, seeds, 0,
+            stop_tokens, check_every)
+        return [[int(t) for t in out['tokens'][r][:int(out['lengths'][r])]] for r in range(rows)]
+
     def reset_state(self) -> None:
         """MI355X extension (rwkv_mi355x_state_upload with NULL): the device-resident state becomes the
         fresh state, as before the first token."""

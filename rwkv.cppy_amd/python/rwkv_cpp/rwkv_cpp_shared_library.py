@@ -239,6 +239,10 @@ class RWKVSharedLibrary:
         L.rwkv_mi355x_batch_load.restype = ctypes.c_bool
         L.rwkv_mi355x_generate_batch.argtypes = [vp, sz, P_BATCH, sz, P_U32, P_U32, P_U32]
         L.rwkv_mi355x_generate_batch.restype = ctypes.c_bool
+        L.rwkv_mi355x_generate_queue.argtypes = [vp, sz, sz, P_BATCH, P_U32, sz, P_U32, P_U32, P_U32, P_U32, P_U32]
+        L.rwkv_mi355x_generate_queue.restype = ctypes.c_bool
+        L.rwkv_mi355x_selftest_gen_turnover.argtypes = [ctypes.c_int, ctypes.c_int, u32] + [P_U32] * 10
+        L.rwkv_mi355x_selftest_gen_turnover.restype = ctypes.c_bool
         P_SIZE = ctypes.POINTER(sz)
         L.rwkv_mi355x_prefill_batch.argtypes = [vp, sz, P_U32, P_U32, P_SIZE, ctypes.POINTER(ctypes.c_uint8)]
         L.rwkv_mi355x_prefill_batch.restype = ctypes.c_bool
@@ -425,6 +429,56 @@ class RWKVSharedLibrary:
                                                        ctypes.byref(steps)):
             raise ValueError('rwkv_mi355x_generate_batch failed, check stderr')
         return tokens[:, :n], lengths, steps.value
+
+    def rwkv_mi355x_generate_queue(self, ctx: RWKVContext, max_tokens, lanes: int, temperature=1.0, top_p=0.8,
+                                   presence=None, frequency=None, logit_bias=None, seeds=None, offsets=0,
+                                   stop_tokens=(), check_every: int = 0, n: Optional[int] = None):
+        """The sequences in slots [0, len(max_tokens)) through a queue over `lanes` decode rows, at most
+        max_tokens[s] tokens each (make_batch_sampling over the sequences, keep_counts false).  Returns
+        a dict: tokens uint32 [Q, n] (n: max(max_tokens) unless given; 0xFFFFFFFF after a sequence's
+        last token), lengths, lane, start uint32 [Q] and steps, the decode steps that were needed."""
+        import numpy as np
+        caps = np.ascontiguousarray(max_tokens, dtype=np.uint32)
+        Q = int(caps.size)
+        params = make_batch_sampling(Q, temperature, top_p, presence, frequency, logit_bias, seeds, offsets,
+                                     stop_tokens, False, check_every)
+        n = int(caps.max()) if n is None else int(n)
+        out = {k: np.zeros(Q, np.uint32) for k in ('lengths', 'lane', 'start')}
+        tokens = np.zeros((Q, max(1, n)), np.uint32)
+        steps = ctypes.c_uint32(0)
+        P_U32 = ctypes.POINTER(ctypes.c_uint32)
+        if not self.library.rwkv_mi355x_generate_queue(ctx.ptr, Q, lanes, ctypes.byref(params), caps.ctypes.data_as(P_U32),
+                                                       n, tokens.ctypes.data_as(P_U32), out['lengths'].ctypes.data_as(P_U32),
+                                                       out['lane'].ctypes.data_as(P_U32), out['start'].ctypes.data_as(P_U32),
+                                                       ctypes.byref(steps)):
+            raise ValueError('rwkv_mi355x_generate_queue failed, check stderr')
+        out['tokens'] = tokens[:, :n]
+        out['steps'] = steps.value
+        return out
+
+    def rwkv_mi355x_selftest_gen_turnover(self, lane_seq, done, length, max_tokens, next_seq: int, step: int = 0,
+                                          fill: int = 0xFFFFFFFE):
+        """The queue's turnover kernel on host operands: lane_seq [lanes] (0xFFFFFFFF: idle), done,
+        length, max_tokens [Q], the first waiting sequence.  Returns a dict of the words afterwards:
+        lane_seq, retire_to, admit_from [lanes]; done, lane, start [Q] (lane and start keep `fill`
+        where no sequence was admitted); next, active."""
+        import numpy as np
+        u32 = lambda a: np.array(a, dtype=np.uint32, copy=True)  # noqa: E731
+        out = dict(lane_seq=u32(lane_seq), done=u32(done))
+        lanes, Q = out['lane_seq'].size, out['done'].size
+        length, max_tokens = u32(length), u32(max_tokens)
+        assert length.size == Q and max_tokens.size == Q
+        out.update(lane=np.full(Q, fill, np.uint32), start=np.full(Q, fill, np.uint32),
+                   retire_to=np.full(lanes, fill, np.uint32), admit_from=np.full(lanes, fill, np.uint32))
+        nxt, act = np.array([next_seq], np.uint32), np.array([fill], np.uint32)
+        P_U32 = ctypes.POINTER(ctypes.c_uint32)
+        ptr = lambda a: a.ctypes.data_as(P_U32)  # noqa: E731
+        if not self.library.rwkv_mi355x_selftest_gen_turnover(
+                lanes, Q, step, ptr(out['lane_seq']), ptr(out['done']), ptr(length), ptr(max_tokens), ptr(out['lane']),
+                ptr(out['start']), ptr(nxt), ptr(act), ptr(out['retire_to']), ptr(out['admit_from'])):
+            raise ValueError('rwkv_mi355x_selftest_gen_turnover failed')
+        out.update(next=int(nxt[0]), active=int(act[0]))
+        return out
 
     def rwkv_mi355x_prefill_batch(self, ctx: RWKVContext, prompts, slots, cont=None) -> None:
         """Evaluates the prompts (token lists, none empty) together in packed sequence passes; prompt i

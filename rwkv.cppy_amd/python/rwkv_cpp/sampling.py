@@ -81,6 +81,30 @@ def penalize(logits, counts, presence: float, frequency: float) -> np.ndarray:
     return l
 
 
+def queue_schedule(lengths, lanes: int):
+    """The schedule of librwkv.so's queue (rwkv_mi355x_generate_queue) on plain integers: sequence s
+    occupies a lane for lengths[s] >= 1 steps.  Before step i the lanes whose sequence has had its
+    steps are freed, and the free lanes, in increasing lane order, take the waiting sequences in
+    increasing sequence order; at step 0 every lane is free.  Returns (lane, start, steps): the lane
+    and the step of every sequence's admission, and the number of steps up to the one after which
+    no lane was busy."""
+    lengths = [int(x) for x in lengths]
+    if lanes < 1 or not lengths or any(x < 1 for x in lengths):
+        raise ValueError('lanes >= 1 and at least one length, each >= 1')
+    L = min(int(lanes), len(lengths))
+    lane, start = [0] * len(lengths), [0] * len(lengths)
+    free_at = [0] * L  # the step at whose turnover the lane is free
+    nxt, step = 0, 0
+    while nxt < len(lengths):
+        for r in range(L):
+            if free_at[r] <= step and nxt < len(lengths):
+                lane[nxt], start[nxt] = r, step
+                free_at[r] = step + lengths[nxt]
+                nxt += 1
+        step += 1
+    return lane, start, max(free_at)
+
+
 def sample_probs_u(probs: np.ndarray, u: float, temperature: float = 1.0, top_p: float = 0.8,
                    logit_bias: Optional[Dict[int, float]] = None) -> int:
     """sample_probs with the uniform draw u in [0, 1) given instead of an rng: the same bias, top-p
