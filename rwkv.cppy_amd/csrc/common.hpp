@@ -21,6 +21,7 @@
 #include <hip/hip_fp16.h>
 #include <stdint.h>
 #include <stddef.h>
+#include <string.h>
 
 namespace rwkvmi {
 
@@ -161,6 +162,40 @@ extern thread_local KLaunchTimer * g_klt;
             hipLaunchKernelGGL(kern, grid, block, lds, st, __VA_ARGS__);                            \
         }                                                                                           \
     } while (0)
+
+// The token id(s) a launch embeds.  imm == 0: the launch reads ptr[t] (a sequence's or a batch's
+// staged tokens; generation: ptr[0], which the sampler wrote on the device).  imm == 1: a one-token
+// step whose id the host knows -- it travels by value in the argument block, so nothing is enqueued
+// ahead of the launch to deliver it and the kernel has it in a scalar register from the start; one
+// lane of the launch stores it to ptr[0], which so stays the id of the last step.
+struct TokArg {
+    uint32_t * ptr;
+    uint32_t id;
+    uint32_t imm;
+};
+__device__ __forceinline__ size_t tok_get(const TokArg & t, int i = 0) { return t.imm ? t.id : t.ptr[i]; }
+// the one store of an imm step: called by one lane of the launch
+__device__ __forceinline__ void tok_keep(const TokArg & t) {
+    if (t.imm) t.ptr[0] = t.id;
+}
+
+// While a decode graph is captured (Engine::capture_tok), the launch that takes the step's TokArg
+// leaves a copy of its argument block -- its kernel's one parameter -- and the TokArg's offset in it
+// here.  The engine keeps the copy with the graph's first kernel node and replays the graph with
+// another id by updating that node.
+struct TokLaunch {
+    char args[1024];
+    size_t size = 0, off = 0;
+};
+extern thread_local TokLaunch * g_tokl;
+template <class A>
+inline void tok_launch_note(const A & a, size_t off) {
+    static_assert(sizeof(A) <= sizeof(TokLaunch::args), "argument block larger than TokLaunch::args");
+    if (!g_tokl) return;
+    memcpy(g_tokl->args, &a, sizeof(A));
+    g_tokl->size = sizeof(A);
+    g_tokl->off = off;
+}
 
 #define HIP_OK(x)                                                                             \
     do {                                                                                      \

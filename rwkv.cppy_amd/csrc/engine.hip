@@ -23,6 +23,7 @@
 namespace rwkvmi {
 
 thread_local KLaunchTimer * g_klt = nullptr;
+thread_local TokLaunch * g_tokl = nullptr;
 
 #ifdef RWKV_STAMP
 // Diagnostic builds (stamp.hpp): every kernel translation unit registers a setter for its copy
@@ -153,10 +154,36 @@ bool Engine::init() {
 void Engine::drop_graphs() {
     for (auto & pc : graphs_)
         for (auto & pl : pc)
-            for (hipGraphExec_t & g : pl) {
-                if (g) (void)hipGraphExecDestroy(g);
-                g = nullptr;
-            }
+            for (TokGraph & g : pl) g.destroy();
+}
+
+void Engine::TokGraph::destroy() {
+    if (ge) (void)hipGraphExecDestroy(ge);
+    if (g) (void)hipGraphDestroy(g);
+    ge = nullptr;
+    g = nullptr;
+    node = nullptr;
+    args.clear();
+}
+
+// The next replay embeds t: nothing to do while the node already holds it (generation: every
+// step reads the word the sampler wrote), else the node's argument block is replaced -- host work
+// only; replays already enqueued keep the arguments they were launched with.
+bool Engine::TokGraph::set_tok(const TokArg & t) {
+    if (!node) {
+        fprintf(stderr, "rwkv: a decode graph without its token node\n");
+        return false;
+    }
+    TokArg cur;
+    memcpy(&cur, args.data() + off, sizeof(cur));
+    if (cur.ptr == t.ptr && cur.imm == t.imm && cur.id == t.id) return true;
+    memcpy(args.data() + off, &t, sizeof(t));
+    void * argv[1] = {args.data()};
+    p.kernelParams = argv;
+    const hipError_t e = hipGraphExecKernelNodeSetParams(ge, node, &p);
+    p.kernelParams = nullptr;
+    HIP_OK(e);
+    return true;
 }
 
 // Contexts of this process with decode work queued per device (a context counts once from its
@@ -758,7 +785,9 @@ bool Engine::forward(int T, const float * sin, float * sout, bool logits) {
 bool Engine::forward_range(int T, const float * sin, float * sout, uint32_t l0, uint32_t l1, bool logits) {
     const size_t C = m_->n_embed;
     last_decode_ = false;
-    if (l0 == 0 && !launch_embed_ln(stream_, dtokens_, T, m_->emb, m_->ln0_w, m_->ln0_b, x_)) return false;
+    // one token of its own sequence: the step's id (tok_arg); batches and packed prompts read dtokens_
+    const TokArg tk = T == 1 && !bs_ && !seg_ ? tok_arg() : TokArg{dtokens_.get(), 0u, 0u};
+    if (l0 == 0 && !launch_embed_ln(stream_, tk, T, m_->emb, m_->ln0_w, m_->ln0_b, x_)) return false;
     const size_t per_layer = layer_state_len();
     // layer matmuls run over all T tokens: Q8 activations go straight into GEMM tiles
     tile_acts_ = T >= 2 && !use_mm_ && (!bs_ || T >= batch_gemm_min_);
@@ -838,6 +867,7 @@ bool Engine::run_tokens(const uint32_t * tokens, size_t T, bool want_logits) {
     const int cur0 = cur_;
     logits_valid_ = false;
     if (!run_tokens_impl(tokens, T, want_logits)) {
+        step_imm_ = false;
         (void)hipStreamSynchronize(stream_);
         (void)gran_.clear_tagged(stream_);  // a replay runs at the same parity (GranuleMem::clear_tagged)
         (void)hipStreamSynchronize(stream_);
@@ -855,12 +885,15 @@ bool Engine::run_tokens_impl(const uint32_t * tokens, size_t T, bool want_logits
         const size_t n = std::min(T - done, kChunkMax);
         const bool last = done + n == T;
         if (!ensure_workspace((int)n)) return false;
+        // one token: its id goes by value in the argument block of the step's first launch (TokArg;
+        // a graph replay: set_tok), and nothing is enqueued to deliver it -- hipStreamWriteValue32,
+        // which stood here, runs as a kernel of the runtime (__amd_rocclr_streamOpsWrite) on this
+        // stream: 4.3 us and one more kernel boundary per token
+        step_imm_ = tokens && n == 1;
+        step_id_ = step_imm_ ? tokens[done] : 0;
         if (!tokens) {
             // generate: the sampler enqueued just before this step writes dtokens_[0]
-        } else if (n == 1) {
-            // one token: a CP write packet in stream order (no blit kernel, no pinned buffer)
-            HIP_OK(hipStreamWriteValue32(stream_, dtokens_, tokens[done], 0));
-        } else if (!stage_tokens(tokens + done, n)) {
+        } else if (n > 1 && !stage_tokens(tokens + done, n)) {
             return false;
         }
         // scoring: a one-token chunk's step writes logits_ (score_chunk reads it), longer chunks get
@@ -877,12 +910,14 @@ bool Engine::run_tokens_impl(const uint32_t * tokens, size_t T, bool want_logits
             g_klt = nullptr;
             if (!ok) return false;
         } else if (n == 1 && use_graphs_) {
-            hipGraphExec_t & ge = graphs_[co][cur_][lg ? 1 : 0];
-            if (!ge && !capture(ge, [&] { return forward(1, dstate_[cur_], dstate_[cur_ ^ 1], lg); })) return false;
-            HIP_OK(hipGraphLaunch(ge, stream_));
+            TokGraph & tg = graphs_[co][cur_][lg ? 1 : 0];
+            if (!tg.ge && !capture_tok(tg, [&] { return forward(1, dstate_[cur_], dstate_[cur_ ^ 1], lg); })) return false;
+            if (!tg.set_tok(tok_arg())) return false;
+            HIP_OK(hipGraphLaunch(tg.ge, stream_));
         } else {
             if (!forward((int)n, dstate_[cur_], dstate_[cur_ ^ 1], lg)) return false;
         }
+        step_imm_ = false;
         if (score_ && !score_chunk(done, n, last)) return false;
         // a step without the fused decode flips the parity (GranuleMem::clear_tagged)
         if (n > 1 || generic_decode_) HIP_OK(gran_.clear_tagged(stream_));
@@ -1046,16 +1081,27 @@ bool Engine::eval_host_chunked(uint32_t token, const float * state_in, float * s
     }
     const bool lg = logits_out != nullptr;
     const bool co = choose_co();
-    std::vector<hipGraphExec_t> & gs = io_graphs_[co][cur_][lg ? 1 : 0];
+    std::vector<TokGraph> & gs = io_graphs_[co][cur_][lg ? 1 : 0];
     if (gs.size() != NC) {
-        for (hipGraphExec_t g : gs)
-            if (g) (void)hipGraphExecDestroy(g);
-        gs.assign(NC, nullptr);
+        for (TokGraph & g : gs) g.destroy();
+        gs.assign(NC, TokGraph{});
     }
     float * din = dstate_[cur_], * dout = dstate_[cur_ ^ 1];
+    // the id by value, as in run_tokens_impl: chunk 0's first launch consumes it, no other chunk's
+    // graph holds one
+    step_imm_ = true;
+    step_id_ = token;
     for (uint32_t c = 0; c < NC; c++) {
-        if (!gs[c] && !capture(gs[c], [&] { return forward_decode(din, dout, lg, c * K, (c + 1) * K); })) return false;
+        if (gs[c].ge) continue;
+        const bool ok = capture_tok(gs[c], [&] { return forward_decode(din, dout, lg, c * K, (c + 1) * K); });
+        if (!ok) {
+            step_imm_ = false;
+            return false;
+        }
     }
+    const TokArg tk = tok_arg();
+    step_imm_ = false;
+    if (!gs[0].set_tok(tk)) return false;
     auto slice = [&](uint32_t c, size_t & off, size_t & bytes) {
         const uint32_t l0 = c * K, l1 = std::min(NL, l0 + K);
         off = l0 * per_layer;
@@ -1063,7 +1109,6 @@ bool Engine::eval_host_chunked(uint32_t token, const float * state_in, float * s
     };
     hipEvent_t * in_ev = io_ev_.data(), * done_ev = io_ev_.data() + NC;
     size_t off, bytes;
-    HIP_OK(hipStreamWriteValue32(stream_, dtokens_, token, 0));
     last_decode_ = true;
     if (!state_in && !init_state(din)) return false;
     auto upload = [&](uint32_t c) -> bool {
@@ -1082,7 +1127,7 @@ bool Engine::eval_host_chunked(uint32_t token, const float * state_in, float * s
     };
     auto launch = [&](uint32_t c) -> bool {
         if (state_in) HIP_OK(hipStreamWaitEvent(stream_, in_ev[c], 0));
-        HIP_OK(hipGraphLaunch(gs[c], stream_));
+        HIP_OK(hipGraphLaunch(gs[c].ge, stream_));
         HIP_OK(hipEventRecord(done_ev[c], stream_));
         return true;
     };
@@ -1123,8 +1168,7 @@ void Engine::drop_io_graphs() {
     for (auto & pc : io_graphs_)
         for (auto & p : pc)
             for (auto & v : p) {
-                for (hipGraphExec_t g : v)
-                    if (g) (void)hipGraphExecDestroy(g);
+                for (TokGraph & g : v) g.destroy();
                 v.clear();
             }
 }

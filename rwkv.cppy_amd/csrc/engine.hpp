@@ -313,9 +313,31 @@ class Engine : public KLaunchTimer, private Workspace, private GenSlots {
     // the tag of layer l's in-launch hand-offs at the current state parity, and what its launches poll with
     unsigned handoff_tag(uint32_t l) const { return (unsigned)(l + 1) | ((unsigned)(cur_ + 1) << 16); }
     Handoff handoff(uint32_t l) const { return Handoff{handoff_tag(l), herr_d_, spin_max_}; }
-    // captures what build() enqueues on stream_ into an executable graph
+    // captures what build() enqueues on stream_ into an executable graph; keep: the graph itself
+    // is handed over instead of destroyed
     template <class F>
-    bool capture(hipGraphExec_t & ge, F && build);
+    bool capture(hipGraphExec_t & ge, F && build, hipGraph_t * keep = nullptr);
+    // A decode graph.  When its first launch takes the step's token id (TokArg: layers from 0), the
+    // graph, that kernel node and a host copy of the node's argument block stay with it, and a
+    // replay with another id updates that one node first (set_tok) -- no stream operation delivers
+    // the id between two replays.
+    struct TokGraph {
+        hipGraphExec_t ge = nullptr;
+        hipGraph_t g = nullptr;
+        hipGraphNode_t node = nullptr;
+        hipKernelNodeParams p = {};
+        std::vector<char> args;  // the node's argument block (its kernel's one parameter)
+        size_t off = 0;          // of the TokArg in it
+        bool set_tok(const TokArg & t);
+        void destroy();
+    };
+    template <class F>
+    bool capture_tok(TokGraph & tg, F && build);
+    // the id of the step being enqueued: by value for a one-token step with a host-known id
+    // (run_tokens_impl, eval_host_chunked), else read from dtokens_
+    uint32_t step_id_ = 0;
+    bool step_imm_ = false;
+    TokArg tok_arg() const { return TokArg{dtokens_.get(), step_imm_ ? step_id_ : 0u, step_imm_ ? 1u : 0u}; }
     // tokens == NULL (T == 1): the token is already in dtokens_[0] (generate: the sampler wrote it)
     bool run_tokens(const uint32_t * tokens, size_t T, bool want_logits);
     bool run_tokens_impl(const uint32_t * tokens, size_t T, bool want_logits);
@@ -363,7 +385,7 @@ class Engine : public KLaunchTimer, private Workspace, private GenSlots {
     // k_wkv6_s64 (default); RWKV_MI355X_WKV_CHUNK=1 or rwkv_mi355x_debug_set(ctx, "wkv_chunk", 1)
     bool wkv_chunk_ = false;
     DevBuf<float> wkvc_;  // its chunk matrices / chunk states, grown on demand
-    hipGraphExec_t graphs_[2][2][2] = {};  // [co-resident layout][cur][logits]
+    TokGraph graphs_[2][2][2];  // [co-resident layout][cur][logits]
     bool use_graphs_ = true;
     bool split_maa_ = false;       // RWKV_MI355X_SPLIT_MAA=1: v6 decode W1 + mix as two launches
     // Decode fusions (RWKV_MI355X_DECODE_FUSION, a mask read at init; rwkv_mi355x_debug_set
@@ -470,7 +492,8 @@ class Engine : public KLaunchTimer, private Workspace, private GenSlots {
     hipStream_t io_stream_[2] = {nullptr, nullptr};
     std::vector<hipEvent_t> io_ev_;
     hipEvent_t io_entry_ev_ = nullptr;  // work already queued on stream_ at entry (copy streams wait)
-    std::vector<hipGraphExec_t> io_graphs_[2][2][2];  // [co-resident layout][cur][logits] per chunk
+    // [co-resident layout][cur][logits] per chunk; chunk 0's takes the token id
+    std::vector<TokGraph> io_graphs_[2][2][2];
     bool eval_host_chunked(uint32_t token, const float * state_in, float * state_out, float * logits_out);
     bool pinned_io(const float * state_in, const float * state_out);
     void drop_io_graphs();
@@ -493,7 +516,7 @@ bool Engine::grow(DevBuf<T> & b, size_t need, size_t cap, unsigned graphs) {
 // Captures what build() enqueues on stream_ and instantiates it as ge.  A failed build still ends
 // the capture (the stream has to leave capture mode) before its graph is dropped.
 template <class F>
-bool Engine::capture(hipGraphExec_t & ge, F && build) {
+bool Engine::capture(hipGraphExec_t & ge, F && build, hipGraph_t * keep) {
     hipGraph_t g = nullptr;
     HIP_OK(hipStreamBeginCapture(stream_, hipStreamCaptureModeThreadLocal));
     const bool ok = build();
@@ -502,8 +525,47 @@ bool Engine::capture(hipGraphExec_t & ge, F && build) {
         (void)hipGraphDestroy(g);
         return false;
     }
-    HIP_OK(hipGraphInstantiate(&ge, g, nullptr, nullptr, 0));
-    (void)hipGraphDestroy(g);
+    const hipError_t e = hipGraphInstantiate(&ge, g, nullptr, nullptr, 0);
+    if (e != hipSuccess || !keep) (void)hipGraphDestroy(g);
+    HIP_OK(e);
+    if (keep) *keep = g;
+    return true;
+}
+
+// As capture(); when a launch of build() took the step's TokArg (it left its argument block in
+// g_tokl), that launch is the chain's first kernel node: the node, its launch parameters and the
+// argument block are kept for set_tok.  The node's own copy of the block must equal the launch's --
+// anything else means the first node is not that launch, and the capture fails.
+template <class F>
+bool Engine::capture_tok(TokGraph & tg, F && build) {
+    tg.destroy();
+    TokLaunch rec;
+    g_tokl = &rec;
+    const bool ok = capture(tg.ge, build, &tg.g);
+    g_tokl = nullptr;
+    if (!ok) return false;
+    if (!rec.size) {  // layers from l0 > 0: no id in this graph
+        (void)hipGraphDestroy(tg.g);
+        tg.g = nullptr;
+        return true;
+    }
+    size_t n = 1;
+    hipKernelNodeParams p;
+    hipGraphNodeType type;
+    if (hipGraphGetRootNodes(tg.g, &tg.node, &n) != hipSuccess || n != 1 ||
+        hipGraphNodeGetType(tg.node, &type) != hipSuccess || type != hipGraphNodeTypeKernel ||
+        hipGraphKernelNodeGetParams(tg.node, &p) != hipSuccess || !p.kernelParams || !p.kernelParams[0] ||
+        memcmp(p.kernelParams[0], rec.args, rec.size) != 0) {
+        (void)hipGetLastError();
+        fprintf(stderr, "rwkv: the decode graph's first node is not the launch that takes the token id\n");
+        tg.destroy();
+        return false;
+    }
+    tg.p = p;
+    tg.p.kernelParams = nullptr;  // set_tok points it at args
+    tg.p.extra = nullptr;
+    tg.args.assign(rec.args, rec.args + rec.size);
+    tg.off = rec.off;
     return true;
 }
 

@@ -186,7 +186,7 @@ bool Engine::decode_att_v4(DecodeRun & d, uint32_t l) {
         memset(&wf, 0, sizeof(wf));
         const bool wo_in = (fuse_ & FUSE_WO4) && L.att_o.type == L.att_r.type && C % 8 == 0;
         if (wo_in && d.emb4_in && l == 0) {
-            wf.tok = dtokens_;
+            wf.tok = tok_arg();
             wf.emb = m_->emb;
             wf.ln0w = m_->ln0_w;
             wf.ln0b = m_->ln0_b;
@@ -536,7 +536,7 @@ bool Engine::forward_decode(const float * sin, float * sout, bool logits, uint32
         const ActBuf o0[5] = {A(1, F.decay_w1), A(2, F.att_k), A(3, F.att_v), A(4, F.att_r), A(5, F.att_g)};
         v6_maa_dec_args(d.emaa, C, m_->maa_D, F.maa_w1, x_, sin + C, sout + C, F.ln1_w, F.ln1_b, F.maa_x, F.maa_w2t,
                         F.maa, o0);
-        d.emaa.tok = dtokens_;
+        d.emaa.tok = tok_arg();
         d.emaa.emb = m_->emb;
         d.emaa.ln0w = m_->ln0_w;
         d.emaa.ln0b = m_->ln0_b;
@@ -550,7 +550,7 @@ bool Engine::forward_decode(const float * sin, float * sout, bool logits, uint32
                     C % 8 == 0 && (m_->emb.type == W_F16 || m_->emb.type == W_F32) && (int)m_->emb.K == C;
         d.emb_in = d.emb4_in;
     }
-    if (l0 == 0 && !d.emb_in && !launch_embed_ln(stream_, dtokens_, 1, m_->emb, m_->ln0_w, m_->ln0_b, x_)) return false;
+    if (l0 == 0 && !d.emb_in && !launch_embed_ln(stream_, tok_arg(), 1, m_->emb, m_->ln0_w, m_->ln0_b, x_)) return false;
     v7_fused_lora_ = false;
     for (uint32_t l = d.l0; l < d.l1; l++) {
         bool ok;

@@ -366,10 +366,20 @@ bool launch_delay(hipStream_t st, int us) {
 // (ln_stats_regs: ln_stats_wave's association, the same bits as the sequence kernels); wave w then
 // normalizes and stores chunks w, w + 4, ...  The LayerNorm weights are loaded at kernel start, before
 // the token id returns: two dependent memory round trips (token, row) instead of a store / reload of
-// the row through L2 between them.
+// the row through L2 between them -- one, the row's, when the id comes with the launch (TokArg::imm).
 constexpr int EMB_NC = 8;  // chunks held per lane: n_embed <= 4096
-__global__ __launch_bounds__(256) void k_embed_ln(const uint32_t * tokens, DMat emb, const float * w,
-                                                  const float * b, float * x) {
+// the one parameter of both kernels (Engine::capture_tok updates tokens in a captured node)
+struct EmbedLn {
+    TokArg tokens;
+    DMat emb;
+    const float * w, * b;
+    float * x;
+};
+__global__ __launch_bounds__(256) void k_embed_ln(EmbedLn a) {
+    const TokArg & tokens = a.tokens;
+    const DMat & emb = a.emb;
+    const float * w = a.w, * b = a.b;
+    float * x = a.x;
     STAMP_BEGIN();
     const int t = blockIdx.x, C = emb.K, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int nc = (C + LN_CHUNK - 1) / LN_CHUNK;
@@ -382,7 +392,8 @@ __global__ __launch_bounds__(256) void k_embed_ln(const uint32_t * tokens, DMat 
             ln_load8(bv[q], b, c * LN_CHUNK + lane * 8, C);
         }
     }
-    const size_t tok = tokens[t];
+    const size_t tok = tok_get(tokens, t);
+    if (threadIdx.x == 0) tok_keep(tokens);
     float v[EMB_NC][8];
 #pragma unroll
     for (int c = 0; c < EMB_NC; c++) {
@@ -430,11 +441,15 @@ __device__ __forceinline__ void emb_load8(float (&v)[8], const DMat & emb, size_
         ln_load8(v, (const float *)emb.qs + tok * C, k, C);
     }
 }
-__global__ __launch_bounds__(256) void k_embed_ln_wide(const uint32_t * tokens, DMat emb, const float * w,
-                                                       const float * b, float * x) {
+__global__ __launch_bounds__(256) void k_embed_ln_wide(EmbedLn a) {
+    const TokArg & tokens = a.tokens;
+    const DMat & emb = a.emb;
+    const float * w = a.w, * b = a.b;
+    float * x = a.x;
     const int t = blockIdx.x, C = emb.K, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int nc = (C + LN_CHUNK - 1) / LN_CHUNK;
-    const size_t tok = tokens[t];
+    const size_t tok = tok_get(tokens, t);
+    if (threadIdx.x == 0) tok_keep(tokens);
     double s1 = 0.0, s2 = 0.0;
     for (int c0 = 0; c0 < nc; c0 += 4) {
         float v[4][8];
@@ -467,14 +482,20 @@ __global__ __launch_bounds__(256) void k_embed_ln_wide(const uint32_t * tokens, 
     }
 }
 
-bool launch_embed_ln(hipStream_t st, const uint32_t * tokens, int T, const DMat & emb, const float * w,
+bool launch_embed_ln(hipStream_t st, const TokArg & tokens, int T, const DMat & emb, const float * w,
                      const float * b, float * x) {
     if (emb.K % 8 || (emb.type != W_F16 && emb.type != W_F32)) {
         fprintf(stderr, "rwkv: embedding row of %d elements (type %d) unsupported\n", emb.K, emb.type);
         return false;
     }
-    if (emb.K > EMB_NC * LN_CHUNK) RK_LAUNCH(k_embed_ln_wide, dim3(T), dim3(256), 0, st, tokens, emb, w, b, x);
-    else RK_LAUNCH(k_embed_ln, dim3(T), dim3(256), 0, st, tokens, emb, w, b, x);
+    if (tokens.imm && T != 1) {
+        fprintf(stderr, "rwkv: a token id passed by value with %d tokens\n", T);
+        return false;
+    }
+    const EmbedLn a{tokens, emb, w, b, x};
+    tok_launch_note(a, offsetof(EmbedLn, tokens));
+    if (emb.K > EMB_NC * LN_CHUNK) RK_LAUNCH(k_embed_ln_wide, dim3(T), dim3(256), 0, st, a);
+    else RK_LAUNCH(k_embed_ln, dim3(T), dim3(256), 0, st, a);
     HIP_OK(hipGetLastError());
     return true;
 }

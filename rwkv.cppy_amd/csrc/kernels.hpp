@@ -20,8 +20,8 @@ extern int kQgCUs;
 bool launch_mvb_group(hipStream_t st, MMGroup & g, int wtype, bool * launched);
 
 // ---- elementwise / recurrence kernels -----------------------------------------------------
-// x[t] = LN(emb[tokens[t]]; w, b)   (rwkv_graph.inc:654-658)
-bool launch_embed_ln(hipStream_t st, const uint32_t * tokens, int T, const DMat & emb,
+// x[t] = LN(emb[tokens[t]]; w, b)   (rwkv_graph.inc:654-658); tokens.imm needs T == 1
+bool launch_embed_ln(hipStream_t st, const TokArg & tokens, int T, const DMat & emb,
                      const float * w, const float * b, float * x);
 
 struct LnMixArgs {
@@ -350,9 +350,9 @@ struct MaaDec {
     const float * maa[5];       // time_maa_{w,k,v,r,g} [C]
     ActBuf out[5];
     int xa_off;                 // LDS byte offset of the fp32 xa image
-    // layer 0 of a decode (k_v6_maa_dec4 only): x = LN0(emb[*tok]) computed in the launch (k_embed_ln's
-    // arithmetic) instead of read from x; workgroup (0, 0) stores it to xout
-    const uint32_t * tok;
+    // layer 0 of a decode (k_v6_maa_dec4 only): x = LN0(emb[tok]) computed in the launch (k_embed_ln's
+    // arithmetic) instead of read from x; workgroup (0, 0) stores it to xout (tok.ptr == null: off)
+    TokArg tok;
     DMat emb;
     const float * ln0w, * ln0b;
     float * xout;
@@ -451,8 +451,9 @@ struct V4WoFused {
     float * xres;
     unsigned long long * ygran;
     Handoff h;
-    // layer 0 of a decode: x = LN0(emb[*tok]) computed in the launch (k_embed_ln's arithmetic)
-    const uint32_t * tok;
+    // layer 0 of a decode: x = LN0(emb[tok]) computed in the launch (k_embed_ln's arithmetic;
+    // tok.ptr == null: off)
+    TokArg tok;
     DMat emb;
     const float * ln0w, * ln0b;
 };

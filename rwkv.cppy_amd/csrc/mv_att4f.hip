@@ -44,10 +44,10 @@ struct Att4Fused {
     float * xres;
     unsigned long long * ygran;
     Handoff h;
-    // EMB (layer 0, Wo fused): x = LN0(emb[*tok]) -- the producers' image waves normalise the
+    // EMB (layer 0, Wo fused): x = LN0(emb[tok]) -- the producers' image waves normalise the
     // embedding row (k_embed_ln's loads, chunk sums in chunk order, ln_apply: the same bits) through
     // one more barrier, and each Wo wave computes its rows' x itself; the Wo rows store x + Wo . y
-    const uint32_t * tok;
+    TokArg tok;
     DMat emb;
     const float * ln0w, * ln0b;
 };
@@ -94,7 +94,7 @@ __global__ __launch_bounds__(512) void k_v4_att_fused(Att4Fused a) {
             float xr;
             if constexpr (EMB) {
                 // this layer's input x = LN0(emb[token]): the row's statistics in this wave's registers
-                const size_t tk = *a.tok;
+                const size_t tk = tok_get(a.tok);
                 const int nc = (C + LN_CHUNK - 1) / LN_CHUNK;
                 float ev[4][8];
 #pragma unroll
@@ -193,7 +193,8 @@ __global__ __launch_bounds__(512) void k_v4_att_fused(Att4Fused a) {
         if constexpr (EMB) {
             // x = LN0(emb[token]) for this wave's chunk (k_embed_ln's arithmetic)
             __shared__ double e_part[2][8];
-            const size_t tk = *a.tok;
+            const size_t tk = tok_get(a.tok);
+            if (blockIdx.x == 0 && pw == 0 && lane == 0) tok_keep(a.tok);
             float w0[8], b0[8];
             ln_load8(w0, a.ln0w, kc, K);
             ln_load8(b0, a.ln0b, kc, K);
@@ -326,7 +327,7 @@ static void launch_att4_t(hipStream_t st, const Att4Fused & a, int units) {
     if (a.wo.qs) {
         // the producers, then the Wo workgroups (16 rows each)
         const dim3 grid(a.C / 8 + (a.C + 8 * A4_WOR - 1) / (8 * A4_WOR));
-        if (a.tok) {
+        if (a.tok.ptr) {
             if (units <= 1) RK_LAUNCH((k_v4_att_fused<WF, 1, 8, true, true>), grid, dim3(512), lds, st, a);
             else RK_LAUNCH((k_v4_att_fused<WF, 2, 8, true, true>), grid, dim3(512), lds, st, a);
             return;
@@ -377,7 +378,7 @@ bool launch_v4_att_fused(hipStream_t st, int C, const DMat & Wr, const DMat & Wk
         a.xres = wf->xres;
         a.ygran = wf->ygran;
         a.h = wf->h;
-        if (wf->tok) {
+        if (wf->tok.ptr) {
             if ((wf->emb.type != W_F16 && wf->emb.type != W_F32) || (int)wf->emb.K != C || !wf->ln0w || !wf->ln0b) {
                 fprintf(stderr, "rwkv: fused v4 attention with the embedding: unsupported embedding\n");
                 return false;
@@ -390,6 +391,7 @@ bool launch_v4_att_fused(hipStream_t st, int C, const DMat & Wr, const DMat & Wk
     }
     a.img = (lds_bytes_for(act_fmt_for(Wr.type), C) + 15) & ~15;
     const int units = mv_units(Wr.type, C);
+    if (a.tok.ptr) tok_launch_note(a, offsetof(Att4Fused, tok));
     switch (Wr.type) {
         case W_F32: launch_att4_t<W_F32>(st, a, units); break;
         case W_F16: launch_att4_t<W_F16>(st, a, units); break;

@@ -253,7 +253,7 @@ void v6_maa_dec_args(MaaDec & a, int C, int D, const DMat & w1, const float * x,
 // layer 0 with the embedding LayerNorm inside (MaaDec::tok): the k_v6_maa_dec4 shapes, an F16 / F32
 // embedding of row length C
 bool v6_maa_emb_supported(const MaaDec & a) {
-    return a.tok && a.xout && a.ln0w && a.ln0b && (a.emb.type == W_F16 || a.emb.type == W_F32) &&
+    return a.tok.ptr && a.xout && a.ln0w && a.ln0b && (a.emb.type == W_F16 || a.emb.type == W_F32) &&
            (int)a.emb.K == a.C && a.D <= 32 && v6_maa_dec_supported(a.C, a.D, a.w1.type) &&
            wtype_quantized(a.w1.type) && (int)a.w1.M == 5 * a.D && (int)a.w1.K == a.C;
 }
@@ -277,6 +277,7 @@ bool launch_v6_maa_dec_emb(hipStream_t st, const MaaDec & a) {
     }
     const int lds = a.xa_off + a.C * 4;
     const bool u1 = mv_units(a.w1.type, a.C) <= 1;
+    tok_launch_note(a, offsetof(MaaDec, tok));
     switch (a.w1.type) {
         case W_Q4_0: launch_maa_emb_t<W_Q4_0>(st, a, lds, u1); break;
         case W_Q4_1: launch_maa_emb_t<W_Q4_1>(st, a, lds, u1); break;

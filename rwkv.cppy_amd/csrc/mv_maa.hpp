@@ -12,7 +12,7 @@
 //
 // XG: the residual stream x is read from tagged granules (xg, tag h.tag; handoff.hpp) written in the
 // same launch, each re-read until its tag matches, instead of from a.x.
-// EMB (layer 0): x = LN0(emb[*a.tok]) -- k_embed_ln's loads, chunk sums in chunk order and ln_apply,
+// EMB (layer 0): x = LN0(emb[a.tok]) -- k_embed_ln's loads, chunk sums in chunk order and ln_apply,
 // so the same bits -- exchanged through one more barrier; workgroup (0, 0) stores it to a.xout.
 #pragma once
 #include "mv_common.hpp"
@@ -48,7 +48,10 @@ __device__ __forceinline__ void maa_dec4_body(const MaaDec & a, int bx, int n, c
         }
         if constexpr (EMB) {
             __shared__ double e_part[2][8];
-            const size_t tk = *a.tok;
+            // the id: a scalar of the argument block (TokArg::imm), else loaded; the row's loads go
+            // out with the LN0 vectors'
+            const size_t tk = tok_get(a.tok);
+            if (bx == 0 && n == 0 && pw == 0 && lane == 0) tok_keep(a.tok);
             float w0[LCW][8], b0[LCW][8];
 #pragma unroll
             for (int q = 0; q < LCW; q++) {
