@@ -41,7 +41,7 @@ __host__ __device__ inline int act_fmt_for(int wtype) {
     }
 }
 
-inline bool wtype_quantized(int t) { return t == W_Q4_0 || t == W_Q4_1 || t == W_Q5_0 || t == W_Q5_1 || t == W_Q8_0; }
+constexpr bool wtype_quantized(int t) { return t == W_Q4_0 || t == W_Q4_1 || t == W_Q5_0 || t == W_Q5_1 || t == W_Q8_0; }
 
 // Activation buffer: T rows of K elements in one format.
 struct ActBuf {

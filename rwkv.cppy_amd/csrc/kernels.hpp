@@ -181,12 +181,7 @@ struct MVGroup {
     int grid;                // set by launch_mv_group: workgroups launched
     int units_max;           // set by launch_mv_group: max 16-byte units per lane over entries
     int rows;                // set by launch_mv_group: rows per wave of the launched shape
-    int late;                // set by launch_mv_group: weights issued after the image inputs land
 };
-
-// Prologue matvecs: RWKV_MI355X_LATE_W=1 makes the streaming waves issue their weights only after
-// the image waves' inputs have landed (default 0: measured slower in the split form).
-int mv_late_weights();
 
 // Busy-waits about `us` microseconds on the device (kernel timing: lets the host queue a whole
 // decode step before the GPU starts it, so event pairs time kernels, not host submission).
@@ -317,7 +312,6 @@ bool launch_xent(hipStream_t st, const float * logits, int rows, int V, const ui
                  uint32_t * argmax);
 
 bool launch_mv_group(hipStream_t st, MVGroup & g);
-int mva_rows();
 
 // Decode channel mix (v4/v5/v6): y[row] += sigmoid(Wr[row] . xr) * (Wv[row] . k) in one launch
 // (mv_sig.hip, k_mvsig): ev = the value matvec (SRC_ACT, y = the residual stream), er = the

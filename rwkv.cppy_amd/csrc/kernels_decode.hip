@@ -22,10 +22,6 @@ extern template bool launch_mv_shape<W_Q8_0>(hipStream_t, MVGroup &, int, int, i
 
 static int g_mv_cus = 256;
 
-// Rows per wave of k_mva: 2.  More rows per wave put more weight loads in flight per lane behind
-// fewer workgroups; measured on the v6-1B6 decode chain (128 tokens): 2 rows 853 us/token, 4 rows
-// 883, 8 rows 876 -- the launch stays latency bound and two rows keep the most waves issuing.
-int mva_rows() { return 2; }
 extern int kQgCUs;
 void set_mv_device_cus(int n) {
     g_mv_cus = n > 0 ? n : 256;
@@ -33,7 +29,6 @@ void set_mv_device_cus(int n) {
 }
 
 bool launch_mv_group(hipStream_t st, MVGroup & g) {
-    g.late = 0;  // weight streams start with the image inputs (holding them: v6-1B6 686 vs 678 us/token)
     bool emit = false;
     for (int i = 0; i < g.n; i++) emit |= g.e[i].emit != 0;
     const int src = g.e[0].src, form = g.e[0].form;
@@ -53,7 +48,7 @@ bool launch_mv_group(hipStream_t st, MVGroup & g) {
         return false;
     }
     // rows per wave: 8 when emitting (a 32-row block per workgroup), else 2; the lean
-    // activation-input kernel k_mva (one weight type, <= 4 units per lane) takes mva_rows()
+    // activation-input kernel k_mva (one weight type, <= 4 units per lane) takes MVA_ROWS
     int wfix = g.e[0].W.type;
     for (int i = 1; i < g.n; i++)
         if (g.e[i].W.type != wfix) wfix = -1;
@@ -63,21 +58,19 @@ bool launch_mv_group(hipStream_t st, MVGroup & g) {
     // LayerNorm-prologue groups (not emitting) with more than two workgroups per CU at 2 rows per
     // wave (v7 r,k,v: 960; v5 r,k,v,g: 2048) take 4 rows per wave: one round of workgroups fewer
     // (v7-2.9B decode 469 -> 490 tok/s alone, with U = 1 above 513; v5-7B 517 -> 573)
-    constexpr int ln_r4 = 1;
     int rows2 = 0;
     for (int i = 0; i < g.n; i++) rows2 += (g.e[i].W.M + 7) / 8;
-    const bool r4 = ln_r4 && prologue && !emit && srck == MVK_LN && (g.n > 1 || rows2 <= 8 * g_mv_cus) &&
+    const bool r4 = prologue && !emit && srck == MVK_LN && (g.n > 1 || rows2 <= 8 * g_mv_cus) &&
                     rows2 > 2 * g_mv_cus;
     // ... and 8 rows per wave when even 4 leave more than four workgroups per CU (K > 2048, two units
     // per lane: v5-7B r,k,v,g, 1024 -> 512 workgroups; decode 1557 -> 1535 us/token, bit-exact; v7's
     // r,k,v at 480 workgroups measured neutral and stays at 4).  That shape takes its two units in two
     // round trips (U = 1, launch_mv_shape): at U = 2 it held 153 VGPRs, one workgroup per CU, and its
     // 512 workgroups ran in two rounds (v5-7B decode 1525-1528 -> 1485-1487 us/token)
-    constexpr int ln_r8 = 1;
     int lnk = 0;
     for (int i = 0; i < g.n; i++) lnk = std::max(lnk, g.e[i].W.K);
-    const bool r8 = ln_r8 && r4 && lnk > 2048 && umax0 == 2 && rows2 > 4 * g_mv_cus;
-    const int R = emit ? 8 : mva ? mva_rows() : r8 ? 8 : r4 ? 4 : 2, RW = 4 * R;
+    const bool r8 = r4 && lnk > 2048 && umax0 == 2 && rows2 > 4 * g_mv_cus;
+    const int R = emit ? 8 : mva ? MVA_ROWS : r8 ? 8 : r4 ? 4 : 2, RW = 4 * R;
     g.rows = R;
     int blocks = 0, umax = 1, lds = 0;
     for (int i = 0; i < g.n; i++) {
@@ -138,15 +131,12 @@ bool launch_mv_group(hipStream_t st, MVGroup & g) {
     // emitting LayerNorm groups at U = 2 hold 16 weight units per wave (184 VGPRs: one workgroup
     // per CU); with more row blocks than CUs, U = 1 (two round trips, 122 VGPRs, two per CU):
     // v7-2.9B FFN key, 320 workgroups -- decode 469 -> 489 tok/s alone
-    constexpr int emit_u1 = 1;
-    if (emit_u1 && emit && U == 2 && blocks > g_mv_cus) U = 1;
+    if (emit && U == 2 && blocks > g_mv_cus) U = 1;
     // activation-input rows of 5..8 quantized units per lane (v7-2.9B FFN value, K = 10240): all
     // units in one round of loads instead of 4 + the rest
-    constexpr int act_u8 = 1;
-    if (act_u8 && srck == MVK_ACT && !mva && umax > 4 && umax <= 8 && wfix >= 0 && wtype_quantized(wfix)) U = 8;
+    if (srck == MVK_ACT && !mva && umax > 4 && umax <= 8 && wfix >= 0 && wtype_quantized(wfix)) U = 8;
     // F16 LayerNorm groups of 5-8 units per lane (v7-2.9B LoRA first stages, K = 2560): one round
-    constexpr int f16_u8 = 1;
-    if (f16_u8 && srck == MVK_LN && !emit && wfix == W_F16 && R == 2 && umax > 4 && umax <= 8 && lnk > 2048) U = 8;
+    if (srck == MVK_LN && !emit && wfix == W_F16 && R == 2 && umax > 4 && umax <= 8 && lnk > 2048) U = 8;
     bool ok = false;
     switch (wfix) {
         case W_F16: ok = launch_mv_shape<W_F16>(st, g, U, srck, form, emit, dim3(grid)); break;

@@ -5,8 +5,8 @@
 // launch that waits at the kernel boundary for every row although channel c only needs r[c],
 // k[c], v[c]).  WKV-4 is per channel, so workgroup b takes channels [32 b, 32 b + 32): it builds
 // the three token-shifted LayerNorm images itself (the k_mv prologue, once per workgroup), dots
-// its 32 rows of each matrix (8 waves x 4 rows x 3 matrices, exactly k_mv's lane/unit order,
-// wave_sum63 tree and epilogues, so r, k, v are bit-identical), runs k_wkv4's per-channel
+// its 32 rows of each matrix (8 waves x 4 rows x 3 matrices, the row block of mv_common.hpp with
+// k_mv's epilogues, so r, k, v are bit-identical), runs k_wkv4's per-channel
 // arithmetic and emits the 32 outputs -- one quantization block of Wo's input -- with no
 // hand-off between workgroups at all.  Small models are launch-bound (v4-169M: 12 layers at
 // C = 768), so this removes one dependent launch per layer.
@@ -86,11 +86,10 @@ __global__ __launch_bounds__(512) void k_v4_att_fused(Att4Fused a) {
             // their first U units loaded now; every wave gathers y once the producers publish it
             STAMP_BEGIN();
             const int row0 = (((int)blockIdx.x - C / CPW) * 8 + wave) * A4_WOR;
+            int rows[A4_WOR];
+            clamp_rows(rows, row0, C);
             WBlk wo[A4_WOR][U];
-#pragma unroll
-            for (int u = 0; u < U; u++)
-#pragma unroll
-                for (int r = 0; r < A4_WOR; r++) wo[r][u] = load_unit<WF>(a.wo, min(row0 + r, C - 1), u, lane);
+            load_rows<WF, A4_WOR, U>(a.wo, rows, 0, lane, wo);
             float xr;
             if constexpr (EMB) {
                 // this layer's input x = LN0(emb[token]): the row's statistics in this wave's registers
@@ -119,13 +118,10 @@ __global__ __launch_bounds__(512) void k_v4_att_fused(Att4Fused a) {
             float acc[A4_WOR], acc2[A4_WOR];
 #pragma unroll
             for (int r = 0; r < A4_WOR; r++) acc[r] = acc2[r] = 0.0f;
+            // (the round form with each activation unit loaded right before its dots: not
+            // dot_rows_rounds' load order, so written out)
             for (int u0 = 0; u0 < units; u0 += U) {
-                if (u0 > 0) {
-#pragma unroll
-                    for (int u = 0; u < U; u++)
-#pragma unroll
-                        for (int r = 0; r < A4_WOR; r++) wo[r][u] = load_unit<WF>(a.wo, min(row0 + r, C - 1), u0 + u, lane);
-                }
+                if (u0 > 0) load_rows<WF, A4_WOR, U>(a.wo, rows, u0, lane, wo);
 #pragma unroll
                 for (int u = 0; u < U; u++) {
                     const AUnit xu = load_act_unit<WF, true>(xq, u0 + u, lane);
@@ -168,14 +164,12 @@ __global__ __launch_bounds__(512) void k_v4_att_fused(Att4Fused a) {
     ld8_buf(mv, a.mix[2], kc, pro);
     asm volatile("" ::"s"(a.W[0].qs), "s"(a.W[1].qs), "s"(a.W[2].qs));
     asm volatile("s_barrier" ::: "memory");  // image inputs issued ahead of the weight stream
-    // ---- rows c0 + 4 wave + r of r, k, v (all waves)
+    // ---- rows c0 + R wave + r of r, k, v (all waves)
+    int rows[R];
+    clamp_rows(rows, c0 + R * wave, C);
     WBlk w[3][R][U];
 #pragma unroll
-    for (int m = 0; m < 3; m++)
-#pragma unroll
-        for (int u = 0; u < U; u++)
-#pragma unroll
-            for (int r = 0; r < R; r++) w[m][r][u] = load_unit<WF>(a.W[m], min(c0 + R * wave + r, C - 1), u, lane);
+    for (int m = 0; m < 3; m++) load_rows<WF, R, U>(a.W[m], rows, 0, lane, w[m]);
     // the recurrence's operands (wave 0, lane = channel)
     float aa = 0.0f, bb = 0.0f, pp = 0.0f, fi = 0.0f, de = 0.0f;
     if (wave == 0 && lane < CPW) {
@@ -249,26 +243,7 @@ __global__ __launch_bounds__(512) void k_v4_att_fused(Att4Fused a) {
 #pragma unroll
     for (int m = 0; m < 3; m++) {
         float acc[R], acc2[R];
-#pragma unroll
-        for (int r = 0; r < R; r++) acc[r] = acc2[r] = 0.0f;
-        for (int u0 = 0; u0 < units; u0 += U) {
-            if (u0 > 0) {
-#pragma unroll
-                for (int u = 0; u < U; u++)
-#pragma unroll
-                    for (int r = 0; r < R; r++) w[m][r][u] = load_unit<WF>(a.W[m], min(c0 + R * wave + r, C - 1), u0 + u, lane);
-            }
-            AUnit xu[U];
-#pragma unroll
-            for (int u = 0; u < U; u++) xu[u] = load_act_unit<WF, true>(img[m], u0 + u, lane);
-#pragma unroll
-            for (int u = 0; u < U; u++) {
-                if (unit_valid<WF>(K, u0 + u, lane)) {
-#pragma unroll
-                    for (int r = 0; r < R; r++) dot_unit<WF>(w[m][r][u], xu[u], acc[r], acc2[r]);
-                }
-            }
-        }
+        dot_rows_rounds<WF, R, U, true>(a.W[m], rows, w[m], img[m], K, units, lane, acc, acc2);
         float s[R];
 #pragma unroll
         for (int r = 0; r < R; r++) s[r] = one ? wave_sum63(acc[r]) + wave_sum63(acc2[r]) : wave_sum63(acc[r]) + 0.0f;

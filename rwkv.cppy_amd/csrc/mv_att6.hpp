@@ -10,7 +10,9 @@ namespace rwkvmi {
 constexpr int AF_P = 8;   // workgroups per head
 constexpr int AF_R = 8;   // rows per wave (4 waves x 8 rows x 8 workgroups = 4 x 64 rows)
 
-// R rows of one matrix by one wave: k_mva's loads, dots, tree and epilogue (lane r: row r)
+// R rows of one matrix by one wave: k_mva's loads, dots, tree and epilogue (lane r: row r) -- the
+// row block of mv_common.hpp, select form, written out: with this site and maa_dec4_body through the
+// helpers v6-1B6 decode sat at the lower edge of the parent's spread (mv_maa.hpp has the figures)
 template <int WF, int R, int U>
 __device__ __forceinline__ float af_rows(const DMat & W, const ActBuf & x, int row0, int epi, int lane) {
     const int M = W.M, K = W.K;

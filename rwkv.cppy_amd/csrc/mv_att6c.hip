@@ -88,6 +88,7 @@ __global__ __launch_bounds__(320) void k_v6_att_co(Att6Fused a) {
         // ---- Wo (rwkv_graph.inc:382-384, x += Wo . y) on the 7 H non-reducer workgroups: wave
         // gw owns rows gw, gw + 28 H, gw + 56 H (k_mva's per-row arithmetic does not depend on
         // which wave computes a row).  Its units are loaded now, under the reducers' attention.
+        // (Strided rows: the row block of mv_common.hpp written out, measured with af_rows.)
         const int nwo = 28 * H, gw = ((sidx - 1) * H + h) * 4 + wave;
         WBlk wo[AF_WOR][U];
         float xr = 0.0f;

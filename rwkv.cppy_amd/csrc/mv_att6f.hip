@@ -64,10 +64,9 @@ __global__ __launch_bounds__(320) void k_v6_att_fused(Att6Fused a) {
             WBlk wo[AF_WOR][U];
             float xr = 0.0f;
             if (wave < 4) {
-#pragma unroll
-                for (int u = 0; u < U; u++)
-#pragma unroll
-                    for (int r = 0; r < AF_WOR; r++) wo[r][u] = load_unit<WF>(a.wo, min(row0 + r, C - 1), u, lane);
+                int rows[AF_WOR];
+                clamp_rows(rows, row0, C);
+                load_rows<WF, AF_WOR, U>(a.wo, rows, 0, lane, wo);
                 xr = a.xres[min(row0 + min(lane, AF_WOR - 1), C - 1)];
             }
             // y arrives as Q8 blocks (pub_q8 in the reducers: the bits Wo's fp32-input prologue

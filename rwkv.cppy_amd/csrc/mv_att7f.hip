@@ -14,18 +14,6 @@
 
 namespace rwkvmi {
 
-// R rows of one matrix by one wave in k_mva's lane/unit order: the weight units first (issued at
-// kernel start, before the inputs exist), then the dots and wave_sum63's tree; lane r returns row
-// r's sum (wave_sum63(acc) + 0.0f, the non-_1 formats' form)
-template <int WF, int R, int U>
-__device__ __forceinline__ void a7_load(const DMat & W, int row0, int lane, WBlk (&w)[R][U]) {
-    const int M = W.M;
-#pragma unroll
-    for (int u = 0; u < U; u++)
-#pragma unroll
-        for (int r = 0; r < R; r++) w[r][u] = load_unit<WF>(W, min(row0 + r, M - 1), u, lane);
-}
-
 // The input unit of lane l in the weights' input format, converted in registers from the fp32
 // LoRA first-stage vector exactly as the matvec prologue converts it into LDS (chunk_store: fp16
 // halves by to_half, or fp32 as is) and read back (load_act_unit: units clamped to K - EL)
@@ -50,21 +38,13 @@ __device__ __forceinline__ void a7_input(const float * x, int K, int lane, AUnit
     }
 }
 
+// R rows of one matrix by one wave, k_mva's row block (select form): the weight units first
+// (load_rows, issued at kernel start, before the inputs exist), then the dots and wave_sum63's
+// tree; lane r returns row r's sum (wave_sum63(acc) + 0.0f, the non-_1 formats' form)
 template <int WF, int R, int U>
 __device__ __forceinline__ float a7_dots(const WBlk (&w)[R][U], int K, const AUnit (&xu)[U], int lane) {
     float acc[R], acc2[R];
-#pragma unroll
-    for (int r = 0; r < R; r++) acc[r] = acc2[r] = 0.0f;
-#pragma unroll
-    for (int u = 0; u < U; u++) {
-        const bool valid = unit_valid<WF>(K, u, lane);
-#pragma unroll
-        for (int r = 0; r < R; r++) {
-            float t = acc[r], t2 = acc2[r];
-            dot_unit<WF>(w[r][u], xu[u], t, t2);
-            acc[r] = valid ? t : acc[r];
-        }
-    }
+    dot_rows<WF, R, U>(w, xu, K, lane, acc, acc2);
     float sr[R];
 #pragma unroll
     for (int r = 0; r < R; r++) sr[r] = wave_sum63(acc[r]) + 0.0f;
@@ -89,7 +69,9 @@ __global__ __launch_bounds__(1024) void k_att7_lora(Att7Lora a) {
     WBlk lw[16][U];
     AUnit lx[U];
     if (lon) {
-        a7_load<WF, 16, U>(LW, lrow0, lane, lw);
+        int rows[16];
+        clamp_rows(rows, lrow0, LW.M);
+        load_rows<WF, 16, U>(LW, rows, 0, lane, lw);
         a7_input<WF, U>(lm == 0 ? a.lin[0] : lm == 1 ? a.lin[1] : lm == 2 ? a.lin[2] : a.lin[3], LW.K, lane, lx);
     }
     // per-channel operands and the state rows first (they stream in under the LoRA rows)

@@ -63,9 +63,9 @@ __host__ __device__ inline int lds_bytes_for(int fmt, int K) {
 // A lane owns 16-byte "units" of a row: quantized weights one 32-block (lane + 64u), F16 eight
 // halves (k = 8*lane + 512u), F32 four floats (k = 4*lane + 256u) -- the same lane/unit
 // assignment and accumulation order as the batched kernel k_mm, so decode and sequence
-// results are bit-identical.  All R*U weight units of a wave are loaded before anything else
-// waits (rows past M clamp to M-1, units past K clamp to the last unit and are skipped in the
-// dot), so the whole row-block is one HBM round trip, overlapped with the prologue.
+// results are bit-identical (the contract: "the row block" below).  All R*U weight units of a
+// wave are loaded before anything else waits, so the whole row-block is one HBM round trip,
+// overlapped with the prologue.
 
 __host__ __device__ inline int mv_units(int type, int K) {
     if (type == W_F32) return (K + 255) / 256;
@@ -167,6 +167,84 @@ __device__ __forceinline__ void dot_unit(const WBlk & w, const AUnit & x, float 
         const int sumi = dot_wblk<WF>(w, x.lo, x.hi, x.qs, dw, mw);
         acc = fmaf(dw * x.d, (float)sumi, acc);
         if constexpr (WF == W_Q4_1 || WF == W_Q5_1) acc2 = fmaf(mw, x.s, acc2);  // m * s exact (fp16 x fp16): = acc2 + m * s
+    }
+}
+
+// ---- the row block: R rows x U units per lane of one wave.
+// The association contract of every decode matvec (with k_mm and the oracle; results are
+// bit-identical only while all of these hold), kept here and nowhere else:
+//  - lane l owns units l, l + 64, ... of a row (load_unit / load_act_unit above), unit u of the
+//    weights against unit u of the activations;
+//  - a lane accumulates its units in ascending u into acc (and acc2, the _1 formats' m * s sums),
+//    one fma chain per row from +0; the 64 lanes are then folded by wave_sum63's tree (row_sums, or
+//    wave_sum63 + lane_row_sum: the same bits);
+//  - rows past the last row clamp to it (their sums are computed and never stored), units past K
+//    clamp to the last unit in the loads and are skipped in the dot (unit_valid).
+// Two forms of the dot.  Select form: all units of the rows are in registers (one round), the dot
+// is branch-free, an invalid unit keeps the old sum.  Round form: mv_units(WF, K) may exceed U, so
+// the units go in rounds of U -- the first round's weights already loaded by the caller (ahead of
+// whatever it waits for), later rounds reloaded here -- and invalid units are branched over.
+template <int R>
+__device__ __forceinline__ void clamp_rows(int (&rows)[R], int row0, int M) {
+#pragma unroll
+    for (int r = 0; r < R; r++) rows[r] = min(row0 + r, M - 1);
+}
+
+// units u0 .. u0 + U - 1 of the R rows, all issued before anything waits (clamped: no branches)
+template <int WF, int R, int U, bool NT = true>
+__device__ __forceinline__ void load_rows(const DMat & W, const int (&rows)[R], int u0, int lane, WBlk (&w)[R][U]) {
+#pragma unroll
+    for (int u = 0; u < U; u++)
+#pragma unroll
+        for (int r = 0; r < R; r++) w[r][u] = load_unit<WF, NT>(W, rows[r], u0 + u, lane);
+}
+
+// select form; xu(u) yields activation unit u (called once per unit, right before its dots)
+template <int WF, int R, int U, class XU>
+__device__ __forceinline__ void dot_rows_with(const WBlk (&w)[R][U], int K, int lane, float (&acc)[R], float (&acc2)[R],
+                                              XU && xu) {
+#pragma unroll
+    for (int r = 0; r < R; r++) acc[r] = acc2[r] = 0.0f;
+#pragma unroll
+    for (int u = 0; u < U; u++) {
+        const AUnit x = xu(u);
+        const bool valid = unit_valid<WF>(K, u, lane);
+#pragma unroll
+        for (int r = 0; r < R; r++) {
+            float t = acc[r], t2 = acc2[r];
+            dot_unit<WF>(w[r][u], x, t, t2);
+            acc[r] = valid ? t : acc[r];
+            acc2[r] = valid ? t2 : acc2[r];
+        }
+    }
+}
+// ... with the activation units already in registers
+template <int WF, int R, int U>
+__device__ __forceinline__ void dot_rows(const WBlk (&w)[R][U], const AUnit (&x)[U], int K, int lane, float (&acc)[R],
+                                         float (&acc2)[R]) {
+    dot_rows_with<WF, R, U>(w, K, lane, acc, acc2, [&](int u) { return x[u]; });
+}
+// (... with each unit read from an LDS activation image: rows_dot_img below)
+
+// round form over units = mv_units(WF, K); LDS: the activation row a is an LDS image, NT: the
+// reloads' cache policy
+template <int WF, int R, int U, bool LDS, bool NT = true>
+__device__ __forceinline__ void dot_rows_rounds(const DMat & W, const int (&rows)[R], WBlk (&w)[R][U], const ActBuf & a,
+                                                int K, int units, int lane, float (&acc)[R], float (&acc2)[R]) {
+#pragma unroll
+    for (int r = 0; r < R; r++) acc[r] = acc2[r] = 0.0f;
+    for (int u0 = 0; u0 < units; u0 += U) {
+        if (u0 > 0) load_rows<WF, R, U, NT>(W, rows, u0, lane, w);
+        AUnit x[U];
+#pragma unroll
+        for (int u = 0; u < U; u++) x[u] = load_act_unit<WF, LDS>(a, u0 + u, lane);
+#pragma unroll
+        for (int u = 0; u < U; u++) {
+            if (unit_valid<WF>(K, u0 + u, lane)) {
+#pragma unroll
+                for (int r = 0; r < R; r++) dot_unit<WF>(w[r][u], x[u], acc[r], acc2[r]);
+            }
+        }
     }
 }
 
@@ -387,26 +465,12 @@ __device__ __forceinline__ float row_sums(const float (&acc)[R], const float (&a
     }
 }
 
-// R rows whose U units per lane are already in registers, dotted with an LDS activation image:
-// k_mva's per-row arithmetic (lane/unit order, wave_sum63 tree; the unit count mv_units(WF, K)
-// must be <= U).  Lane r < R returns row r's sum.
+// R rows whose U units per lane are already in registers, dotted with an LDS activation image
+// (select form: mv_units(WF, K) <= U).  Lane r < R returns row r's sum.
 template <int WF, int R, int U>
 __device__ __forceinline__ float rows_dot_img(const WBlk (&w)[R][U], const ActBuf & img, int K, int lane) {
     float acc[R], acc2[R];
-#pragma unroll
-    for (int r = 0; r < R; r++) acc[r] = acc2[r] = 0.0f;
-#pragma unroll
-    for (int u = 0; u < U; u++) {
-        const AUnit xu = load_act_unit<WF, true>(img, u, lane);
-        const bool uv = unit_valid<WF>(K, u, lane);
-#pragma unroll
-        for (int r = 0; r < R; r++) {
-            float t = acc[r], t2 = acc2[r];
-            dot_unit<WF>(w[r][u], xu, t, t2);
-            acc[r] = uv ? t : acc[r];
-            acc2[r] = uv ? t2 : acc2[r];
-        }
-    }
+    dot_rows_with<WF, R, U>(w, K, lane, acc, acc2, [&](int u) { return load_act_unit<WF, true>(img, u, lane); });
     return row_sums<WF, R>(acc, acc2, lane);
 }
 
@@ -480,26 +544,24 @@ __device__ __forceinline__ float decay_row_thread(const DMat & W, int row, const
     return one ? tree_wave32(p) + tree_wave32(p2) : tree_wave32(p) + 0.0f;
 }
 
-// One workgroup = NW waves (SRC_ACT) or 2 NW waves (prologue sources); RW rows per row block.
-// stride > 0: the workgroup walks row blocks wgi, wgi+stride, ... with one prologue.
-// Prologue sources (SRC_F32 / SRC_LNMIX): waves NW..2NW-1 build the activation image in LDS
-// (LayerNorm statistics, one 512-element chunk each, token shift, quantization); their input
-// loads go out first (issue-order barrier) and the streaming waves' weight loads right behind
-// them, then the streaming waves dot the block's rows once the image is ready.
-template <int WF, int R, int U, int SRCK, int FORM, bool EMIT, int NW, int LNP>
-__device__ __forceinline__ void mv_body(const MVEntry & Ent, int wgi, int b0, int stride, char * smem, float * red,
-                                        int late, unsigned long long * stamp_mid = nullptr,
+// The k_mv body of the groups without a LayerNorm: SRC_ACT (NW waves, the activation row read from
+// global memory) and SRC_F32 (2 NW waves; LayerNorm groups: mv_body_split below).  RW rows per row
+// block, R per wave.  stride > 0: the workgroup walks row blocks wgi, wgi+stride, ... with one
+// prologue.  Never emitting: an emitting group has a LayerNorm source (launch_mv_group).
+// SRC_F32: waves NW..2NW-1 build the activation image in LDS (one 512-element chunk each per pass,
+// quantization); their input loads go out first (issue-order barrier) and every wave's weight
+// loads right behind them -- the image waves carry rows too, so the per-wave dot and reduction
+// chains are half as long -- then all waves dot the block's rows once the image is ready.  (Keeping
+// these groups here and not in mv_body_split is measured: there k_mv<1, 1, MVK_F32, 0, false,
+// Q5_1, 0> takes 73 instead of 64 VGPRs, occupancy 6 instead of 8.)
+template <int WF, int R, int U, int SRCK, int FORM, bool EMIT, int NW>
+__device__ __forceinline__ void mv_body(const MVEntry & Ent, int wgi, int b0, int stride, char * smem,
+                                        unsigned long long * stamp_mid = nullptr,
                                         unsigned long long * stamp_x = nullptr) {
+    static_assert(SRCK != MVK_LN && !EMIT, "LayerNorm groups, emitting or not: mv_body_split");
     constexpr bool PRO = SRCK != MVK_ACT;
-    // LayerNorm chunks per prologue wave held in registers: LNP 32 -> K <= 2048, 64 -> K <= 4096
-    constexpr int LCW = LNP > 32 ? 2 : 1;
-    // Prologue groups with K <= 2048 (one LayerNorm chunk per image wave; larger K: mv_body_split):
-    // the rows of a block go over all 2 NW waves -- the image waves too, so the per-wave dot and
-    // reduction chains are half as long.
-    constexpr bool IMGR = PRO;
-    constexpr int NWT = (PRO && IMGR) ? 2 * NW : NW;  // waves with rows
-    constexpr int RR = (PRO && !IMGR) ? 2 * R : R;    // rows per wave with rows
-    constexpr int RW = NWT * RR;
+    constexpr int NWT = PRO ? 2 * NW : NW;  // waves (all with rows)
+    constexpr int RW = NWT * R;
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);  // wave-uniform branches
     const DMat & W = Ent.W;
     const int M = W.M, K = W.K;
@@ -510,81 +572,42 @@ __device__ __forceinline__ void mv_body(const MVEntry & Ent, int wgi, int b0, in
     // after the dots is a scalar-cache round trip on the kernel's critical path
     const int epi = Ent.epi;
     float * const ey = Ent.y;
-    ActBuf ao = Ent.act_out;
-    const bool emit_on = EMIT && Ent.emit && ao.fmt >= 0;
     asm volatile("" ::"s"(epi), "s"(ey));
-    if constexpr (EMIT) pin_act(ao);
     ActBuf a;
     const bool pro_wave = PRO && wave >= NW;
     const int pw = wave - NW, nch = (K + LN_CHUNK - 1) / LN_CHUNK;
-    const bool write_carry = PRO && Ent.carry_out && (int)blockIdx.x == b0;  // one writer per entry
-    ChunkIn ci[LCW];
-    int kc[LCW];
-    float mean = 0.0f, scale = 0.0f;
+    ChunkIn ci;
+    int kc = 0;
     if constexpr (PRO) {
         a = lds_act(smem, act_fmt_for(WF), K);
-        // the image waves' inputs: chunks pw, pw + NW (512 elements each, 8 per lane); issued
-        // by every wave without a branch (chunk_load_all: the dot waves' loads are empty)
-#pragma unroll
-        for (int q = 0; q < LCW; q++) {
-            kc[q] = (pw + q * NW) * LN_CHUNK + lane * 8;
-            chunk_load_all<SRCK, FORM>(Ent, max(min(kc[q], K - 8), 0), ci[q], pro_wave);
-        }
+        // the image waves' inputs: chunk pw (512 elements, 8 per lane); issued by every wave
+        // without a branch (chunk_load_all: the other waves' loads are empty)
+        kc = pw * LN_CHUNK + lane * 8;
+        chunk_load_all<SRCK, FORM>(Ent, max(min(kc, K - 8), 0), ci, pro_wave);
         // the weight pointers reach SGPRs before the issue-order barrier, so the stream starts
         // right after it (a kernarg scalar load behind the barrier is a round trip in the path)
         asm volatile("" ::"s"(W.qs), "s"(W.sc), "s"(W.qh));
         // issue order: the image inputs go out before any weight stream starts
         asm volatile("s_barrier" ::: "memory");
     }
-    // ---- this wave's weight units (HBM), all in flight before anything waits
-    const bool has_rows = !pro_wave || IMGR;
-    int row0 = wgi * RW + wave * RR;
-    int rows[RR];
-#pragma unroll
-    for (int r = 0; r < RR; r++) rows[r] = min(row0 + r, M - 1);
-    WBlk w[RR][U];
-    auto issue_w = [&]() {
-#pragma unroll
-        for (int u = 0; u < U; u++)
-#pragma unroll
-            for (int r = 0; r < RR; r++) w[r][u] = load_unit<WF>(W, rows[r], u, lane);
-    };
-    if (has_rows) issue_w();
+    // ---- this wave's weight units (HBM), all in flight before anything waits (the row block
+    // contract: above, at load_rows)
+    int row0 = wgi * RW + wave * R;
+    int rows[R];
+    clamp_rows(rows, row0, M);
+    WBlk w[R][U];
+    load_rows<WF, R, U>(W, rows, 0, lane, w);
     if constexpr (PRO) {
         if (pro_wave) {
-            if constexpr (SRCK == MVK_LN) {
-                // LayerNorm statistics in the chunk association (device_common.hpp, one pass): each
-                // image wave sums its chunks and their squares, the chunk sums meet in LDS (one
-                // barrier every wave joins)
-                __shared__ double ln_part[2][8];
-#pragma unroll
-                for (int q = 0; q < LCW; q++)
-                    if (pw + q * NW < nch) {
-                        double c1, c2;
-                        ln_chunk_sums(ci[q].x, kc[q] < K, c1, c2);
-                        if (lane == 0) {
-                            ln_part[0][pw + q * NW] = c1;
-                            ln_part[1][pw + q * NW] = c2;
-                        }
-                    }
-                asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-                double s1 = 0.0, s2 = 0.0;
-                for (int c = 0; c < nch; c++) s1 += ln_part[0][c], s2 += ln_part[1][c];
-                ln_finish(s1, s2, K, 1e-5f, mean, scale);
-            }
 #ifdef RWKV_STAMP
-            if (pw == 0 && stamp_x && lane == 0) stamp_x[1] = __builtin_amdgcn_s_memrealtime() + (scale == 1.2345f);
+            if (pw == 0 && stamp_x && lane == 0) stamp_x[1] = __builtin_amdgcn_s_memrealtime();
 #endif
-#pragma unroll
-            for (int q = 0; q < LCW; q++)
-                if (pw + q * NW < nch) chunk_store<WF, SRCK, FORM>(Ent, a, ci[q], mean, scale, false, kc[q], kc[q] < K, lane);
-            if constexpr (SRCK == MVK_F32) {
-                // plain fp32 input: any K, further chunks streamed
-                for (int c = pw + LCW * NW; c < nch; c += NW) {
-                    const int kk = c * LN_CHUNK + lane * 8;
-                    chunk_load<SRCK, FORM>(Ent, min(kk, K - 8), ci[0]);
-                    chunk_store<WF, SRCK, FORM>(Ent, a, ci[0], mean, scale, write_carry, kk, kk < K, lane);
-                }
+            if (pw < nch) chunk_store<WF, SRCK, FORM>(Ent, a, ci, 0.0f, 0.0f, false, kc, kc < K, lane);
+            // any K: further chunks streamed
+            for (int c = pw + NW; c < nch; c += NW) {
+                const int kk = c * LN_CHUNK + lane * 8;
+                chunk_load<SRCK, FORM>(Ent, min(kk, K - 8), ci);
+                chunk_store<WF, SRCK, FORM>(Ent, a, ci, 0.0f, 0.0f, false, kk, kk < K, lane);
             }
 #ifdef RWKV_STAMP
             if (pw == 0 && stamp_x) {
@@ -592,14 +615,10 @@ __device__ __forceinline__ void mv_body(const MVEntry & Ent, int wgi, int b0, in
                 if (lane == 0) stamp_x[2] = __builtin_amdgcn_s_memrealtime();
             }
 #endif
-        } else if constexpr (SRCK == MVK_LN) {
-            asm volatile("s_barrier" ::: "memory");  // the image waves' statistics exchange
         }
     }
-    // epilogue operands: !EMIT lane r < R runs row row0 + r's epilogue; EMIT thread tid < RW row tid
-    EpiIn ep;
-    if constexpr (!EMIT) ep = epi_load(Ent, min(row0 + min(lane, RR - 1), M - 1));
-    else ep = epi_load(Ent, min(wgi * RW + (tid < RW ? tid : 0), M - 1));
+    // epilogue operands: lane r < R runs row row0 + r's epilogue
+    EpiIn ep = epi_load(Ent, min(row0 + min(lane, R - 1), M - 1));
     if constexpr (PRO) __syncthreads();  // activation image ready
     else a = Ent.act;
     PROBE(1);
@@ -611,111 +630,35 @@ __device__ __forceinline__ void mv_body(const MVEntry & Ent, int wgi, int b0, in
 #endif
 
     for (;;) {
-        // dots (the waves with rows)
-        float s = 0.0f;  // lane r < RR: row r's sum
-        if (has_rows) {
-            float acc[RR], acc2[RR];
-#pragma unroll
-            for (int r = 0; r < RR; r++) acc[r] = acc2[r] = 0.0f;
-            for (int u0 = 0; u0 < units; u0 += U) {
-                if (u0 > 0) {
-#pragma unroll
-                    for (int u = 0; u < U; u++)
-#pragma unroll
-                        for (int r = 0; r < RR; r++) w[r][u] = load_unit<WF>(W, rows[r], u0 + u, lane);
-                }
-                AUnit x[U];
-#pragma unroll
-                for (int u = 0; u < U; u++) x[u] = load_act_unit<WF, PRO>(a, u0 + u, lane);
-#pragma unroll
-                for (int u = 0; u < U; u++) {
-                    if (unit_valid<WF>(K, u0 + u, lane)) {
-#pragma unroll
-                        for (int r = 0; r < RR; r++) dot_unit<WF>(w[r][u], x[u], acc[r], acc2[r]);
-                    }
-                }
-            }
-            // reduce
-            s = row_sums<WF, RR>(acc, acc2, lane);
-        }
-        if constexpr (!EMIT) {
+        float acc[R], acc2[R];
+        dot_rows_rounds<WF, R, U, PRO>(W, rows, w, a, K, units, lane, acc, acc2);
+        const float s = row_sums<WF, R>(acc, acc2, lane);  // lane r < R: row r's sum
 #ifdef MV_PROBE
-            if (s == 1.2345f) g_probe[0] = 0;  // orders the stamp after the dots
+        if (s == 1.2345f) g_probe[0] = 0;  // orders the stamp after the dots
 #endif
-            PROBE(2);
-            const float v = epi_apply(epi, s, ep);
-            if (has_rows && lane < RR && row0 + lane < M) ey[row0 + lane] = v;
-        } else {
-            // RW rows per block (a multiple of 32): apply the epilogue and emit each 32 rows as
-            // one quantization block of the next matmul's input (ggml Q8 / fp16 / fp32)
-            if (has_rows && lane < RR) red[wave * RR + lane] = s;
-#ifdef RWKV_STAMP
-            if (wave == 0 && stamp_x && lane == 0) stamp_x[3] = __builtin_amdgcn_s_memrealtime() + (s == 1.2345f);
-#endif
-            __syncthreads();
-            PROBE(2);
-            if (tid < RW) {
-                const int row = wgi * RW + tid;
-                float vv = 0.0f;
-                if (row < M) {
-                    vv = epi_apply(epi, red[tid], ep);
-                    if (ey) ey[row] = vv;
-                }
-                if (emit_on) emit32(ao, 0, row, vv);
-            }
-        }
+        PROBE(2);
+        const float v = epi_apply(epi, s, ep);
+        if (lane < R && row0 + lane < M) ey[row0 + lane] = v;
         PROBE(3);
         wgi += stride;
         if (stride <= 0 || wgi >= nblk) break;
-        if constexpr (EMIT) __syncthreads();  // red[] reuse
-        row0 = wgi * RW + wave * RR;
-#pragma unroll
-        for (int r = 0; r < RR; r++) rows[r] = min(row0 + r, M - 1);
-        if (has_rows) issue_w();
-        if constexpr (!EMIT) ep = epi_load(Ent, min(row0 + min(lane, RR - 1), M - 1));
-        else ep = epi_load(Ent, min(wgi * RW + (tid < RW ? tid : 0), M - 1));
-    }
-    if constexpr (SRCK == MVK_LN) {
-        // the carry (this LayerNorm output, the next token's shift input) after the rows: vmcnt
-        // counts loads and stores in one order, so a store ahead of the dots would make waits
-        // for earlier loads also wait for the weight stream behind it
-        if (pro_wave && write_carry) {
-#pragma unroll
-            for (int q = 0; q < LCW; q++)
-                if (pw + q * NW < nch && kc[q] < K) {
-                    float xa[8];
-#pragma unroll
-                    for (int j = 0; j < 8; j++) xa[j] = ln_apply(ci[q].x[j], mean, scale, ci[q].w[j], ci[q].b[j]);
-                    *(float4 *)(Ent.carry_out + kc[q]) = make_float4(xa[0], xa[1], xa[2], xa[3]);
-                    *(float4 *)(Ent.carry_out + kc[q] + 4) = make_float4(xa[4], xa[5], xa[6], xa[7]);
-                }
-        }
-    }
-    if constexpr (SRCK == MVK_LN && FORM != 2) {
-        // the entry's first workgroup, after its rows: the same LayerNorm output mixed with mu2
-        // into a global activation row (the channel-mix receptance input of k_mvsig).  (Spread
-        // block-interleaved over all workgroups instead: 704 vs 695 us/token -- every workgroup's
-        // image waves then pay the reload and quantization pass.)
-        if (pro_wave && Ent.mu2 && (int)blockIdx.x == b0) {
-            MVEntry E2 = Ent;
-            E2.mu = Ent.mu2;
-#pragma unroll
-            for (int q = 0; q < LCW; q++)
-                if (pw + q * NW < nch) {
-                    ld8(ci[q].m, Ent.mu2 + min(kc[q], K - 8));
-                    chunk_store<WF, SRCK, FORM>(E2, Ent.act2_out, ci[q], mean, scale, false, kc[q], kc[q] < K, lane);
-                }
-        }
+        row0 = wgi * RW + wave * R;
+        clamp_rows(rows, row0, M);
+        load_rows<WF, R, U>(W, rows, 0, lane, w);
+        ep = epi_load(Ent, min(row0 + min(lane, R - 1), M - 1));
     }
 }
 
-// Prologue groups with K > 2048: the image waves hold two LayerNorm chunks of inputs, so they stay
+// The k_mv body of the LayerNorm groups (SRC_LNMIX, any K <= 4096): the image waves hold one or two
+// LayerNorm chunks of inputs (LNP 32: K <= 2048, 64: K <= 4096 elements per lane group) and stay
 // rowless (the NW streaming waves take 2 R rows each), and the two roles run as separate straight
 // paths that meet only at barriers.  With both roles in one path the compiler keeps the streaming
 // waves' weight registers live through the image waves' statistics (it cannot tell the two wave
 // conditions apart), the kernel needs 145-235 VGPRs -- one workgroup per CU -- and the multi-round
-// LayerNorm groups of the 2.9B / 7B models ran 10-14 % slower.  Same arithmetic and association as
-// mv_body (bit-identical); the barrier sequence of both paths matches one for one.
+// LayerNorm groups of the 2.9B / 7B models ran 10-14 % slower; K <= 2048 too is faster this way than
+// with the image waves carrying rows (v6-1B6 decode 686-692 vs 696-698 us per token, v4-169M 244 vs
+// 251).  The row block contract: at load_rows; the barrier sequence of both paths matches one for one.
+//
 // Outputs of a producer group handed to consumers in the same launch (mv_ffnf.hpp): an emitting
 // entry publishes each 32-row Q8 block as KG_STRIDE granules {tag, dword} -- the block's 32 int8 (4
 // per granule), its fp16-rounded d and Q8_1's fp16-rounded d * sum (the qsum is an exact integer sum
@@ -741,7 +684,8 @@ __device__ __forceinline__ void pub_q8(unsigned long long * kg, int b, float v, 
 
 template <int WF, int R, int U, int SRCK, int FORM, bool EMIT, int NW, int LNP, bool PUB = false>
 __device__ __forceinline__ void mv_body_split(const MVEntry & Ent, int wgi, int b0, int stride, char * smem,
-                                              float * red, int late, const GranPub * pub = nullptr) {
+                                              float * red, const GranPub * pub = nullptr) {
+    static_assert(SRCK == MVK_LN, "the other sources: mv_body");
     constexpr int LCW = LNP > 32 ? 2 : 1;
     constexpr int RR = 2 * R, RW = NW * RR;
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -763,34 +707,28 @@ __device__ __forceinline__ void mv_body_split(const MVEntry & Ent, int wgi, int 
             chunk_load<SRCK, FORM>(Ent, min(kc[q], K - 8), ci[q]);
         }
         asm volatile("s_barrier" ::: "memory");  // issue order: the image inputs ahead of the weights
-        float mean = 0.0f, scale = 0.0f;
-        if constexpr (SRCK == MVK_LN) {
-            __shared__ double ln_part[2][8];
+        // LayerNorm statistics in the chunk association (device_common.hpp, one pass): each image
+        // wave sums its chunks and their squares, the chunk sums meet in LDS (one barrier every
+        // wave joins)
+        __shared__ double ln_part[2][8];
 #pragma unroll
-            for (int q = 0; q < LCW; q++)
-                if (pw + q * NW < nch) {
-                    double c1, c2;
-                    ln_chunk_sums(ci[q].x, kc[q] < K, c1, c2);
-                    if (lane == 0) {
-                        ln_part[0][pw + q * NW] = c1;
-                        ln_part[1][pw + q * NW] = c2;
-                    }
+        for (int q = 0; q < LCW; q++)
+            if (pw + q * NW < nch) {
+                double c1, c2;
+                ln_chunk_sums(ci[q].x, kc[q] < K, c1, c2);
+                if (lane == 0) {
+                    ln_part[0][pw + q * NW] = c1;
+                    ln_part[1][pw + q * NW] = c2;
                 }
-            asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-            double s1 = 0.0, s2 = 0.0;
-            for (int c = 0; c < nch; c++) s1 += ln_part[0][c], s2 += ln_part[1][c];
-            ln_finish(s1, s2, K, 1e-5f, mean, scale);
-        }
+            }
+        asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+        double s1 = 0.0, s2 = 0.0;
+        for (int c = 0; c < nch; c++) s1 += ln_part[0][c], s2 += ln_part[1][c];
+        float mean, scale;
+        ln_finish(s1, s2, K, 1e-5f, mean, scale);
 #pragma unroll
         for (int q = 0; q < LCW; q++)
             if (pw + q * NW < nch) chunk_store<WF, SRCK, FORM>(Ent, a, ci[q], mean, scale, false, kc[q], kc[q] < K, lane);
-        if constexpr (SRCK == MVK_F32) {
-            for (int c = pw + LCW * NW; c < nch; c += NW) {
-                const int kk = c * LN_CHUNK + lane * 8;
-                chunk_load<SRCK, FORM>(Ent, min(kk, K - 8), ci[0]);
-                chunk_store<WF, SRCK, FORM>(Ent, a, ci[0], mean, scale, false, kk, kk < K, lane);
-            }
-        }
         __syncthreads();  // activation image ready
         for (;;) {
             if constexpr (EMIT) __syncthreads();  // the streaming waves' row sums in red[]
@@ -798,20 +736,25 @@ __device__ __forceinline__ void mv_body_split(const MVEntry & Ent, int wgi, int 
             if (stride <= 0 || wgi >= nblk) break;
             if constexpr (EMIT) __syncthreads();  // red[] reuse
         }
-        if constexpr (SRCK == MVK_LN) {
-            if (write_carry) {  // after the rows (see mv_body)
+        // the carry (this LayerNorm output, the next token's shift input) after the rows: vmcnt
+        // counts loads and stores in one order, so a store ahead of the dots would make waits
+        // for earlier loads also wait for the weight stream behind it
+        if (write_carry) {
 #pragma unroll
-                for (int q = 0; q < LCW; q++)
-                    if (pw + q * NW < nch && kc[q] < K) {
-                        float xa[8];
+            for (int q = 0; q < LCW; q++)
+                if (pw + q * NW < nch && kc[q] < K) {
+                    float xa[8];
 #pragma unroll
-                        for (int j = 0; j < 8; j++) xa[j] = ln_apply(ci[q].x[j], mean, scale, ci[q].w[j], ci[q].b[j]);
-                        *(float4 *)(Ent.carry_out + kc[q]) = make_float4(xa[0], xa[1], xa[2], xa[3]);
-                        *(float4 *)(Ent.carry_out + kc[q] + 4) = make_float4(xa[4], xa[5], xa[6], xa[7]);
-                    }
-            }
+                    for (int j = 0; j < 8; j++) xa[j] = ln_apply(ci[q].x[j], mean, scale, ci[q].w[j], ci[q].b[j]);
+                    *(float4 *)(Ent.carry_out + kc[q]) = make_float4(xa[0], xa[1], xa[2], xa[3]);
+                    *(float4 *)(Ent.carry_out + kc[q] + 4) = make_float4(xa[4], xa[5], xa[6], xa[7]);
+                }
         }
-        if constexpr (SRCK == MVK_LN && FORM != 2) {
+        if constexpr (FORM != 2) {
+            // the entry's first workgroup, after its rows: the same LayerNorm output mixed with mu2
+            // into a global activation row (the channel-mix receptance input of k_mvsig).  (Spread
+            // block-interleaved over all workgroups instead: 704 vs 695 us/token -- every workgroup's
+            // image waves then pay the reload and quantization pass.)
             if (Ent.mu2 && (int)blockIdx.x == b0) {
                 MVEntry E2 = Ent;
                 E2.mu = Ent.mu2;
@@ -833,6 +776,11 @@ __device__ __forceinline__ void mv_body_split(const MVEntry & Ent, int wgi, int 
         if constexpr (EMIT) pin_act(ao);
         asm volatile("" ::"s"(W.qs), "s"(W.sc), "s"(W.qh));
         asm volatile("s_barrier" ::: "memory");  // issue order
+        // the weight streams start with the image inputs (holding them until the inputs land:
+        // v6-1B6 686 vs 678 us/token).  The row block (contract: at load_rows) is written out in
+        // this path: through clamp_rows / load_rows / dot_rows_rounds the same loops compile to a
+        // slightly different schedule, and v7-2.9B Q5_1 decoded at 553.5 instead of 555.4 tok/s
+        // (parent 555.8, spread 1.8)
         int row0 = wgi * RW + wave * RR;
         int rows[RR];
 #pragma unroll
@@ -842,7 +790,7 @@ __device__ __forceinline__ void mv_body_split(const MVEntry & Ent, int wgi, int 
         for (int u = 0; u < U; u++)
 #pragma unroll
             for (int r = 0; r < RR; r++) w[r][u] = load_unit<WF>(W, rows[r], u, lane);
-        if constexpr (SRCK == MVK_LN) asm volatile("s_barrier" ::: "memory");  // the statistics exchange
+        asm volatile("s_barrier" ::: "memory");  // the statistics exchange
         EpiIn ep;
         if constexpr (!EMIT) ep = epi_load(Ent, min(row0 + min(lane, RR - 1), M - 1));
         else ep = epi_load(Ent, min(wgi * RW + (tid < RW ? tid : 0), M - 1));
@@ -851,7 +799,7 @@ __device__ __forceinline__ void mv_body_split(const MVEntry & Ent, int wgi, int 
             float acc[RR], acc2[RR];
 #pragma unroll
             for (int r = 0; r < RR; r++) acc[r] = acc2[r] = 0.0f;
-            for (int u0 = 0; u0 < units; u0 += U) {
+            for (int u0 = 0; u0 < units; u0 += U) {  // dot_rows_rounds, written out (above)
                 if (u0 > 0) {
 #pragma unroll
                     for (int u = 0; u < U; u++)
@@ -909,19 +857,12 @@ __device__ __forceinline__ void mv_body_split(const MVEntry & Ent, int wgi, int 
     }
 }
 
-// mv_body, or mv_body_split for the prologue groups with K > 2048
+// The body by input source: LayerNorm groups run mv_body_split, SRC_ACT and SRC_F32 groups mv_body.
 template <int WF, int R, int U, int SRCK, int FORM, bool EMIT, int NW, int LNP>
 __device__ __forceinline__ void mv_run(const MVEntry & Ent, int wgi, int b0, int stride, char * smem, float * red,
-                                       int late, unsigned long long * stamp_mid, unsigned long long * stamp_x) {
-    // every prologue group in the split form (K <= 2048 too: v6-1B6 decode 686-692 vs 696-698 us per
-    // token with the image waves carrying rows in mv_body, v4-169M 244 vs 251); MV_IMG_ROWS: mv_body
-#ifdef MV_IMG_ROWS
-    constexpr int LNS = 32;
-#else
-    constexpr int LNS = 0;
-#endif
-    if constexpr (SRCK != MVK_ACT && LNP > LNS) mv_body_split<WF, R, U, SRCK, FORM, EMIT, NW, LNP>(Ent, wgi, b0, stride, smem, red, late);
-    else mv_body<WF, R, U, SRCK, FORM, EMIT, NW, LNP>(Ent, wgi, b0, stride, smem, red, late, stamp_mid, stamp_x);
+                                       unsigned long long * stamp_mid, unsigned long long * stamp_x) {
+    if constexpr (SRCK == MVK_LN) mv_body_split<WF, R, U, SRCK, FORM, EMIT, NW, LNP>(Ent, wgi, b0, stride, smem, red);
+    else mv_body<WF, R, U, SRCK, FORM, EMIT, NW>(Ent, wgi, b0, stride, smem, stamp_mid, stamp_x);
 }
 
 // WFIX >= 0: every entry of the group has weight type WFIX (one body, fewer registers);
@@ -952,16 +893,16 @@ __global__ __launch_bounds__(512) void k_mv(int b1, int b2, int b3, int b4, int 
     unsigned long long * sx = nullptr;
 #endif
     if constexpr (WFIX >= 0) {
-        mv_run<WFIX, R, U, SRCK, FORM, EMIT, NW, LNP>(Ent, wgi, b0, g.stride, smem, red, g.late, smid, sx);
+        mv_run<WFIX, R, U, SRCK, FORM, EMIT, NW, LNP>(Ent, wgi, b0, g.stride, smem, red, smid, sx);
     } else {
         switch (Ent.W.type) {
-            case W_F32: mv_run<W_F32, R, U, SRCK, FORM, EMIT, NW, LNP>(Ent, wgi, b0, g.stride, smem, red, g.late, nullptr, nullptr); break;
-            case W_F16: mv_run<W_F16, R, U, SRCK, FORM, EMIT, NW, LNP>(Ent, wgi, b0, g.stride, smem, red, g.late, nullptr, nullptr); break;
-            case W_Q4_0: mv_run<W_Q4_0, R, U, SRCK, FORM, EMIT, NW, LNP>(Ent, wgi, b0, g.stride, smem, red, g.late, nullptr, nullptr); break;
-            case W_Q4_1: mv_run<W_Q4_1, R, U, SRCK, FORM, EMIT, NW, LNP>(Ent, wgi, b0, g.stride, smem, red, g.late, nullptr, nullptr); break;
-            case W_Q5_0: mv_run<W_Q5_0, R, U, SRCK, FORM, EMIT, NW, LNP>(Ent, wgi, b0, g.stride, smem, red, g.late, nullptr, nullptr); break;
-            case W_Q5_1: mv_run<W_Q5_1, R, U, SRCK, FORM, EMIT, NW, LNP>(Ent, wgi, b0, g.stride, smem, red, g.late, nullptr, nullptr); break;
-            case W_Q8_0: mv_run<W_Q8_0, R, U, SRCK, FORM, EMIT, NW, LNP>(Ent, wgi, b0, g.stride, smem, red, g.late, nullptr, nullptr); break;
+            case W_F32: mv_run<W_F32, R, U, SRCK, FORM, EMIT, NW, LNP>(Ent, wgi, b0, g.stride, smem, red, nullptr, nullptr); break;
+            case W_F16: mv_run<W_F16, R, U, SRCK, FORM, EMIT, NW, LNP>(Ent, wgi, b0, g.stride, smem, red, nullptr, nullptr); break;
+            case W_Q4_0: mv_run<W_Q4_0, R, U, SRCK, FORM, EMIT, NW, LNP>(Ent, wgi, b0, g.stride, smem, red, nullptr, nullptr); break;
+            case W_Q4_1: mv_run<W_Q4_1, R, U, SRCK, FORM, EMIT, NW, LNP>(Ent, wgi, b0, g.stride, smem, red, nullptr, nullptr); break;
+            case W_Q5_0: mv_run<W_Q5_0, R, U, SRCK, FORM, EMIT, NW, LNP>(Ent, wgi, b0, g.stride, smem, red, nullptr, nullptr); break;
+            case W_Q5_1: mv_run<W_Q5_1, R, U, SRCK, FORM, EMIT, NW, LNP>(Ent, wgi, b0, g.stride, smem, red, nullptr, nullptr); break;
+            case W_Q8_0: mv_run<W_Q8_0, R, U, SRCK, FORM, EMIT, NW, LNP>(Ent, wgi, b0, g.stride, smem, red, nullptr, nullptr); break;
             default: break;
         }
     }
@@ -971,10 +912,10 @@ __global__ __launch_bounds__(512) void k_mv(int b1, int b2, int b3, int b4, int 
 }
 
 // Activation-input matvec (SRC_ACT, no emission, one weight type): the lean form of mv_body's
-// dot-wave path.  Every scalar the launch needs (weights, activation, epilogue) is read from
+// SRC_ACT path.  Every scalar the launch needs (weights, activation, epilogue) is read from
 // the group before any arithmetic, so they arrive in one scalar-load round trip and the weight
-// stream is issued right after it; no persistent walk, no prologue waves.  Same lane/unit
-// assignment and accumulation order as mv_body (bit-identical results).
+// stream is issued right after it; no persistent walk, no prologue waves.  The row block in the
+// select form (contract: at load_rows).
 template <int WF, int R, int U>
 __global__ __launch_bounds__(256) void k_mva(int b1, int b2, int b3, int b4, int b5, int b6, int b7, MVGroup g) {
     const int bx = (int)blockIdx.x;
@@ -1005,14 +946,9 @@ __global__ __launch_bounds__(256) void k_mva(int b1, int b2, int b3, int b4, int
     STAMP_BEGIN();
     const int row0 = (bx - b0) * (4 * R) + wave * R;
     int rows[R];
-#pragma unroll
-    for (int r = 0; r < R; r++) rows[r] = min(row0 + r, M - 1);
-    // all U units of every row in flight before anything waits (clamped loads, no branches)
+    clamp_rows(rows, row0, M);
     WBlk w[R][U];
-#pragma unroll
-    for (int u = 0; u < U; u++)
-#pragma unroll
-        for (int r = 0; r < R; r++) w[r][u] = load_unit<WF>(W, rows[r], u, lane);
+    load_rows<WF, R, U>(W, rows, 0, lane, w);
     AUnit x[U];
 #pragma unroll
     for (int u = 0; u < U; u++) x[u] = load_act_unit<WF, false>(a, u, lane);
@@ -1026,19 +962,7 @@ __global__ __launch_bounds__(256) void k_mva(int b1, int b2, int b3, int b4, int
     __builtin_amdgcn_sched_barrier(0);
     STAMP_MID();
     float acc[R], acc2[R];
-#pragma unroll
-    for (int r = 0; r < R; r++) acc[r] = acc2[r] = 0.0f;
-#pragma unroll
-    for (int u = 0; u < U; u++) {
-        const bool valid = unit_valid<WF>(K, u, lane);
-#pragma unroll
-        for (int r = 0; r < R; r++) {
-            float t = acc[r], t2 = acc2[r];
-            dot_unit<WF>(w[r][u], x[u], t, t2);
-            acc[r] = valid ? t : acc[r];
-            acc2[r] = valid ? t2 : acc2[r];
-        }
-    }
+    dot_rows<WF, R, U>(w, x, K, lane, acc, acc2);
     // epilogue on lane r for row r, on every lane (the operand loads stay ahead of the dots
     // instead of being sunk into the store branch: a dependent round trip at the kernel's end)
     const float v = epi_apply(h.epi, row_sums<WF, R>(acc, acc2, lane), ep);
@@ -1049,7 +973,7 @@ __global__ __launch_bounds__(256) void k_mva(int b1, int b2, int b3, int b4, int
 // Channel mix value + receptance in one launch (decode v4/v5/v6, rwkv_graph.inc:484-531):
 // y[row] += sigmoid(Wr[row] . xr) * (Wv[row] . k).  Wave w of the workgroup owns rows row0..row0+R-1 of
 // BOTH matrices (Wv units U over the FFN width, Wr units U2 over n_embed), so the receptance of
-// a row never leaves the wave; each product is k_mva's arithmetic (lane/unit order, wave_sum63
+// a row never leaves the wave; each product is k_mva's row block (select form, wave_sum63
 // tree), and the epilogue is EPI_SIGMUL_ADD with aux = the receptance row (EPI_STORE) -- the same
 // bits as the Wr matvec + k_mva pair it replaces.  hv: Wv / k / y, hr: Wr / xr.
 template <int WF, int R, int U, int U2>
@@ -1069,17 +993,10 @@ __global__ __launch_bounds__(256) void k_mvsig(MVHot hv, MVHot hr) {
     STAMP_BEGIN();
     const int row0 = (int)blockIdx.x * (4 * R) + wave * R;
     int rows[R];
-#pragma unroll
-    for (int r = 0; r < R; r++) rows[r] = min(row0 + r, M - 1);
+    clamp_rows(rows, row0, M);
     WBlk w[R][U], w2[R][U2];
-#pragma unroll
-    for (int u = 0; u < U; u++)
-#pragma unroll
-        for (int r = 0; r < R; r++) w[r][u] = load_unit<WF>(W, rows[r], u, lane);
-#pragma unroll
-    for (int u = 0; u < U2; u++)
-#pragma unroll
-        for (int r = 0; r < R; r++) w2[r][u] = load_unit<WF>(W2, rows[r], u, lane);
+    load_rows<WF, R, U>(W, rows, 0, lane, w);
+    load_rows<WF, R, U2>(W2, rows, 0, lane, w2);
     AUnit x[U], x2[U2];
 #pragma unroll
     for (int u = 0; u < U; u++) x[u] = load_act_unit<WF, false>(a, u, lane);
@@ -1092,37 +1009,13 @@ __global__ __launch_bounds__(256) void k_mvsig(MVHot hv, MVHot hr) {
     float sv[R], sr[R];
     {
         float acc[R], acc2[R];
-#pragma unroll
-        for (int r = 0; r < R; r++) acc[r] = acc2[r] = 0.0f;
-#pragma unroll
-        for (int u = 0; u < U2; u++) {
-            const bool valid = unit_valid<WF>(W2.K, u, lane);
-#pragma unroll
-            for (int r = 0; r < R; r++) {
-                float t = acc[r], t2 = acc2[r];
-                dot_unit<WF>(w2[r][u], x2[u], t, t2);
-                acc[r] = valid ? t : acc[r];
-                acc2[r] = valid ? t2 : acc2[r];
-            }
-        }
+        dot_rows<WF, R, U2>(w2, x2, W2.K, lane, acc, acc2);
 #pragma unroll
         for (int r = 0; r < R; r++) sr[r] = one ? wave_sum63(acc[r]) + wave_sum63(acc2[r]) : wave_sum63(acc[r]) + 0.0f;
     }
     {
         float acc[R], acc2[R];
-#pragma unroll
-        for (int r = 0; r < R; r++) acc[r] = acc2[r] = 0.0f;
-#pragma unroll
-        for (int u = 0; u < U; u++) {
-            const bool valid = unit_valid<WF>(W.K, u, lane);
-#pragma unroll
-            for (int r = 0; r < R; r++) {
-                float t = acc[r], t2 = acc2[r];
-                dot_unit<WF>(w[r][u], x[u], t, t2);
-                acc[r] = valid ? t : acc[r];
-                acc2[r] = valid ? t2 : acc2[r];
-            }
-        }
+        dot_rows<WF, R, U>(w, x, W.K, lane, acc, acc2);
 #pragma unroll
         for (int r = 0; r < R; r++) sv[r] = one ? wave_sum63(acc[r]) + wave_sum63(acc2[r]) : wave_sum63(acc[r]) + 0.0f;
     }
@@ -1131,6 +1024,12 @@ __global__ __launch_bounds__(256) void k_mvsig(MVHot hv, MVHot hr) {
     if (lane < R && row0 + lane < M) hv.y[row0 + lane] = v;
     STAMP_END(7);
 }
+
+// Rows per wave of k_mva (launch_mv_group's choice for its groups, the one shape instantiated here):
+// 2.  More rows per wave put more weight loads in flight per lane behind fewer workgroups; measured
+// on the v6-1B6 decode chain (128 tokens): 2 rows 853 us/token, 4 rows 883, 8 rows 876 -- the launch
+// stays latency bound and two rows keep the most waves issuing.
+constexpr int MVA_ROWS = 2;
 
 // One weight-type translation unit (mv_*.hip) instantiates every launch shape for WFIX.
 // LayerNorm prologues hold the normalized vector in registers: LNP = 32 (K <= 2048) or 64
@@ -1146,19 +1045,12 @@ bool launch_mv_shape(hipStream_t st, MVGroup & g, int U, int srck, int form, boo
     const int K = g.e[0].W.K;
     if constexpr (WFIX >= 0) {
         if (srck == MVK_ACT && !emit && g.units_max <= U && U <= 4) {  // k_mva: <= 4 units per lane
-#define MVA_R(Rv, Uv) \
-    RK_LAUNCH((k_mva<WFIX, Rv, Uv>), grid, dim3(256), 0, st, b[1], b[2], b[3], b[4], b[5], b[6], b[7], g)
-#define MVA_L(Uv)                          \
-    do {                                   \
-        if (g.rows == 2) MVA_R(2, Uv);     \
-        else if (g.rows == 8) MVA_R(8, Uv); \
-        else MVA_R(4, Uv);                 \
-    } while (0)
+#define MVA_L(Uv) \
+    RK_LAUNCH((k_mva<WFIX, MVA_ROWS, Uv>), grid, dim3(256), 0, st, b[1], b[2], b[3], b[4], b[5], b[6], b[7], g)
             if (U == 1) MVA_L(1);
             else if (U == 2) MVA_L(2);
             else MVA_L(4);
 #undef MVA_L
-#undef MVA_R
             return true;
         }
     }
@@ -1183,19 +1075,28 @@ bool launch_mv_shape(hipStream_t st, MVGroup & g, int U, int srck, int form, boo
         fprintf(stderr, "rwkv: LayerNorm matvec prologue needs K <= 4096 (K=%d)\n", K);
         return false;
     }
-    // prologue groups: the rows of a block over all 8 waves (image waves included), so R here is
-    // half of launch_mv_group's rows per wave (g.rows, which counts the 4 streaming waves)
+    // Quantized rows hold 2048 elements per unit round (64 lanes x one 32-block), so a LayerNorm
+    // group (K <= 4096, one K, one type) has mv_units = ceil(K / 2048) <= 2 units per lane and
+    // launch_mv_group's U = units_max rounded up to 1, 2, 4 is 1 or 2 (its U = 8 cases are SRC_ACT or
+    // F16 only): the U = 4 LayerNorm shapes are not instantiated for these types.  F16 / F32 rows (512 /
+    // 256 elements per round) and mixed-type groups (WFIX = -1) keep them.
+    constexpr bool U4 = !wtype_quantized(WFIX);
+    if (!U4 && U > 2) {
+        fprintf(stderr, "rwkv: LayerNorm matvec of quantized rows takes <= 2 units per lane (U=%d)\n", U);
+        return false;
+    }
+    // LayerNorm groups run mv_body_split: the rows of a block over the 4 streaming waves, 2 R each (the
+    // image waves have none), so R here is half of launch_mv_group's rows per wave (g.rows)
+#define MV_PU(Rv, S, F, E, P)                                 \
+    do {                                                      \
+        if (U == 1) MV_L(Rv, 1, S, F, E, P);                  \
+        else if (U == 2) MV_L(Rv, 2, S, F, E, P);             \
+        else if constexpr (U4) MV_L(Rv, 4, S, F, E, P);       \
+    } while (0)
 #define MV_PR(Rv, S, F, E)                                    \
     do {                                                      \
-        if (K <= 2048) {                                      \
-            if (U == 1) MV_L(Rv, 1, S, F, E, 32);             \
-            else if (U == 2) MV_L(Rv, 2, S, F, E, 32);        \
-            else MV_L(Rv, 4, S, F, E, 32);                    \
-        } else {                                              \
-            if (U == 1) MV_L(Rv, 1, S, F, E, 64);             \
-            else if (U == 2) MV_L(Rv, 2, S, F, E, 64);        \
-            else MV_L(Rv, 4, S, F, E, 64);                    \
-        }                                                     \
+        if (K <= 2048) MV_PU(Rv, S, F, E, 32);                \
+        else MV_PU(Rv, S, F, E, 64);                          \
     } while (0)
     // not emitting: g.rows rows per streaming wave (2, or 4 for large LayerNorm groups, or 8 with
     // one unit per round trip: <= 128 VGPRs, two workgroups per CU); emitting: 8
@@ -1221,6 +1122,7 @@ bool launch_mv_shape(hipStream_t st, MVGroup & g, int U, int srck, int form, boo
     }
 #undef MV_P
 #undef MV_PR
+#undef MV_PU
 #undef MV_L
     return true;
 }

@@ -45,7 +45,7 @@ __global__ __launch_bounds__(512) void k_ffn_fused(FfnFused f) {
         const int b0 = e ? f.e[1].block0 : 0;
         const GranPub pub{f.kg, f.rg, f.h.tag};
         STAMP_BEGIN();
-        mv_body_split<WF, 4, 1, MVK_LN, FORM, true, 4, LNP, true>(Ent, bx - b0, b0, 0, smem, red, 0, &pub);
+        mv_body_split<WF, 4, 1, MVK_LN, FORM, true, 4, LNP, true>(Ent, bx - b0, b0, 0, smem, red, &pub);
         if constexpr (!CO) {
             STAMP_END(9);
             return;
@@ -65,11 +65,10 @@ __global__ __launch_bounds__(512) void k_ffn_fused(FfnFused f) {
         const unsigned long long t0 = __builtin_amdgcn_s_memrealtime();
         while (__builtin_amdgcn_s_memrealtime() - t0 < (unsigned long long)f.wdelay) __builtin_amdgcn_s_sleep(8);
     }
+    int rows[RC];
+    clamp_rows(rows, row0, C);
     WBlk w[RC][UV];
-#pragma unroll
-    for (int u = 0; u < UV; u++)
-#pragma unroll
-        for (int r = 0; r < RC; r++) w[r][u] = load_unit<WF>(f.wv, min(row0 + r, C - 1), u, lane);
+    load_rows<WF, RC, UV>(f.wv, rows, 0, lane, w);
     const int myrow = min(row0 + min(lane, RC - 1), C - 1);
     const float xr = f.x[myrow];
     const ActBuf img = lds_act(smem, act_fmt_for(WF), F);

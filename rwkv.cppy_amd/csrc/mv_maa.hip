@@ -57,7 +57,9 @@ __global__ __launch_bounds__(512) void k_v6_maa_dec(MaaDec a) {
     }
     asm volatile("" ::"s"(a.w1.qs), "s"(a.w1.sc), "s"(a.w1.qh));  // pointers before the barrier
     asm volatile("s_barrier" ::: "memory");  // image inputs issued ahead of the weight stream
-    // ---- rows n*D + wave*R + r of W1 (all waves)
+    // ---- rows n*D + wave*R + r of W1 (all waves); the row block of mv_common.hpp, round form,
+    // written out as in maa_dec4_body: the helper form moved registers and scratch at the 256-VGPR
+    // limit and no benchmark configuration reaches this kernel (D > 32)
     const int units = mv_units(WF, K);
     const int row0 = n * D + wave * R, rlast = n * D + D - 1;
     int rows[R];

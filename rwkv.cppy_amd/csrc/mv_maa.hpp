@@ -144,6 +144,9 @@ __device__ __forceinline__ void maa_dec4_body(const MaaDec & a, int bx, int n, c
         const DMat & W = a.w1;
         asm volatile("" ::"s"(W.qs), "s"(W.sc), "s"(W.qh));
         // ---- rows n*D + wave*R + r of W1 and this thread's mix channel: W2 column, carry, maa
+        // (the row block of mv_common.hpp, round form, written out: with this site and af_rows
+        // through the helpers v6-1B6 decode sat at the lower edge of the parent's spread -- median
+        // -3.5 and -5.7 tok/s of 1667 at spreads of 4.7 and 5.1 -- and written out it did not)
         const int units = mv_units(WF, K);
         const int row0 = n * D + wave * R, rlast = n * D + D - 1;
         int rows[R];
