@@ -193,6 +193,62 @@ RWKV_API bool rwkv_mi355x_generate_queue(struct rwkv_context * ctx, size_t Q, si
                                          uint32_t * lane_out /* [Q] */, uint32_t * start_out /* [Q] */,
                                          uint32_t * steps_out);
 
+/* Log-probabilities of the tokens the four calls above draw: the drawn token's, and the top_k most
+ * likely alternatives (what OpenAI-style APIs return as logprobs / top_logprobs).  They are taken
+ * inside the sampling step, of the distribution the token was drawn from, so nothing but the results
+ * crosses PCIe and no second pass over the weights is needed.
+ *
+ * For one draw of a live row let l be the float32 row the sampler samples from: the logits, then the
+ * presence / frequency penalty over the counts before this draw's increment, then the bias, in the
+ * order and roundings stated above (rwkv_cpp.sampling.penalize).  Temperature and top_p do not enter:
+ * this is the p = softmax(l) of rwkv_mi355x_sample.
+ *   m    = max l, exact in float32
+ *   S    = sum_i exp((double)l_i - (double)m), exponentials and sum in double, one fixed association
+ *   logZ = (double)m + log(S)
+ *   token_logprob   = (double)l[token] - logZ
+ *   top_ids[0 .. K) = the K first indices in the order "larger l first, lower index first among equal
+ *                     l" (exact float32 compares).  A NaN element is never listed; with fewer than K
+ *                     elements that are not NaN the remaining entries keep the fill (below).
+ *   top_logprobs[j] = (double)l[top_ids[j]] - logZ, with the same logZ word: where the drawn token is
+ *                     top_ids[j], token_logprob and top_logprobs[j] are bit-equal.
+ * rwkv_cpp.sampling.logprobs restates this in float64 numpy.  A call is a pure function of its inputs.
+ * Non-finite logits may give NaN or infinite values; they cannot hang or fault a call.
+ *
+ * Layout: rows = 1 for sample and generate, B for generate_batch, Q for generate_queue; n is the call's
+ * n (1 for sample); the rows are n columns apart, as in tokens_out.  Draw i of row r fills column i of
+ * row r (for the queue: the column the token goes to).  A column no draw filled -- past lengths_out[r],
+ * or any column of a row that was already finished under keep_counts -- and a top entry left unlisted
+ * hold the fill: every byte 0xFF, so an id of 0xFFFFFFFF and a NaN.  A row that stops reports the stop
+ * token's own log-probability and alternatives: the stop token is a drawn token. */
+#define RWKV_MI355X_MAX_TOP_LOGPROBS 20
+struct rwkv_mi355x_logprobs {
+    uint32_t top_k;          /* 0 .. 20 and <= n_vocab */
+    double   * token_logprob;/* host [rows][n]; required */
+    uint32_t * top_ids;      /* host [rows][n][top_k]; required iff top_k > 0 */
+    double   * top_logprobs; /* host [rows][n][top_k]; required iff top_k > 0 */
+};
+/* Each is its sibling above plus lp; with lp == NULL it is that call (which forwards here).  Tokens,
+ * lengths, states, logits and every other result are, bit for bit, those of the call without lp.
+ * Besides the sibling's errors: top_k > 20, top_k > n_vocab, a NULL token_logprob, or top_k > 0 with a
+ * NULL top_ids / top_logprobs fail with RWKV_ERROR_ARGS, and a failed allocation of the device arrays
+ * (rows * n * (8 + 12 top_k) bytes and a word per row, grown before the loop) with RWKV_ERROR_ALLOC;
+ * both before anything is enqueued: slots, state and logits are untouched. */
+RWKV_API bool rwkv_mi355x_sample_logprobs(struct rwkv_context * ctx, const struct rwkv_mi355x_sampling * params,
+                                          uint32_t * token_out, const struct rwkv_mi355x_logprobs * lp);
+RWKV_API bool rwkv_mi355x_generate_logprobs(struct rwkv_context * ctx, const struct rwkv_mi355x_sampling * params,
+                                            size_t n, uint32_t * tokens_out, float * logits_out,
+                                            const struct rwkv_mi355x_logprobs * lp);
+RWKV_API bool rwkv_mi355x_generate_batch_logprobs(struct rwkv_context * ctx, size_t B,
+                                                  const struct rwkv_mi355x_batch_sampling * params, size_t n,
+                                                  uint32_t * tokens_out /* [B][n] */, uint32_t * lengths_out /* [B] */,
+                                                  uint32_t * steps_out, const struct rwkv_mi355x_logprobs * lp);
+RWKV_API bool rwkv_mi355x_generate_queue_logprobs(struct rwkv_context * ctx, size_t Q, size_t lanes,
+                                                  const struct rwkv_mi355x_batch_sampling * params,
+                                                  const uint32_t * max_tokens /* host [Q] */, size_t n,
+                                                  uint32_t * tokens_out /* [Q][n] */, uint32_t * lengths_out /* [Q] */,
+                                                  uint32_t * lane_out /* [Q] */, uint32_t * start_out /* [Q] */,
+                                                  uint32_t * steps_out, const struct rwkv_mi355x_logprobs * lp);
+
 /* Batched prefill: n_rows prompts, concatenated in `tokens` (lengths[i] >= 1 tokens each), are
  * evaluated together in packed sequence passes and land in slots[i] (distinct, each < the reserved
  * slots).  cont == NULL or cont[i] == 0: row i starts from the fresh state (the slot need not have
@@ -444,6 +500,23 @@ RWKV_API bool rwkv_mi355x_selftest_sample_rows(const float * logits, int rows, i
                                                uint32_t step, uint32_t * counts, uint32_t * done, uint32_t * tokens,
                                                uint32_t * decode_tokens, uint32_t * kept, float * cutoff,
                                                uint32_t * lengths, uint32_t * active);
+
+/* The two self-tests above with log-probabilities: k_logprobs in front of the sampler's LP form, as
+ * the rwkv_mi355x_*_logprobs calls launch them.  top_k in [0, 20] and <= V; token_logprob [rows],
+ * top_ids and top_logprobs [rows][top_k] (not NULL, also for top_k == 0) are uploaded first and
+ * downloaded afterwards, so an entry the kernels do not write keeps the caller's value.  Everything
+ * else is the argument of the same name above. */
+RWKV_API bool rwkv_mi355x_selftest_sample_logprobs(const float * logits, int rows, int V,
+                                                   const struct rwkv_mi355x_sampling * params, const float * u,
+                                                   uint32_t * tokens, uint32_t * kept, float * cutoff, uint32_t top_k,
+                                                   double * token_logprob, uint32_t * top_ids, double * top_logprobs);
+RWKV_API bool rwkv_mi355x_selftest_sample_rows_logprobs(const float * logits, int rows, int V,
+                                                        const struct rwkv_mi355x_batch_sampling * params,
+                                                        const float * u, uint32_t step, uint32_t * counts,
+                                                        uint32_t * done, uint32_t * tokens, uint32_t * decode_tokens,
+                                                        uint32_t * kept, float * cutoff, uint32_t * lengths,
+                                                        uint32_t * active, uint32_t top_k, double * token_logprob,
+                                                        uint32_t * top_ids, double * top_logprobs);
 
 /* The turnover kernel of rwkv_mi355x_generate_queue (k_gen_turnover) on host operands, as before step
  * `step`: lane_seq [lanes] (a sequence id < Q or 0xFFFFFFFF: idle), done / lane / start [Q], *next

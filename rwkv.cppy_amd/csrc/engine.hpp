@@ -170,6 +170,15 @@ struct BatchSamplingParams {
     uint32_t check_every = 0;
 };
 
+// rwkv_mi355x_logprobs, checked by the caller (include/rwkv_mi355x.h): the host arrays that receive
+// the log-probabilities of a call's draws, [rows][n] columns with the rows n apart, as tokens_out
+struct LogprobsOut {
+    uint32_t top_k = 0;
+    double * token_logprob = nullptr;
+    uint32_t * top_ids = nullptr;      // top_k per column
+    double * top_logprobs = nullptr;   // top_k per column
+};
+
 class Engine : public KLaunchTimer, private Workspace, private GenSlots {
   public:
     explicit Engine(DeviceModel * m) : m_(m) {}
@@ -191,8 +200,16 @@ class Engine : public KLaunchTimer, private Workspace, private GenSlots {
     // n tokens (and, logits_out != NULL, of the final logits) and one synchronisation at the end.  A
     // hand-off timeout anywhere in the chain fails the call (no re-run: the state has moved on).
     // Both need logits_valid().
-    bool sample(const SamplingParams & p, uint32_t * token_out);
-    bool generate(const SamplingParams & p, size_t n, uint32_t * tokens_out, float * logits_out);
+    // lp != NULL (all four generation calls): k_logprobs runs in front of every sampler launch and the
+    // sampler's LP form writes the drawn token's log-probability; the device arrays start as 0xFF bytes
+    // and are copied out with the tokens.  lp == NULL: the call as it was.
+    bool sample(const SamplingParams & p, uint32_t * token_out, const LogprobsOut * lp = nullptr);
+    bool generate(const SamplingParams & p, size_t n, uint32_t * tokens_out, float * logits_out,
+                  const LogprobsOut * lp = nullptr);
+    // The device arrays of a call with log-probabilities: rows * n columns of 8 + 12 top_k bytes and one
+    // logZ word per row, grown here and never inside a loop.  Enqueues nothing; the callers of the four
+    // calls run it first, so that a failed allocation fails the call before anything else happens.
+    bool lp_reserve(size_t rows, size_t n, uint32_t top_k);
     // Scoring (rwkv_mi355x_score_sequence): eval_device(tokens, T, want_logits = true, sync = true)
     // with the head on every token.  Each chunk's final residual rows go through the head in tiles
     // of kScoreRows rows (LayerNorm, the batched decode's head matmul, k_xent); losses and argmaxes
@@ -222,7 +239,7 @@ class Engine : public KLaunchTimer, private Workspace, private GenSlots {
     bool batch_store(size_t slot);
     bool batch_load(size_t slot);
     bool generate_batch(size_t B, const BatchSamplingParams & p, size_t n, uint32_t * tokens_out, uint32_t * lengths_out,
-                        uint32_t * steps_out);
+                        uint32_t * steps_out, const LogprobsOut * lp = nullptr);
     // A queue of Q sequences (slots [0, Q)) over L = min(lanes, Q) decode rows
     // (rwkv_mi355x_generate_queue): per step k_gen_turnover frees the lanes of ended
     // sequences and admits the waiting ones, k_gen_move copies a capped sequence's result out of its
@@ -230,7 +247,7 @@ class Engine : public KLaunchTimer, private Workspace, private GenSlots {
     // lanes as in generate_batch.  Every per-row array of p is [Q]; max_tokens[s] in [1, n].
     bool generate_queue(size_t Q, size_t lanes, const BatchSamplingParams & p, const uint32_t * max_tokens, size_t n,
                         uint32_t * tokens_out, uint32_t * lengths_out, uint32_t * lane_out, uint32_t * start_out,
-                        uint32_t * steps_out);
+                        uint32_t * steps_out, const LogprobsOut * lp = nullptr);
     // Batched prefill (rwkv_mi355x_prefill_batch; engine_prefill.hip): n_rows prompts, concatenated in
     // tokens, are packed into chunks of at most prefill_chunk_ tokens (prefill_plan.hpp) and each chunk
     // runs as one sequence pass whose token shift and WKV kernels follow a segment table (SegTab);
@@ -374,6 +391,14 @@ class Engine : public KLaunchTimer, private Workspace, private GenSlots {
     DevBuf<uint32_t> gen_tokens_;   // generate: the drawn tokens
     DevBuf<uint32_t> bias_ids_;     // the sampler's logit bias [SAMPLE_MAX_BIAS]
     DevBuf<float> bias_vals_;
+    // log-probabilities of a call's draws (lp_reserve): one double per column, top_k ids and doubles
+    // per column, logZ per row of a sampler launch [kBatchMax]
+    DevBuf<double> lp_token_, lp_top_, lp_logz_;
+    DevBuf<uint32_t> lp_ids_;
+    // the fill of a call's columns (every byte 0xFF) and the arrays into the sampler's arguments;
+    // the copies out at the end of the call
+    bool lp_begin(const LogprobsOut * lp, size_t rows, size_t n, SampleArgs & a);
+    bool lp_copy_out(const LogprobsOut * lp, size_t rows, size_t n);
     DevBuf<float> dstate_[2];
     int cur_ = 0;
     unsigned * herr_h_ = nullptr;  // hand-off timeout flag, host-mapped (herr_d_ = its device address)

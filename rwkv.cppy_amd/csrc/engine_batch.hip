@@ -220,7 +220,7 @@ bool Engine::gen_fail(size_t rows) {
 }
 
 bool Engine::generate_batch(size_t B, const BatchSamplingParams & p, size_t n, uint32_t * tokens_out,
-                            uint32_t * lengths_out, uint32_t * steps_out) {
+                            uint32_t * lengths_out, uint32_t * steps_out, const LogprobsOut * lp) {
     HIP_OK(hipSetDevice(m_->device));
     if (B == 0 || B > gslots_ || n == 0 || !tokens_out || !lengths_out || !p.temperature || !p.top_p || !p.seed ||
         !p.offset || p.n_bias > (uint32_t)SAMPLE_MAX_BIAS || p.n_stop > (uint32_t)SAMPLE_MAX_STOP)
@@ -230,7 +230,7 @@ bool Engine::generate_batch(size_t B, const BatchSamplingParams & p, size_t n, u
     const size_t S = m_->state_len, V = m_->n_vocab;
     // everything that allocates, before anything is enqueued: dtokens_ moves when the workspace
     // grows (and the batch graphs are dropped with it), the token buffer grows with B * n
-    if (!ensure_workspace((int)B)) return false;
+    if (!ensure_workspace((int)B) || (lp && !lp_reserve(B, n, lp->top_k))) return false;
     if (!grow(gtokens_, B * n, doubled(1024, B * n), GRAPHS_NONE) || !upload_bias(p.n_bias, p.bias_ids, p.bias_values))
         return false;
     // from here on a failure leaves the slots of the call undefined
@@ -238,6 +238,7 @@ bool Engine::generate_batch(size_t B, const BatchSamplingParams & p, size_t n, u
     bool ok = gen_upload(B, p, n);
     if (ok && !p.keep_counts) ok = hipMemsetAsync(gcounts_, 0, B * V * 4, stream_) == hipSuccess;
     SampleArgs a = gen_sample_args(B, p, n);
+    ok = ok && lp_begin(lp, B, n, a);
     ok = ok && launch_gen_begin(stream_, (int)B, p.keep_counts ? 1 : 0, a.done, a.length, a.fin_step, a.active);
     if (!ok) return fail();
     GenRows g{(int)B, S, V, a.done, a.fin_step};
@@ -249,8 +250,8 @@ bool Engine::generate_batch(size_t B, const BatchSamplingParams & p, size_t n, u
         a.counter = i;
         a.step = (uint32_t)i;
         if (timing_) g_klt = this;
-        ok = launch_sample(stream_, a) && launch_gen_snapshot(stream_, g, (uint32_t)i, gstate_[steps & 1], glogits_,
-                                                              gsnap_state_, gsnap_logits_);
+        ok = (!lp || launch_logprobs(stream_, a)) && launch_sample(stream_, a) &&
+             launch_gen_snapshot(stream_, g, (uint32_t)i, gstate_[steps & 1], glogits_, gsnap_state_, gsnap_logits_);
         g_klt = nullptr;
         ok = ok && eval_batch(nullptr, B, gstate_[steps & 1], gstate_[(steps & 1) ^ 1], glogits_, true);
         if (!ok) break;
@@ -264,7 +265,8 @@ bool Engine::generate_batch(size_t B, const BatchSamplingParams & p, size_t n, u
     ok = launch_gen_restore(stream_, g, gsnap_state_, gsnap_logits_, gstate_[steps & 1], gstate_[0], glogits_);
     // [B][n] tokens with the rows n apart, as the caller's
     ok = ok && hipMemcpyAsync(tokens_out, gtokens_, B * n * 4, hipMemcpyDeviceToHost, stream_) == hipSuccess &&
-         hipMemcpyAsync(lengths_out, a.length, B * 4, hipMemcpyDeviceToHost, stream_) == hipSuccess;
+         hipMemcpyAsync(lengths_out, a.length, B * 4, hipMemcpyDeviceToHost, stream_) == hipSuccess &&
+         lp_copy_out(lp, B, n);
     if (!ok) return fail();
     if (hipStreamSynchronize(stream_) != hipSuccess) return fail();
     if (!handoff_check()) {
@@ -283,7 +285,7 @@ bool Engine::generate_batch(size_t B, const BatchSamplingParams & p, size_t n, u
 // slot at the end.  done[s] == 1 from then on, so the restore needs no table.
 bool Engine::generate_queue(size_t Q, size_t lanes, const BatchSamplingParams & p, const uint32_t * max_tokens, size_t n,
                             uint32_t * tokens_out, uint32_t * lengths_out, uint32_t * lane_out, uint32_t * start_out,
-                            uint32_t * steps_out) {
+                            uint32_t * steps_out, const LogprobsOut * lp) {
     HIP_OK(hipSetDevice(m_->device));
     const size_t K = (size_t)kBatchMax;
     if (Q == 0 || Q > gslots_ || lanes == 0 || lanes > K || n == 0 || !max_tokens || !tokens_out || !lengths_out ||
@@ -299,7 +301,7 @@ bool Engine::generate_queue(size_t Q, size_t lanes, const BatchSamplingParams & 
     const size_t L = std::min(lanes, Q), S = m_->state_len, V = m_->n_vocab;
     // list scheduling ends within sum / L + max steps (Graham), whatever the lengths drawn
     const size_t bound = (total + L - 1) / L + longest;
-    if (!ensure_workspace((int)L)) return false;
+    if (!ensure_workspace((int)L) || (lp && !lp_reserve(Q, n, lp->top_k))) return false;
     if (!grow(gtokens_, Q * n, doubled(1024, Q * n), GRAPHS_NONE) || !upload_bias(p.n_bias, p.bias_ids, p.bias_values))
         return false;
     auto fail = [&] { return gen_fail(Q); };
@@ -327,7 +329,7 @@ bool Engine::generate_queue(size_t Q, size_t lanes, const BatchSamplingParams & 
               hipMemcpyAsync(maxtok, gqueue_h_.data(), Q * 4, hipMemcpyHostToDevice, stream_) == hipSuccess &&
               hipMemsetAsync(q.lane_seq, 0xff, 5 * K * 4, stream_) == hipSuccess &&
               hipMemsetAsync(q.next, 0, 4, stream_) == hipSuccess &&
-              launch_gen_begin(stream_, (int)Q, 0, a.done, a.length, a.fin_step, a.active);
+              launch_gen_begin(stream_, (int)Q, 0, a.done, a.length, a.fin_step, a.active) && lp_begin(lp, Q, n, a);
     if (!ok) return fail();
     GenRows g{(int)L, S, V, a.done, a.fin_step, q.lane_seq};
 
@@ -339,7 +341,7 @@ bool Engine::generate_queue(size_t Q, size_t lanes, const BatchSamplingParams & 
         if (timing_) g_klt = this;
         ok = launch_gen_turnover(stream_, q, (uint32_t)i) &&
              launch_gen_move(stream_, q, S, V, cur, glogits_, gstate_[0], gsnap_state_, gsnap_logits_) &&
-             launch_sample(stream_, a) &&
+             (!lp || launch_logprobs(stream_, a)) && launch_sample(stream_, a) &&
              launch_gen_snapshot(stream_, g, (uint32_t)i, cur, glogits_, gsnap_state_, gsnap_logits_);
         g_klt = nullptr;
         ok = ok && eval_batch(nullptr, L, cur, gstate_[(steps & 1) ^ 1], glogits_, true);
@@ -362,7 +364,8 @@ bool Engine::generate_queue(size_t Q, size_t lanes, const BatchSamplingParams & 
     ok = ok && hipMemcpyAsync(tokens_out, gtokens_, Q * n * 4, hipMemcpyDeviceToHost, stream_) == hipSuccess &&
          hipMemcpyAsync(lengths_out, a.length, Q * 4, hipMemcpyDeviceToHost, stream_) == hipSuccess &&
          hipMemcpyAsync(lane_h, q.lane, Q * 4, hipMemcpyDeviceToHost, stream_) == hipSuccess &&
-         hipMemcpyAsync(start_h, q.start, Q * 4, hipMemcpyDeviceToHost, stream_) == hipSuccess;
+         hipMemcpyAsync(start_h, q.start, Q * 4, hipMemcpyDeviceToHost, stream_) == hipSuccess &&
+         lp_copy_out(lp, Q, n);
     if (!ok) return fail();
     if (hipStreamSynchronize(stream_) != hipSuccess) return fail();
     if (!handoff_check()) {

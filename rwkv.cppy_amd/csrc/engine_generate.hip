@@ -40,39 +40,90 @@ bool Engine::upload_bias(uint32_t n_bias, const uint32_t * ids, const float * va
     return true;
 }
 
-bool Engine::sample(const SamplingParams & p, uint32_t * token_out) {
+bool Engine::lp_reserve(size_t rows, size_t n, uint32_t top_k) {
+    HIP_OK(hipSetDevice(m_->device));
+    const size_t cols = rows * n, tops = cols * top_k;
+    return grow(lp_token_, cols, doubled(1024, cols), GRAPHS_NONE) && grow(lp_top_, tops, doubled(1024, tops), GRAPHS_NONE) &&
+           grow(lp_ids_, tops, doubled(1024, tops), GRAPHS_NONE) &&
+           grow(lp_logz_, (size_t)kBatchMax, (size_t)kBatchMax, GRAPHS_NONE);
+}
+
+bool Engine::lp_begin(const LogprobsOut * lp, size_t rows, size_t n, SampleArgs & a) {
+    if (!lp) return true;
+    if (lp->top_k > (uint32_t)LOGPROBS_MAX_TOP || lp->top_k > m_->n_vocab || !lp->token_logprob ||
+        (lp->top_k && (!lp->top_ids || !lp->top_logprobs)) || !lp_reserve(rows, n, lp->top_k))
+        return false;
+    const size_t cols = rows * n, tops = cols * lp->top_k;
+    // one fill per array: 0xFFFFFFFF ids, NaN doubles
+    HIP_OK(hipMemsetAsync(lp_token_, 0xff, cols * 8, stream_));
+    if (tops) {
+        HIP_OK(hipMemsetAsync(lp_top_, 0xff, tops * 8, stream_));
+        HIP_OK(hipMemsetAsync(lp_ids_, 0xff, tops * 4, stream_));
+    }
+    a.lp_logz = lp_logz_;
+    a.lp_token = lp_token_;
+    a.lp_top_ids = lp_ids_;
+    a.lp_top = lp_top_;
+    a.lp_k = (int)lp->top_k;
+    return true;
+}
+
+bool Engine::lp_copy_out(const LogprobsOut * lp, size_t rows, size_t n) {
+    if (!lp) return true;
+    const size_t cols = rows * n, tops = cols * lp->top_k;
+    HIP_OK(hipMemcpyAsync(lp->token_logprob, lp_token_, cols * 8, hipMemcpyDeviceToHost, stream_));
+    if (tops) {
+        HIP_OK(hipMemcpyAsync(lp->top_ids, lp_ids_, tops * 4, hipMemcpyDeviceToHost, stream_));
+        HIP_OK(hipMemcpyAsync(lp->top_logprobs, lp_top_, tops * 8, hipMemcpyDeviceToHost, stream_));
+    }
+    return true;
+}
+
+bool Engine::sample(const SamplingParams & p, uint32_t * token_out, const LogprobsOut * lp) {
     HIP_OK(hipSetDevice(m_->device));
     if (!logits_valid_ || !token_out) return false;
     SampleArgs a;
-    if (!sampler_buffers(p, 1, a) || !launch_sample(stream_, a)) return false;
+    if (lp && !lp_reserve(1, 1, lp->top_k)) return false;
+    if (!sampler_buffers(p, 1, a) || !lp_begin(lp, 1, 1, a)) return false;
+    if (lp && !launch_logprobs(stream_, a)) return false;
+    if (!launch_sample(stream_, a)) return false;
     HIP_OK(hipMemcpyAsync(token_out, gen_tokens_, 4, hipMemcpyDeviceToHost, stream_));
+    if (!lp_copy_out(lp, 1, 1)) return false;
     HIP_OK(hipStreamSynchronize(stream_));
     return handoff_check();
 }
 
-bool Engine::generate(const SamplingParams & p, size_t n, uint32_t * tokens_out, float * logits_out) {
+bool Engine::generate(const SamplingParams & p, size_t n, uint32_t * tokens_out, float * logits_out,
+                      const LogprobsOut * lp) {
     HIP_OK(hipSetDevice(m_->device));
     if (!logits_valid_ || !tokens_out || n == 0) return false;
     SampleArgs a;
     // dtokens_ moves when the workspace grows (the graphs are dropped with it): settle it first
-    if (!ensure_workspace(1) || !sampler_buffers(p, n, a)) return false;
+    if (!ensure_workspace(1) || (lp && !lp_reserve(1, n, lp->top_k)) || !sampler_buffers(p, n, a)) return false;
     const int cur0 = cur_;
     co_retry_ = false;
-    bool ok = true;
+    bool ok = lp_begin(lp, 1, n, a);
+    const size_t K = lp ? lp->top_k : 0;
     for (size_t i = 0; ok && i < n; i++) {
         // the counter is a kernel argument of an eager launch between the decode graphs' replays:
         // nothing per step is baked into a captured node
         a.counter = p.offset + i;
         a.tok = gen_tokens_ + i;
         a.tok2 = dtokens_;
+        if (lp) {  // column i
+            a.lp_token = lp_token_ + i;
+            a.lp_top_ids = lp_ids_ + i * K;
+            a.lp_top = lp_top_ + i * K;
+        }
         if (timing_) g_klt = this;
-        ok = launch_sample(stream_, a);
+        ok = (!lp || launch_logprobs(stream_, a)) && launch_sample(stream_, a);
         g_klt = nullptr;
         ok = ok && run_tokens(nullptr, 1, true);
     }
     if (ok) {
         ok = hipMemcpyAsync(tokens_out, gen_tokens_, n * 4, hipMemcpyDeviceToHost, stream_) == hipSuccess;
         if (ok && logits_out) ok = copy_logits(logits_out);
+        ok = ok && lp_copy_out(lp, 1, n);
     }
     ok = (hipStreamSynchronize(stream_) == hipSuccess) && ok;
     ok = handoff_check() && ok;

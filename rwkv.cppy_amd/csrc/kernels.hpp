@@ -250,10 +250,24 @@ struct SampleArgs {
     // max_tokens[s] without a stop token takes one off *active as a stopped one does.
     const uint32_t * lane_seq;   // [rows]
     const uint32_t * max_tokens; // [sequences]
+    // Log-probabilities of the draw (rwkv_mi355x_logprobs; all NULL: none, and the kernels above are
+    // what runs).  A column is the index the draw's token has in tok.  launch_logprobs, in front of
+    // launch_sample on the same arguments, writes logZ = log sum exp l of every live row to
+    // lp_logz[row] and the lp_k leading (id, l - logZ) pairs to the column's lp_k entries of lp_top_ids
+    // / lp_top; the sampler (its LP form) then writes l[token] - lp_logz[row] to the column of lp_token.
+    double * lp_logz;            // [rows]
+    double * lp_token;           // one per column
+    uint32_t * lp_top_ids;       // lp_k per column
+    double * lp_top;             // lp_k per column
+    int lp_k;                    // <= LOGPROBS_MAX_TOP and <= V
 };
 constexpr int SAMPLE_MAX_STOP = 16;
+constexpr int LOGPROBS_MAX_TOP = 20;  // RWKV_MI355X_MAX_TOP_LOGPROBS
 // One workgroup per row: bias, greedy or top-p / temperature sampling (rwkv_mi355x.h).
 bool launch_sample(hipStream_t st, const SampleArgs & a);
+// One workgroup per row (logprobs.hip): logZ and the leading lp_k elements of the row the sampler is
+// about to draw from.  A row the sampler skips (finished, idle) writes nothing.  Needs lp_logz.
+bool launch_logprobs(hipStream_t st, const SampleArgs & a);
 
 // Batched generation (Engine::generate_batch; sample.hip).  Row r of a [rows][n] buffer is at r * n.
 struct GenRows {

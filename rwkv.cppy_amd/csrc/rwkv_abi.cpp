@@ -615,29 +615,73 @@ static bool sampling_ok(struct rwkv_context * ctx, const struct rwkv_mi355x_samp
     return true;
 }
 
-RWKV_API bool rwkv_mi355x_sample(struct rwkv_context * ctx, const struct rwkv_mi355x_sampling * params,
-                                 uint32_t * token_out) {
+// The checks of a rwkv_mi355x_logprobs (NULL: none asked for), the first of a call's argument checks:
+// they need nothing but the model's vocabulary.
+static bool logprobs_ok(struct rwkv_context * ctx, const struct rwkv_mi355x_logprobs * lp, LogprobsOut & out) {
+    if (!lp) return true;
+    CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, lp->top_k <= RWKV_MI355X_MAX_TOP_LOGPROBS, "top_k %" PRIu32 " is above %d",
+              lp->top_k, RWKV_MI355X_MAX_TOP_LOGPROBS);
+    CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, lp->top_k <= ctx->model->dm.n_vocab, "top_k %" PRIu32 " is above the vocabulary",
+              lp->top_k);
+    CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, lp->token_logprob != nullptr, "NULL token_logprob");
+    CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, lp->top_k == 0 || (lp->top_ids != nullptr && lp->top_logprobs != nullptr),
+              "NULL top_ids or top_logprobs with top_k > 0");
+    out.top_k = lp->top_k;
+    out.token_logprob = lp->token_logprob;
+    out.top_ids = lp->top_ids;
+    out.top_logprobs = lp->top_logprobs;
+    return true;
+}
+
+// After every argument check, the one thing that may fail before anything is enqueued: the device
+// arrays of rows * n columns.
+static bool logprobs_reserve(struct rwkv_context * ctx, const struct rwkv_mi355x_logprobs * lp, size_t rows, size_t n) {
+    if (!lp) return true;
+    use_device(ctx);
+    CTX_CHECK(ctx, RWKV_ERROR_CTX | RWKV_ERROR_ALLOC, false, ctx->engine->lp_reserve(rows, n, lp->top_k),
+              "Allocation of the log-probability arrays failed");
+    return true;
+}
+
+RWKV_API bool rwkv_mi355x_sample_logprobs(struct rwkv_context * ctx, const struct rwkv_mi355x_sampling * params,
+                                          uint32_t * token_out, const struct rwkv_mi355x_logprobs * lp) {
     if (!ctx || !ctx->engine) return false;
     ctx->last_error = RWKV_ERROR_NONE;
     SamplingParams sp;
-    if (!sampling_ok(ctx, params, sp)) return false;
+    LogprobsOut lo;
+    if (!logprobs_ok(ctx, lp, lo) || !sampling_ok(ctx, params, sp)) return false;
     CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, token_out != nullptr, "NULL token_out");
+    if (!logprobs_reserve(ctx, lp, 1, 1)) return false;
     use_device(ctx);
-    CTX_CHECK(ctx, RWKV_ERROR_CTX, false, ctx->engine->sample(sp, token_out), "GPU sampling failed");
+    CTX_CHECK(ctx, RWKV_ERROR_CTX, false, ctx->engine->sample(sp, token_out, lp ? &lo : nullptr), "GPU sampling failed");
+    return true;
+}
+
+RWKV_API bool rwkv_mi355x_sample(struct rwkv_context * ctx, const struct rwkv_mi355x_sampling * params,
+                                 uint32_t * token_out) {
+    return rwkv_mi355x_sample_logprobs(ctx, params, token_out, nullptr);
+}
+
+RWKV_API bool rwkv_mi355x_generate_logprobs(struct rwkv_context * ctx, const struct rwkv_mi355x_sampling * params,
+                                            size_t n, uint32_t * tokens_out, float * logits_out,
+                                            const struct rwkv_mi355x_logprobs * lp) {
+    if (!ctx || !ctx->engine) return false;
+    ctx->last_error = RWKV_ERROR_NONE;
+    SamplingParams sp;
+    LogprobsOut lo;
+    if (!logprobs_ok(ctx, lp, lo) || !sampling_ok(ctx, params, sp)) return false;
+    CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, n > 0 && n <= 65536, "Token count %zu is outside [1, 65536]", n);
+    CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, tokens_out != nullptr, "NULL tokens_out");
+    if (!logprobs_reserve(ctx, lp, 1, n)) return false;
+    use_device(ctx);
+    CTX_CHECK(ctx, RWKV_ERROR_CTX, false, ctx->engine->generate(sp, n, tokens_out, logits_out, lp ? &lo : nullptr),
+              "GPU generation failed");
     return true;
 }
 
 RWKV_API bool rwkv_mi355x_generate(struct rwkv_context * ctx, const struct rwkv_mi355x_sampling * params, size_t n,
                                    uint32_t * tokens_out, float * logits_out) {
-    if (!ctx || !ctx->engine) return false;
-    ctx->last_error = RWKV_ERROR_NONE;
-    SamplingParams sp;
-    if (!sampling_ok(ctx, params, sp)) return false;
-    CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, n > 0 && n <= 65536, "Token count %zu is outside [1, 65536]", n);
-    CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, tokens_out != nullptr, "NULL tokens_out");
-    use_device(ctx);
-    CTX_CHECK(ctx, RWKV_ERROR_CTX, false, ctx->engine->generate(sp, n, tokens_out, logits_out), "GPU generation failed");
-    return true;
+    return rwkv_mi355x_generate_logprobs(ctx, params, n, tokens_out, logits_out, nullptr);
 }
 
 // ---- batched generation: every check returns before any GPU call
@@ -727,11 +771,14 @@ static bool batch_sampling_ok(struct rwkv_context * ctx, size_t rows, const stru
     return true;
 }
 
-RWKV_API bool rwkv_mi355x_generate_batch(struct rwkv_context * ctx, size_t B, const struct rwkv_mi355x_batch_sampling * p,
-                                         size_t n, uint32_t * tokens_out, uint32_t * lengths_out, uint32_t * steps_out) {
+RWKV_API bool rwkv_mi355x_generate_batch_logprobs(struct rwkv_context * ctx, size_t B,
+                                                  const struct rwkv_mi355x_batch_sampling * p, size_t n,
+                                                  uint32_t * tokens_out, uint32_t * lengths_out, uint32_t * steps_out,
+                                                  const struct rwkv_mi355x_logprobs * lp) {
     if (!ctx || !ctx->engine) return false;
     ctx->last_error = RWKV_ERROR_NONE;
-    if (!batch_ctx_ok(ctx)) return false;
+    LogprobsOut lo;
+    if (!logprobs_ok(ctx, lp, lo) || !batch_ctx_ok(ctx)) return false;
     CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, B > 0 && B <= ctx->engine->batch_slots(), "Batch of %zu rows with %zu slots reserved",
               B, ctx->engine->batch_slots());
     for (size_t r = 0; r < B; r++)
@@ -741,19 +788,28 @@ RWKV_API bool rwkv_mi355x_generate_batch(struct rwkv_context * ctx, size_t B, co
     CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, tokens_out != nullptr && lengths_out != nullptr, "NULL tokens_out or lengths_out");
     BatchSamplingParams bp;
     if (!batch_sampling_ok(ctx, B, p, bp)) return false;
+    if (!logprobs_reserve(ctx, lp, B, n)) return false;
     use_device(ctx);
-    CTX_CHECK(ctx, RWKV_ERROR_CTX, false, ctx->engine->generate_batch(B, bp, n, tokens_out, lengths_out, steps_out),
+    CTX_CHECK(ctx, RWKV_ERROR_CTX, false,
+              ctx->engine->generate_batch(B, bp, n, tokens_out, lengths_out, steps_out, lp ? &lo : nullptr),
               "GPU batched generation failed");
     return true;
 }
 
-RWKV_API bool rwkv_mi355x_generate_queue(struct rwkv_context * ctx, size_t Q, size_t lanes,
-                                         const struct rwkv_mi355x_batch_sampling * p, const uint32_t * max_tokens, size_t n,
-                                         uint32_t * tokens_out, uint32_t * lengths_out, uint32_t * lane_out,
-                                         uint32_t * start_out, uint32_t * steps_out) {
+RWKV_API bool rwkv_mi355x_generate_batch(struct rwkv_context * ctx, size_t B, const struct rwkv_mi355x_batch_sampling * p,
+                                         size_t n, uint32_t * tokens_out, uint32_t * lengths_out, uint32_t * steps_out) {
+    return rwkv_mi355x_generate_batch_logprobs(ctx, B, p, n, tokens_out, lengths_out, steps_out, nullptr);
+}
+
+RWKV_API bool rwkv_mi355x_generate_queue_logprobs(struct rwkv_context * ctx, size_t Q, size_t lanes,
+                                                  const struct rwkv_mi355x_batch_sampling * p,
+                                                  const uint32_t * max_tokens, size_t n, uint32_t * tokens_out,
+                                                  uint32_t * lengths_out, uint32_t * lane_out, uint32_t * start_out,
+                                                  uint32_t * steps_out, const struct rwkv_mi355x_logprobs * lp) {
     if (!ctx || !ctx->engine) return false;
     ctx->last_error = RWKV_ERROR_NONE;
-    if (!batch_ctx_ok(ctx)) return false;
+    LogprobsOut lo;
+    if (!logprobs_ok(ctx, lp, lo) || !batch_ctx_ok(ctx)) return false;
     CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, Q > 0 && Q <= ctx->engine->batch_slots(), "Queue of %zu sequences with %zu slots reserved",
               Q, ctx->engine->batch_slots());
     CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, lanes > 0 && lanes <= (size_t)Engine::kBatchMax, "%zu lanes (1 to %d)", lanes,
@@ -770,11 +826,21 @@ RWKV_API bool rwkv_mi355x_generate_queue(struct rwkv_context * ctx, size_t Q, si
     if (!batch_sampling_ok(ctx, Q, p, bp)) return false;
     CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, p->keep_counts == 0,
               "keep_counts is not supported by the queue (continue a capped sequence with rwkv_mi355x_generate_batch)");
+    if (!logprobs_reserve(ctx, lp, Q, n)) return false;
     use_device(ctx);
     CTX_CHECK(ctx, RWKV_ERROR_CTX, false,
-              ctx->engine->generate_queue(Q, lanes, bp, max_tokens, n, tokens_out, lengths_out, lane_out, start_out, steps_out),
+              ctx->engine->generate_queue(Q, lanes, bp, max_tokens, n, tokens_out, lengths_out, lane_out, start_out, steps_out,
+                                          lp ? &lo : nullptr),
               "GPU queued generation failed");
     return true;
+}
+
+RWKV_API bool rwkv_mi355x_generate_queue(struct rwkv_context * ctx, size_t Q, size_t lanes,
+                                         const struct rwkv_mi355x_batch_sampling * p, const uint32_t * max_tokens, size_t n,
+                                         uint32_t * tokens_out, uint32_t * lengths_out, uint32_t * lane_out,
+                                         uint32_t * start_out, uint32_t * steps_out) {
+    return rwkv_mi355x_generate_queue_logprobs(ctx, Q, lanes, p, max_tokens, n, tokens_out, lengths_out, lane_out, start_out,
+                                               steps_out, nullptr);
 }
 
 RWKV_API bool rwkv_mi355x_prefill_batch(struct rwkv_context * ctx, size_t n_rows, const uint32_t * slots,

@@ -27,13 +27,11 @@
 // (generate_queue).
 #include "device_common.hpp"
 #include "kernels.hpp"
+#include "sample_row.hpp"
 
 namespace rwkvmi {
 
 namespace {
-
-constexpr int SM_THREADS = 1024, SM_REGS = 64, SM_WAVES = 16;
-constexpr int SM_MAX_ROWS = SAMPLE_MAX_VOCAB / SM_THREADS;
 
 struct SampleShared {
     uint32_t bid[SAMPLE_MAX_BIAS];
@@ -69,7 +67,11 @@ __device__ __forceinline__ float sm_block_sum(float part, SampleShared & sh, int
 // true is k_sample_rows: per-row parameters, penalties, stops and finished rows (SampleArgs); every
 // addition is behind `if constexpr (ROWS)`, so the two kernels share one copy of the arithmetic and
 // k_sample keeps the registers, LDS and occupancy it had before its sibling existed.
-template <bool ROWS>
+// LP = true (k_sample_lp, k_sample_rows_lp; launch_sample picks them when SampleArgs::lp_token is
+// set) adds one store to emit: the drawn token's log-probability, l_t - logZ, with the logZ that
+// k_logprobs (logprobs.hip) left for the row.  Nothing else differs, and the LP = false kernels are
+// the kernels they were before the flag existed.
+template <bool ROWS, bool LP>
 __device__ __forceinline__ void sample_row(const SampleArgs & a, SampleShared & sh) {
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int V = a.V, nb = a.n_bias;
@@ -78,10 +80,7 @@ __device__ __forceinline__ void sample_row(const SampleArgs & a, SampleShared & 
     const float NEG_INF = __int_as_float(0xff800000);
     int phase = 0;
     float temperature = a.temperature, top_p = a.top_p;
-    // penalties: pen is uniform over the workgroup
-    bool pen = false;
-    float presence = 0.0f, frequency = 0.0f;
-    const uint32_t * cnt_row = nullptr;
+    SmPenalty pen;
     // the sequence of this row and the index of its draw (a queue: SampleArgs::lane_seq); uniform
     uint32_t seq = blockIdx.x, at = a.step;
     if constexpr (ROWS) {
@@ -99,15 +98,18 @@ __device__ __forceinline__ void sample_row(const SampleArgs & a, SampleShared & 
         }
         if (a.temperature_r) temperature = a.temperature_r[r];
         if (a.top_p_r) top_p = a.top_p_r[r];
-        if (a.counts) {
-            if (a.presence_r) presence = a.presence_r[r];
-            if (a.frequency_r) frequency = a.frequency_r[r];
-            pen = presence != 0.0f || frequency != 0.0f;
-            cnt_row = a.counts + (size_t)r * (size_t)V;
-        }
+        sm_row_penalty(a, r, pen);
     }
+    // l_i of an element outside the registers (and of kept elements at a temperature other than 1):
+    // the same additions in the same order as the register copy below
+    auto biased = [&](int i) -> float { return sm_biased<ROWS>(lg, pen, nb, sh.bid, sh.bval, i); };
     // the one thread that holds the drawn token publishes it
     auto emit = [&](uint32_t t) {
+        if constexpr (LP) {
+            // before the count of t grows: the l the token was drawn from
+            const size_t col = !ROWS ? (size_t)blockIdx.x : a.tok_stride ? (size_t)seq * a.tok_stride + at : (size_t)seq;
+            a.lp_token[col] = (double)biased((int)t) - a.lp_logz[blockIdx.x];
+        }
         if constexpr (!ROWS) {
             a.tok[blockIdx.x] = t;
             if (a.tok2) a.tok2[blockIdx.x] = t;
@@ -132,30 +134,12 @@ __device__ __forceinline__ void sample_row(const SampleArgs & a, SampleShared & 
             }
         }
     };
-    // the penalty of SampleArgs::counts: exactly one multiply, one add, one subtract in float32
-    auto penalized = [&](float x, int i) -> float {
-        const uint32_t c = cnt_row[i];
-        return c > 0u ? __fsub_rn(x, __fadd_rn(presence, __fmul_rn((float)c, frequency))) : x;
-    };
-
     for (int j = tid; j < nb; j += SM_THREADS) {
         sh.bid[j] = a.bias_ids[j];
         sh.bval[j] = a.bias_vals[j];
     }
     if (tid == 0) sh.sel = 0x7fffffff;
     __syncthreads();
-
-    // l_i of an element outside the registers (and of kept elements at a temperature other than 1):
-    // the same additions in the same order as the register copy below
-    auto biased = [&](int i) -> float {
-        float x = lg[i];
-        if constexpr (ROWS) {
-            if (pen) x = penalized(x, i);
-        }
-        for (int j = 0; j < nb; j++)
-            if (sh.bid[j] == (uint32_t)i) x += sh.bval[j];
-        return x;
-    };
 
     float v[SM_REGS];
 #pragma unroll
@@ -165,11 +149,11 @@ __device__ __forceinline__ void sample_row(const SampleArgs & a, SampleShared & 
         v[k] = i < V ? x : NEG_INF;
     }
     if constexpr (ROWS) {
-        if (pen) {
+        if (pen.pen) {
 #pragma unroll
             for (int k = 0; k < SM_REGS; k++) {
                 const int i = k * SM_THREADS + tid;
-                if (i < V) v[k] = penalized(v[k], i);
+                if (i < V) v[k] = sm_penalized(pen, v[k], i);
             }
         }
     }
@@ -377,12 +361,22 @@ __device__ __forceinline__ void sample_row(const SampleArgs & a, SampleShared & 
 
 __global__ __launch_bounds__(SM_THREADS) void k_sample(const SampleArgs a) {
     __shared__ SampleShared sh;
-    sample_row<false>(a, sh);
+    sample_row<false, false>(a, sh);
 }
 
 __global__ __launch_bounds__(SM_THREADS) void k_sample_rows(const SampleArgs a) {
     __shared__ SampleShared sh;
-    sample_row<true>(a, sh);
+    sample_row<true, false>(a, sh);
+}
+
+__global__ __launch_bounds__(SM_THREADS) void k_sample_lp(const SampleArgs a) {
+    __shared__ SampleShared sh;
+    sample_row<false, true>(a, sh);
+}
+
+__global__ __launch_bounds__(SM_THREADS) void k_sample_rows_lp(const SampleArgs a) {
+    __shared__ SampleShared sh;
+    sample_row<true, true>(a, sh);
 }
 
 // ---- batched generation: the rows' snapshots ------------------------------------------------
@@ -540,12 +534,16 @@ bool launch_sample(hipStream_t st, const SampleArgs & a) {
     if (a.n_stop < 0 || a.n_stop > SAMPLE_MAX_STOP) return false;
     const bool rows = a.temperature_r || a.top_p_r || a.seed_r || a.counter_r || a.presence_r || a.frequency_r ||
                       a.counts || a.n_stop || a.done || a.length || a.fin_step || a.active || a.tok_stride || a.lane_seq;
+    const bool lp = a.lp_token != nullptr;
+    if (lp && !a.lp_logz) return false;  // k_logprobs leaves the row's logZ there
     if (rows) {
         if ((a.seed_r == nullptr) != (a.counter_r == nullptr)) return false;
         if (a.lane_seq && !a.length) return false;  // a queue's draw index is the sequence's length
-        RK_LAUNCH(k_sample_rows, dim3((unsigned)a.rows), dim3(SM_THREADS), 0, st, a);
+        if (lp) RK_LAUNCH(k_sample_rows_lp, dim3((unsigned)a.rows), dim3(SM_THREADS), 0, st, a);
+        else RK_LAUNCH(k_sample_rows, dim3((unsigned)a.rows), dim3(SM_THREADS), 0, st, a);
     } else {
-        RK_LAUNCH(k_sample, dim3((unsigned)a.rows), dim3(SM_THREADS), 0, st, a);
+        if (lp) RK_LAUNCH(k_sample_lp, dim3((unsigned)a.rows), dim3(SM_THREADS), 0, st, a);
+        else RK_LAUNCH(k_sample, dim3((unsigned)a.rows), dim3(SM_THREADS), 0, st, a);
     }
     HIP_OK(hipGetLastError());
     return true;

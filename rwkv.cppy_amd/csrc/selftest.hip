@@ -329,12 +329,41 @@ extern "C" RWKV_API bool rwkv_mi355x_selftest_wkv_layouts(int kind, int H, int S
     return true;
 }
 
+// The host arrays of a self-test with log-probabilities (NULL: the plain self-test): device copies,
+// uploaded before the launches and downloaded after them
+struct SelftestLogprobs {
+    uint32_t top_k;
+    double * token_logprob;
+    uint32_t * top_ids;
+    double * top_logprobs;
+    bool ok(int V) const {
+        return top_k <= (uint32_t)LOGPROBS_MAX_TOP && top_k <= (uint32_t)V && token_logprob && top_ids && top_logprobs;
+    }
+    bool up(DevBufs & b, int rows, SampleArgs & a) const {
+        const size_t R = (size_t)rows, T = R * top_k;
+        a.lp_logz = (double *)b.alloc(R * 8);
+        a.lp_token = (double *)b.alloc(R * 8);
+        a.lp_top_ids = (uint32_t *)b.alloc(T * 4 + 4);
+        a.lp_top = (double *)b.alloc(T * 8 + 8);
+        a.lp_k = (int)top_k;
+        return a.lp_logz && a.lp_token && a.lp_top_ids && a.lp_top &&
+               hipMemcpy(a.lp_token, token_logprob, R * 8, hipMemcpyHostToDevice) == hipSuccess &&
+               (!T || (hipMemcpy(a.lp_top_ids, top_ids, T * 4, hipMemcpyHostToDevice) == hipSuccess &&
+                       hipMemcpy(a.lp_top, top_logprobs, T * 8, hipMemcpyHostToDevice) == hipSuccess));
+    }
+    bool down(int rows, const SampleArgs & a) const {
+        const size_t R = (size_t)rows, T = R * top_k;
+        return hipMemcpy(token_logprob, a.lp_token, R * 8, hipMemcpyDeviceToHost) == hipSuccess &&
+               (!T || (hipMemcpy(top_ids, a.lp_top_ids, T * 4, hipMemcpyDeviceToHost) == hipSuccess &&
+                       hipMemcpy(top_logprobs, a.lp_top, T * 8, hipMemcpyDeviceToHost) == hipSuccess));
+    }
+};
+
 // The sampler kernel (sample.hip) on host logits with the uniform draws given: what
 // rwkv_mi355x_sample / _generate launch, one workgroup per row.
-extern "C" RWKV_API bool rwkv_mi355x_selftest_sample(const float * logits, int rows, int V,
-                                                    const struct rwkv_mi355x_sampling * p, const float * u,
-                                                    uint32_t * tokens, uint32_t * kept, float * cutoff) {
-    if (!logits || !p || !u || !tokens || rows < 1 || V < 1 || V > SAMPLE_MAX_VOCAB) return false;
+static bool selftest_sample(const float * logits, int rows, int V, const struct rwkv_mi355x_sampling * p, const float * u,
+                            uint32_t * tokens, uint32_t * kept, float * cutoff, const SelftestLogprobs * lp) {
+    if (!logits || !p || !u || !tokens || rows < 1 || V < 1 || V > SAMPLE_MAX_VOCAB || (lp && !lp->ok(V))) return false;
     if (!(p->temperature >= 0.0f) || !(p->top_p >= 0.0f && p->top_p <= 1.0f) || p->n_bias > (uint32_t)SAMPLE_MAX_BIAS)
         return false;
     if (p->n_bias && (!p->bias_ids || !p->bias_values)) return false;
@@ -367,21 +396,37 @@ extern "C" RWKV_API bool rwkv_mi355x_selftest_sample(const float * logits, int r
     a.bias_ids = bi;
     a.bias_vals = bv;
     a.u = du;
+    if (lp && (!lp->up(b, rows, a) || !launch_logprobs(nullptr, a))) return false;
     if (!launch_sample(nullptr, a) || hipDeviceSynchronize() != hipSuccess) return false;
     if (hipMemcpy(tokens, a.tok, (size_t)rows * 4, hipMemcpyDeviceToHost) != hipSuccess) return false;
     if (kept && hipMemcpy(kept, a.kept, (size_t)rows * 4, hipMemcpyDeviceToHost) != hipSuccess) return false;
     if (cutoff && hipMemcpy(cutoff, a.cutoff, (size_t)rows * 4, hipMemcpyDeviceToHost) != hipSuccess) return false;
-    return true;
+    return !lp || lp->down(rows, a);
+}
+
+extern "C" RWKV_API bool rwkv_mi355x_selftest_sample(const float * logits, int rows, int V,
+                                                    const struct rwkv_mi355x_sampling * p, const float * u,
+                                                    uint32_t * tokens, uint32_t * kept, float * cutoff) {
+    return selftest_sample(logits, rows, V, p, u, tokens, kept, cutoff, nullptr);
+}
+
+extern "C" RWKV_API bool rwkv_mi355x_selftest_sample_logprobs(const float * logits, int rows, int V,
+                                                             const struct rwkv_mi355x_sampling * p, const float * u,
+                                                             uint32_t * tokens, uint32_t * kept, float * cutoff,
+                                                             uint32_t top_k, double * token_logprob, uint32_t * top_ids,
+                                                             double * top_logprobs) {
+    const SelftestLogprobs lp{top_k, token_logprob, top_ids, top_logprobs};
+    return selftest_sample(logits, rows, V, p, u, tokens, kept, cutoff, &lp);
 }
 
 // The batched sampler kernel (sample.hip, k_sample_rows) on host operands: what
 // rwkv_mi355x_generate_batch launches per step, with the uniform draws given.
-extern "C" RWKV_API bool rwkv_mi355x_selftest_sample_rows(const float * logits, int rows, int V,
-                                                         const struct rwkv_mi355x_batch_sampling * p, const float * u,
-                                                         uint32_t step, uint32_t * counts, uint32_t * done,
-                                                         uint32_t * tokens, uint32_t * decode_tokens, uint32_t * kept,
-                                                         float * cutoff, uint32_t * lengths, uint32_t * active) {
+static bool selftest_sample_rows(const float * logits, int rows, int V, const struct rwkv_mi355x_batch_sampling * p,
+                                 const float * u, uint32_t step, uint32_t * counts, uint32_t * done, uint32_t * tokens,
+                                 uint32_t * decode_tokens, uint32_t * kept, float * cutoff, uint32_t * lengths,
+                                 uint32_t * active, const SelftestLogprobs * lp) {
     if (!logits || !p || !u || !done || !tokens || !decode_tokens || !kept || !cutoff || !lengths || !active) return false;
+    if (lp && (V < 1 || !lp->ok(V))) return false;
     if (rows < 1 || V < 1 || V > SAMPLE_MAX_VOCAB || !p->temperature || !p->top_p) return false;
     if (p->n_bias > (uint32_t)SAMPLE_MAX_BIAS || (p->n_bias && (!p->bias_ids || !p->bias_values))) return false;
     if (p->n_stop > (uint32_t)SAMPLE_MAX_STOP || (p->n_stop && !p->stop_tokens)) return false;
@@ -427,13 +472,34 @@ extern "C" RWKV_API bool rwkv_mi355x_selftest_sample_rows(const float * logits, 
     a.n_stop = (int)p->n_stop;
     for (uint32_t i = 0; i < p->n_stop; i++) a.stop[i] = p->stop_tokens[i];
     a.step = step;
+    if (lp && (!lp->up(b, rows, a) || !launch_logprobs(nullptr, a))) return false;
     if (!launch_sample(nullptr, a) || hipDeviceSynchronize() != hipSuccess) return false;
     const std::pair<void *, const void *> down[] = {{done, a.done},     {tokens, a.tok},     {decode_tokens, a.tok2},
                                                     {kept, a.kept},     {cutoff, a.cutoff}, {lengths, a.length}};
     for (const auto & d : down)
         if (hipMemcpy(d.first, d.second, R, hipMemcpyDeviceToHost) != hipSuccess) return false;
     if (counts && hipMemcpy(counts, a.counts, n * 4, hipMemcpyDeviceToHost) != hipSuccess) return false;
+    if (lp && !lp->down(rows, a)) return false;
     return hipMemcpy(active, a.active, 4, hipMemcpyDeviceToHost) == hipSuccess;
+}
+
+extern "C" RWKV_API bool rwkv_mi355x_selftest_sample_rows(const float * logits, int rows, int V,
+                                                         const struct rwkv_mi355x_batch_sampling * p, const float * u,
+                                                         uint32_t step, uint32_t * counts, uint32_t * done,
+                                                         uint32_t * tokens, uint32_t * decode_tokens, uint32_t * kept,
+                                                         float * cutoff, uint32_t * lengths, uint32_t * active) {
+    return selftest_sample_rows(logits, rows, V, p, u, step, counts, done, tokens, decode_tokens, kept, cutoff, lengths,
+                                active, nullptr);
+}
+
+extern "C" RWKV_API bool rwkv_mi355x_selftest_sample_rows_logprobs(
+    const float * logits, int rows, int V, const struct rwkv_mi355x_batch_sampling * p, const float * u, uint32_t step,
+    uint32_t * counts, uint32_t * done, uint32_t * tokens, uint32_t * decode_tokens, uint32_t * kept, float * cutoff,
+    uint32_t * lengths, uint32_t * active, uint32_t top_k, double * token_logprob, uint32_t * top_ids,
+    double * top_logprobs) {
+    const SelftestLogprobs lp{top_k, token_logprob, top_ids, top_logprobs};
+    return selftest_sample_rows(logits, rows, V, p, u, step, counts, done, tokens, decode_tokens, kept, cutoff, lengths,
+                                active, &lp);
 }
 
 // The queue's turnover kernel (sample.hip, k_gen_turnover) on host operands: what

@@ -149,16 +149,22 @@ class RWKVModel:
         return logits, states
 
     def sample(self, temperature: float = 1.0, top_p: float = 0.8, logit_bias=None, seed: int = 0,
-               offset: int = 0) -> int:
+               offset: int = 0, logprobs: Optional[int] = None):
         """MI355X extension (rwkv_mi355x_sample): draws one token on the device from the logits of the
         last evaluation on this model (sampling.sample_logits semantics; draw `offset` of the stream
-        `seed`, sampling.uniform).  The state is untouched."""
+        `seed`, sampling.uniform).  The state is untouched.
+
+        logprobs=K (0 <= K <= 20): returns (token, Logprobs(token_logprob, top_ids, top_logprobs)), the
+        token's log-probability under softmax(logits + bias) and the K most likely tokens with theirs
+        (sampling.logprobs), taken on the device inside the sampling step."""
         if not self._valid:
             raise ValueError('Model was freed')
-        return self._library.rwkv_mi355x_sample(self._ctx, temperature, top_p, logit_bias, seed, offset)
+        if logprobs is None:
+            return self._library.rwkv_mi355x_sample(self._ctx, temperature, top_p, logit_bias, seed, offset)
+        return self._library.rwkv_mi355x_sample(self._ctx, temperature, top_p, logit_bias, seed, offset, logprobs=logprobs)
 
     def generate(self, n: int, temperature: float = 1.0, top_p: float = 0.8, logit_bias=None, seed: int = 0,
-                 offset: int = 0, stop_tokens=(), block: int = 16) -> List[int]:
+                 offset: int = 0, stop_tokens=(), block: int = 16, logprobs: Optional[int] = None):
         """MI355X extension (rwkv_mi355x_generate): generates up to n tokens on the device, continuing
         from the state and logits the last evaluation on this model left there (eval, eval_sequence, or
         an earlier generate).  Sampling and decoding run back to back on the GPU in blocks of `block`
@@ -166,22 +172,45 @@ class RWKVModel:
 
         Generation stops after a block that contains one of stop_tokens, and the tokens up to and
         including the first stop token are returned.  The device state has then consumed the whole
-        block: it may have run up to block - 1 tokens past the stop token.  block=1 stops exactly."""
+        block: it may have run up to block - 1 tokens past the stop token.  block=1 stops exactly.
+
+        logprobs=K (0 <= K <= 20): returns (tokens, Logprobs) with one entry per returned token, cut
+        where the tokens are cut: token_logprob float64 [len], top_ids uint32 and top_logprobs float64
+        [len, K] (sampling.logprobs of every draw, taken on the device)."""
         if not self._valid:
             raise ValueError('Model was freed')
         if not block > 0:
             raise ValueError('block must be > 0')
         stop = set(stop_tokens)
         out: List[int] = []
+        parts = []
+
+        def result(tokens, last):
+            if logprobs is None:
+                return tokens
+            import numpy as np
+            # an empty block in front, so that n == 0 gives empty arrays of the right shapes
+            empty = rwkv_cpp_shared_library.make_logprobs(1, 1, logprobs)[1]
+            kept = [[x[0, :0] for x in empty]] + parts + ([last] if last is not None else [])
+            return tokens, rwkv_cpp_shared_library.Logprobs(*(np.concatenate(x) for x in zip(*kept)))
+
         while len(out) < n:
             m = min(block, n - len(out))
-            tokens = self._library.rwkv_mi355x_generate(self._ctx, m, temperature, top_p, logit_bias, seed,
-                                                        offset + len(out))
+            lp = None
+            if logprobs is None:  # the call as it always was
+                tokens = self._library.rwkv_mi355x_generate(self._ctx, m, temperature, top_p, logit_bias, seed,
+                                                            offset + len(out))
+            else:
+                tokens, lp = self._library.rwkv_mi355x_generate(self._ctx, m, temperature, top_p, logit_bias, seed,
+                                                                offset + len(out), logprobs=logprobs)
             for i, t in enumerate(tokens):
                 if t in stop:
-                    return out + tokens[:i + 1]
+                    cut = None if lp is None else rwkv_cpp_shared_library.Logprobs(*(x[:i + 1] for x in lp))
+                    return result(out + tokens[:i + 1], cut)
             out += tokens
-        return out
+            if lp is not None:
+                parts.append(lp)
+        return result(out, None)
 
     # ---- batched generation (rwkv_mi355x_generate_batch) --------------------------------------
     def batch_reserve(self, n_slots: int) -> None:
@@ -236,7 +265,7 @@ class RWKVModel:
 
     def generate_batch(self, prompts: List[List[int]], n: int, temperature=1.0, top_p=0.8, presence_penalty=0.0,
                        frequency_penalty=0.0, logit_bias=None, seeds=None, stop_tokens=(),
-                       check_every: int = 16, batched_prefill: bool = False) -> List[List[int]]:
+                       check_every: int = 16, batched_prefill: bool = False, logprobs: Optional[int] = None):
         """MI355X extension (rwkv_mi355x_generate_batch): generates up to n tokens for every prompt, all
         rows together on the device: sampling, penalties over the tokens a row has drawn, exact stops
         and one batched decode step per token, with only the tokens coming back.  temperature, top_p,
@@ -245,7 +274,12 @@ class RWKVModel:
         device and stored into slot i (slots are reserved as needed); batched_prefill evaluates the
         prompts together (prefill_batch) instead of one after the other, with the same bits.  Returns one token list per
         prompt; a list that ends early ends with a stop token, which is not evaluated: slot i then
-        holds the state before it, and batch_load(i) continues from there."""
+        holds the state before it, and batch_load(i) continues from there.
+
+        logprobs=K (0 <= K <= 20): returns (token lists, [Logprobs per prompt]); prompt i's Logprobs
+        has one entry per token of its list, the stop token included: token_logprob float64 [len],
+        top_ids uint32 and top_logprobs float64 [len, K], of the penalised and biased distribution each
+        token was drawn from (sampling.logprobs)."""
         if not self._valid:
             raise ValueError('Model was freed')
         rows = len(prompts)
@@ -266,19 +300,27 @@ class RWKVModel:
             self.reset_state()
             self._library.rwkv_mi355x_eval_device(self._ctx, list(prompt))
             self._library.rwkv_mi355x_batch_store(self._ctx, slot)
-        tokens, lengths, _ = self._library.rwkv_mi355x_generate_batch(self._ctx, rows, n, params)
-        return [[int(t) for t in tokens[r][:int(lengths[r])]] for r in range(rows)]
+        if logprobs is None:  # the call as it always was
+            out = self._library.rwkv_mi355x_generate_batch(self._ctx, rows, n, params)
+        else:
+            out = self._library.rwkv_mi355x_generate_batch(self._ctx, rows, n, params, logprobs=logprobs)
+        tokens, lengths = out[0], out[1]
+        lists = [[int(t) for t in tokens[r][:int(lengths[r])]] for r in range(rows)]
+        if logprobs is None:
+            return lists
+        return lists, [rwkv_cpp_shared_library.Logprobs(*(x[r, :int(lengths[r])] for x in out[3])) for r in range(rows)]
 
     def generate_queue(self, prompts: List[List[int]], max_tokens, lanes: int = 32, temperature=1.0, top_p=0.8,
                        presence_penalty=0.0, frequency_penalty=0.0, logit_bias=None, seeds=None, stop_tokens=(),
-                       check_every: int = 16) -> List[List[int]]:
+                       check_every: int = 16, logprobs: Optional[int] = None):
         """MI355X extension (rwkv_mi355x_generate_queue): continuous batching.  Up to 256 prompts are
         evaluated together (prefill_batch) into slots 0 .. Q-1 and generated through a queue over
         `lanes` decode rows: a row whose sequence has ended -- a stop token, or its max_tokens (a scalar
         or one value per prompt) -- takes the next waiting prompt between two decode steps, so the rows
         stay full.  The other parameters are those of generate_batch, per prompt.  Returns one token
         list per prompt, each exactly what that prompt generates alone; slot i holds its final state
-        and logits, and batch_load(i) continues from there."""
+        and logits, and batch_load(i) continues from there.  logprobs=K: as generate_batch, (token
+        lists, [Logprobs per prompt])."""
         if not self._valid:
             raise ValueError('Model was freed')
         rows = len(prompts)
@@ -297,10 +339,15 @@ class RWKVModel:
         if self._library.rwkv_mi355x_batch_slots(self._ctx) < rows:
             self._library.rwkv_mi355x_batch_reserve(self._ctx, rows)
         self._library.rwkv_mi355x_prefill_batch(self._ctx, [list(p) for p in prompts], list(range(rows)), None)
+        extra = {} if logprobs is None else {'logprobs': logprobs}
         out = self._library.rwkv_mi355x_generate_queue(
             self._ctx, caps, lanes, temperature, top_p, presence_penalty, frequency_penalty, logit_bias, seeds, 0,
-            stop_tokens, check_every)
-        return [[int(t) for t in out['tokens'][r][:int(out['lengths'][r])]] for r in range(rows)]
+            stop_tokens, check_every, **extra)
+        lists = [[int(t) for t in out['tokens'][r][:int(out['lengths'][r])]] for r in range(rows)]
+        if logprobs is None:
+            return lists
+        return lists, [rwkv_cpp_shared_library.Logprobs(*(x[r, :len(lists[r])] for x in out['logprobs']))
+                       for r in range(rows)]
 
     def reset_state(self) -> None:
         """MI355X extension (rwkv_mi355x_state_upload with NULL): the device-resident state becomes the

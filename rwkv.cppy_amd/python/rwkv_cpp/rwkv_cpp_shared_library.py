@@ -7,6 +7,7 @@ against the reference run unchanged.  Argument types match the reference binding
 (rwkv_cpp_shared_library.py:49-107): tokens are passed as int32 (same bits as uint32).
 The additive rwkv_mi355x_* entry points (include/rwkv_mi355x.h) are bound too.
 """
+import collections
 import ctypes
 import os
 import pathlib
@@ -56,6 +57,37 @@ class RWKVBatchSampling(ctypes.Structure):
                 ('n_bias', ctypes.c_uint32), ('bias_ids', ctypes.POINTER(ctypes.c_uint32)), ('bias_values', P_FLOAT),
                 ('n_stop', ctypes.c_uint32), ('stop_tokens', ctypes.POINTER(ctypes.c_uint32)),
                 ('keep_counts', ctypes.c_uint32), ('check_every', ctypes.c_uint32)]
+
+
+class RWKVLogprobs(ctypes.Structure):
+    """struct rwkv_mi355x_logprobs (include/rwkv_mi355x.h)."""
+    _fields_ = [('top_k', ctypes.c_uint32), ('token_logprob', ctypes.POINTER(ctypes.c_double)),
+                ('top_ids', ctypes.POINTER(ctypes.c_uint32)), ('top_logprobs', ctypes.POINTER(ctypes.c_double))]
+
+
+# What a call with logprobs=K returns besides its tokens: the drawn tokens' log-probabilities
+# (float64 [n]) and the K most likely alternatives of every draw (uint32 / float64 [n, K]).
+Logprobs = collections.namedtuple('Logprobs', ('token_logprob', 'top_ids', 'top_logprobs'))
+
+MAX_TOP_LOGPROBS = 20
+
+
+def make_logprobs(rows: int, n: int, top_k: int):
+    """Host arrays [rows, n] (and [rows, n, top_k]) for a call with log-probabilities and the
+    RWKVLogprobs pointing at them.  The arrays start as a pattern the library never writes (0xA5
+    bytes); the library fills every column: drawn values, or its own fill (0xFF bytes) elsewhere."""
+    import numpy as np
+    top_k = int(top_k)
+    if not 0 <= top_k <= MAX_TOP_LOGPROBS:
+        raise ValueError(f'logprobs must be in [0, {MAX_TOP_LOGPROBS}]')
+    arrays = Logprobs(np.full((rows, n), 0xA5A5A5A5A5A5A5A5, np.uint64).view(np.float64),
+                      np.full((rows, n, top_k), 0xA5A5A5A5, np.uint32),
+                      np.full((rows, n, top_k), 0xA5A5A5A5A5A5A5A5, np.uint64).view(np.float64))
+    lp = RWKVLogprobs(top_k, arrays.token_logprob.ctypes.data_as(ctypes.POINTER(ctypes.c_double)),
+                      arrays.top_ids.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)),
+                      arrays.top_logprobs.ctypes.data_as(ctypes.POINTER(ctypes.c_double)))
+    lp._keep = arrays
+    return lp, arrays
 
 
 def _per_row(value, rows: int, name: str) -> list:
@@ -251,7 +283,17 @@ class RWKVSharedLibrary:
         L.rwkv_mi355x_selftest_sample_rows.argtypes = [P_FLOAT, ctypes.c_int, ctypes.c_int, P_BATCH, P_FLOAT, u32, P_U32,
                                                        P_U32, P_U32, P_U32, P_U32, P_FLOAT, P_U32, P_U32]
         L.rwkv_mi355x_selftest_sample_rows.restype = ctypes.c_bool
-        P_DOUBLE = ctypes.POINTER(ctypes.c_double)
+        P_DOUBLE, P_LP = ctypes.POINTER(ctypes.c_double), ctypes.POINTER(RWKVLogprobs)
+        L.rwkv_mi355x_sample_logprobs.argtypes = L.rwkv_mi355x_sample.argtypes + [P_LP]
+        L.rwkv_mi355x_generate_logprobs.argtypes = L.rwkv_mi355x_generate.argtypes + [P_LP]
+        L.rwkv_mi355x_generate_batch_logprobs.argtypes = L.rwkv_mi355x_generate_batch.argtypes + [P_LP]
+        L.rwkv_mi355x_generate_queue_logprobs.argtypes = L.rwkv_mi355x_generate_queue.argtypes + [P_LP]
+        L.rwkv_mi355x_selftest_sample_logprobs.argtypes = L.rwkv_mi355x_selftest_sample.argtypes + [
+            u32, P_DOUBLE, P_U32, P_DOUBLE]
+        L.rwkv_mi355x_selftest_sample_rows_logprobs.argtypes = L.rwkv_mi355x_selftest_sample_rows.argtypes + [
+            u32, P_DOUBLE, P_U32, P_DOUBLE]
+        for name in ('sample', 'generate', 'generate_batch', 'generate_queue', 'selftest_sample', 'selftest_sample_rows'):
+            getattr(L, f'rwkv_mi355x_{name}_logprobs').restype = ctypes.c_bool
         L.rwkv_mi355x_score_sequence.argtypes = [vp, P_U32, sz, P_U32, P_DOUBLE, P_U32, P_FLOAT]
         L.rwkv_mi355x_score_sequence.restype = ctypes.c_bool
         L.rwkv_mi355x_selftest_xent.argtypes = [P_FLOAT, ctypes.c_int, ctypes.c_int, P_U32, P_DOUBLE, P_U32]
@@ -350,30 +392,46 @@ class RWKVSharedLibrary:
 
     # ---- additive: sampling and the generation loop on the device ---------------------------
     def rwkv_mi355x_sample(self, ctx: RWKVContext, temperature: float = 1.0, top_p: float = 0.8, logit_bias=None,
-                           seed: int = 0, offset: int = 0) -> int:
+                           seed: int = 0, offset: int = 0, logprobs: Optional[int] = None):
         """One token drawn on the device from the context's logits (draw `offset` of stream `seed`);
-        the state is untouched."""
+        the state is untouched.  logprobs=K (rwkv_mi355x_sample_logprobs): returns (token, Logprobs)
+        with the token's log-probability (a float) and the K most likely alternatives ([K] arrays)."""
         token = ctypes.c_uint32(0)
         p = make_sampling(temperature, top_p, logit_bias, seed, offset)
-        if not self.library.rwkv_mi355x_sample(ctx.ptr, ctypes.byref(p), ctypes.byref(token)):
-            raise ValueError('rwkv_mi355x_sample failed, check stderr')
-        return token.value
+        if logprobs is None:
+            if not self.library.rwkv_mi355x_sample(ctx.ptr, ctypes.byref(p), ctypes.byref(token)):
+                raise ValueError('rwkv_mi355x_sample failed, check stderr')
+            return token.value
+        lp, out = make_logprobs(1, 1, logprobs)
+        if not self.library.rwkv_mi355x_sample_logprobs(ctx.ptr, ctypes.byref(p), ctypes.byref(token), ctypes.byref(lp)):
+            raise ValueError('rwkv_mi355x_sample_logprobs failed, check stderr')
+        return token.value, Logprobs(float(out.token_logprob[0, 0]), out.top_ids[0, 0], out.top_logprobs[0, 0])
 
     def rwkv_mi355x_generate(self, ctx: RWKVContext, n: int, temperature: float = 1.0, top_p: float = 0.8,
                              logit_bias=None, seed: int = 0, offset: int = 0,
-                             logits_out_address: Optional[int] = None) -> List[int]:
+                             logits_out_address: Optional[int] = None, logprobs: Optional[int] = None):
         """n times (draw a token on the device, evaluate it) without a host round trip; returns the
-        tokens.  Draw i uses counter offset + i, so a call with offset + n continues the stream."""
+        tokens.  Draw i uses counter offset + i, so a call with offset + n continues the stream.
+        logprobs=K (rwkv_mi355x_generate_logprobs): returns (tokens, Logprobs of [n] / [n, K] arrays)."""
         tokens = (ctypes.c_uint32 * max(1, n))()
         p = make_sampling(temperature, top_p, logit_bias, seed, offset)
-        if not self.library.rwkv_mi355x_generate(ctx.ptr, ctypes.byref(p), n, tokens,
-                                                 ctypes.cast(logits_out_address or 0, P_FLOAT)):
-            raise ValueError('rwkv_mi355x_generate failed, check stderr')
-        return list(tokens[:n])
+        logits_out = ctypes.cast(logits_out_address or 0, P_FLOAT)
+        if logprobs is None:
+            if not self.library.rwkv_mi355x_generate(ctx.ptr, ctypes.byref(p), n, tokens, logits_out):
+                raise ValueError('rwkv_mi355x_generate failed, check stderr')
+            return list(tokens[:n])
+        lp, out = make_logprobs(1, max(1, n), logprobs)
+        if not self.library.rwkv_mi355x_generate_logprobs(ctx.ptr, ctypes.byref(p), n, tokens, logits_out,
+                                                          ctypes.byref(lp)):
+            raise ValueError('rwkv_mi355x_generate_logprobs failed, check stderr')
+        return list(tokens[:n]), Logprobs(*(x[0, :n] for x in out))
 
-    def rwkv_mi355x_selftest_sample(self, logits, u, temperature: float = 1.0, top_p: float = 0.8, logit_bias=None):
+    def rwkv_mi355x_selftest_sample(self, logits, u, temperature: float = 1.0, top_p: float = 0.8, logit_bias=None,
+                                    logprobs: Optional[int] = None, fill: int = 0xA5):
         """The sampler kernel on host logits [rows][V] (float32 numpy) with the draws u [rows] given.
-        Returns (tokens, kept, cutoff) numpy arrays [rows]."""
+        Returns (tokens, kept, cutoff) numpy arrays [rows].  logprobs=K
+        (rwkv_mi355x_selftest_sample_logprobs): a fourth element, Logprobs of [rows] / [rows, K] arrays
+        that start as bytes of `fill`, so an entry the kernels do not write keeps them."""
         import numpy as np
         logits = np.ascontiguousarray(logits, dtype=np.float32)
         if logits.ndim == 1:
@@ -383,11 +441,28 @@ class RWKVSharedLibrary:
         tokens, kept, cutoff = np.zeros(rows, np.uint32), np.zeros(rows, np.uint32), np.zeros(rows, np.float32)
         p = make_sampling(temperature, top_p, logit_bias)
         P_U32 = ctypes.POINTER(ctypes.c_uint32)
-        if not self.library.rwkv_mi355x_selftest_sample(
-                logits.ctypes.data_as(P_FLOAT), rows, V, ctypes.byref(p), u.ctypes.data_as(P_FLOAT),
-                tokens.ctypes.data_as(P_U32), kept.ctypes.data_as(P_U32), cutoff.ctypes.data_as(P_FLOAT)):
-            raise ValueError('rwkv_mi355x_selftest_sample failed')
-        return tokens, kept, cutoff
+        args = (logits.ctypes.data_as(P_FLOAT), rows, V, ctypes.byref(p), u.ctypes.data_as(P_FLOAT),
+                tokens.ctypes.data_as(P_U32), kept.ctypes.data_as(P_U32), cutoff.ctypes.data_as(P_FLOAT))
+        if logprobs is None:
+            if not self.library.rwkv_mi355x_selftest_sample(*args):
+                raise ValueError('rwkv_mi355x_selftest_sample failed')
+            return tokens, kept, cutoff
+        lp = self._selftest_logprobs(rows, logprobs, fill)
+        if not self.library.rwkv_mi355x_selftest_sample_logprobs(*args, *lp[0]):
+            raise ValueError('rwkv_mi355x_selftest_sample_logprobs failed')
+        return tokens, kept, cutoff, lp[1]
+
+    @staticmethod
+    def _selftest_logprobs(rows: int, top_k: int, fill: int):
+        """The four trailing arguments of the *_logprobs self-tests and the Logprobs they fill."""
+        import numpy as np
+        out = Logprobs(np.full(rows * 8, fill, np.uint8).view(np.float64),
+                       np.full(rows * max(1, top_k) * 4, fill, np.uint8).view(np.uint32).reshape(rows, -1),
+                       np.full(rows * max(1, top_k) * 8, fill, np.uint8).view(np.float64).reshape(rows, -1))
+        P_U32, P_DOUBLE = ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_double)
+        args = (top_k, out.token_logprob.ctypes.data_as(P_DOUBLE), out.top_ids.ctypes.data_as(P_U32),
+                out.top_logprobs.ctypes.data_as(P_DOUBLE))
+        return args, Logprobs(out.token_logprob, out.top_ids[:, :top_k], out.top_logprobs[:, :top_k])
 
     def rwkv_mi355x_eval_device(self, ctx: RWKVContext, tokens: List[int], compute_logits: bool = True) -> None:
         """Evaluates the tokens on the device-resident state (the logits stay on the device);
@@ -416,27 +491,38 @@ class RWKVSharedLibrary:
         if not self.library.rwkv_mi355x_batch_load(ctx.ptr, slot):
             raise ValueError('rwkv_mi355x_batch_load failed, check stderr')
 
-    def rwkv_mi355x_generate_batch(self, ctx: RWKVContext, rows: int, n: int, params: RWKVBatchSampling):
+    def rwkv_mi355x_generate_batch(self, ctx: RWKVContext, rows: int, n: int, params: RWKVBatchSampling,
+                                   logprobs: Optional[int] = None):
         """Up to n tokens for each of slots [0, rows) (make_batch_sampling).  Returns (tokens uint32
-        [rows, n], 0xFFFFFFFF after a row's last token; lengths uint32 [rows]; the decode steps run)."""
+        [rows, n], 0xFFFFFFFF after a row's last token; lengths uint32 [rows]; the decode steps run).
+        logprobs=K (rwkv_mi355x_generate_batch_logprobs): a fourth element, Logprobs of [rows, n] /
+        [rows, n, K] arrays whose columns past a row's length hold the fill (NaN, 0xFFFFFFFF)."""
         import numpy as np
         tokens = np.zeros((rows, max(1, n)), np.uint32)
         lengths = np.zeros(rows, np.uint32)
         steps = ctypes.c_uint32(0)
         P_U32 = ctypes.POINTER(ctypes.c_uint32)
-        if not self.library.rwkv_mi355x_generate_batch(ctx.ptr, rows, ctypes.byref(params), n,
-                                                       tokens.ctypes.data_as(P_U32), lengths.ctypes.data_as(P_U32),
-                                                       ctypes.byref(steps)):
-            raise ValueError('rwkv_mi355x_generate_batch failed, check stderr')
-        return tokens[:, :n], lengths, steps.value
+        args = (ctx.ptr, rows, ctypes.byref(params), n, tokens.ctypes.data_as(P_U32), lengths.ctypes.data_as(P_U32),
+                ctypes.byref(steps))
+        if logprobs is None:
+            if not self.library.rwkv_mi355x_generate_batch(*args):
+                raise ValueError('rwkv_mi355x_generate_batch failed, check stderr')
+            return tokens[:, :n], lengths, steps.value
+        lp, out = make_logprobs(rows, max(1, n), logprobs)
+        if not self.library.rwkv_mi355x_generate_batch_logprobs(*args, ctypes.byref(lp)):
+            raise ValueError('rwkv_mi355x_generate_batch_logprobs failed, check stderr')
+        return tokens[:, :n], lengths, steps.value, Logprobs(*(x[:, :n] for x in out))
 
     def rwkv_mi355x_generate_queue(self, ctx: RWKVContext, max_tokens, lanes: int, temperature=1.0, top_p=0.8,
                                    presence=None, frequency=None, logit_bias=None, seeds=None, offsets=0,
-                                   stop_tokens=(), check_every: int = 0, n: Optional[int] = None):
+                                   stop_tokens=(), check_every: int = 0, n: Optional[int] = None,
+                                   logprobs: Optional[int] = None):
         """The sequences in slots [0, len(max_tokens)) through a queue over `lanes` decode rows, at most
         max_tokens[s] tokens each (make_batch_sampling over the sequences, keep_counts false).  Returns
         a dict: tokens uint32 [Q, n] (n: max(max_tokens) unless given; 0xFFFFFFFF after a sequence's
-        last token), lengths, lane, start uint32 [Q] and steps, the decode steps that were needed."""
+        last token), lengths, lane, start uint32 [Q] and steps, the decode steps that were needed.
+        logprobs=K (rwkv_mi355x_generate_queue_logprobs) adds 'logprobs': Logprobs of [Q, n] / [Q, n, K]
+        arrays."""
         import numpy as np
         caps = np.ascontiguousarray(max_tokens, dtype=np.uint32)
         Q = int(caps.size)
@@ -447,11 +533,17 @@ class RWKVSharedLibrary:
         tokens = np.zeros((Q, max(1, n)), np.uint32)
         steps = ctypes.c_uint32(0)
         P_U32 = ctypes.POINTER(ctypes.c_uint32)
-        if not self.library.rwkv_mi355x_generate_queue(ctx.ptr, Q, lanes, ctypes.byref(params), caps.ctypes.data_as(P_U32),
-                                                       n, tokens.ctypes.data_as(P_U32), out['lengths'].ctypes.data_as(P_U32),
-                                                       out['lane'].ctypes.data_as(P_U32), out['start'].ctypes.data_as(P_U32),
-                                                       ctypes.byref(steps)):
-            raise ValueError('rwkv_mi355x_generate_queue failed, check stderr')
+        args = (ctx.ptr, Q, lanes, ctypes.byref(params), caps.ctypes.data_as(P_U32), n, tokens.ctypes.data_as(P_U32),
+                out['lengths'].ctypes.data_as(P_U32), out['lane'].ctypes.data_as(P_U32),
+                out['start'].ctypes.data_as(P_U32), ctypes.byref(steps))
+        if logprobs is None:
+            if not self.library.rwkv_mi355x_generate_queue(*args):
+                raise ValueError('rwkv_mi355x_generate_queue failed, check stderr')
+        else:
+            lp, arrays = make_logprobs(Q, max(1, n), logprobs)
+            if not self.library.rwkv_mi355x_generate_queue_logprobs(*args, ctypes.byref(lp)):
+                raise ValueError('rwkv_mi355x_generate_queue_logprobs failed, check stderr')
+            out['logprobs'] = Logprobs(*(x[:, :n] for x in arrays))
         out['tokens'] = tokens[:, :n]
         out['steps'] = steps.value
         return out
@@ -511,12 +603,15 @@ class RWKVSharedLibrary:
 
     def rwkv_mi355x_selftest_sample_rows(self, logits, u, temperature, top_p, presence=None, frequency=None,
                                          counts=None, done=None, logit_bias=None, stop_tokens=(), step: int = 0,
-                                         fill: int = 0xFFFFFFFF, active: Optional[int] = None):
+                                         fill: int = 0xFFFFFFFF, active: Optional[int] = None,
+                                         logprobs: Optional[int] = None, lp_fill: int = 0xA5):
         """The batched sampler kernel on host logits [rows][V] with the draws u [rows] given and
         per-row parameters (scalars or [rows]).  counts (uint32 [rows][V]) and done (uint32 [rows]) are
         updated in place when given.  Every output starts as `fill` (cutoff: its bits), so an entry
         the kernel does not write keeps it.  Returns a dict: tokens, decode_tokens, kept, cutoff,
-        lengths, done [rows] and active (the live rows, starting from `active`, default rows)."""
+        lengths, done [rows] and active (the live rows, starting from `active`, default rows).
+        logprobs=K (rwkv_mi355x_selftest_sample_rows_logprobs) adds 'logprobs': Logprobs of [rows] /
+        [rows, K] arrays that start as bytes of `lp_fill`."""
         import numpy as np
         logits = np.ascontiguousarray(logits, dtype=np.float32)
         rows, V = logits.shape
@@ -530,13 +625,19 @@ class RWKVSharedLibrary:
         out = {k: np.full(rows, fill, np.uint32) for k in ('tokens', 'decode_tokens', 'kept', 'cutoff', 'lengths')}
         act = np.array([rows if active is None else active], np.uint32)
         P_U32 = ctypes.POINTER(ctypes.c_uint32)
-        if not self.library.rwkv_mi355x_selftest_sample_rows(
-                logits.ctypes.data_as(P_FLOAT), rows, V, ctypes.byref(p), u.ctypes.data_as(P_FLOAT), step,
+        args = (logits.ctypes.data_as(P_FLOAT), rows, V, ctypes.byref(p), u.ctypes.data_as(P_FLOAT), step,
                 counts.ctypes.data_as(P_U32) if counts is not None else None, done.ctypes.data_as(P_U32),
                 out['tokens'].ctypes.data_as(P_U32), out['decode_tokens'].ctypes.data_as(P_U32),
                 out['kept'].ctypes.data_as(P_U32), out['cutoff'].ctypes.data_as(P_FLOAT),
-                out['lengths'].ctypes.data_as(P_U32), act.ctypes.data_as(P_U32)):
-            raise ValueError('rwkv_mi355x_selftest_sample_rows failed')
+                out['lengths'].ctypes.data_as(P_U32), act.ctypes.data_as(P_U32))
+        if logprobs is None:
+            if not self.library.rwkv_mi355x_selftest_sample_rows(*args):
+                raise ValueError('rwkv_mi355x_selftest_sample_rows failed')
+        else:
+            lp = self._selftest_logprobs(rows, logprobs, lp_fill)
+            if not self.library.rwkv_mi355x_selftest_sample_rows_logprobs(*args, *lp[0]):
+                raise ValueError('rwkv_mi355x_selftest_sample_rows_logprobs failed')
+            out['logprobs'] = lp[1]
         out['cutoff'] = out['cutoff'].view(np.float32)
         out['done'] = done
         out['active'] = int(act[0])

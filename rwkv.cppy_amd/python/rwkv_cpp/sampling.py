@@ -81,6 +81,37 @@ def penalize(logits, counts, presence: float, frequency: float) -> np.ndarray:
     return l
 
 
+def logprobs(l, top_k: int):
+    """The log-probabilities librwkv.so reports for one draw (rwkv_mi355x_logprobs), in float64 numpy;
+    the specification the device kernels are measured against.
+
+    l is the float32 row the sampler samples from: the logits, then penalize() with the counts before
+    this draw's increment, then the bias.  Temperature and top-p do not enter: this is softmax(l).
+      m      = max l, exact in float32 (a NaN never wins)
+      S      = sum_i exp(float64(l_i) - float64(m)), exponentials and sum in float64
+      logZ   = float64(m) + log(S)
+      token_logprob   = float64(l[token]) - logZ         (the caller subtracts: it knows the token)
+      top_ids[0 .. K) = the K first indices in the order "larger l first, lower index first among
+                        equal l", exact float32 compares; NaN elements are never listed, so fewer
+                        than K come back when fewer than K elements are not NaN
+      top_logprobs[j] = float64(l[top_ids[j]]) - logZ, with the same logZ: where the drawn token is
+                        top_ids[j] the two values are bit-equal.
+    Non-finite elements may make the values NaN or infinite.  The device fixes the association of the
+    sum (it is a pure function of its inputs); this one is numpy's, and the two differ by at most
+    V * 2**-53 relative in S, whatever the association, since every term is non-negative.
+    Returns (logZ float64, top_ids uint32 [<= top_k], top_logprobs float64 [<= top_k])."""
+    l32 = np.asarray(l, dtype=np.float32)
+    if l32.ndim != 1 or not 0 <= top_k <= l32.size:
+        raise ValueError('one row of logits and 0 <= top_k <= its length')
+    ld = l32.astype(np.float64)
+    listed = np.flatnonzero(~np.isnan(l32))
+    with np.errstate(all='ignore'):
+        m = ld[listed].max() if listed.size else -np.inf
+        log_z = m + np.log(np.exp(ld - m).sum())
+        top = listed[np.argsort(-l32[listed], kind='stable')][:top_k]
+        return float(log_z), top.astype(np.uint32), ld[top] - log_z
+
+
 def queue_schedule(lengths, lanes: int):
     """The schedule of librwkv.so's queue (rwkv_mi355x_generate_queue) on plain integers: sequence s
     occupies a lane for lengths[s] >= 1 steps.  Before step i the lanes whose sequence has had its
