@@ -81,6 +81,30 @@ struct Workspace {
     bool alloc(size_t cap, size_t C, size_t kmax, size_t H);
 };
 
+// The words a generation call drives on the device, as views of one allocation (GenSlots::gwords_).
+// bind() is the layout: the arrays follow one another in the order of the members, K words each,
+// `active` and `next` one word each.  Nothing else computes an address in gwords_.
+struct GenWords {
+    // every call (SampleArgs, GenRows): per sequence; active = the sequences not yet ended
+    uint32_t *done = nullptr, *length = nullptr, *fin_step = nullptr, *active = nullptr;
+    // the queue's (GenQueue): max_tokens per sequence; the table lane_seq per lane; lane, start per
+    // sequence; retire_to, admit_from per lane; next = the first waiting sequence
+    uint32_t *max_tokens = nullptr, *lane_seq = nullptr, *lane = nullptr, *start = nullptr, *retire_to = nullptr,
+             *admit_from = nullptr, *next = nullptr;
+    // points the members into base (NULL: nowhere) and returns the words the layout takes
+    size_t bind(uint32_t * base, size_t K) {
+        size_t at = 0;
+        auto take = [&](uint32_t *& p, size_t n) {
+            p = base ? base + at : nullptr;
+            at += n;
+        };
+        take(done, K), take(length, K), take(fin_step, K), take(active, 1);
+        take(max_tokens, K), take(lane_seq, K), take(lane, K), take(start, K), take(retire_to, K), take(admit_from, K);
+        take(next, 1);
+        return at;
+    }
+};
+
 // The generation slots' buffers (Engine::batch_reserve), replaced as a whole in the same way: the
 // live states [2][slots][state_len] (slots are stored in and loaded from gstate_[0]; the batched step
 // alternates the two) and one fresh state behind them, all one allocation, so that a prefill's segment
@@ -93,10 +117,8 @@ struct GenSlots {
     DevBuf<uint32_t> gcounts_;
     DevBuf<float> gparams_;      // temperature, top_p, presence, frequency: [4][kBatchMax]
     DevBuf<uint64_t> gstreams_;  // seed, offset: [2][kBatchMax]
-    // done, length, fin_step: [3][kBatchMax], active; then the queue's words (generate_queue):
-    // max_tokens, lane_seq, lane, start, retire_to, admit_from: [6][kBatchMax], next
     DevBuf<uint32_t> gwords_;
-    static constexpr size_t kWordRows = 9;  // arrays of batch_max words; two single words besides
+    GenWords gw_;  // views of gwords_
     bool alloc(size_t n_slots, size_t state_len, size_t n_vocab, size_t batch_max);
 };
 
@@ -504,12 +526,22 @@ class Engine : public KLaunchTimer, private Workspace, private GenSlots {
     std::vector<uint64_t> gstreams_h_;
     std::vector<uint32_t> gqueue_h_;  // max_tokens up, start down (generate_queue)
     void free_slots();
-    // the shared pieces of generate_batch and generate_queue: the per-row arrays of `rows` rows to the
-    // device and the token buffer [rows][n] set to 0xFFFFFFFF; the sampler's arguments for them; the
-    // way out after a failure (the stream drained, slots [0, rows) invalid)
-    bool gen_upload(size_t rows, const BatchSamplingParams & p, size_t n);
+    // generate_batch and generate_queue are one driver (engine_batch.hip): sequences [0, Q) over the
+    // rows of a batched step; with a QueueCall the rows are lanes the sequences pass through
+    struct QueueCall {
+        size_t lanes;
+        const uint32_t * max_tokens;
+        uint32_t *lane_out, *start_out;
+    };
+    bool generate_slots(size_t Q, const BatchSamplingParams & p, size_t n, uint32_t * tokens_out, uint32_t * lengths_out,
+                        uint32_t * steps_out, const LogprobsOut * lp, const QueueCall * qc);
+    // the per-sequence arrays of Q sequences to the device and the token buffer [Q][n] set to
+    // 0xFFFFFFFF; the sampler's arguments for `rows` rows
+    bool gen_upload(size_t Q, const BatchSamplingParams & p, size_t n);
     SampleArgs gen_sample_args(size_t rows, const BatchSamplingParams & p, size_t n);
-    bool gen_fail(size_t rows);
+    // the one way out of a call on slots[0 .. n) (NULL: slots 0 .. n - 1) that fails after its first
+    // enqueue: the stream drained, the hand-off checked, the slots invalid.  Returns false.
+    bool slots_fail(size_t n, const uint32_t * slots = nullptr);
     // rwkv_eval with host state buffers: the decode as io_chunk_-layer graphs with the state
     // copies of other chunks overlapped (eval_host_chunked)
     bool io_pipeline_ = true;

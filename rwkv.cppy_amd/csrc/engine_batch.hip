@@ -99,13 +99,6 @@ void Engine::drop_batch_graphs() {
     bgraphs_.clear();
 }
 
-// Slots [0, B) of the context generate together: per step one k_sample_rows launch over the slots'
-// logits (per-row parameters, penalties, stops), k_gen_snapshot of the rows that just stopped, and
-// one batched decode step (eval_batch, tokens already in dtokens_) from gstate_[p] to gstate_[p ^ 1].
-// A finished row keeps being decoded on token 0 -- the batched kernels take row t's state at
-// t * state_len, so leaving a row out would need a per-row offset through every one of them -- and
-// its live state and logits are garbage from then on; what the caller sees is the snapshot, which
-// k_gen_restore puts back into gstate_[0] / glogits_ at the end of the call.
 void Engine::free_slots() {
     static_cast<GenSlots &>(*this) = GenSlots{};
     gslots_ = 0;
@@ -117,9 +110,12 @@ bool GenSlots::alloc(size_t n_slots, size_t state_len, size_t n_vocab, size_t ba
     gstate_[0] = gstates_;
     gstate_[1] = gstates_ + n_slots * state_len;
     gfresh_ = gstates_ + 2 * n_slots * state_len;
-    return gsnap_state_.alloc(n_slots * state_len) && glogits_.alloc(n_slots * n_vocab) &&
-           gsnap_logits_.alloc(n_slots * n_vocab) && gcounts_.alloc(n_slots * n_vocab) && gparams_.alloc(4 * batch_max) &&
-           gstreams_.alloc(2 * batch_max) && gwords_.alloc(kWordRows * batch_max + 2);
+    if (!(gsnap_state_.alloc(n_slots * state_len) && glogits_.alloc(n_slots * n_vocab) &&
+          gsnap_logits_.alloc(n_slots * n_vocab) && gcounts_.alloc(n_slots * n_vocab) && gparams_.alloc(4 * batch_max) &&
+          gstreams_.alloc(2 * batch_max) && gwords_.alloc(GenWords().bind(nullptr, batch_max))))
+        return false;
+    gw_.bind(gwords_, batch_max);
+    return true;
 }
 
 bool Engine::batch_reserve(size_t n_slots) {
@@ -150,7 +146,7 @@ bool Engine::batch_store(size_t slot) {
     HIP_OK(hipMemcpyAsync(glogits_ + slot * V, logits_, V * 4, hipMemcpyDeviceToDevice, stream_));
     // a new sequence in the slot: no token counted yet, not finished
     HIP_OK(hipMemsetAsync(gcounts_ + slot * V, 0, V * 4, stream_));
-    HIP_OK(hipMemsetAsync(gwords_ + slot, 0, 4, stream_));
+    HIP_OK(hipMemsetAsync(gw_.done + slot, 0, 4, stream_));
     gvalid_[slot] = 1;
     return true;
 }
@@ -166,21 +162,28 @@ bool Engine::batch_load(size_t slot) {
     return true;
 }
 
-bool Engine::gen_upload(size_t rows, const BatchSamplingParams & p, size_t n) {
+bool Engine::slots_fail(size_t n, const uint32_t * slots) {
+    (void)hipStreamSynchronize(stream_);
+    (void)handoff_check();
+    for (size_t i = 0; i < n; i++) gvalid_[slots ? slots[i] : i] = 0;
+    return false;
+}
+
+bool Engine::gen_upload(size_t Q, const BatchSamplingParams & p, size_t n) {
     const size_t K = (size_t)kBatchMax;
     gparams_h_.assign(4 * K, 0.0f);
     gstreams_h_.assign(2 * K, 0);
-    for (size_t r = 0; r < rows; r++) {
-        gparams_h_[r] = p.temperature[r];
-        gparams_h_[K + r] = p.top_p[r];
-        gparams_h_[2 * K + r] = p.presence ? p.presence[r] : 0.0f;
-        gparams_h_[3 * K + r] = p.frequency ? p.frequency[r] : 0.0f;
-        gstreams_h_[r] = p.seed[r];
-        gstreams_h_[K + r] = p.offset[r];
+    for (size_t s = 0; s < Q; s++) {
+        gparams_h_[s] = p.temperature[s];
+        gparams_h_[K + s] = p.top_p[s];
+        gparams_h_[2 * K + s] = p.presence ? p.presence[s] : 0.0f;
+        gparams_h_[3 * K + s] = p.frequency ? p.frequency[s] : 0.0f;
+        gstreams_h_[s] = p.seed[s];
+        gstreams_h_[K + s] = p.offset[s];
     }
     return hipMemcpyAsync(gparams_, gparams_h_.data(), 4 * K * 4, hipMemcpyHostToDevice, stream_) == hipSuccess &&
            hipMemcpyAsync(gstreams_, gstreams_h_.data(), 2 * K * 8, hipMemcpyHostToDevice, stream_) == hipSuccess &&
-           hipMemsetAsync(gtokens_, 0xff, rows * n * 4, stream_) == hipSuccess;
+           hipMemsetAsync(gtokens_, 0xff, Q * n * 4, stream_) == hipSuccess;
 }
 
 SampleArgs Engine::gen_sample_args(size_t rows, const BatchSamplingParams & p, size_t n) {
@@ -202,182 +205,151 @@ SampleArgs Engine::gen_sample_args(size_t rows, const BatchSamplingParams & p, s
     a.counter_r = gstreams_ + K;
     a.n_stop = (int)p.n_stop;
     for (uint32_t j = 0; j < p.n_stop; j++) a.stop[j] = p.stop_tokens[j];
-    a.done = gwords_;
-    a.length = gwords_ + K;
-    a.fin_step = gwords_ + 2 * K;
-    a.active = gwords_ + 3 * K;
+    a.done = gw_.done;
+    a.length = gw_.length;
+    a.fin_step = gw_.fin_step;
+    a.active = gw_.active;
     a.tok = gtokens_;
     a.tok_stride = (uint32_t)n;
     a.tok2 = dtokens_;
     return a;
 }
 
-bool Engine::gen_fail(size_t rows) {
-    (void)hipStreamSynchronize(stream_);
-    (void)handoff_check();
-    for (size_t r = 0; r < rows; r++) gvalid_[r] = 0;
-    return false;
-}
-
 bool Engine::generate_batch(size_t B, const BatchSamplingParams & p, size_t n, uint32_t * tokens_out,
                             uint32_t * lengths_out, uint32_t * steps_out, const LogprobsOut * lp) {
-    HIP_OK(hipSetDevice(m_->device));
-    if (B == 0 || B > gslots_ || n == 0 || !tokens_out || !lengths_out || !p.temperature || !p.top_p || !p.seed ||
-        !p.offset || p.n_bias > (uint32_t)SAMPLE_MAX_BIAS || p.n_stop > (uint32_t)SAMPLE_MAX_STOP)
-        return false;
-    for (size_t r = 0; r < B; r++)
-        if (!gvalid_[r]) return false;
-    const size_t S = m_->state_len, V = m_->n_vocab;
-    // everything that allocates, before anything is enqueued: dtokens_ moves when the workspace
-    // grows (and the batch graphs are dropped with it), the token buffer grows with B * n
-    if (!ensure_workspace((int)B) || (lp && !lp_reserve(B, n, lp->top_k))) return false;
-    if (!grow(gtokens_, B * n, doubled(1024, B * n), GRAPHS_NONE) || !upload_bias(p.n_bias, p.bias_ids, p.bias_values))
-        return false;
-    // from here on a failure leaves the slots of the call undefined
-    auto fail = [&] { return gen_fail(B); };
-    bool ok = gen_upload(B, p, n);
-    if (ok && !p.keep_counts) ok = hipMemsetAsync(gcounts_, 0, B * V * 4, stream_) == hipSuccess;
-    SampleArgs a = gen_sample_args(B, p, n);
-    ok = ok && lp_begin(lp, B, n, a);
-    ok = ok && launch_gen_begin(stream_, (int)B, p.keep_counts ? 1 : 0, a.done, a.length, a.fin_step, a.active);
-    if (!ok) return fail();
-    GenRows g{(int)B, S, V, a.done, a.fin_step};
-
-    size_t steps = 0;
-    uint32_t live = 1;
-    for (size_t i = 0; ok && i < n && live; i++) {
-        // the step is a kernel argument of eager launches between the decode graph's replays
-        a.counter = i;
-        a.step = (uint32_t)i;
-        if (timing_) g_klt = this;
-        ok = (!lp || launch_logprobs(stream_, a)) && launch_sample(stream_, a) &&
-             launch_gen_snapshot(stream_, g, (uint32_t)i, gstate_[steps & 1], glogits_, gsnap_state_, gsnap_logits_);
-        g_klt = nullptr;
-        ok = ok && eval_batch(nullptr, B, gstate_[steps & 1], gstate_[(steps & 1) ^ 1], glogits_, true);
-        if (!ok) break;
-        steps++;
-        if (p.check_every && (i + 1) % p.check_every == 0 && i + 1 < n) {
-            ok = hipMemcpyAsync(&live, a.active, 4, hipMemcpyDeviceToHost, stream_) == hipSuccess &&
-                 hipStreamSynchronize(stream_) == hipSuccess;
-        }
-    }
-    if (!ok) return fail();
-    ok = launch_gen_restore(stream_, g, gsnap_state_, gsnap_logits_, gstate_[steps & 1], gstate_[0], glogits_);
-    // [B][n] tokens with the rows n apart, as the caller's
-    ok = ok && hipMemcpyAsync(tokens_out, gtokens_, B * n * 4, hipMemcpyDeviceToHost, stream_) == hipSuccess &&
-         hipMemcpyAsync(lengths_out, a.length, B * 4, hipMemcpyDeviceToHost, stream_) == hipSuccess &&
-         lp_copy_out(lp, B, n);
-    if (!ok) return fail();
-    if (hipStreamSynchronize(stream_) != hipSuccess) return fail();
-    if (!handoff_check()) {
-        for (size_t r = 0; r < B; r++) gvalid_[r] = 0;
-        return false;
-    }
-    if (steps_out) *steps_out = (uint32_t)steps;
-    return true;
+    return generate_slots(B, p, n, tokens_out, lengths_out, steps_out, lp, nullptr);
 }
 
-// The queue.  Lanes [0, L) are the rows of the batched step, densely, as in generate_batch; what
-// changes between two steps is which sequence a lane holds.  Sequence s waits in its slot (row s of
-// gstate_[0] / glogits_, s >= L: a step over L lanes writes rows [0, L) of the state buffers and of
-// glogits_ only), runs in a lane, and ends in its snapshot (row s of gsnap_*), taken by
-// k_gen_snapshot at a stop and by k_gen_move at its cap; k_gen_restore puts every snapshot into its
-// slot at the end.  done[s] == 1 from then on, so the restore needs no table.
 bool Engine::generate_queue(size_t Q, size_t lanes, const BatchSamplingParams & p, const uint32_t * max_tokens, size_t n,
                             uint32_t * tokens_out, uint32_t * lengths_out, uint32_t * lane_out, uint32_t * start_out,
                             uint32_t * steps_out, const LogprobsOut * lp) {
+    const QueueCall qc{lanes, max_tokens, lane_out, start_out};
+    return generate_slots(Q, p, n, tokens_out, lengths_out, steps_out, lp, &qc);
+}
+
+// The driver of both calls.  Per step one sampler launch over the rows' logits (per-sequence
+// parameters, penalties, stops), k_gen_snapshot of the rows that just stopped, and one batched decode
+// step (eval_batch, tokens already in dtokens_) from gstate_[p] to gstate_[p ^ 1].  A finished row
+// keeps being decoded on token 0 -- the batched kernels take row t's state at t * state_len, so
+// leaving a row out would need a per-row offset through every one of them -- and its live state and
+// logits are garbage from then on; what the caller sees is the snapshot, which k_gen_restore puts
+// back into gstate_[0] / glogits_ at the end of the call.
+// Batch (qc == NULL): row r is sequence r throughout, no table (lane_seq == NULL), Q rows, n steps.
+// Queue: the rows are L = min(lanes, Q) lanes, and what changes between two steps is which sequence
+// a lane holds.  Sequence s waits in its slot (row s of gstate_[0] / glogits_, s >= L: a step over L
+// lanes writes rows [0, L) of the state buffers and of glogits_ only), runs in a lane, and ends in its
+// snapshot (row s of gsnap_*), taken by k_gen_snapshot at a stop and by k_gen_move at its cap.
+// done[s] == 1 from then on, so the restore needs no table.  What the queue adds is under `qc`.
+bool Engine::generate_slots(size_t Q, const BatchSamplingParams & p, size_t n, uint32_t * tokens_out, uint32_t * lengths_out,
+                            uint32_t * steps_out, const LogprobsOut * lp, const QueueCall * qc) {
     HIP_OK(hipSetDevice(m_->device));
-    const size_t K = (size_t)kBatchMax;
-    if (Q == 0 || Q > gslots_ || lanes == 0 || lanes > K || n == 0 || !max_tokens || !tokens_out || !lengths_out ||
-        !p.temperature || !p.top_p || !p.seed || !p.offset || p.keep_counts || p.n_bias > (uint32_t)SAMPLE_MAX_BIAS ||
-        p.n_stop > (uint32_t)SAMPLE_MAX_STOP)
+    // ---- the arguments; the per-sequence values of p are the caller's to check (BatchSamplingParams)
+    if (Q == 0 || Q > gslots_ || n == 0 || !tokens_out || !lengths_out || !p.temperature || !p.top_p || !p.seed ||
+        !p.offset || p.n_bias > (uint32_t)SAMPLE_MAX_BIAS || p.n_stop > (uint32_t)SAMPLE_MAX_STOP)
         return false;
-    size_t total = 0, longest = 0;
-    for (size_t s = 0; s < Q; s++) {
-        if (!gvalid_[s] || max_tokens[s] == 0 || max_tokens[s] > n) return false;
-        total += max_tokens[s];
-        longest = std::max<size_t>(longest, max_tokens[s]);
+    for (size_t s = 0; s < Q; s++)
+        if (!gvalid_[s]) return false;
+    size_t rows = Q, bound = n;
+    if (qc) {
+        if (qc->lanes == 0 || qc->lanes > (size_t)kBatchMax || !qc->max_tokens || p.keep_counts) return false;
+        size_t total = 0, longest = 0;
+        for (size_t s = 0; s < Q; s++) {
+            const size_t cap = qc->max_tokens[s];
+            if (cap == 0 || cap > n) return false;
+            total += cap;
+            longest = std::max(longest, cap);
+        }
+        rows = std::min(qc->lanes, Q);
+        // list scheduling ends within sum / L + max steps (Graham), whatever the lengths drawn
+        bound = (total + rows - 1) / rows + longest;
     }
-    const size_t L = std::min(lanes, Q), S = m_->state_len, V = m_->n_vocab;
-    // list scheduling ends within sum / L + max steps (Graham), whatever the lengths drawn
-    const size_t bound = (total + L - 1) / L + longest;
-    if (!ensure_workspace((int)L) || (lp && !lp_reserve(Q, n, lp->top_k))) return false;
+    const size_t S = m_->state_len, V = m_->n_vocab;
+    // ---- everything that allocates, before anything is enqueued: dtokens_ moves when the workspace
+    // grows (and the batch graphs are dropped with it), the token buffer grows with Q * n
+    if (!ensure_workspace((int)rows) || (lp && !lp_reserve(Q, n, lp->top_k))) return false;
     if (!grow(gtokens_, Q * n, doubled(1024, Q * n), GRAPHS_NONE) || !upload_bias(p.n_bias, p.bias_ids, p.bias_values))
         return false;
-    auto fail = [&] { return gen_fail(Q); };
-    gqueue_h_.assign(max_tokens, max_tokens + Q);
-    SampleArgs a = gen_sample_args(L, p, n);
-    GenQueue q;
-    q.lanes = (int)L;
-    q.Q = (int)Q;
-    q.done = a.done;
-    q.length = a.length;
-    q.active = a.active;
-    uint32_t * w = gwords_ + 3 * K + 1;
-    uint32_t * maxtok = w;
-    q.max_tokens = maxtok;
-    q.lane_seq = w + K;
-    q.lane = w + 2 * K;
-    q.start = w + 3 * K;
-    q.retire_to = w + 4 * K;
-    q.admit_from = w + 5 * K;
-    q.next = w + 6 * K;
-    a.lane_seq = q.lane_seq;
-    a.max_tokens = q.max_tokens;
-    // every lane idle, nothing admitted, the first waiting sequence is 0
-    bool ok = gen_upload(Q, p, n) && hipMemsetAsync(gcounts_, 0, Q * V * 4, stream_) == hipSuccess &&
-              hipMemcpyAsync(maxtok, gqueue_h_.data(), Q * 4, hipMemcpyHostToDevice, stream_) == hipSuccess &&
-              hipMemsetAsync(q.lane_seq, 0xff, 5 * K * 4, stream_) == hipSuccess &&
-              hipMemsetAsync(q.next, 0, 4, stream_) == hipSuccess &&
-              launch_gen_begin(stream_, (int)Q, 0, a.done, a.length, a.fin_step, a.active) && lp_begin(lp, Q, n, a);
-    if (!ok) return fail();
-    GenRows g{(int)L, S, V, a.done, a.fin_step, q.lane_seq};
+    // from here on a failure leaves the slots of the call undefined
+    auto fail = [&] { return slots_fail(Q); };
 
+    // ---- the start of the call: uploads and fills that do not depend on one another
+    SampleArgs a = gen_sample_args(rows, p, n);
+    bool ok = gen_upload(Q, p, n) && (p.keep_counts || hipMemsetAsync(gcounts_, 0, Q * V * 4, stream_) == hipSuccess);
+    // the queue's argument block, in the order of GenQueue's members (launched under qc only)
+    const GenQueue q{(int)rows,  (int)Q,    gw_.lane_seq,  gw_.done,       gw_.length, gw_.max_tokens,
+                     gw_.lane,   gw_.start, gw_.retire_to, gw_.admit_from, gw_.next,   gw_.active};
+    if (qc) {
+        a.lane_seq = gw_.lane_seq;
+        a.max_tokens = gw_.max_tokens;
+        gqueue_h_.assign(qc->max_tokens, qc->max_tokens + Q);
+        // every lane idle, nothing admitted, the first waiting sequence is 0: GEN_NONE in lane_seq, lane,
+        // start, retire_to and admit_from, the arrays from lane_seq up to next (GenWords::bind)
+        ok = ok && hipMemcpyAsync(gw_.max_tokens, gqueue_h_.data(), Q * 4, hipMemcpyHostToDevice, stream_) == hipSuccess &&
+             hipMemsetAsync(gw_.lane_seq, 0xff, (size_t)(gw_.next - gw_.lane_seq) * 4, stream_) == hipSuccess &&
+             hipMemsetAsync(gw_.next, 0, 4, stream_) == hipSuccess;
+    }
+    ok = ok && lp_begin(lp, Q, n, a) &&
+         launch_gen_begin(stream_, (int)Q, p.keep_counts ? 1 : 0, a.done, a.length, a.fin_step, a.active);
+    if (!ok) return fail();
+    const GenRows g{(int)rows, S, V, a.done, a.fin_step, a.lane_seq};
+    // the queue's turnover and move in front of step `step`, on the live rows that step reads
+    auto turnover = [&](size_t step, float * cur) {
+        return launch_gen_turnover(stream_, q, (uint32_t)step) &&
+               launch_gen_move(stream_, q, S, V, cur, glogits_, gstate_[0], gsnap_state_, gsnap_logits_);
+    };
+
+    // ---- the steps
     size_t steps = 0;
     uint32_t live = 1;
-    for (size_t i = 0; ok && i < bound && live; i++) {
+    for (size_t i = 0; i < bound && live; i++) {
         float * cur = gstate_[steps & 1];
+        // the step is a kernel argument of eager launches between the decode graph's replays; a row
+        // without a table draws at counter_r + counter, a lane at counter_r + its sequence's length
+        a.counter = i;
         a.step = (uint32_t)i;
         if (timing_) g_klt = this;
-        ok = launch_gen_turnover(stream_, q, (uint32_t)i) &&
-             launch_gen_move(stream_, q, S, V, cur, glogits_, gstate_[0], gsnap_state_, gsnap_logits_) &&
-             (!lp || launch_logprobs(stream_, a)) && launch_sample(stream_, a) &&
+        ok = (!qc || turnover(i, cur)) && (!lp || launch_logprobs(stream_, a)) && launch_sample(stream_, a) &&
              launch_gen_snapshot(stream_, g, (uint32_t)i, cur, glogits_, gsnap_state_, gsnap_logits_);
         g_klt = nullptr;
-        ok = ok && eval_batch(nullptr, L, cur, gstate_[(steps & 1) ^ 1], glogits_, true);
-        if (!ok) break;
+        ok = ok && eval_batch(nullptr, rows, cur, gstate_[(steps & 1) ^ 1], glogits_, true);
+        if (!ok) return fail();
         steps++;
-        if (p.check_every && (i + 1) % p.check_every == 0 && i + 1 < bound) {
-            ok = hipMemcpyAsync(&live, a.active, 4, hipMemcpyDeviceToHost, stream_) == hipSuccess &&
-                 hipStreamSynchronize(stream_) == hipSuccess;
-        }
+        if (p.check_every && (i + 1) % p.check_every == 0 && i + 1 < bound &&
+            (hipMemcpyAsync(&live, a.active, 4, hipMemcpyDeviceToHost, stream_) != hipSuccess ||
+             hipStreamSynchronize(stream_) != hipSuccess))
+            return fail();
     }
-    if (!ok) return fail();
-    // every sequence has ended; those whose cap ended them at the last step are still in their lanes
-    ok = launch_gen_turnover(stream_, q, (uint32_t)steps) &&
-         launch_gen_move(stream_, q, S, V, gstate_[steps & 1], glogits_, gstate_[0], gsnap_state_, gsnap_logits_);
-    GenRows all{(int)Q, S, V, a.done, a.fin_step};
-    ok = ok && launch_gen_restore(stream_, all, gsnap_state_, gsnap_logits_, gstate_[0], gstate_[0], glogits_);
-    gqueue_h_.assign(2 * Q, 0);
-    uint32_t * lane_h = lane_out ? lane_out : gqueue_h_.data();
-    uint32_t * start_h = gqueue_h_.data() + Q;
+
+    // ---- the end.  Queue: every sequence has ended; those whose cap ended them at the last step are
+    // still in their lanes, and one more turnover and move takes them out: every row is then a
+    // snapshot, restored in place.  Batch: a live row's state is in the buffer the last step wrote.
+    ok = !qc || turnover(steps, gstate_[steps & 1]);
+    const GenRows all{(int)Q, S, V, a.done, a.fin_step};
+    ok = ok && launch_gen_restore(stream_, all, gsnap_state_, gsnap_logits_, qc ? gstate_[0] : gstate_[steps & 1], gstate_[0],
+                                  glogits_);
+    // [Q][n] tokens with the rows n apart, as the caller's
     ok = ok && hipMemcpyAsync(tokens_out, gtokens_, Q * n * 4, hipMemcpyDeviceToHost, stream_) == hipSuccess &&
-         hipMemcpyAsync(lengths_out, a.length, Q * 4, hipMemcpyDeviceToHost, stream_) == hipSuccess &&
-         hipMemcpyAsync(lane_h, q.lane, Q * 4, hipMemcpyDeviceToHost, stream_) == hipSuccess &&
-         hipMemcpyAsync(start_h, q.start, Q * 4, hipMemcpyDeviceToHost, stream_) == hipSuccess &&
-         lp_copy_out(lp, Q, n);
-    if (!ok) return fail();
-    if (hipStreamSynchronize(stream_) != hipSuccess) return fail();
-    if (!handoff_check()) {
-        for (size_t s = 0; s < Q; s++) gvalid_[s] = 0;
-        return false;
+         hipMemcpyAsync(lengths_out, a.length, Q * 4, hipMemcpyDeviceToHost, stream_) == hipSuccess;
+    uint32_t * start_h = nullptr;
+    if (qc) {
+        gqueue_h_.assign(2 * Q, 0);
+        start_h = gqueue_h_.data() + Q;
+        ok = ok &&
+             hipMemcpyAsync(qc->lane_out ? qc->lane_out : gqueue_h_.data(), gw_.lane, Q * 4, hipMemcpyDeviceToHost, stream_) ==
+                 hipSuccess &&
+             hipMemcpyAsync(start_h, gw_.start, Q * 4, hipMemcpyDeviceToHost, stream_) == hipSuccess;
     }
-    // the steps up to the one after which nothing was busy; the loop may have run more of them
-    // (check_every looks only now and then), all on token 0 in idle lanes
-    size_t used = 0;
-    for (size_t s = 0; s < Q; s++) used = std::max<size_t>(used, (size_t)start_h[s] + lengths_out[s]);
-    if (used > steps) return fail();  // a sequence that never ended: the bound does not allow it
-    if (start_out) memcpy(start_out, start_h, Q * 4);
+    ok = ok && lp_copy_out(lp, Q, n);
+    if (!ok || hipStreamSynchronize(stream_) != hipSuccess || !handoff_check()) return fail();
+    size_t used = steps;
+    if (qc) {
+        // the steps up to the one after which nothing was busy; the loop may have run more of them
+        // (check_every looks only now and then), all on token 0 in idle lanes
+        used = 0;
+        for (size_t s = 0; s < Q; s++) used = std::max<size_t>(used, (size_t)start_h[s] + lengths_out[s]);
+        if (used > steps) return fail();  // a sequence that never ended: the bound does not allow it
+        if (qc->start_out) memcpy(qc->start_out, start_h, Q * 4);
+    }
     if (steps_out) *steps_out = (uint32_t)used;
     return true;
 }

@@ -114,10 +114,7 @@ bool Engine::prefill_batch(size_t n_rows, const uint32_t * slots, const uint32_t
         seg_ = nullptr;
         bs_ = 0;
         g_klt = nullptr;
-        (void)hipStreamSynchronize(stream_);
-        (void)handoff_check();
-        for (size_t i = 0; i < n_rows; i++) gvalid_[slots[i]] = 0;
-        return false;
+        return slots_fail(n_rows, slots);
     };
     for (size_t i = 0; i < n_rows; i++)
         if (!(cont && cont[i])) gvalid_[slots[i]] = 0;
@@ -161,13 +158,8 @@ bool Engine::prefill_batch(size_t n_rows, const uint32_t * slots, const uint32_t
     if (!launch_copy_rows(stream_, gstate_[1], d_back, gstate_[0], d_back, (int)n_back, n)) return fail();
     // a new sequence in every slot: no token counted yet, not finished
     RK_LAUNCH(k_prefill_clear, dim3((unsigned)std::min<size_t>((V + 255) / 256, 256), (unsigned)n_rows), dim3(256), 0, stream_,
-              d_slot, V, gcounts_.get(), gwords_.get());
-    if (hipGetLastError() != hipSuccess) return fail();
-    if (hipStreamSynchronize(stream_) != hipSuccess) return fail();
-    if (!handoff_check()) {
-        for (size_t i = 0; i < n_rows; i++) gvalid_[slots[i]] = 0;
-        return false;
-    }
+              d_slot, V, gcounts_.get(), gw_.done);
+    if (hipGetLastError() != hipSuccess || hipStreamSynchronize(stream_) != hipSuccess || !handoff_check()) return fail();
     for (size_t i = 0; i < n_rows; i++) gvalid_[slots[i]] = 1;
     return true;
 }

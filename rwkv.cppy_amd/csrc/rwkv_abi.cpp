@@ -771,6 +771,23 @@ static bool batch_sampling_ok(struct rwkv_context * ctx, size_t rows, const stru
     return true;
 }
 
+// What the two batched generation calls check alike, in this order: the log-probability arrays, the
+// context, `rows` sequences in valid slots [0, rows) over `lanes` decode rows (generate_batch: its rows),
+// n, and the two arrays every call fills.
+static bool batch_call_ok(struct rwkv_context * ctx, const struct rwkv_mi355x_logprobs * lp, LogprobsOut & lo, size_t rows,
+                          size_t lanes, size_t n, const uint32_t * tokens_out, const uint32_t * lengths_out) {
+    if (!logprobs_ok(ctx, lp, lo) || !batch_ctx_ok(ctx)) return false;
+    CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, rows > 0 && rows <= ctx->engine->batch_slots(), "%zu sequences with %zu slots reserved",
+              rows, ctx->engine->batch_slots());
+    CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, lanes > 0 && lanes <= (size_t)Engine::kBatchMax, "%zu lanes (1 to %d)", lanes,
+              Engine::kBatchMax);
+    for (size_t s = 0; s < rows; s++)
+        CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, ctx->engine->batch_slot_valid(s), "Slot %zu holds nothing", s);
+    CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, n > 0 && n <= 65536, "Token count %zu is outside [1, 65536]", n);
+    CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, tokens_out != nullptr && lengths_out != nullptr, "NULL tokens_out or lengths_out");
+    return true;
+}
+
 RWKV_API bool rwkv_mi355x_generate_batch_logprobs(struct rwkv_context * ctx, size_t B,
                                                   const struct rwkv_mi355x_batch_sampling * p, size_t n,
                                                   uint32_t * tokens_out, uint32_t * lengths_out, uint32_t * steps_out,
@@ -778,16 +795,8 @@ RWKV_API bool rwkv_mi355x_generate_batch_logprobs(struct rwkv_context * ctx, siz
     if (!ctx || !ctx->engine) return false;
     ctx->last_error = RWKV_ERROR_NONE;
     LogprobsOut lo;
-    if (!logprobs_ok(ctx, lp, lo) || !batch_ctx_ok(ctx)) return false;
-    CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, B > 0 && B <= ctx->engine->batch_slots(), "Batch of %zu rows with %zu slots reserved",
-              B, ctx->engine->batch_slots());
-    for (size_t r = 0; r < B; r++)
-        CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, ctx->engine->batch_slot_valid(r), "Slot %zu holds nothing", r);
-    CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, n > 0 && n <= 65536, "Token count %zu is outside [1, 65536]", n);
-    CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, p != nullptr, "NULL sampling parameters");
-    CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, tokens_out != nullptr && lengths_out != nullptr, "NULL tokens_out or lengths_out");
     BatchSamplingParams bp;
-    if (!batch_sampling_ok(ctx, B, p, bp)) return false;
+    if (!batch_call_ok(ctx, lp, lo, B, B, n, tokens_out, lengths_out) || !batch_sampling_ok(ctx, B, p, bp)) return false;
     if (!logprobs_reserve(ctx, lp, B, n)) return false;
     use_device(ctx);
     CTX_CHECK(ctx, RWKV_ERROR_CTX, false,
@@ -809,22 +818,14 @@ RWKV_API bool rwkv_mi355x_generate_queue_logprobs(struct rwkv_context * ctx, siz
     if (!ctx || !ctx->engine) return false;
     ctx->last_error = RWKV_ERROR_NONE;
     LogprobsOut lo;
-    if (!logprobs_ok(ctx, lp, lo) || !batch_ctx_ok(ctx)) return false;
-    CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, Q > 0 && Q <= ctx->engine->batch_slots(), "Queue of %zu sequences with %zu slots reserved",
-              Q, ctx->engine->batch_slots());
-    CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, lanes > 0 && lanes <= (size_t)Engine::kBatchMax, "%zu lanes (1 to %d)", lanes,
-              Engine::kBatchMax);
-    for (size_t s = 0; s < Q; s++)
-        CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, ctx->engine->batch_slot_valid(s), "Slot %zu holds nothing", s);
-    CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, n > 0 && n <= 65536, "Token count %zu is outside [1, 65536]", n);
-    CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, max_tokens != nullptr && tokens_out != nullptr && lengths_out != nullptr,
-              "NULL max_tokens, tokens_out or lengths_out");
+    BatchSamplingParams bp;
+    if (!batch_call_ok(ctx, lp, lo, Q, lanes, n, tokens_out, lengths_out)) return false;
+    CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, max_tokens != nullptr, "NULL max_tokens");
     for (size_t s = 0; s < Q; s++)
         CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, max_tokens[s] > 0 && max_tokens[s] <= n, "Sequence %zu: max_tokens %" PRIu32 " is outside [1, %zu]",
                   s, max_tokens[s], n);
-    BatchSamplingParams bp;
     if (!batch_sampling_ok(ctx, Q, p, bp)) return false;
-    CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, p->keep_counts == 0,
+    CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, !bp.keep_counts,
               "keep_counts is not supported by the queue (continue a capped sequence with rwkv_mi355x_generate_batch)");
     if (!logprobs_reserve(ctx, lp, Q, n)) return false;
     use_device(ctx);

@@ -491,27 +491,36 @@ class RWKVSharedLibrary:
         if not self.library.rwkv_mi355x_batch_load(ctx.ptr, slot):
             raise ValueError('rwkv_mi355x_batch_load failed, check stderr')
 
+    def _generate_slots(self, name: str, ctx: RWKVContext, rows: int, n: int, logprobs: Optional[int], head: tuple,
+                        extra: tuple = ()):
+        """What rwkv_mi355x_generate_batch and rwkv_mi355x_generate_queue share: the output arrays of
+        `rows` sequences and the plain / _logprobs entry point `name`, called with (ctx, *head, n,
+        tokens, lengths, *extra, steps[, logprobs]).  Returns (tokens [rows, n], lengths [rows], steps,
+        Logprobs of [rows, n] / [rows, n, K] arrays or None)."""
+        import numpy as np
+        tokens = np.zeros((rows, max(1, n)), np.uint32)
+        lengths = np.zeros(rows, np.uint32)
+        steps = ctypes.c_uint32(0)
+        P_U32 = ctypes.POINTER(ctypes.c_uint32)
+        args = (ctx.ptr, *head, n, tokens.ctypes.data_as(P_U32), lengths.ctypes.data_as(P_U32),
+                *(x.ctypes.data_as(P_U32) for x in extra), ctypes.byref(steps))
+        out = None
+        if logprobs is not None:
+            name += '_logprobs'
+            lp, out = make_logprobs(rows, max(1, n), logprobs)
+            args += (ctypes.byref(lp),)
+        if not getattr(self.library, name)(*args):
+            raise ValueError(f'{name} failed, check stderr')
+        return tokens[:, :n], lengths, steps.value, out and Logprobs(*(x[:, :n] for x in out))
+
     def rwkv_mi355x_generate_batch(self, ctx: RWKVContext, rows: int, n: int, params: RWKVBatchSampling,
                                    logprobs: Optional[int] = None):
         """Up to n tokens for each of slots [0, rows) (make_batch_sampling).  Returns (tokens uint32
         [rows, n], 0xFFFFFFFF after a row's last token; lengths uint32 [rows]; the decode steps run).
         logprobs=K (rwkv_mi355x_generate_batch_logprobs): a fourth element, Logprobs of [rows, n] /
         [rows, n, K] arrays whose columns past a row's length hold the fill (NaN, 0xFFFFFFFF)."""
-        import numpy as np
-        tokens = np.zeros((rows, max(1, n)), np.uint32)
-        lengths = np.zeros(rows, np.uint32)
-        steps = ctypes.c_uint32(0)
-        P_U32 = ctypes.POINTER(ctypes.c_uint32)
-        args = (ctx.ptr, rows, ctypes.byref(params), n, tokens.ctypes.data_as(P_U32), lengths.ctypes.data_as(P_U32),
-                ctypes.byref(steps))
-        if logprobs is None:
-            if not self.library.rwkv_mi355x_generate_batch(*args):
-                raise ValueError('rwkv_mi355x_generate_batch failed, check stderr')
-            return tokens[:, :n], lengths, steps.value
-        lp, out = make_logprobs(rows, max(1, n), logprobs)
-        if not self.library.rwkv_mi355x_generate_batch_logprobs(*args, ctypes.byref(lp)):
-            raise ValueError('rwkv_mi355x_generate_batch_logprobs failed, check stderr')
-        return tokens[:, :n], lengths, steps.value, Logprobs(*(x[:, :n] for x in out))
+        out = self._generate_slots('rwkv_mi355x_generate_batch', ctx, rows, n, logprobs, (rows, ctypes.byref(params)))
+        return out if logprobs is not None else out[:3]
 
     def rwkv_mi355x_generate_queue(self, ctx: RWKVContext, max_tokens, lanes: int, temperature=1.0, top_p=0.8,
                                    presence=None, frequency=None, logit_bias=None, seeds=None, offsets=0,
@@ -529,23 +538,12 @@ class RWKVSharedLibrary:
         params = make_batch_sampling(Q, temperature, top_p, presence, frequency, logit_bias, seeds, offsets,
                                      stop_tokens, False, check_every)
         n = int(caps.max()) if n is None else int(n)
-        out = {k: np.zeros(Q, np.uint32) for k in ('lengths', 'lane', 'start')}
-        tokens = np.zeros((Q, max(1, n)), np.uint32)
-        steps = ctypes.c_uint32(0)
-        P_U32 = ctypes.POINTER(ctypes.c_uint32)
-        args = (ctx.ptr, Q, lanes, ctypes.byref(params), caps.ctypes.data_as(P_U32), n, tokens.ctypes.data_as(P_U32),
-                out['lengths'].ctypes.data_as(P_U32), out['lane'].ctypes.data_as(P_U32),
-                out['start'].ctypes.data_as(P_U32), ctypes.byref(steps))
-        if logprobs is None:
-            if not self.library.rwkv_mi355x_generate_queue(*args):
-                raise ValueError('rwkv_mi355x_generate_queue failed, check stderr')
-        else:
-            lp, arrays = make_logprobs(Q, max(1, n), logprobs)
-            if not self.library.rwkv_mi355x_generate_queue_logprobs(*args, ctypes.byref(lp)):
-                raise ValueError('rwkv_mi355x_generate_queue_logprobs failed, check stderr')
-            out['logprobs'] = Logprobs(*(x[:, :n] for x in arrays))
-        out['tokens'] = tokens[:, :n]
-        out['steps'] = steps.value
+        out = {k: np.zeros(Q, np.uint32) for k in ('lane', 'start')}
+        head = (Q, lanes, ctypes.byref(params), caps.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)))
+        out['tokens'], out['lengths'], out['steps'], lp = self._generate_slots(
+            'rwkv_mi355x_generate_queue', ctx, Q, n, logprobs, head, (out['lane'], out['start']))
+        if logprobs is not None:
+            out['logprobs'] = lp
         return out
 
     def rwkv_mi355x_selftest_gen_turnover(self, lane_seq, done, length, max_tokens, next_seq: int, step: int = 0,

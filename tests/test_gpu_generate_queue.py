@@ -319,7 +319,117 @@ def test_a_slot_continues_as_the_sequence_alone():
         ref.free()
 
 
-# ------------------------------------------------------------------ 9. errors
+# ------------------------------------------------------------------ 9. one context's words under both calls
+def test_batch_and_queue_calls_share_one_context():
+    """generate_batch and generate_queue drive the same device words (done, length, fin_step, active;
+    the queue's own behind them).  One reservation of 7 slots serves a batch call, a queue call and the
+    batch call again, so the second batch call starts from the words the queue left."""
+    c, ref, qref = (QCtx(os.path.join(GOLD, V6)) for _ in range(3))
+    try:
+        B, n, n2 = 3, 6, 5
+        kw = {k: v[:B] for k, v in SAMPLED8.items()}
+        more = dict(kw, offsets=[o + n for o in kw['offsets']])
+        R, _, _ = ref.run(B, n=n, **kw)
+        stops = [int(R[1][2])]  # row 1 draws it at its third token unless it or another row draws it sooner
+
+        def stored(rows):
+            for r in range(rows):
+                c.start(r)
+                assert c.L.rwkv_mi355x_batch_store(c.ptr, r)
+
+        def batch(x, keep=False):
+            p = make_batch_sampling(B, kw['temperature'], kw['top_p'], None, None, None, kw['seeds'],
+                                    (more if keep else kw)['offsets'], stops, keep, 0)
+            ok, toks, lens, steps = x.run_raw(B, n2 if keep else n, p)
+            assert ok
+            return toks, lens, steps, [x.slot(r) for r in range(B)]
+
+        def same(a, b):
+            assert np.array_equal(a[0], b[0]) and np.array_equal(a[1], b[1]) and a[2] == b[2]
+            for (st, lg), (st0, lg0) in zip(a[3], b[3]):
+                assert np.array_equal(bits(st), bits(st0)) and np.array_equal(bits(lg), bits(lg0))
+
+        assert c.L.rwkv_mi355x_batch_reserve(c.ptr, 7)
+        stored(B)
+        first = batch(c)
+        assert first[1][1] <= 3 and first[2] == n, 'row 1 did not end by the stop'
+        stored(7)
+        out = c.queue(CAPS7, 2, ROWS7, fill=False)
+        out_slots = [c.slot(s) for s in range(7)]
+        stored(B)
+        third = batch(c)
+        fourth = batch(c, keep=True)
+
+        ref.fill(B)
+        want = batch(ref)
+        same(first, third)
+        same(first, want)
+        same(fourth, batch(ref, keep=True))
+        qwant = qref.queue(CAPS7, 2, ROWS7)
+        for key in ('tokens', 'lengths', 'lane', 'start'):
+            assert np.array_equal(out[key], qwant[key]), key
+        assert out['steps'] == qwant['steps'] and list(out['lengths']) == CAPS7
+        for s in range(7):
+            st, lg = qref.slot(s)
+            assert np.array_equal(bits(out_slots[s][0]), bits(st)) and np.array_equal(bits(out_slots[s][1]), bits(lg)), s
+    finally:
+        for x in (c, ref, qref):
+            x.free()
+
+
+# ------------------------------------------------------------------ 10. the launches of a step
+def launches(c, run):
+    """run()'s result and {kernel class: launches} of rwkv_mi355x_kernel_stats for it."""
+    c.L.rwkv_mi355x_set_kernel_timing(c.ptr, True)  # clears the table
+    out = run()
+    table = {}
+    for i in range(c.L.rwkv_mi355x_kernel_stats(c.ptr, -1, None, 0, None, None, None, None)):
+        name = ctypes.create_string_buffer(128)
+        la, ms, by, fl = ctypes.c_longlong(), ctypes.c_double(), ctypes.c_double(), ctypes.c_double()
+        c.L.rwkv_mi355x_kernel_stats(c.ptr, i, name, 128, ctypes.byref(la), ctypes.byref(ms), ctypes.byref(by), ctypes.byref(fl))
+        table[name.value.decode()] = la.value
+    return out, table
+
+
+def test_launches_per_step():
+    """What a step enqueues besides the batched decode, counted from the loop bounds: the batch runs n
+    steps of {sampler, snapshot}; the queue ceil(sum caps / lanes) + max caps steps of {turnover,
+    move, sampler, snapshot}, or as many as were needed when the host looks at `active` every step."""
+    c = QCtx(os.path.join(GOLD, V6), timing=True)
+    try:
+        B, n, lanes = 3, 5, 3
+        bound = -(-sum(CAPS7) // lanes) + max(CAPS7)
+        assert bound == 16
+        kw = {k: v[:B] for k, v in SAMPLED8.items()}
+        p = make_batch_sampling(B, kw['temperature'], kw['top_p'], None, None, None, kw['seeds'], kw['offsets'], (), False, 0)
+        per_step = ('k_gen_turnover', 'k_gen_move', 'k_sample_rows', 'k_gen_snapshot')
+
+        def queue(check_every, logprobs=None):
+            return library().rwkv_mi355x_generate_queue(c, CAPS7, lanes, ROWS7['temperature'], ROWS7['top_p'], None, None,
+                                                        ROWS7['logit_bias'], ROWS7['seeds'], ROWS7['offsets'], (),
+                                                        check_every, None, logprobs)
+
+        for lp in (None, 2):
+            sampler = 'k_sample_rows_lp' if lp else 'k_sample_rows'
+            c.fill(B)
+            (_, lens, steps, *_), t = launches(c, lambda: library().rwkv_mi355x_generate_batch(c, B, n, p, lp))
+            assert list(lens) == [n] * B and steps == n
+            assert t[sampler] == n and t['k_gen_snapshot'] == n
+            assert 'k_gen_turnover' not in t and 'k_gen_move' not in t
+            assert t.get('k_logprobs') == (n if lp else None) and ('k_sample_rows' in t) == (lp is None)
+            for check_every in (0, 1):
+                c.fill(7)
+                out, t = launches(c, lambda: queue(check_every, lp))
+                assert list(out['lengths']) == CAPS7 and out['steps'] < bound
+                want = out['steps'] if check_every else bound
+                assert [t[k if k != 'k_sample_rows' else sampler] for k in per_step] == [want] * 4, (lp, check_every, t)
+                assert t.get('k_logprobs') == (want if lp else None) and ('k_sample_rows' in t) == (lp is None)
+    finally:
+        c.L.rwkv_mi355x_set_kernel_timing(c.ptr, False)
+        c.free()
+
+
+# ------------------------------------------------------------------ 11. errors
 def test_argument_errors_leave_the_slots_alone():
     c, ref = QCtx(os.path.join(GOLD, V6)), QCtx(os.path.join(GOLD, V6))
     try:
