@@ -451,6 +451,38 @@ RWKV_API bool rwkv_mi355x_selftest_gemm(int wtype, const void * W, int K, int M,
 RWKV_API bool rwkv_mi355x_selftest_gemm_split(int wtype, const void * W, int K, int M, const float * x, int T,
                                               float * y, int split);
 
+/* One entry of a matmul group (MMGroup, csrc/common.hpp) on host operands: y [T][M] = epi(W x).
+ * W: ggml block bytes of type wtype, ne = [K, M]; epi: the Epi value 0..10.  y0 (initial y), aux:
+ * [T][M], bias: [M]; NULL where the epilogue does not read them (y then starts as zeros).  emit != 0:
+ * the post-epilogue values are also emitted as the next matmul's input, Q8_0 blocks or (out_q8_1)
+ * Q8_1, returned row-major: q [T][M], d / s / qsum [T][M / 32] (any may be NULL; s is written for
+ * Q8_1 only).  out_tiled: emit into token-tile records instead (not returned: a shape the launchers'
+ * coverage rules must tell apart). */
+struct rwkv_mi355x_selftest_mm_entry {
+    int wtype;
+    const void * W;
+    int M;
+    int epi;
+    const float * y0;
+    const float * aux;
+    const float * bias;
+    int emit;
+    int out_q8_1;
+    int out_tiled;
+    float * y;
+    int8_t * q;
+    float * d;
+    float * s;
+    int32_t * qsum;
+};
+/* Runs a whole group of n <= 8 entries over x [T][K] (host, shared by the entries, in entry 0's
+ * activation format) through one launcher: form 0 = launch_mm_group (k_mm / k_mm_small, or k_fmm where
+ * it applies), 1 = launch_mvb_group (k_mvb), 2 = launch_qgemm (token-tile input; no emitting entries),
+ * 3 = launch_fmm_group.  split (0, 1, 4, 8) is MMGroup::split.  *launched = 1 when the launcher took
+ * the group, 0 when forms 1 / 3 declined it (the outputs are then untouched).  false only on an error. */
+RWKV_API bool rwkv_mi355x_selftest_matmul_group(int form, int split, int T, int K, const float * x, int n,
+                                                const struct rwkv_mi355x_selftest_mm_entry * entries, int * launched);
+
 /* WKV-6 (v5 / v6 time mixing, head size 64) over T tokens of one context on host operands:
  * chunked = 0 runs the serial kernel (bit-exact with decode), 1 the chunk-parallel form
  * (RWKV_MI355X_WKV_CHUNK; re-associated sums).  k, v, r: [T][H*64]; w: [T][H*64] (w_per_token = 1,

@@ -168,6 +168,115 @@ extern "C" RWKV_API bool rwkv_mi355x_selftest_gemm_split(int wtype, const void *
     return (wtype == W_F16 || wtype == W_F32) && T >= 16 && K >= 512 && selftest_mm(wtype, W, K, M, x, T, y, false, split);
 }
 
+// A whole MMGroup on host operands through one launcher (include/rwkv_mi355x.h has the contract):
+// every entry its own weights, epilogue, epilogue operands and emission, one input shared by all.
+extern "C" RWKV_API bool rwkv_mi355x_selftest_matmul_group(int form, int split, int T, int K, const float * x, int n,
+                                                           const struct rwkv_mi355x_selftest_mm_entry * ent,
+                                                           int * launched) {
+    if (!launched) return false;
+    *launched = 0;
+    if (form < 0 || form > 3 || (split != 0 && split != 1 && split != 4 && split != 8)) return false;
+    if (T <= 0 || K <= 0 || K % 32 || !x || n < 1 || n > MM_MAX_ENTRIES || !ent) return false;
+    const int wtype = ent[0].wtype;
+    if (form == 2 && (!wtype_quantized(wtype) || T < 2)) return false;
+    size_t msum = 0;
+    for (int i = 0; i < n; i++) {
+        const rwkv_mi355x_selftest_mm_entry & s = ent[i];
+        if (!s.W || s.M <= 0 || !s.y || s.epi < EPI_STORE || s.epi > EPI_VMIX7) return false;
+        // the operands an epilogue dereferences must be there
+        if ((s.epi == EPI_SIGMUL_ADD || s.epi == EPI_VMIX7) && !s.aux) return false;
+        if ((s.epi == EPI_DECAY6 || s.epi == EPI_DECAY7 || s.epi == EPI_SIGMOID_BIAS || s.epi == EPI_VMIX7) && !s.bias)
+            return false;
+        if (s.emit && form == 2) return false;  // the GEMM leaves emission to its caller
+        msum += (size_t)s.M;
+    }
+    DeviceModel dm;
+    DevBufs b;
+    ActBuf a;
+    float * dx = (float *)b.alloc((size_t)T * K * 4);
+    bool ok = dx && make_act(b, act_fmt_for(wtype), T, K, a);
+    a.tiled = form == 2 ? 1 : 0;  // the GEMM reads token tiles, the other forms row-major blocks
+    ok = ok && hipMemcpy(dx, x, (size_t)T * K * 4, hipMemcpyHostToDevice) == hipSuccess;
+    ok = ok && launch_act_from_f32(nullptr, dx, T, K, a);
+    MMGroup g;
+    memset(&g, 0, sizeof(g));
+    g.n = n;
+    g.T = T;
+    g.split = split;
+    g.fmm = 1;  // as selftest_mm: the f32-MFMA form for float weights from T = 16
+    for (int i = 0; ok && i < n; i++) {
+        const rwkv_mi355x_selftest_mm_entry & s = ent[i];
+        const size_t TM = (size_t)T * s.M;
+        HostTensor ht;
+        ht.name = "selftest";
+        ht.type = (uint32_t)s.wtype;
+        ht.ndim = 2;
+        ht.ne[0] = (uint32_t)K;
+        ht.ne[1] = (uint32_t)s.M;
+        const size_t nbytes = type_nbytes(ht.type, ht.nel());
+        if (!nbytes) {
+            ok = false;
+            break;
+        }
+        ht.data.assign((const uint8_t *)s.W, (const uint8_t *)s.W + nbytes);
+        MMEntry & e = g.e[i];
+        ok = upload_mat(dm, &ht, e.W, false, false);
+        // a host array on the device (NULL stays NULL)
+        auto up = [&](const float * h, size_t count) -> float * {
+            if (!h) return nullptr;
+            float * d = (float *)b.alloc(count * 4);
+            ok = ok && d && hipMemcpy(d, h, count * 4, hipMemcpyHostToDevice) == hipSuccess;
+            return d;
+        };
+        e.in = a;
+        e.y = s.y0 ? up(s.y0, TM) : (float *)b.alloc(TM * 4);
+        e.ldy = s.M;
+        e.aux = up(s.aux, TM);
+        e.bias = up(s.bias, (size_t)s.M);
+        e.epi = s.epi;
+        e.emit = s.emit ? 1 : 0;
+        ok = ok && e.y;
+        if (s.emit) {
+            ok = ok && make_act(b, s.out_q8_1 ? A_Q8_1 : A_Q8_0, T, s.M, e.out);
+            e.out.tiled = s.out_tiled ? 1 : 0;
+        }
+    }
+    if (ok) {
+        g.part_floats = (size_t)8 * T * msum;
+        g.part = (float *)b.alloc(g.part_floats * 4);
+        ok = g.part != nullptr;
+        if (form == 2) {
+            g.m2_floats = (size_t)T * msum;
+            g.m2 = (float *)b.alloc(g.m2_floats * 4);
+            ok = ok && g.m2 != nullptr;
+        }
+    }
+    bool ran = true;
+    if (ok) {
+        switch (form) {
+            case 0: ok = launch_mm_group(nullptr, g, wtype); break;
+            case 1: ok = launch_mvb_group(nullptr, g, wtype, &ran); break;
+            case 2: ok = launch_qgemm(nullptr, g, wtype); break;
+            default: ok = launch_fmm_group(nullptr, g, wtype, &ran); break;
+        }
+    }
+    ok = ok && hipDeviceSynchronize() == hipSuccess;
+    for (int i = 0; ok && ran && i < n; i++) {
+        const rwkv_mi355x_selftest_mm_entry & s = ent[i];
+        const MMEntry & e = g.e[i];
+        const size_t TM = (size_t)T * s.M, nb = TM / 32;
+        ok = hipMemcpy(s.y, e.y, TM * 4, hipMemcpyDeviceToHost) == hipSuccess;
+        if (!s.emit || s.out_tiled) continue;
+        if (s.q) ok = ok && hipMemcpy(s.q, e.out.q, TM, hipMemcpyDeviceToHost) == hipSuccess;
+        if (s.d) ok = ok && hipMemcpy(s.d, e.out.d, nb * 4, hipMemcpyDeviceToHost) == hipSuccess;
+        if (s.s && s.out_q8_1) ok = ok && hipMemcpy(s.s, e.out.s, nb * 4, hipMemcpyDeviceToHost) == hipSuccess;
+        if (s.qsum) ok = ok && hipMemcpy(s.qsum, e.out.qsum, nb * 4, hipMemcpyDeviceToHost) == hipSuccess;
+    }
+    free_model(dm);
+    *launched = ok && ran ? 1 : 0;
+    return ok;
+}
+
 // WKV-6 (v5 / v6) over T tokens of one context: chunked = 0 the serial k_wkv6_s64 (decode's
 // association), 1 the chunk-parallel form (wkv_chunk.hip).  k, v, r, w: [T][H*64] (w: [H*64] when
 // w_per_token = 0); u: [H*64]; state_in / state_out: [H][64][64]; y: [T][H*64]; all host.

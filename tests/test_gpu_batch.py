@@ -122,11 +122,23 @@ def cfg_dir(tmp_path_factory):
 @pytest.mark.parametrize('B', [8, 56])
 def test_batch_real_width_bit_exact(cfg_dir, name, B):
     """BASELINE widths (2 layers, 4096-token vocabulary); B = 8 (decode matvec over the contexts)
-    and B = 56 (past batch_gemm_min_ = 48: the int8-MFMA GEMM on token tiles)."""
+    and B = 56 (past batch_gemm_min_ = 16: the int8-MFMA GEMM on token tiles)."""
     arch, C, F, fmt = CONFIGS[name]
     p = os.path.join(str(cfg_dir), f'{name}.bin')
     if not os.path.isfile(p):
         assert library().library.rwkv_mi355x_write_synthetic_model(p.encode(), arch, 4096, C, 2, F, fmt.encode(), 5)
+    check_batch(p, B)
+
+
+@pytest.mark.parametrize('arch,fmt', [(6, 'Q5_1'), (7, 'FP16')])
+@pytest.mark.parametrize('B', [15, 16, 17])
+def test_batch_dispatch_boundary(cfg_dir, arch, fmt, B):
+    """Around batch_gemm_min_ = 16 on 512-wide, 2-layer, 1024-token-vocabulary models: the quantized
+    matmuls go from k_mvb (B = 15: the last quantized batch size, no multiple of its ring depths) to the
+    int8-MFMA GEMM on token tiles (16, 17); the float weights from k_mvb to the f32 MFMA where it applies."""
+    p = os.path.join(str(cfg_dir), f'boundary-v{arch}-{fmt}.bin')
+    if not os.path.isfile(p):
+        assert library().library.rwkv_mi355x_write_synthetic_model(p.encode(), arch, 1024, 512, 2, 0, fmt.encode(), 7)
     check_batch(p, B)
 
 
