@@ -456,8 +456,12 @@ RWKV_API bool rwkv_mi355x_selftest_gemm_split(int wtype, const void * W, int K, 
  * [T][M], bias: [M]; NULL where the epilogue does not read them (y then starts as zeros).  emit != 0:
  * the post-epilogue values are also emitted as the next matmul's input, Q8_0 blocks or (out_q8_1)
  * Q8_1, returned row-major: q [T][M], d / s / qsum [T][M / 32] (any may be NULL; s is written for
- * Q8_1 only).  out_tiled: emit into token-tile records instead (not returned: a shape the launchers'
- * coverage rules must tell apart). */
+ * Q8_1 only).  out_tiled: emit into token-tile records instead.  Forms 0, 1, 3 do not return those (a
+ * shape the launchers' coverage rules must tell apart).  Form 2 (the GEMM) takes emitting entries with
+ * out_tiled only and reports in `fused` whether launch_qgemm emitted inside the launch (fuse_emit):
+ * fused = 1: the tile records come back de-tiled into q / d / s / qsum (qsum = the sums of the returned
+ * codes), and y is NOT written by the direct kernel (it keeps what the caller's y held; the split-K
+ * combine writes both); fused = 0: y is written and nothing is emitted (that pass is the caller's). */
 struct rwkv_mi355x_selftest_mm_entry {
     int wtype;
     const void * W;
@@ -469,6 +473,11 @@ struct rwkv_mi355x_selftest_mm_entry {
     int emit;
     int out_q8_1;
     int out_tiled;
+    /* out, form 2: MMEntry::fuse_emit as launch_qgemm set it (0 from the other forms).  It is the last
+     * of the int fields and not the struct's last member on purpose: here it fills what was alignment
+     * padding in front of y, so sizeof (104 on LP64) and every older field's offset are what they were
+     * and a caller built against the struct without it still walks an array of entries correctly. */
+    int fused;
     float * y;
     int8_t * q;
     float * d;
@@ -477,11 +486,69 @@ struct rwkv_mi355x_selftest_mm_entry {
 };
 /* Runs a whole group of n <= 8 entries over x [T][K] (host, shared by the entries, in entry 0's
  * activation format) through one launcher: form 0 = launch_mm_group (k_mm / k_mm_small, or k_fmm where
- * it applies), 1 = launch_mvb_group (k_mvb), 2 = launch_qgemm (token-tile input; no emitting entries),
- * 3 = launch_fmm_group.  split (0, 1, 4, 8) is MMGroup::split.  *launched = 1 when the launcher took
- * the group, 0 when forms 1 / 3 declined it (the outputs are then untouched).  false only on an error. */
+ * it applies), 1 = launch_mvb_group (k_mvb), 2 = launch_qgemm (token-tile input; emitting entries with
+ * out_tiled), 3 = launch_fmm_group.  split (0, 1, 4, 8) is MMGroup::split.  *launched = 1 when the
+ * launcher took the group, 0 when forms 1 / 3 declined it (the outputs are then untouched).  false only
+ * on an error. */
 RWKV_API bool rwkv_mi355x_selftest_matmul_group(int form, int split, int T, int K, const float * x, int n,
-                                                const struct rwkv_mi355x_selftest_mm_entry * entries, int * launched);
+                                                struct rwkv_mi355x_selftest_mm_entry * entries, int * launched);
+
+/* One entry of a decode matvec group (MVGroup, csrc/kernels.hpp) on host operands: y [M] = epi(W v),
+ * v the entry's input row.  W: ggml block bytes of type wtype, ne = [K, M].  src 0 (SRC_ACT): v = x [K]
+ * quantized on the device into wtype's activation format (entries of one format, K and x share the
+ * buffer); 1 (SRC_F32): v = x [K], quantized by the kernel; 2 (SRC_LNMIX): v = the token-shift mix of
+ * xa = LayerNorm(x; lnw, lnb) with carry [K] and mu [K] -- form 0: xa * mu + (carry - carry * mu),
+ * 1: (carry - xa) * mu + xa, 2: xa (carry and mu unused).  carry_out [K] (optional) receives xa.  mu2
+ * (optional, forms 0 / 1, quantized wtype): the same mix with mu2, quantized, comes back in q2 [K],
+ * d2 / s2 / qsum2 [K / 32].  epi, y0, aux [M], bias [M], emit / out_q8_1 and q [M], d / s / qsum
+ * [M / 32]: as in rwkv_mi355x_selftest_mm_entry with T = 1.  Every output starts on the device as
+ * 0xA5 bytes (y: as y0 where given), so what the kernel leaves unwritten shows. */
+struct rwkv_mi355x_selftest_mv_entry {
+    int wtype;
+    const void * W;
+    int M, K;
+    int src;
+    const float * x;
+    const float * carry;
+    const float * lnw;
+    const float * lnb;
+    const float * mu;
+    const float * mu2;
+    int form;
+    int epi;
+    const float * y0;
+    const float * aux;
+    const float * bias;
+    int emit;
+    int out_q8_1;
+    float * y;
+    int8_t * q;
+    float * d;
+    float * s;
+    int32_t * qsum;
+    float * carry_out;
+    int8_t * q2;
+    float * d2;
+    float * s2;
+    int32_t * qsum2;
+};
+/* What launch_mv_group decided: MVGroup::rows, grid, stride, units_max, and the compute-unit count its
+ * thresholds used. */
+struct rwkv_mi355x_selftest_mv_shape {
+    int rows, grid, stride, units_max, cus;
+};
+/* Runs one MVGroup of n <= 8 entries through launch_mv_group.  *launched = 0 when the launcher refused
+ * the group (nothing enqueued, the outputs untouched; shape is then not written either), else 1 with the
+ * outputs and *shape filled.  false only on an error of the harness itself (bad arguments, allocation,
+ * a HIP error). */
+RWKV_API bool rwkv_mi355x_selftest_mv_group(int n, const struct rwkv_mi355x_selftest_mv_entry * entries,
+                                            struct rwkv_mi355x_selftest_mv_shape * shape, int * launched);
+/* launch_mv_sigmul (k_mvsig): y [M] = y0 + sigmoid(Wr xr) * (Wv k).  Wv: ggml block bytes of type
+ * wtype_v, ne = [F, Mv], k [F]; Wr: type wtype_r, ne = [C, Mr], xr [C].  *launched =
+ * mv_sigmul_supported's answer; 0 leaves y untouched. */
+RWKV_API bool rwkv_mi355x_selftest_mv_sigmul(int wtype_v, const void * Wv, int Mv, int F, const float * k, int wtype_r,
+                                             const void * Wr, int Mr, int C, const float * xr, const float * y0,
+                                             float * y, int * launched);
 
 /* WKV-6 (v5 / v6 time mixing, head size 64) over T tokens of one context on host operands:
  * chunked = 0 runs the serial kernel (bit-exact with decode), 1 the chunk-parallel form

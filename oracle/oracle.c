@@ -1130,6 +1130,10 @@ static void norm_row(const float * x, float * y, int64_t n, float eps, const flo
     if (b) for (int64_t i = 0; i < n; i++) y[i] = y[i] + b[i];
 }
 
+void oracle_norm_row(const float * x, float * y, int64_t n, float eps, const float * w, const float * b) {
+    norm_row(x, y, n, eps, w, b);
+}
+
 static inline float sigmoidf_(float x) { return 1.0f / (1.0f + o_exp(-x)); }
 static inline float siluf_(float x) { return x / (1.0f + o_exp(-x)); }
 

@@ -77,6 +77,9 @@ void oracle_dequantize_row(int type, const void * src, float * dst, int64_t k);
 /* y[t*M + m] = sum_k W[m,k] * x[t*K + k] with ggml CPU matmul numerics. */
 void oracle_matmul(int wtype, const void * W, int64_t K, int64_t M,
                    const float * x, int64_t T, float * y);
+/* The row LayerNorm of the current variant: y = (x - mean) / sqrt(var + eps) (* w) (+ b); w, b may
+ * be NULL.  GPU-association variant, n % 64 == 0: the kernels' chunk statistics. */
+void oracle_norm_row(const float * x, float * y, int64_t n, float eps, const float * w, const float * b);
 uint16_t oracle_f32_to_f16(float f);
 float    oracle_f16_to_f32(uint16_t h);
 

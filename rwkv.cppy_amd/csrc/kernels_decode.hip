@@ -43,8 +43,10 @@ bool launch_mv_group(hipStream_t st, MVGroup & g) {
         fprintf(stderr, "rwkv: emitting matvec with a plain LayerNorm input is not instantiated\n");
         return false;
     }
-    if (emit && !prologue) {
-        fprintf(stderr, "rwkv: emitting matvec needs a prologue source\n");
+    // (SRC_F32 too: launch_mv_shape has no emitting SRC_F32 shape, and its 8-row workgroups would be
+    // launched over the 32-row blocks counted here -- three rows in four never written)
+    if (emit && srck != MVK_LN) {
+        fprintf(stderr, "rwkv: emitting matvec needs a LayerNorm source\n");
         return false;
     }
     // rows per wave: 8 when emitting (a 32-row block per workgroup), else 2; the lean

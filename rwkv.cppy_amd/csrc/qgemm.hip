@@ -1070,9 +1070,12 @@ bool launch_qg_combine(hipStream_t st, MMGroup & g, int split) {
     return true;
 }
 
-// Every entry must have y (the engine gives emitting entries a scratch y); emission into the
-// next matmul's activation format is a separate launch_act_from_f32 pass by the caller.  The
-// weights need their tile records (upload_mat) and the activations must be token tiles.
+// Every entry must have y (the engine gives emitting entries a scratch y).  Emission into the next
+// matmul's activation format: the launch sets MMEntry::fuse_emit where it emits itself -- the direct
+// kernel's epilogue writes Q8_0 token tiles INSTEAD of y (the conditions: below), the split-K combine
+// writes y and emits any format -- and an emitting entry left with fuse_emit == 0 is a separate
+// launch_act_from_f32 pass by the caller.  The weights need their tile records (upload_mat) and the
+// activations must be token tiles.
 int g_qgemm_generic = 0;  // 1: K = 2048 through the generic kernel too (tools, comparison)
 int kQgCUs = 256;          // compute units of the device (set_mv_device_cus): the split-K threshold
 

@@ -77,6 +77,31 @@ bool make_act(DevBufs & b, int fmt, int T, int K, ActBuf & a) {
     return a.f && a.h && a.q && a.d && a.s && a.qsum && a.tq;
 }
 
+// Token-tile records (common.hpp qg_*: what the GEMM's operand copy reads) of a [T][K] Q8 activation,
+// back on the host as row-major q [T][K], d / s / qsum [T][K / 32] (any may be NULL; the records hold
+// no block sums: qsum is the sum of the returned codes).
+bool detile_act(const ActBuf & a, int T, int K, int8_t * q, float * d, float * s, int32_t * qsum) {
+    const bool one = a.fmt == A_Q8_1;
+    const size_t nbk = (size_t)K / 32, rb = qg_a_bytes(one);
+    std::vector<uint8_t> h(((size_t)T + QG_TOK - 1) / QG_TOK * nbk * rb);
+    if (hipMemcpy(h.data(), a.tq, h.size(), hipMemcpyDeviceToHost) != hipSuccess) return false;
+    for (int t = 0; t < T; t++)
+        for (size_t b = 0; b < nbk; b++) {
+            const uint8_t * rec = h.data() + ((size_t)(t / QG_TOK) * nbk + b) * rb;
+            const int tl = t % QG_TOK;
+            int sum = 0;
+            for (int k = 0; k < 32; k++) {
+                const int8_t v = (int8_t)rec[(k >> 4) * QG_TOK * 16 + tl * 16 + (k & 15)];
+                sum += v;
+                if (q) q[(size_t)t * K + b * 32 + k] = v;
+            }
+            if (d) d[t * nbk + b] = ((const float *)(rec + QG_A_D))[tl];
+            if (s && one) s[t * nbk + b] = ((const float *)(rec + QG_A_S))[tl];
+            if (qsum) qsum[t * nbk + b] = sum;
+        }
+    return true;
+}
+
 }  // namespace
 
 extern "C" RWKV_API bool rwkv_mi355x_selftest_quantize_act(int wtype, const float * x, int T, int K, int8_t * q,
@@ -168,11 +193,15 @@ extern "C" RWKV_API bool rwkv_mi355x_selftest_gemm_split(int wtype, const void *
     return (wtype == W_F16 || wtype == W_F32) && T >= 16 && K >= 512 && selftest_mm(wtype, W, K, M, x, T, y, false, split);
 }
 
+// `fused` sits in the former padding in front of y: the layout older callers were built against holds
+static_assert(sizeof(rwkv_mi355x_selftest_mm_entry) == 104 && offsetof(rwkv_mi355x_selftest_mm_entry, y) == 64 &&
+                  offsetof(rwkv_mi355x_selftest_mm_entry, fused) == 60,
+              "rwkv_mi355x_selftest_mm_entry layout");
+
 // A whole MMGroup on host operands through one launcher (include/rwkv_mi355x.h has the contract):
 // every entry its own weights, epilogue, epilogue operands and emission, one input shared by all.
 extern "C" RWKV_API bool rwkv_mi355x_selftest_matmul_group(int form, int split, int T, int K, const float * x, int n,
-                                                           const struct rwkv_mi355x_selftest_mm_entry * ent,
-                                                           int * launched) {
+                                                           struct rwkv_mi355x_selftest_mm_entry * ent, int * launched) {
     if (!launched) return false;
     *launched = 0;
     if (form < 0 || form > 3 || (split != 0 && split != 1 && split != 4 && split != 8)) return false;
@@ -187,7 +216,8 @@ extern "C" RWKV_API bool rwkv_mi355x_selftest_matmul_group(int form, int split, 
         if ((s.epi == EPI_SIGMUL_ADD || s.epi == EPI_VMIX7) && !s.aux) return false;
         if ((s.epi == EPI_DECAY6 || s.epi == EPI_DECAY7 || s.epi == EPI_SIGMOID_BIAS || s.epi == EPI_VMIX7) && !s.bias)
             return false;
-        if (s.emit && form == 2) return false;  // the GEMM leaves emission to its caller
+        // the GEMM emits token tiles or nothing (launch_qgemm's fuse_emit; else the pass is its caller's)
+        if (s.emit && form == 2 && !s.out_tiled) return false;
         msum += (size_t)s.M;
     }
     DeviceModel dm;
@@ -229,7 +259,8 @@ extern "C" RWKV_API bool rwkv_mi355x_selftest_matmul_group(int form, int split, 
             return d;
         };
         e.in = a;
-        e.y = s.y0 ? up(s.y0, TM) : (float *)b.alloc(TM * 4);
+        // form 2: y starts as the caller's s.y (a fused entry must leave it alone)
+        e.y = s.y0 ? up(s.y0, TM) : form == 2 ? up(s.y, TM) : (float *)b.alloc(TM * 4);
         e.ldy = s.M;
         e.aux = up(s.aux, TM);
         e.bias = up(s.bias, (size_t)s.M);
@@ -239,6 +270,10 @@ extern "C" RWKV_API bool rwkv_mi355x_selftest_matmul_group(int form, int split, 
         if (s.emit) {
             ok = ok && make_act(b, s.out_q8_1 ? A_Q8_1 : A_Q8_0, T, s.M, e.out);
             e.out.tiled = s.out_tiled ? 1 : 0;
+            // form 2 returns the records: poisoned, so a record nobody wrote shows
+            if (form == 2 && ok)
+                ok = hipMemset(e.out.tq, 0xA5, ((size_t)T + QG_TOK - 1) / QG_TOK * (s.M / 32) * qg_a_bytes(true)) ==
+                     hipSuccess;
         }
     }
     if (ok) {
@@ -262,16 +297,192 @@ extern "C" RWKV_API bool rwkv_mi355x_selftest_matmul_group(int form, int split, 
     }
     ok = ok && hipDeviceSynchronize() == hipSuccess;
     for (int i = 0; ok && ran && i < n; i++) {
-        const rwkv_mi355x_selftest_mm_entry & s = ent[i];
+        rwkv_mi355x_selftest_mm_entry & s = ent[i];
         const MMEntry & e = g.e[i];
         const size_t TM = (size_t)T * s.M, nb = TM / 32;
         ok = hipMemcpy(s.y, e.y, TM * 4, hipMemcpyDeviceToHost) == hipSuccess;
+        s.fused = form == 2 ? e.fuse_emit : 0;
+        if (ok && s.fused) ok = detile_act(e.out, T, s.M, s.q, s.d, s.out_q8_1 ? s.s : nullptr, s.qsum);
         if (!s.emit || s.out_tiled) continue;
         if (s.q) ok = ok && hipMemcpy(s.q, e.out.q, TM, hipMemcpyDeviceToHost) == hipSuccess;
         if (s.d) ok = ok && hipMemcpy(s.d, e.out.d, nb * 4, hipMemcpyDeviceToHost) == hipSuccess;
         if (s.s && s.out_q8_1) ok = ok && hipMemcpy(s.s, e.out.s, nb * 4, hipMemcpyDeviceToHost) == hipSuccess;
         if (s.qsum) ok = ok && hipMemcpy(s.qsum, e.out.qsum, nb * 4, hipMemcpyDeviceToHost) == hipSuccess;
     }
+    free_model(dm);
+    *launched = ok && ran ? 1 : 0;
+    return ok;
+}
+
+namespace {
+
+// n bytes of 0xA5 on the device: an output nobody has written yet
+void * alloc_poison(DevBufs & b, size_t n) {
+    void * p = b.alloc(n);
+    return p && hipMemset(p, 0xA5, n) == hipSuccess ? p : nullptr;
+}
+
+// one poisoned output row of K elements in format fmt
+bool make_act_poison(DevBufs & b, int fmt, int K, ActBuf & a) {
+    if (!make_act(b, fmt, 1, K, a)) return false;
+    const size_t nb = (size_t)K / 32 + 1;
+    return hipMemset(a.q, 0xA5, (size_t)K) == hipSuccess && hipMemset(a.d, 0xA5, nb * 4) == hipSuccess &&
+           hipMemset(a.s, 0xA5, nb * 4) == hipSuccess && hipMemset(a.qsum, 0xA5, nb * 4) == hipSuccess;
+}
+
+bool act_down(const ActBuf & a, int K, int8_t * q, float * d, float * s, int32_t * qsum) {
+    const size_t nb = (size_t)K / 32;
+    return (!q || hipMemcpy(q, a.q, (size_t)K, hipMemcpyDeviceToHost) == hipSuccess) &&
+           (!d || hipMemcpy(d, a.d, nb * 4, hipMemcpyDeviceToHost) == hipSuccess) &&
+           (!s || hipMemcpy(s, a.s, nb * 4, hipMemcpyDeviceToHost) == hipSuccess) &&
+           (!qsum || hipMemcpy(qsum, a.qsum, nb * 4, hipMemcpyDeviceToHost) == hipSuccess);
+}
+
+bool upload_w(DeviceModel & dm, int wtype, const void * W, int K, int M, DMat & out) {
+    HostTensor ht;
+    ht.name = "selftest";
+    ht.type = (uint32_t)wtype;
+    ht.ndim = 2;
+    ht.ne[0] = (uint32_t)K;
+    ht.ne[1] = (uint32_t)M;
+    const size_t nbytes = type_nbytes(ht.type, ht.nel());
+    if (!nbytes) return false;
+    ht.data.assign((const uint8_t *)W, (const uint8_t *)W + nbytes);
+    return upload_mat(dm, &ht, out, false, false);
+}
+
+float * up_floats(DevBufs & b, const float * h, size_t count, bool & ok) {
+    if (!h) return nullptr;
+    float * d = (float *)b.alloc(count * 4);
+    ok = ok && d && hipMemcpy(d, h, count * 4, hipMemcpyHostToDevice) == hipSuccess;
+    return d;
+}
+
+// x [K] quantized on the device into wtype's activation format (a decode matvec's SRC_ACT input)
+bool act_row(DevBufs & b, int wtype, const float * x, int K, ActBuf & a) {
+    bool ok = true;
+    float * dx = up_floats(b, x, (size_t)K, ok);
+    return ok && make_act(b, act_fmt_for(wtype), 1, K, a) && launch_act_from_f32(nullptr, dx, 1, K, a);
+}
+
+// the compute units launch_mv_group's thresholds count: the device's, as the engine sets them
+int mv_device_cus() {
+    int dev = 0, cus = 0;
+    if (hipGetDevice(&dev) != hipSuccess ||
+        hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
+        return 0;
+    set_mv_device_cus(cus);
+    return kQgCUs;
+}
+
+}  // namespace
+
+// One MVGroup on host operands through launch_mv_group (include/rwkv_mi355x.h has the contract).  The
+// shapes the launcher declines come back as *launched = 0: they are refused on the host, before a launch.
+extern "C" RWKV_API bool rwkv_mi355x_selftest_mv_group(int n, const struct rwkv_mi355x_selftest_mv_entry * ent,
+                                                       struct rwkv_mi355x_selftest_mv_shape * shape, int * launched) {
+    if (!launched) return false;
+    *launched = 0;
+    if (n < 1 || n > MM_MAX_ENTRIES || !ent || !shape) return false;
+    for (int i = 0; i < n; i++) {
+        const rwkv_mi355x_selftest_mv_entry & s = ent[i];
+        if (!s.W || s.M <= 0 || s.K < 8 || !s.x || !s.y || s.src < SRC_ACT || s.src > SRC_LNMIX) return false;
+        if (s.epi < EPI_STORE || s.epi > EPI_VMIX7 || s.form < 0 || s.form > 2) return false;
+        if ((s.epi == EPI_SIGMUL_ADD || s.epi == EPI_VMIX7) && !s.aux) return false;
+        if ((s.epi == EPI_DECAY6 || s.epi == EPI_DECAY7 || s.epi == EPI_SIGMOID_BIAS || s.epi == EPI_VMIX7) && !s.bias)
+            return false;
+        if (s.src == SRC_LNMIX && (!s.lnw || !s.lnb || (s.form != 2 && (!s.carry || !s.mu)))) return false;
+        if (s.mu2 && (s.src != SRC_LNMIX || s.form == 2 || !wtype_quantized(s.wtype))) return false;
+    }
+    const int cus = mv_device_cus();
+    if (cus <= 0) return false;
+    DeviceModel dm;
+    DevBufs b;
+    MVGroup g;
+    memset(&g, 0, sizeof(g));
+    g.n = n;
+    bool ok = true;
+    for (int i = 0; ok && i < n; i++) {
+        const rwkv_mi355x_selftest_mv_entry & s = ent[i];
+        MVEntry & e = g.e[i];
+        const size_t K = (size_t)s.K, M = (size_t)s.M;
+        ok = upload_w(dm, s.wtype, s.W, s.K, s.M, e.W);
+        e.src = s.src;
+        e.form = s.form;
+        if (s.src == SRC_ACT) {
+            // entries of one format, K and x share their activation row
+            int j = 0;
+            while (j < i && !(ent[j].src == SRC_ACT && ent[j].K == s.K && ent[j].x == s.x &&
+                              act_fmt_for(ent[j].wtype) == act_fmt_for(s.wtype)))
+                j++;
+            if (j < i) e.act = g.e[j].act;
+            else ok = ok && act_row(b, s.wtype, s.x, s.K, e.act);
+        } else if (s.src == SRC_F32) {
+            e.f = up_floats(b, s.x, K, ok);
+        } else {
+            e.x = up_floats(b, s.x, K, ok);
+            e.lnw = up_floats(b, s.lnw, K, ok);
+            e.lnb = up_floats(b, s.lnb, K, ok);
+            e.carry = up_floats(b, s.carry, K, ok);
+            e.mu = up_floats(b, s.mu, K, ok);
+            e.mu2 = up_floats(b, s.mu2, K, ok);
+            if (s.carry_out) ok = ok && (e.carry_out = (float *)alloc_poison(b, K * 4)) != nullptr;
+            if (s.mu2) ok = ok && make_act_poison(b, act_fmt_for(s.wtype), s.K, e.act2_out);
+        }
+        e.y = s.y0 ? up_floats(b, s.y0, M, ok) : (float *)alloc_poison(b, M * 4);
+        e.aux = up_floats(b, s.aux, M, ok);
+        e.bias = up_floats(b, s.bias, M, ok);
+        e.epi = s.epi;
+        e.emit = s.emit ? 1 : 0;
+        ok = ok && e.y;
+        if (s.emit) ok = ok && make_act_poison(b, s.out_q8_1 ? A_Q8_1 : A_Q8_0, s.M, e.act_out);
+    }
+    ok = ok && hipDeviceSynchronize() == hipSuccess;
+    const bool ran = ok && launch_mv_group(nullptr, g);
+    ok = ok && hipDeviceSynchronize() == hipSuccess;
+    for (int i = 0; ok && ran && i < n; i++) {
+        const rwkv_mi355x_selftest_mv_entry & s = ent[i];
+        const MVEntry & e = g.e[i];
+        ok = hipMemcpy(s.y, e.y, (size_t)s.M * 4, hipMemcpyDeviceToHost) == hipSuccess;
+        if (s.emit) ok = ok && act_down(e.act_out, s.M, s.q, s.d, s.s, s.qsum);
+        if (e.carry_out) ok = ok && hipMemcpy(s.carry_out, e.carry_out, (size_t)s.K * 4, hipMemcpyDeviceToHost) == hipSuccess;
+        if (e.mu2) ok = ok && act_down(e.act2_out, s.K, s.q2, s.d2, s.s2, s.qsum2);
+    }
+    free_model(dm);
+    if (ok && ran) {
+        shape->rows = g.rows;
+        shape->grid = g.grid;
+        shape->stride = g.stride;
+        shape->units_max = g.units_max;
+        shape->cus = cus;
+        *launched = 1;
+    }
+    return ok;
+}
+
+// launch_mv_sigmul (k_mvsig) on host operands: the value matvec Wv k with the receptance Wr xr as its
+// EPI_SIGMUL_ADD gate, one launch.
+extern "C" RWKV_API bool rwkv_mi355x_selftest_mv_sigmul(int wtype_v, const void * Wv, int Mv, int F, const float * k,
+                                                        int wtype_r, const void * Wr, int Mr, int C, const float * xr,
+                                                        const float * y0, float * y, int * launched) {
+    if (!launched) return false;
+    *launched = 0;
+    if (!Wv || !Wr || !k || !xr || !y0 || !y || Mv <= 0 || Mr <= 0 || F <= 0 || C <= 0 || F % 32 || C % 32) return false;
+    DeviceModel dm;
+    DevBufs b;
+    MVEntry ev, er;
+    memset(&ev, 0, sizeof(ev));
+    memset(&er, 0, sizeof(er));
+    bool ok = upload_w(dm, wtype_v, Wv, F, Mv, ev.W) && upload_w(dm, wtype_r, Wr, C, Mr, er.W);
+    ev.src = er.src = SRC_ACT;
+    ok = ok && act_row(b, wtype_v, k, F, ev.act) && act_row(b, wtype_r, xr, C, er.act);
+    ev.y = up_floats(b, y0, (size_t)Mv, ok);
+    ev.epi = EPI_SIGMUL_ADD;
+    er.epi = EPI_STORE;
+    ok = ok && hipDeviceSynchronize() == hipSuccess;
+    const bool ran = ok && mv_sigmul_supported(ev, er) && launch_mv_sigmul(nullptr, ev, er);
+    ok = ok && hipDeviceSynchronize() == hipSuccess;
+    if (ok && ran) ok = hipMemcpy(y, ev.y, (size_t)Mv * 4, hipMemcpyDeviceToHost) == hipSuccess;
     free_model(dm);
     *launched = ok && ran ? 1 : 0;
     return ok;

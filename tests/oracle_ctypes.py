@@ -46,6 +46,8 @@ def lib():
         L.oracle_quantize_act.argtypes = [ctypes.c_int, vp, vp, ctypes.c_int64]
         L.oracle_dequantize_row.argtypes = [ctypes.c_int, vp, vp, ctypes.c_int64]
         L.oracle_matmul.argtypes = [ctypes.c_int, vp, ctypes.c_int64, ctypes.c_int64, vp, ctypes.c_int64, vp]
+        L.oracle_norm_row.argtypes = [vp, vp, ctypes.c_int64, ctypes.c_float, vp, vp]
+        L.oracle_norm_row.restype = None
         _lib = L
     return _lib
 
@@ -145,6 +147,16 @@ def matmul(fmt, w_bytes, K, M, x):
     y = np.zeros((T, M), np.float32)
     w_bytes = np.ascontiguousarray(w_bytes)
     lib().oracle_matmul(TYPE_IDS[fmt], _p(w_bytes), K, M, _p(x), T, _p(y))
+    return y
+
+
+def norm_row(x, w=None, b=None, eps=1e-5):
+    """The oracle's row LayerNorm under the current variant: x [n] float32 -> y [n]."""
+    x = np.ascontiguousarray(x, np.float32)
+    w = None if w is None else np.ascontiguousarray(w, np.float32)
+    b = None if b is None else np.ascontiguousarray(b, np.float32)
+    y = np.zeros_like(x)
+    lib().oracle_norm_row(_p(x), _p(y), x.shape[0], eps, _p(w), _p(b))
     return y
 
 

@@ -12,6 +12,9 @@ a. k_mvb (form 1, EPI_STORE) over its shape space: every weight format, K with 1
 b. In-kernel Q8 emission of k_mm / k_mm_small / k_mvb / k_fmm (and k_fmm's combine), with a
    non-emitting entry behind the emitting one, an all-zero block and a block whose scale is an fp16
    subnormal.
+b2. The int8-MFMA GEMM's own emission (form 2, token-tile records returned de-tiled): the epilogue of
+   the direct kernel emitting instead of writing y (fuse_emit), the split-K combine writing y and
+   emitting, and the entries that must not fuse.
 c. Each of the ten non-STORE epilogues at each site apply_epi is applied at (matmul_group_ref.EPI_SITES).
 """
 import ctypes
@@ -29,8 +32,11 @@ pytestmark = pytest.mark.gpu
 class Entry(ctypes.Structure):
     _fields_ = [('wtype', ctypes.c_int), ('W', ctypes.c_void_p), ('M', ctypes.c_int), ('epi', ctypes.c_int),
                 ('y0', ctypes.c_void_p), ('aux', ctypes.c_void_p), ('bias', ctypes.c_void_p), ('emit', ctypes.c_int),
-                ('out_q8_1', ctypes.c_int), ('out_tiled', ctypes.c_int), ('y', ctypes.c_void_p), ('q', ctypes.c_void_p),
-                ('d', ctypes.c_void_p), ('s', ctypes.c_void_p), ('qsum', ctypes.c_void_p)]
+                ('out_q8_1', ctypes.c_int), ('out_tiled', ctypes.c_int), ('fused', ctypes.c_int), ('y', ctypes.c_void_p),
+                ('q', ctypes.c_void_p), ('d', ctypes.c_void_p), ('s', ctypes.c_void_p), ('qsum', ctypes.c_void_p)]
+
+
+assert ctypes.sizeof(Entry) == 104 and Entry.y.offset == 64  # the layout without `fused`: it fills former padding
 
 
 def lib():
@@ -62,12 +68,14 @@ def run_group(form, split, T, K, x, entries):
         keep.append(ops)
         p = lambda a: None if a is None else a.ctypes.data
         arr[i] = Entry(TYPE_IDS[e['fmt']], p(ops[0]), M, epi, p(ops[1]), p(ops[2]), p(ops[3]), int(bool(e.get('emit'))),
-                       int(bool(e.get('q8_1'))), int(bool(e.get('tiled'))), p(o['y']), p(o.get('q')), p(o.get('d')),
+                       int(bool(e.get('q8_1'))), int(bool(e.get('tiled'))), -1, p(o['y']), p(o.get('q')), p(o.get('d')),
                        p(o.get('s')), p(o.get('qsum')))
         outs.append(o)
     launched = ctypes.c_int(-1)
     x = np.ascontiguousarray(x, np.float32)
     ok = lib().rwkv_mi355x_selftest_matmul_group(form, split, T, K, x.ctypes.data, n, arr, ctypes.byref(launched))
+    for i, o in enumerate(outs):
+        o['fused'] = arr[i].fused
     return ok, launched.value, outs
 
 
@@ -226,6 +234,102 @@ def test_emission_edge_blocks(form, fmt, K, T, q8_1):
                                                            epi=R.EPI_RELU_SQ, emit=1, q8_1=q8_1)])
     assert ok and launched == 1
     check_emit(o, ref, q8_1, f'form {form} {fmt} K {K} T {T} relu^2 edge blocks')
+
+
+# ------------------------------------------------------------- b2. the GEMM's fused tiled emission
+# launch_qgemm sets fuse_emit on an entry whose epilogue can emit Q8_0 token tiles itself; the direct
+# kernel (split 1) then writes the tile records INSTEAD of y.  Form 2 returns the flag and the records
+# de-tiled; y starts as NaN on the device, so a fused entry must come back all NaN.
+FUSABLE = [R.EPI_STORE, R.EPI_SIGMOID, R.EPI_TANH, R.EPI_SILU, R.EPI_RELU_SQ]
+FUSE_T = [2, 63, 64, 65, 130]
+
+
+def fused_cases():
+    """Every fusable epilogue on every _0 format and on Q4_1 (the fused branch adds the m * s totals
+    itself); T around the 64-token tile, M of one and three row tiles, and K = 2048 (k_qgemm_k64) / 2560
+    (k_qgemm) rotate so each meets each of the others."""
+    cases = []
+    for ei, epi in enumerate(FUSABLE):
+        for fi, fmt in enumerate(('Q4_0', 'Q5_0', 'Q8_0', 'Q4_1')):
+            i = ei * 4 + fi
+            cases.append((epi, fmt, (2048, 2560)[(ei + fi // 2) % 2], (64, 192)[(ei + fi) % 2], FUSE_T[i % 5]))
+    return cases
+
+
+def check_tiles(o, ref_y, q8_1, what):
+    q, d, s, qsum = R.emit_reference(ref_y, q8_1)
+    assert np.array_equal(o['q'], q), what + ' q'
+    assert_bits_equal(o['d'], d, what + ' d')
+    assert np.array_equal(o['qsum'], qsum), what + ' qsum'
+    if q8_1:
+        assert_bits_equal(o['s'], s, what + ' s')
+
+
+def emission_untouched(o):
+    return np.all(o['q'] == 77) and np.all(o['d'] == -1) and np.all(o['s'] == -1) and np.all(o['qsum'] == 12345)
+
+
+@pytest.mark.parametrize('epi,fmt,K,M,T', fused_cases())
+def test_gemm_fused_emission(epi, fmt, K, M, T):
+    kind = 'wide' if epi != R.EPI_STORE else 'unit'
+    ref = R.epilogue_f32(epi, R.acc_gpu(fmt, K, M, T, kind))
+    ok, launched, (o,) = run_group(2, 1, T, K, R.activations(K, T),
+                                   [dict(fmt=fmt, wb=R.weights(fmt, K, M, kind)[0], M=M, epi=epi, emit=1, tiled=1)])
+    assert ok and launched == 1 and o['fused'] == 1
+    assert np.all(np.isnan(o['y'])), 'a fused entry writes no y'
+    check_tiles(o, ref, False, f'fused {R.EPI_NAMES[epi]} {fmt} K {K} M {M} T {T}')
+
+
+@pytest.mark.parametrize('fmt,q8_1', [('Q4_0', False), ('Q5_0', False), ('Q8_0', False), ('Q4_1', True), ('Q5_1', False)])
+@pytest.mark.parametrize('M,T', [(64, 33), (96, 65)])
+def test_gemm_split_combine_emits(fmt, q8_1, M, T):
+    """Split 4: k_qg_combine applies the epilogue, writes y AND emits for every emitting entry (any M
+    % 32 == 0, either output format), beside a non-emitting entry."""
+    K = 2048
+    ref = R.epilogue_f32(R.EPI_SILU, R.acc_gpu(fmt, K, M, T, 'wide'))
+    group = [dict(fmt=fmt, wb=R.weights(fmt, K, M, 'wide')[0], M=M, epi=R.EPI_SILU, emit=1, tiled=1, q8_1=q8_1),
+             dict(fmt=fmt, wb=R.weights(fmt, K, 64)[0], M=64)]
+    ok, launched, (o, o2) = run_group(2, 4, T, K, R.activations(K, T), group)
+    assert ok and launched == 1 and o['fused'] == 1 and o2['fused'] == 0
+    assert_bits_equal(o['y'], ref, 'combine y')
+    check_tiles(o, ref, q8_1, f'combine {fmt} M {M} T {T}')
+    assert_bits_equal(o2['y'], R.acc_gpu(fmt, K, 64, T), 'second entry')
+
+
+@pytest.mark.parametrize('fmt,K,T', [('Q4_0', 2048, 65), ('Q8_0', 2560, 5)])
+def test_gemm_entries_that_must_not_fuse(fmt, K, T):
+    """Beside a fusing entry in the same launch: M = 96 (no whole 64-row tiles), an ADD epilogue (reads
+    y) and a Q8_1 output each keep the plain store -- y written, nothing emitted."""
+    x = R.activations(K, T)
+    y0, _, _ = R.epi_operands(R.EPI_ADD, T, 64)
+    group = [dict(fmt=fmt, wb=R.weights(fmt, K, 64)[0], M=64, emit=1, tiled=1),
+             dict(fmt=fmt, wb=R.weights(fmt, K, 96)[0], M=96, emit=1, tiled=1),
+             dict(fmt=fmt, wb=R.weights(fmt, K, 64, 'wide')[0], M=64, epi=R.EPI_ADD, y0=y0, emit=1, tiled=1),
+             dict(fmt=fmt, wb=R.weights(fmt, K, 128)[0], M=128, emit=1, tiled=1, q8_1=True)]
+    ok, launched, outs = run_group(2, 1, T, K, x, group)
+    assert ok and launched == 1 and [o['fused'] for o in outs] == [1, 0, 0, 0]
+    assert np.all(np.isnan(outs[0]['y']))
+    check_tiles(outs[0], R.acc_gpu(fmt, K, 64, T), False, 'the fusing entry')
+    refs = [R.acc_gpu(fmt, K, 96, T), R.epilogue_f32(R.EPI_ADD, R.acc_gpu(fmt, K, 64, T, 'wide'), y0),
+            R.acc_gpu(fmt, K, 128, T)]
+    for o, ref in zip(outs[1:], refs):
+        assert_bits_equal(o['y'], ref, 'a non-fused entry')
+        assert emission_untouched(o)
+
+
+@pytest.mark.parametrize('fmt,K,T', [('Q4_0', 2048, 5), ('Q5_0', 2560, 65), ('Q8_0', 2048, 64)])
+def test_gemm_fused_emission_edge_blocks(fmt, K, T):
+    """EPI_RELU_SQ over the 'edge' operands (test_emission_edge_blocks): an all-zero block and a block
+    whose scale is an fp16 subnormal, through the fused emission."""
+    M = 64
+    acc = R.acc_gpu(fmt, K, M, T, 'edge')
+    ref = R.epilogue_f32(R.EPI_RELU_SQ, acc)
+    _, d, _, _ = R.emit_reference(ref, False)
+    assert np.all(acc[:, :32] < 0) and np.all(d[:, 0] == 0) and np.all((d[:, 1] > 0) & (d[:, 1] < 2.0 ** -14))
+    ok, launched, (o,) = run_group(2, 1, T, K, R.activations(K, T, 'edge'),
+                                   [dict(fmt=fmt, wb=R.weights(fmt, K, M, 'edge')[0], M=M, epi=R.EPI_RELU_SQ, emit=1, tiled=1)])
+    assert ok and launched == 1 and o['fused'] == 1 and np.all(np.isnan(o['y']))
+    check_tiles(o, ref, False, f'fused relu^2 edge blocks {fmt} K {K} T {T}')
 
 
 # ------------------------------------------------------------------------ c. every epilogue, every site
