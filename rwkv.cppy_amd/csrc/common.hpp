@@ -65,7 +65,7 @@ struct ActBuf {
 //                 [rows x 32 int8 (the block's integer weights, offset applied: q-8 / q-16 for
 //                  _0, q for _1, 5th bit merged)][rows x f32 d] (the fp16 scales widened exactly,
 //                  so the GEMM epilogue needs no conversion); the _1 formats' mins m go to DMat::mt
-//                  ([block][row] f32), read by the m*s chain kernel (qgemm.hip k_qg_msum)
+//                  ([block][row] f32), read by the m*s chain kernel (qg_msum.hip k_qg_msum)
 //   activations per (QG_TOK-token tile, block b), ordered [token tile][b]:
 //                 [2 halves x QG_TOK tokens x 16 B int8][QG_TOK x f32 d][Q8_1: QG_TOK x f32 s]
 constexpr int QG_TOK = 64;

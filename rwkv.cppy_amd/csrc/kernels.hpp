@@ -13,7 +13,12 @@ bool launch_mm_group(hipStream_t st, MMGroup & g, int wtype);
 bool launch_qgemm(hipStream_t st, MMGroup & g, int wtype);
 // F16 / F32 weights over T >= 16 tokens on the f32 MFMA (mv_fmfma.hip); *launched = false: not covered
 bool launch_fmm_group(hipStream_t st, MMGroup & g, int wtype, bool * launched);
-bool launch_qg_combine(hipStream_t st, MMGroup & g, int split);
+// The _1 formats' m*s totals of a GEMM group into g.m2, ahead of the GEMM (qg_msum.hip; launch_qgemm
+// calls it); nothing for the other formats
+bool launch_qg_msum(hipStream_t st, MMGroup & g, int wtype);
+// The split-K combine (k_qg_combine) of a group's partials at g.part + poff: split = 2, 4 or 8
+// subtrees; one: plus the m*s totals
+bool launch_qg_combine(hipStream_t st, MMGroup & g, int split, bool one);
 extern int kQgCUs;
 // Batched decode matvec (mv_batch.hip): the T rows are T independent contexts; same results as
 // launch_mm_group.  *launched = false (and nothing enqueued) for shapes it does not cover.

@@ -340,7 +340,7 @@ bool launch_fmm_group(hipStream_t st, MMGroup & g, int wtype, bool * launched) {
     else FMM_L(W_F32);
 #undef FMM_L
     HIP_OK(hipGetLastError());
-    if (split > 1 && !launch_qg_combine(st, g, split)) return false;
+    if (split > 1 && !launch_qg_combine(st, g, split, false)) return false;
     *launched = true;
     return true;
 }

@@ -83,7 +83,8 @@ def test_activation_quantizer_bit_exact(wfmt, afmt):
 @pytest.mark.parametrize('fmt', ['FP32', 'FP16', 'Q4_0', 'Q4_1', 'Q5_0', 'Q5_1', 'Q8_0'])
 @pytest.mark.parametrize('M,K,T', [(2048, 2048, 1), (100, 96, 1), (64, 7168, 1), (160, 2048, 5), (72, 320, 9),
                                    (96, 2560, 16), (2560, 64, 40), (200, 2048, 64), (64, 160, 33),
-                                   (4096, 2048, 128), (512, 7168, 80)])
+                                   (4096, 2048, 128), (512, 7168, 80), (64, 2560, 33), (64, 7168, 5),
+                                   (64, 2048, 5)])
 def test_matmul_kernel(fmt, M, K, T):
     """The sequence / batched matmul vs the GPU-association oracle, bit for bit; from T = 16 the FP16 and
     FP32 weights run on the f32 MFMA (mv_fmfma.hip)."""
@@ -113,9 +114,12 @@ def test_matmul_kernel(fmt, M, K, T):
 
 @pytest.mark.parametrize('fmt', ['Q4_0', 'Q4_1', 'Q5_0', 'Q5_1', 'Q8_0'])
 @pytest.mark.parametrize('M,K,T', [(2048, 2048, 70), (100, 96, 3), (64, 7168, 33), (160, 2048, 64), (72, 320, 9),
-                                   (2048, 64, 17), (40, 4096, 2), (64, 20480, 40), (96, 14336, 70)])
+                                   (2048, 64, 17), (40, 4096, 2), (64, 20480, 40), (96, 14336, 70),
+                                   (64, 160, 33), (64, 2560, 33), (64, 7168, 5), (64, 2048, 5)])
 def test_mfma_gemm_matches_matmul_bit_exact(fmt, M, K, T):
-    """K up to 20480 (a 14B-class FFN value width): the _1 formats' m*s pass at 9-16 blocks per class."""
+    """K up to 20480 (a 14B-class FFN value width): the _1 formats' m*s pass at 9-16 blocks per class.
+    The last four shapes: its tile form with empty classes (K = 160) and with classes of two blocks and
+    of one (K = 2560), its row form with classes of 4 and 3 blocks (K = 7168, T <= 32) and of one."""
     rng = np.random.default_rng(M * 3 + K * 5 + T)
     w = (rng.standard_normal((M, K)) / np.sqrt(K)).astype(np.float32)
     x = rng.standard_normal((T, K)).astype(np.float32)

@@ -3,6 +3,7 @@
 // with random F16 weights and activations, and prints an output hash (for A/B of variants).
 #include "mv_fmfma.hip"
 #include "qgemm.hip"
+#include "qg_msum.hip"
 
 #include <string.h>
 #include <vector>

@@ -2,6 +2,7 @@
 // launch_mm_group (k_mm) on the v6-1B6 layer shapes at T = 1024 with random Q4_0 weights.
 #include "kernels.hip"
 #include "qgemm.hip"
+#include "qg_msum.hip"
 
 #include <string.h>
 #include <vector>
