@@ -1,13 +1,12 @@
-// engine.hip -- the engine core: lifetime, workspace, the per-version sequence / batched forward
-// programs, the state I/O and the evaluation entry points on host or device state.  The
-// single-token decode program: engine_decode.hip; batched decode and generation: engine_batch.hip;
-// sampling, generation and scoring: engine_generate.hip; the weights: model_upload.hip.
+// engine.hip -- the engine core: lifetime, workspace, the timing tables, the state I/O, the
+// evaluation entry points on host or device state and the debug hooks.  The two forward programs:
+// engine_decode.hip (one token) and engine_sequence.hip (T rows: sequences, batched steps, packed
+// chunks); batched decode and generation: engine_batch.hip; sampling, generation and scoring:
+// engine_generate.hip; batched prefill: engine_prefill.hip; the weights: model_upload.hip.
 //
 // A token step is a fixed sequence of launches on the context's stream.  The T == 1 step
 // is captured once into a hipGraph per (state parity, logits) and replayed, so decode pays
-// no host launch cost.  Per-layer programs restate rwkv_graph.inc:
-//   v4  :84-197 + FFN :484-511      v5  :199-292 + FFN :484-511
-//   v6  :294-385 + FFN :513-531     v7  :387-482 + FFN :533-543
+// no host launch cost.
 #include "engine.hpp"
 
 #include <stdio.h>
@@ -290,11 +289,11 @@ bool Engine::init_state(float * st, size_t n) {
     return true;
 }
 
-ActBuf Engine::Aview(int slot, int K, int fmt) const {
+ActBuf Engine::A(int slot, const DMat & W, bool tiled) const {
     const ActSlot & s = slots_[slot];
     ActBuf a;
-    a.fmt = fmt;
-    a.K = K;
+    a.fmt = act_fmt_for(W.type);
+    a.K = W.K;
     a.f = s.f;
     a.h = s.h;
     a.q = s.q;
@@ -302,175 +301,15 @@ ActBuf Engine::Aview(int slot, int K, int fmt) const {
     a.s = s.s;
     a.qsum = s.qsum;
     a.tq = s.tq;
-    a.tiled = tile_acts_ && (fmt == A_Q8_0 || fmt == A_Q8_1);
+    a.tiled = tiled && (a.fmt == A_Q8_0 || a.fmt == A_Q8_1);
     return a;
 }
-
-ActBuf Engine::A(int slot, const DMat & W) const { return Aview(slot, W.K, act_fmt_for(W.type)); }
-
-// Collects matmul entries and launches them grouped by weight type.
-struct MMBatch {
-    std::vector<MMEntry> e;
-    void add(const DMat & W, const ActBuf & in, float * y, int ldy, int epi, const float * aux = nullptr,
-             const float * bias = nullptr, const ActBuf * out = nullptr) {
-        MMEntry m;
-        memset(&m, 0, sizeof(m));
-        m.W = W;
-        m.in = in;
-        m.y = y;
-        m.ldy = ldy;
-        m.aux = aux;
-        m.bias = bias;
-        m.epi = epi;
-        if (out) {
-            m.out = *out;
-            m.emit = 1;
-        }
-        e.push_back(m);
-    }
-    bool run(Engine & eng, int T) {
-        std::vector<bool> done(e.size(), false);
-        for (size_t i = 0; i < e.size(); i++) {
-            if (done[i]) continue;
-            MMGroup g;
-            memset(&g, 0, sizeof(g));
-            g.T = T;
-            const int type = e[i].W.type;
-            for (size_t j = i; j < e.size() && g.n < MM_MAX_ENTRIES; j++) {
-                if (!done[j] && e[j].W.type == type) {
-                    g.e[g.n++] = e[j];
-                    done[j] = true;
-                }
-            }
-            if (!eng.mm_launch(g, type)) return false;
-        }
-        e.clear();
-        return true;
-    }
-};
 
 void Engine::set_timing(bool on) {
     (void)hipStreamSynchronize(stream_);
     collect_timing();
     timing_ = on;
     if (on) stats_.clear();
-}
-
-// Sequence matmuls on quantized weights go to the int8-MFMA GEMM; entries that only emit get
-// a scratch y, and emission is a separate quantization pass (same bits as k_mm's epilogue).
-bool Engine::mm_dispatch(MMGroup & g, int wtype) {
-    // batched decode (bs_ > 0): the decode matvec over the contexts (k_mvb; k_mm for shapes it
-    // does not cover -- the same bits); from batch_gemm_min_ contexts on, the quantized matmuls
-    // take the int8-MFMA sequence GEMM on token tiles instead (tile_acts_; also the same bits)
-    if (!wtype_quantized(wtype) && g.T >= 32) {
-        // k_fmm may split the class tree of a small grid (the v7 LoRA first stage): partials, only
-        // when launch_fmm_group's rule can split this group (below 2 workgroups per CU)
-        size_t msum = 0;
-        int blocks = 0;
-        bool splittable = true;
-        for (int i = 0; i < g.n; i++) {
-            msum += g.e[i].W.M;
-            blocks += (g.e[i].W.M + 63) / 64 * ((g.T + 63) / 64);
-            splittable = splittable && g.e[i].W.K >= 512 && g.e[i].W.M % 32 == 0;
-        }
-        if (splittable && blocks < 2 * kQgCUs) {
-            const size_t split = (size_t)blocks * 4 >= (size_t)2 * kQgCUs ? 4 : 8;
-            const size_t pneed = split * g.T * msum;
-            if (!grow(part_, pneed, pneed, GRAPHS_BATCH)) return false;
-            g.part = part_;
-            g.part_floats = part_.size();
-        }
-    }
-    if (bs_ && !(tile_acts_ && wtype_quantized(wtype))) {
-        bool launched = false;
-        // float weights (the F16 head, LoRA) over 16+ contexts: the f32-MFMA form, same bits
-        if (!launch_fmm_group(stream_, g, wtype, &launched)) return false;
-        if (launched) return true;
-        if (!launch_mvb_group(stream_, g, wtype, &launched)) return false;
-        if (launched) return true;
-        return launch_mm_group(stream_, g, wtype);
-    }
-    if (g.T < 2 || !wtype_quantized(wtype) || use_mm_) return launch_mm_group(stream_, g, wtype);
-    size_t need = 0;
-    for (int i = 0; i < g.n; i++)
-        if (!g.e[i].y) need += (size_t)g.T * g.e[i].W.M;
-    if (!grow(gy_, need, need, GRAPHS_BATCH)) return false;
-    // split-K partials (launch_qgemm splits groups with few tiles: small T or small M)
-    {
-        const int rows = qg_rows(wtype), tilesT = (g.T + QG_TOK - 1) / QG_TOK;
-        size_t msum = 0, tiles = 0;
-        for (int i = 0; i < g.n; i++) {
-            msum += g.e[i].W.M;
-            tiles += (size_t)(g.e[i].W.M + rows - 1) / rows * tilesT;
-        }
-        if (tiles < 1024) {
-            const size_t pneed = (size_t)8 * g.T * msum;
-            if (!grow(part_, pneed, pneed, GRAPHS_BATCH)) return false;
-            g.part = part_;
-            g.part_floats = part_.size();
-        }
-        if (qg_one(wtype)) {
-            const size_t mneed = (size_t)g.T * msum;
-            if (!grow(m2_, mneed, mneed, GRAPHS_BATCH)) return false;
-            g.m2 = m2_;
-            g.m2_floats = m2_.size();
-        }
-    }
-    size_t off = 0;
-    for (int i = 0; i < g.n; i++) {
-        MMEntry & e = g.e[i];
-        if (!e.y) {
-            e.y = gy_ + off;
-            e.ldy = e.W.M;
-            off += (size_t)g.T * e.W.M;
-        }
-    }
-    if (!launch_qgemm(stream_, g, wtype)) return false;
-    for (int i = 0; i < g.n; i++) {
-        const MMEntry & e = g.e[i];
-        if (e.emit && !e.fuse_emit && e.ldy == e.W.M && !launch_act_from_f32(stream_, e.y, g.T, e.W.M, e.out))
-            return false;
-        if (e.emit && e.ldy != e.W.M) {
-            fprintf(stderr, "rwkv: emitting GEMM entry needs ldy == M\n");
-            return false;
-        }
-    }
-    return true;
-}
-
-bool Engine::mm_launch(MMGroup & g, int wtype) {
-    if (!timing_) return mm_dispatch(g, wtype);
-    bool emit = false;
-    double bytes = 0, flops = 0;
-    for (int i = 0; i < g.n; i++) {
-        const MMEntry & e = g.e[i];
-        emit |= e.emit != 0;
-        bytes += (double)type_nbytes((uint32_t)e.W.type, (uint64_t)e.W.M * e.W.K) + act_bytes(e.in, g.T);
-        if (e.y) bytes += (double)g.T * e.W.M * 4 * ((e.epi == EPI_ADD || e.epi == EPI_SIGMUL_ADD || e.epi == EPI_VMIX7) ? 2 : 1);
-        if (e.emit) bytes += act_bytes(e.out, g.T);
-        flops += 2.0 * e.W.M * e.W.K * g.T;
-    }
-    // kernel class = the template instantiation rocprofv3 reports: k_mm<WF, RPW, NT>
-    const bool mfma = g.T >= 2 && wtype_quantized(wtype) && !use_mm_ && (!bs_ || tile_acts_);
-    const std::string name = mfma ? "k_qgemm<" + std::to_string(wtype) + ">"
-                           : bs_ ? "k_mvb<" + std::to_string(wtype) + ">"
-                                  : "k_mm<" + std::to_string(wtype) + ", " + (emit ? "8" : "2") + ", " + (g.T == 1 ? "1" : "4") + ">";
-    const int si = add_stat(name);
-    hipEvent_t a, b;
-    if (event_pool_.size() >= 2) {
-        a = event_pool_.back();
-        event_pool_.pop_back();
-        b = event_pool_.back();
-        event_pool_.pop_back();
-    } else {
-        HIP_OK(hipEventCreate(&a));
-        HIP_OK(hipEventCreate(&b));
-    }
-    HIP_OK(hipEventRecord(a, stream_));
-    const bool ok = mm_dispatch(g, wtype);
-    HIP_OK(hipEventRecord(b, stream_));
-    pending_.push_back(Pending{si, a, b, bytes, flops});
-    return ok;
 }
 
 int Engine::add_stat(const std::string & name) {
@@ -502,328 +341,9 @@ const std::vector<KernelStat> & Engine::stats() {
     return stats_;
 }
 
-// The LayerNorm + token shift + mix launch of a sequence / batched layer, up to its outputs:
-// carry_in / carry_out = the layer's *_xx state row (context t's at + t * bs_ in a batched step)
-LnMixArgs Engine::ln_mix_args(int T, const float * carry_in, float * carry_out, const float * lnw, const float * lnb) const {
-    LnMixArgs a;
-    memset(&a, 0, sizeof(a));
-    a.T = T;
-    a.C = (int)m_->n_embed;
-    a.x = x_;
-    a.carry_in = carry_in;
-    a.carry_out = carry_out;
-    a.bs = bs_;
-    a.lnw = lnw;
-    a.lnb = lnb;
-    return a;
-}
-
-bool Engine::ffn(int l, int T, const float * si, float * so) {
-    const DLayer & L = m_->layers[l];
-    const int C = (int)m_->n_embed;
-    LnMixArgs a = ln_mix_args(T, si, so, L.ln2_w, L.ln2_b);  // ffn_xx at layer offset 0
-    MMBatch b;
-    if (m_->major == 7) {
-        // rwkv_graph.inc:533-543
-        a.form = 1;
-        a.n_out = 1;
-        a.mu[0] = L.ffn_x_k;
-        a.out[0] = A(0, L.ffn_k);
-        if (!launch_ln_mix(stream_, a, seg_)) return false;
-        ActBuf kin = A(1, L.ffn_v);
-        b.add(L.ffn_k, A(0, L.ffn_k), nullptr, 0, EPI_RELU_SQ, nullptr, nullptr, &kin);
-        if (!b.run(*this, T)) return false;
-        b.add(L.ffn_v, kin, x_, C, EPI_ADD);
-        return b.run(*this, T);
-    }
-    // v4/v5: rwkv_graph.inc:484-511 (form 0); v6: :513-531 (form 1)
-    a.form = m_->major == 6 ? 1 : 0;
-    a.n_out = 2;
-    a.mu[0] = m_->major == 6 ? L.ffn_maa_k : L.ffn_mix_k;
-    a.mu[1] = m_->major == 6 ? L.ffn_maa_r : L.ffn_mix_r;
-    a.out[0] = A(0, L.ffn_k);
-    a.out[1] = A(1, L.ffn_r);
-    if (!launch_ln_mix(stream_, a, seg_)) return false;
-    ActBuf kin = A(2, L.ffn_v);
-    b.add(L.ffn_r, A(1, L.ffn_r), fr_, C, EPI_STORE);
-    b.add(L.ffn_k, A(0, L.ffn_k), nullptr, 0, EPI_RELU_SQ, nullptr, nullptr, &kin);
-    if (!b.run(*this, T)) return false;
-    b.add(L.ffn_v, kin, x_, C, EPI_SIGMUL_ADD, fr_);
-    return b.run(*this, T);
-}
-
-static bool launch_att_dec(hipStream_t st, const Att6Dec & a) { return launch_att6_dec(st, a); }
-static bool launch_att_dec(hipStream_t st, const Att7Dec & a) { return launch_att7_dec(st, a); }
-
-// Batched decode (bs_ > 0): the attention core of every context is the decode kernel itself (one
-// workgroup per head and context, k_att6_dec / k_att7_dec); its output goes to Wo's input `o`
-// (emitted by the kernel when heads are whole quantization blocks, else fp32 y_ converted).
-// The rest of such a layer: a = att6_args / att7_args, then Wo (input slot wo_slot) and the FFN.
-template <class Att>
-bool Engine::batch_att_tail(Att a, int wo_slot, int l, int T, const float * si, float * so) {
-    const DLayer & L = m_->layers[l];
-    const int C = (int)m_->n_embed;
-    ActBuf o = A(wo_slot, L.att_o);
-    a.nb = T;
-    a.bs = bs_;
-    if (a.S >= 32) a.yq = o;
-    if (!launch_att_dec(stream_, a)) return false;
-    if (a.S < 32 && !launch_act_from_f32(stream_, y_, T, C, o)) return false;
-    MMBatch b;
-    b.add(L.att_o, o, x_, C, EPI_ADD);
-    if (!b.run(*this, T)) return false;
-    return ffn(l, T, si, so);
-}
-
-bool Engine::layer_v4(int l, int T, const float * si, float * so) {
-    const DLayer & L = m_->layers[l];
-    const int C = (int)m_->n_embed;
-    LnMixArgs a = ln_mix_args(T, si + C, so + C, L.ln1_w, L.ln1_b);
-    a.form = 0;
-    a.n_out = 3;
-    a.mu[0] = L.att_mix_k;
-    a.mu[1] = L.att_mix_v;
-    a.mu[2] = L.att_mix_r;
-    a.out[0] = A(0, L.att_k);
-    a.out[1] = A(1, L.att_v);
-    a.out[2] = A(2, L.att_r);
-    if (!launch_ln_mix(stream_, a, seg_)) return false;
-    MMBatch b;
-    b.add(L.att_r, A(2, L.att_r), r_, C, EPI_SIGMOID);
-    b.add(L.att_k, A(0, L.att_k), k_, C, EPI_STORE);
-    b.add(L.att_v, A(1, L.att_v), v_, C, EPI_STORE);
-    if (!b.run(*this, T)) return false;
-    ActBuf o = A(3, L.att_o);
-    if (!launch_wkv4(stream_, T, C, r_, k_, v_, L.att_first, L.att_decay, si, so, o, (int)bs_, seg_)) return false;
-    b.add(L.att_o, o, x_, C, EPI_ADD);
-    if (!b.run(*this, T)) return false;
-    return ffn(l, T, si, so);
-}
-
-// v5/v6 sequence wkv: the serial recurrence (k_wkv6_s64, bit-exact with decode; a prefill's packed
-// chunk always: its segmented form), or behind the wkv_chunk_ switch the chunk-parallel form (RA / KB in the v7-only nb_ / bb_ buffers, free during a
-// v5/v6 layer; the chunk matrices and states in wkvc_, grown on demand)
-bool Engine::wkv6(int T, int H, int S, const float * u, const float * w, int wpt, const float * sin, float * sout) {
-    if (wkv_chunk_ && !seg_ && wkv6_chunked_supported(T, S, (int)bs_)) {
-        const size_t need = wkv6_chunked_scratch_floats(T, H);
-        if (!grow(wkvc_, need, need, GRAPHS_NONE)) return false;
-        return launch_wkv6_chunked(stream_, T, H, k_, v_, r_, u, w, wpt, sin, sout, y_, nb_, bb_, wkvc_);
-    }
-    return launch_wkv6(stream_, T, H, S, k_, v_, r_, u, w, wpt, sin, sout, y_, seg_);
-}
-
-bool Engine::layer_v5(int l, int T, const float * si, float * so) {
-    const DLayer & L = m_->layers[l];
-    const int C = (int)m_->n_embed, H = (int)m_->H, S = (int)m_->S;
-    const bool v52 = m_->minor >= 2;
-    LnMixArgs a = ln_mix_args(T, si + C, so + C, L.ln1_w, L.ln1_b);
-    a.form = 0;
-    a.n_out = v52 ? 4 : 3;
-    a.mu[0] = L.att_mix_k;
-    a.mu[1] = L.att_mix_v;
-    a.mu[2] = L.att_mix_r;
-    a.out[0] = A(0, L.att_k);
-    a.out[1] = A(1, L.att_v);
-    a.out[2] = A(2, L.att_r);
-    if (v52) {
-        a.mu[3] = L.att_mix_g;
-        a.out[3] = A(3, L.att_g);
-    }
-    if (!launch_ln_mix(stream_, a, seg_)) return false;
-    MMBatch b;
-    b.add(L.att_r, A(2, L.att_r), r_, C, EPI_STORE);
-    b.add(L.att_k, A(0, L.att_k), k_, C, EPI_STORE);
-    b.add(L.att_v, A(1, L.att_v), v_, C, EPI_STORE);
-    if (v52) b.add(L.att_g, A(3, L.att_g), g_, C, EPI_SILU);
-    if (!b.run(*this, T)) return false;
-    if (bs_) return batch_att_tail(att6_args(L, si, so), 4, l, T, si, so);
-    if (!wkv6(T, H, S, L.att_u, L.att_w, 0, si + 2 * C, so + 2 * C)) return false;
-    ActBuf o = A(4, L.att_o);
-    if (!launch_groupnorm(stream_, T, H, S, 1e-5f, y_, L.att_lnx_w, L.att_lnx_b, v52 ? 1 : 0, g_, nullptr, nullptr, o))
-        return false;
-    b.add(L.att_o, o, x_, C, EPI_ADD);
-    if (!b.run(*this, T)) return false;
-    return ffn(l, T, si, so);
-}
-
-bool Engine::layer_v6(int l, int T, const float * si, float * so) {
-    const DLayer & L = m_->layers[l];
-    const int C = (int)m_->n_embed, H = (int)m_->H, S = (int)m_->S, D = m_->maa_D;
-    LnMixArgs a = ln_mix_args(T, si + C, so + C, L.ln1_w, L.ln1_b);
-    a.form = 1;
-    a.n_out = 1;
-    a.mu[0] = L.maa_x;
-    a.out[0] = A(0, L.maa_w1);
-    a.out_xa = xa_;
-    a.out_sx = sx_;
-    if (!launch_ln_mix(stream_, a, seg_)) return false;
-    MMBatch b;
-    b.add(L.maa_w1, A(0, L.maa_w1), lora_, 5 * D, EPI_TANH);
-    if (!b.run(*this, T)) return false;
-    // order w, k, v, r, g (rwkv_graph.inc:336-346)
-    ActBuf outs[5] = {A(1, L.decay_w1), A(2, L.att_k), A(3, L.att_v), A(4, L.att_r), A(5, L.att_g)};
-    // batched decode: the decode kernel's per-(mix, channel) arithmetic over the contexts; from
-    // batch_gemm_min_ contexts on (token-tile outputs) the sequence kernel's f32-MFMA form over the
-    // contexts as tokens -- W2 read once per 64 contexts instead of once per context, same bits
-    if ((bs_ && !tile_acts_) ? !launch_v6_mix5_dec(stream_, C, D, xa_, nullptr, lora_, L.maa_w2t, L.maa, outs, T, sx_)
-                             : !launch_v6_mix5(stream_, T, C, D, lora_, L.maa_w2t, L.maa, xa_, sx_, outs))
-        return false;
-    ActBuf dl = A(6, L.decay_w2);
-    // decay tail by threads (k_att6_dec's rows) when Wd2 is quantized; dl fp32 then reuses lora_
-    // (consumed by mix5 above)
-    const int DD = L.decay_w2.K;  // decay LoRA width (64 for the released checkpoints)
-    const bool dseq = v6_decay_seq_supported(L.decay_w2.type, DD) && L.decay_w1.M == DD;
-    if (bs_) {
-        // decode's split: decay W1 (tanh) with r,k,v,g; the LoRA tail, wkv and GroupNorm per head
-        b.add(L.att_r, outs[3], r_, C, EPI_STORE);
-        b.add(L.att_k, outs[1], k_, C, EPI_STORE);
-        b.add(L.att_v, outs[2], v_, C, EPI_STORE);
-        b.add(L.att_g, outs[4], g_, C, EPI_SILU);
-        b.add(L.decay_w1, outs[0], lora_, L.decay_w1.M, EPI_TANH);
-        if (!b.run(*this, T)) return false;
-        return batch_att_tail(att6_args(L, si, so), 7, l, T, si, so);
-    }
-    b.add(L.att_r, outs[3], r_, C, EPI_STORE);
-    b.add(L.att_k, outs[1], k_, C, EPI_STORE);
-    b.add(L.att_v, outs[2], v_, C, EPI_STORE);
-    b.add(L.att_g, outs[4], g_, C, EPI_SILU);
-    if (dseq) b.add(L.decay_w1, outs[0], lora_, DD, EPI_TANH);
-    else b.add(L.decay_w1, outs[0], nullptr, 0, EPI_TANH, nullptr, nullptr, &dl);
-    if (!b.run(*this, T)) return false;
-    if (dseq) {
-        if (!launch_v6_decay_seq(stream_, T, C, L.decay_w2, lora_, L.decay6, w_)) return false;
-    } else {
-        b.add(L.decay_w2, dl, w_, C, EPI_DECAY6, nullptr, L.decay6);
-        if (!b.run(*this, T)) return false;
-    }
-    if (!wkv6(T, H, S, L.att_u, w_, 1, si + 2 * C, so + 2 * C)) return false;
-    ActBuf o = A(7, L.att_o);
-    if (!launch_groupnorm(stream_, T, H, S, 64e-5f, y_, L.att_lnx_w, L.att_lnx_b, 1, g_, nullptr, nullptr, o)) return false;
-    b.add(L.att_o, o, x_, C, EPI_ADD);
-    if (!b.run(*this, T)) return false;
-    return ffn(l, T, si, so);
-}
-
-bool Engine::layer_v7(int l, int T, const float * si, float * so) {
-    const DLayer & L = m_->layers[l];
-    const int C = (int)m_->n_embed, H = (int)m_->H, S = (int)m_->S;
-    LnMixArgs a = ln_mix_args(T, si + C, so + C, L.ln1_w, L.ln1_b);
-    a.form = 1;
-    // order r, w, k, v, a, g (rwkv_graph.inc:404-413)
-    const DMat * cons[6] = {&L.att_r, &L.w1, &L.att_k, &L.att_v, &L.a1, &L.g1};
-    a.n_out = 6;
-    for (int n = 0; n < 6; n++) {
-        a.mu[n] = L.x_rwkvag + (size_t)n * C;
-        a.out[n] = A(n, *cons[n]);
-    }
-    const bool vlora = l != 0;
-    ActBuf xv1;
-    if (vlora) {
-        xv1 = A(9, L.v1);
-        if (xv1.fmt == a.out[3].fmt) {
-            xv1 = a.out[3];
-            xv1.K = L.v1.K;
-        } else {
-            // second emission of xv in the LoRA's input format; mix kernels take <= 6 outputs,
-            // so re-run the mix for this one vector
-            LnMixArgs a2 = a;
-            a2.n_out = 1;
-            a2.mu[0] = a.mu[3];
-            a2.out[0] = xv1;
-            a2.carry_out = nullptr;
-            if (!launch_ln_mix(stream_, a2, seg_)) return false;
-        }
-    }
-    if (!launch_ln_mix(stream_, a, seg_)) return false;
-    MMBatch b;
-    ActBuf lw = A(6, L.w2), la = A(7, L.a2), lg = A(8, L.g2);
-    b.add(L.att_r, a.out[0], r_, C, EPI_STORE);
-    b.add(L.att_k, a.out[2], k_, C, EPI_STORE);
-    b.add(L.att_v, a.out[3], v_, C, EPI_STORE);
-    b.add(L.w1, a.out[1], nullptr, 0, EPI_TANH, nullptr, nullptr, &lw);
-    b.add(L.a1, a.out[4], nullptr, 0, EPI_STORE, nullptr, nullptr, &la);
-    b.add(L.g1, a.out[5], nullptr, 0, EPI_SIGMOID, nullptr, nullptr, &lg);
-    ActBuf lvv;
-    if (vlora) {
-        lvv = A(10, L.v2);
-        b.add(L.v1, xv1, nullptr, 0, EPI_STORE, nullptr, nullptr, &lvv);
-    }
-    if (!b.run(*this, T)) return false;
-    if (l == 0) {
-        HIP_OK(hipMemcpyAsync(vfirst_, v_, (size_t)T * C * 4, hipMemcpyDeviceToDevice, stream_));
-    }
-    b.add(L.w2, lw, w_, C, EPI_DECAY7, nullptr, L.w0);
-    b.add(L.a2, la, a_, C, EPI_SIGMOID_BIAS, nullptr, L.a0);
-    b.add(L.g2, lg, g_, C, EPI_STORE);
-    if (vlora) b.add(L.v2, lvv, v_, C, EPI_VMIX7, vfirst_, L.v0);
-    if (!b.run(*this, T)) return false;
-    if (bs_) return batch_att_tail(att7_args(L, si, so), 0, l, T, si, so);
-    if (!launch_v7_prep(stream_, T, H, S, k_, a_, r_, L.k_k, L.k_a, L.r_k, nb_, bb_, bonus_)) return false;
-    // the serial recurrence (bit-exact with decode), or behind the wkv_chunk_ switch the chunk-parallel
-    // form (wkv7_chunk.hip; scratch in wkvc_)
-    if (wkv_chunk_ && !seg_ && wkv7_chunked_supported(T, S, (int)bs_)) {
-        const size_t need = wkv7_chunked_scratch_floats(T, H);
-        if (!grow(wkvc_, need, need, GRAPHS_NONE)) return false;
-        if (!launch_wkv7_chunked(stream_, T, H, r_, w_, k_, v_, nb_, bb_, si + 2 * C, so + 2 * C, y_, wkvc_)) return false;
-    } else if (!launch_wkv7(stream_, T, H, S, r_, w_, k_, v_, nb_, bb_, si + 2 * C, so + 2 * C, y_, seg_)) {
-        return false;
-    }
-    ActBuf o = A(0, L.att_o);
-    if (!launch_groupnorm(stream_, T, H, S, 64e-5f, y_, L.att_lnx_w, L.att_lnx_b, 2, g_, v_, bonus_, o)) return false;
-    b.add(L.att_o, o, x_, C, EPI_ADD);
-    if (!b.run(*this, T)) return false;
-    return ffn(l, T, si, so);
-}
-
-bool Engine::forward(int T, const float * sin, float * sout, bool logits) {
-    if (T == 1 && !generic_decode_) return forward_decode(sin, sout, logits);
-    return forward_range(T, sin, sout, 0, m_->n_layer, logits);
-}
-
-// Layers [l0, l1) over T tokens; l0 == 0 embeds the tokens into x_, otherwise x_ (and, v7,
-// vfirst_) already hold the stream entering l0.  Head on the last token when l1 == n_layer.
-bool Engine::forward_range(int T, const float * sin, float * sout, uint32_t l0, uint32_t l1, bool logits) {
-    const size_t C = m_->n_embed;
-    last_decode_ = false;
-    // one token of its own sequence: the step's id (tok_arg); batches and packed prompts read dtokens_
-    const TokArg tk = T == 1 && !bs_ && !seg_ ? tok_arg() : TokArg{dtokens_.get(), 0u, 0u};
-    if (l0 == 0 && !launch_embed_ln(stream_, tk, T, m_->emb, m_->ln0_w, m_->ln0_b, x_)) return false;
-    const size_t per_layer = layer_state_len();
-    // layer matmuls run over all T tokens: Q8 activations go straight into GEMM tiles
-    tile_acts_ = T >= 2 && !use_mm_ && (!bs_ || T >= batch_gemm_min_);
-    for (uint32_t l = l0; l < l1; l++) {
-        const float * si = sin + l * per_layer;
-        float * so = sout + l * per_layer;
-        bool ok = false;
-        switch (m_->major) {
-            case 4: ok = layer_v4((int)l, T, si, so); break;
-            case 5: ok = layer_v5((int)l, T, si, so); break;
-            case 6: ok = layer_v6((int)l, T, si, so); break;
-            case 7: ok = layer_v7((int)l, T, si, so); break;
-            default: break;
-        }
-        if (!ok) {
-            tile_acts_ = false;
-            return false;
-        }
-    }
-    // the head runs on the last token only (batched decode: on every context; scoring runs it over
-    // every token afterwards, score_chunk)
-    tile_acts_ = false;
-    if (logits && l1 == m_->n_layer) {
-        const int rows = bs_ ? T : 1;
-        return head_rows(x_ + (size_t)(T - rows) * C, rows, head_out_ ? head_out_ : logits_);
-    }
-    return true;
-}
-
-// rwkv_graph.inc:704-708 / :850-854
-bool Engine::head_rows(const float * x, int rows, float * out) {
-    ActBuf hin = A(0, m_->head);
-    if (!launch_ln_emit(stream_, (int)m_->n_embed, x, m_->lnout_w, m_->lnout_b, hin, rows)) return false;
-    MMBatch b;
-    b.add(m_->head, hin, out, (int)m_->n_vocab, EPI_STORE);
-    return b.run(*this, rows);
+bool Engine::forward(int T, const float * sin, float * sout, bool logits, const TokArg & tok) {
+    if (T == 1 && !generic_decode_) return forward_decode(sin, sout, logits, tok);
+    return forward_range(seq_run(T, sin, sout, 0, m_->n_layer, tok, logits ? logits_.get() : nullptr));
 }
 
 // KLaunchTimer (common.hpp): while a decode step is timed, every RK_LAUNCH takes an event pair
@@ -860,14 +380,13 @@ void Engine::end(const char * kernel) {
 }
 
 // Runs T tokens from dstate_[cur_] (ping-pong), chunked by the workspace capacity.
-bool Engine::run_tokens(const uint32_t * tokens, size_t T, bool want_logits) {
+bool Engine::run_tokens(const uint32_t * tokens, size_t T, bool want_logits, const ScoreRun * score) {
     // a failed call restores the ping-pong parity it started with, so the next state upload
     // (every rwkv_eval with state_in, rwkv_mi355x_state_upload) lands where the next step reads;
     // the device state's contents after a failure are unspecified (re-upload it)
     const int cur0 = cur_;
     logits_valid_ = false;
-    if (!run_tokens_impl(tokens, T, want_logits)) {
-        step_imm_ = false;
+    if (!run_tokens_impl(tokens, T, want_logits, score)) {
         (void)hipStreamSynchronize(stream_);
         (void)gran_.clear_tagged(stream_);  // a replay runs at the same parity (GranuleMem::clear_tagged)
         (void)hipStreamSynchronize(stream_);
@@ -879,7 +398,7 @@ bool Engine::run_tokens(const uint32_t * tokens, size_t T, bool want_logits) {
     return true;
 }
 
-bool Engine::run_tokens_impl(const uint32_t * tokens, size_t T, bool want_logits) {
+bool Engine::run_tokens_impl(const uint32_t * tokens, size_t T, bool want_logits, const ScoreRun * score) {
     size_t done = 0;
     while (done < T) {
         const size_t n = std::min(T - done, kChunkMax);
@@ -889,36 +408,28 @@ bool Engine::run_tokens_impl(const uint32_t * tokens, size_t T, bool want_logits
         // a graph replay: set_tok), and nothing is enqueued to deliver it -- hipStreamWriteValue32,
         // which stood here, runs as a kernel of the runtime (__amd_rocclr_streamOpsWrite) on this
         // stream: 4.3 us and one more kernel boundary per token
-        step_imm_ = tokens && n == 1;
-        step_id_ = step_imm_ ? tokens[done] : 0;
-        if (!tokens) {
-            // generate: the sampler enqueued just before this step writes dtokens_[0]
-        } else if (n > 1 && !stage_tokens(tokens + done, n)) {
-            return false;
-        }
+        const bool imm = tokens && n == 1;
+        const TokArg tok{dtokens_.get(), imm ? tokens[done] : 0u, imm ? 1u : 0u};
+        // (tokens == NULL, generate: the sampler enqueued just before this step writes dtokens_[0])
+        if (tokens && n > 1 && !stage_tokens(tokens + done, n)) return false;
         // scoring: a one-token chunk's step writes logits_ (score_chunk reads it), longer chunks get
         // their head from score_chunk
-        const bool lg = score_ ? n == 1 : last && want_logits;
+        const bool lg = score ? n == 1 : last && want_logits;
         last_decode_ = n == 1 && !generic_decode_;
         const bool co = last_decode_ ? choose_co() : (co_ = false);
-        if (timing_) {
-            // eager launches; a decode step's kernels each carry a dispatch-bound event pair
-            // (RK_LAUNCH through g_klt), the sequence path's matmul groups an event pair around
-            // the group (mm_launch)
-            if (n == 1) g_klt = this;
-            const bool ok = forward((int)n, dstate_[cur_], dstate_[cur_ ^ 1], lg);
-            g_klt = nullptr;
-            if (!ok) return false;
-        } else if (n == 1 && use_graphs_) {
+        if (n == 1 && use_graphs_ && !timing_) {
             TokGraph & tg = graphs_[co][cur_][lg ? 1 : 0];
-            if (!tg.ge && !capture_tok(tg, [&] { return forward(1, dstate_[cur_], dstate_[cur_ ^ 1], lg); })) return false;
-            if (!tg.set_tok(tok_arg())) return false;
+            if (!tg.ge && !capture_tok(tg, [&] { return forward(1, dstate_[cur_], dstate_[cur_ ^ 1], lg, tok); })) return false;
+            if (!tg.set_tok(tok)) return false;
             HIP_OK(hipGraphLaunch(tg.ge, stream_));
         } else {
-            if (!forward((int)n, dstate_[cur_], dstate_[cur_ ^ 1], lg)) return false;
+            // eager launches; timed, a decode step's kernels each carry a dispatch-bound event pair
+            // (RK_LAUNCH through g_klt), the sequence path's matmul groups an event pair around
+            // the group (mm_launch)
+            const LaunchTimerScope timed(this, timing_ && n == 1);
+            if (!forward((int)n, dstate_[cur_], dstate_[cur_ ^ 1], lg, tok)) return false;
         }
-        step_imm_ = false;
-        if (score_ && !score_chunk(done, n, last)) return false;
+        if (score && !score_chunk(*score, done, n, last)) return false;
         // a step without the fused decode flips the parity (GranuleMem::clear_tagged)
         if (n > 1 || generic_decode_) HIP_OK(gran_.clear_tagged(stream_));
         // tokens buffer is reused by the next chunk: wait before overwriting the pinned copy
@@ -1089,19 +600,11 @@ bool Engine::eval_host_chunked(uint32_t token, const float * state_in, float * s
     float * din = dstate_[cur_], * dout = dstate_[cur_ ^ 1];
     // the id by value, as in run_tokens_impl: chunk 0's first launch consumes it, no other chunk's
     // graph holds one
-    step_imm_ = true;
-    step_id_ = token;
-    for (uint32_t c = 0; c < NC; c++) {
-        if (gs[c].ge) continue;
-        const bool ok = capture_tok(gs[c], [&] { return forward_decode(din, dout, lg, c * K, (c + 1) * K); });
-        if (!ok) {
-            step_imm_ = false;
+    const TokArg tok{dtokens_.get(), token, 1u};
+    for (uint32_t c = 0; c < NC; c++)
+        if (!gs[c].ge && !capture_tok(gs[c], [&] { return forward_decode(din, dout, lg, tok, c * K, (c + 1) * K); }))
             return false;
-        }
-    }
-    const TokArg tk = tok_arg();
-    step_imm_ = false;
-    if (!gs[0].set_tok(tk)) return false;
+    if (!gs[0].set_tok(tok)) return false;
     auto slice = [&](uint32_t c, size_t & off, size_t & bytes) {
         const uint32_t l0 = c * K, l1 = std::min(NL, l0 + K);
         off = l0 * per_layer;
@@ -1229,7 +732,8 @@ bool Engine::eval_layers(const uint32_t * tokens, size_t T, uint32_t l0, uint32_
     }
     const bool lg = (want_logits || logits_out) && l1 == m_->n_layer;
     logits_valid_ = false;
-    if (!forward_range((int)T, dstate_[cur_], dstate_[cur_ ^ 1], l0, l1, lg)) return false;
+    if (!forward_range(seq_run((int)T, dstate_[cur_], dstate_[cur_ ^ 1], l0, l1, dtok(), lg ? logits_.get() : nullptr)))
+        return false;
     // only this range's slices were written: copy them back instead of flipping the ping-pong
     // pair, so later calls on other ranges still read a complete current state
     const size_t per_layer = layer_state_len();

@@ -168,6 +168,30 @@ inline double act_bytes(const ActBuf & a, double T) {
 }
 
 struct DecodeRun;  // engine_decode.hip
+struct MMBatch;    // engine_sequence.hip
+
+// One forward of the sequence program (engine_sequence.hip) over T rows: all that its layer functions
+// know of their caller -- a forward's mode is an argument, never an engine member written around the call.
+// Made only by Engine::seq_run (a sequence), rows_run (B contexts) and packed_run (a packed prefill chunk).
+struct SeqRun {
+    int T;
+    const float * sin;
+    float * sout;
+    uint32_t l0, l1;
+    size_t bs;            // state floats between two contexts; 0: one sequence, or rows without state (a head tile)
+    const SegTab * seg;   // the packed chunk's segment table, or NULL
+    bool rows;            // the matmuls take the T rows as independent contexts (k_fmm / k_mvb / k_mm)
+    bool tile_acts;       // the layers' Q8 activations go into sequence-GEMM token tiles
+    TokArg tok;           // one token of its own sequence: the step's id; else read from dtokens_
+    float * head_out;     // where the head writes its rows; NULL: no head
+};
+
+// The scope of the launch timer (common.hpp): while one made with `on` lives, every RK_LAUNCH of
+// this thread takes its event pair from t.  Nothing else assigns g_klt.
+struct LaunchTimerScope {
+    LaunchTimerScope(KLaunchTimer * t, bool on) { if (on) g_klt = t; }
+    ~LaunchTimerScope() { g_klt = nullptr; }
+};
 
 // rwkv_mi355x_sampling with the bias arrays still on the host (include/rwkv_mi355x.h)
 struct SamplingParams {
@@ -294,7 +318,6 @@ class Engine : public KLaunchTimer, private Workspace, private GenSlots {
     bool sync();
     hipStream_t stream() const { return stream_; }
     void set_timing(bool on);
-    bool mm_launch(MMGroup & g, int wtype);
     const std::vector<KernelStat> & stats();
     float * device_state() const { return dstate_[cur_]; }
     // debugging aid (rwkv_mi355x_debug_buffer): copies a workspace buffer of the last evaluation
@@ -333,22 +356,33 @@ class Engine : public KLaunchTimer, private Workspace, private GenSlots {
     // the sampler's logit bias, (allocated and) uploaded in stream order
     bool upload_bias(uint32_t n_bias, const uint32_t * ids, const float * values);
     bool init_state(float * st, size_t n = 0);
-    bool forward(int T, const float * sin, float * sout, bool logits);
-    bool forward_range(int T, const float * sin, float * sout, uint32_t l0, uint32_t l1, bool logits);
+    // tok: the step's token id, handed on to the program that runs (DecodeRun / SeqRun)
+    bool forward(int T, const float * sin, float * sout, bool logits, const TokArg & tok);
+    // the sequence program (engine_sequence.hip) and the three makers of its argument
+    bool forward_range(const SeqRun & s);
+    SeqRun seq_run(int T, const float * sin, float * sout, uint32_t l0, uint32_t l1, const TokArg & tok,
+                   float * head_out) const;
+    // bs == 0: rows without state, for head_rows only (score_chunk, prefill_batch)
+    SeqRun rows_run(int B, size_t bs, const float * sin, float * sout, float * head_out) const;
+    SeqRun packed_run(int T, const SegTab * seg, float * states) const;  // every segment's state at its offset in states
+    SeqRun make_run(SeqRun s) const;
+    TokArg dtok() const { return TokArg{dtokens_.get(), 0u, 0u}; }  // row t's id is dtokens_[t]
     // the decode program (engine_decode.hip): per layer one decode_att_v* and decode_ffn
-    bool forward_decode(const float * sin, float * sout, bool logits, uint32_t l0 = 0, uint32_t l1 = UINT32_MAX);
+    bool forward_decode(const float * sin, float * sout, bool logits, const TokArg & tok, uint32_t l0 = 0,
+                        uint32_t l1 = UINT32_MAX);
     bool decode_att_v4(DecodeRun & d, uint32_t l);
     bool decode_att_v5(DecodeRun & d, uint32_t l);
     bool decode_att_v6(DecodeRun & d, uint32_t l);
     bool decode_att_v7(DecodeRun & d, uint32_t l);
     bool decode_ffn(DecodeRun & d, uint32_t l);
     bool mv(MVGroup & g, hipStream_t st = nullptr);
-    // argument blocks shared by the decode program and the batched step (bs_ > 0) of layer_v5/6/7
-    Att6Dec att6_args(const DLayer & L, const float * si, float * so) const;
+    // argument blocks shared by the decode program (bs == 0) and the batched step (SeqRun::bs) of layer_v5/6/7
+    Att6Dec att6_args(const DLayer & L, const float * si, float * so, size_t bs) const;
     Att7Dec att7_args(const DLayer & L, const float * si, float * so) const;
-    LnMixArgs ln_mix_args(int T, const float * carry_in, float * carry_out, const float * lnw, const float * lnb) const;
+    LnMixArgs ln_mix_args(const SeqRun & s, const float * carry_in, float * carry_out, const float * lnw,
+                          const float * lnb) const;
     template <class Att>
-    bool batch_att_tail(Att a, int wo_slot, int l, int T, const float * si, float * so);
+    bool batch_att_tail(const SeqRun & s, Att a, int wo_slot, int l, const float * si, float * so);
     // the tag of layer l's in-launch hand-offs at the current state parity, and what its launches poll with
     unsigned handoff_tag(uint32_t l) const { return (unsigned)(l + 1) | ((unsigned)(cur_ + 1) << 16); }
     Handoff handoff(uint32_t l) const { return Handoff{handoff_tag(l), herr_d_, spin_max_}; }
@@ -372,37 +406,33 @@ class Engine : public KLaunchTimer, private Workspace, private GenSlots {
     };
     template <class F>
     bool capture_tok(TokGraph & tg, F && build);
-    // the id of the step being enqueued: by value for a one-token step with a host-known id
-    // (run_tokens_impl, eval_host_chunked), else read from dtokens_
-    uint32_t step_id_ = 0;
-    bool step_imm_ = false;
-    TokArg tok_arg() const { return TokArg{dtokens_.get(), step_imm_ ? step_id_ : 0u, step_imm_ ? 1u : 0u}; }
-    // tokens == NULL (T == 1): the token is already in dtokens_[0] (generate: the sampler wrote it)
-    bool run_tokens(const uint32_t * tokens, size_t T, bool want_logits);
-    bool run_tokens_impl(const uint32_t * tokens, size_t T, bool want_logits);
-    bool sampler_buffers(const SamplingParams & p, size_t n, SampleArgs & a);
-    // final LayerNorm + head over `rows` residual rows at x into out [rows][n_vocab]
-    bool head_rows(const float * x, int rows, float * out);
-    // score(): what run_tokens_impl does after the layers of each chunk while score_ is set
+    // score(): what run_tokens_impl does after the layers of each chunk of a scoring call
     struct ScoreRun {
         const uint32_t * targets;
         float * logits_out;
     };
+    // tokens == NULL (T == 1): the token is already in dtokens_[0] (generate: the sampler wrote it);
+    // score: NULL when not scoring
+    bool run_tokens(const uint32_t * tokens, size_t T, bool want_logits, const ScoreRun * score = nullptr);
+    bool run_tokens_impl(const uint32_t * tokens, size_t T, bool want_logits, const ScoreRun * score);
+    bool sampler_buffers(const SamplingParams & p, size_t n, SampleArgs & a);
+    // final LayerNorm + head over the h.T residual rows at x into h.head_out [h.T][n_vocab]
+    bool head_rows(const SeqRun & h, const float * x);
     bool score_buffers(size_t T);
-    bool score_chunk(size_t done, size_t n, bool last);
-    ScoreRun * score_ = nullptr;
+    bool score_chunk(const ScoreRun & score, size_t done, size_t n, bool last);
     DevBuf<float> score_tile_;         // [kScoreRows][n_vocab] head tile (lazily allocated)
     DevBuf<uint32_t> score_targets_;   // one element per token of the longest call so far
     DevBuf<double> score_loss_;
     DevBuf<uint32_t> score_argmax_;
-    bool layer_v4(int l, int T, const float * si, float * so);
-    bool wkv6(int T, int H, int S, const float * u, const float * w, int wpt, const float * sin, float * sout);
-    bool layer_v5(int l, int T, const float * si, float * so);
-    bool layer_v6(int l, int T, const float * si, float * so);
-    bool layer_v7(int l, int T, const float * si, float * so);
-    bool ffn(int l, int T, const float * si, float * so);
-    ActBuf A(int slot, const DMat & W) const;
-    ActBuf Aview(int slot, int K, int fmt) const;
+    bool layer_v4(const SeqRun & s, int l, const float * si, float * so);
+    bool wkv6(const SeqRun & s, int H, int S, const float * u, const float * w, int wpt, const float * sin, float * sout);
+    bool layer_v5(const SeqRun & s, int l, const float * si, float * so);
+    bool layer_v6(const SeqRun & s, int l, const float * si, float * so);
+    bool layer_v7(const SeqRun & s, int l, const float * si, float * so);
+    bool ffn(const SeqRun & s, int l, const float * si, float * so);
+    // workspace slot `slot` as the input of W; tiled: Q8 activations in sequence-GEMM token tiles
+    ActBuf A(int slot, const DMat & W, bool tiled = false) const;
+    ActBuf A(const SeqRun & s, int slot, const DMat & W) const { return A(slot, W, s.tile_acts); }
 
     DeviceModel * m_;
     hipStream_t stream_ = nullptr;
@@ -489,25 +519,24 @@ class Engine : public KLaunchTimer, private Workspace, private GenSlots {
     int add_stat(const std::string & name);
     double kt_bytes_ = 0, kt_flops_ = 0;  // algorithmic work of the next timed launch
     hipEvent_t kt_a_ = nullptr, kt_b_ = nullptr;
-    bool mm_dispatch(MMGroup & g, int wtype);
+    // a matmul group of the sequence program: where it goes (mm_route, the one place that decides),
+    // the launches (mm_dispatch) and, timed, its stat named after the route (mm_launch)
+    friend struct MMBatch;
+    enum MMRoute { MM_QGEMM, MM_ROWS, MM_KMM };  // the sequence GEMM; rows as contexts; k_mm
+    MMRoute mm_route(int T, int wtype, bool rows, bool tile_acts) const;
+    bool mm_dispatch(MMGroup & g, int wtype, MMRoute route);
+    bool mm_launch(MMGroup & g, int wtype, MMRoute route);
     // the GEMM scratch, grown to the exact size a group needs (captured batched graphs point at it)
     DevBuf<float> gy_;    // scratch y of emit-only GEMM entries
     DevBuf<float> part_;  // split-K partials (launch_qgemm, k_fmm)
     DevBuf<float> m2_;    // _1 formats: m*s chain totals (launch_qgemm, k_qg_msum)
     bool use_mm_ = false;
-    bool tile_acts_ = false;  // Aview: Q8 activations in sequence-GEMM tiles (forward, T >= 2)
-    // batched decode (eval_batch): state floats per context while a batched forward is built
-    // (0 otherwise), the head's output rows, and the engine-owned staging buffers / graphs
-    size_t bs_ = 0;
-    // batched prefill: the segment table of the packed chunk while its forward is being enqueued (NULL
-    // otherwise) -- the third mode of the layer functions beside bs_ == 0 and bs_ > 0
-    const SegTab * seg_ = nullptr;
     size_t prefill_chunk_ = kChunkMax;  // debug knob "prefill_chunk": the packing cap in tokens
     DevBuf<uint32_t> ptokens_;          // a prefill's tokens
     DevBuf<uint64_t> ptab_;             // its segment tables and row lists
     DevBuf<float> pend_x_;              // [kBatchMax][C] the residual rows that end its prompts
-    int batch_gemm_min_ = 16;
-    float * head_out_ = nullptr;
+    int batch_gemm_min_ = 16;  // batched decode: contexts from which the quantized matmuls take the sequence GEMM
+    // batched decode (eval_batch): the engine-owned staging buffers / graphs
     DevBuf<float> bstate_[2], blogits_;  // staging of host states / logits: a power of two >= B rows
     struct BatchGraph {
         size_t B;

@@ -48,15 +48,9 @@ bool Engine::eval_batch(const uint32_t * tokens, size_t B, const float * state_i
     float * sout = (dev && state_out) ? state_out : bstate_[1].get();
     float * lout = (dev && logits_out) ? logits_out : blogits_.get();
     const bool lg = logits_out != nullptr;
-    // the batched forward: bs_ / head_out_ are set only while it is being enqueued
-    auto step = [&] {
-        bs_ = n;
-        head_out_ = lout;
-        const bool ok = forward_range((int)B, sin, sout, 0, m_->n_layer, lg);
-        bs_ = 0;
-        head_out_ = nullptr;
-        return ok;
-    };
+    // the batched forward: the eager step and the captured one enqueue from the same value
+    const SeqRun run = rows_run((int)B, n, sin, sout, lg ? lout : nullptr);
+    auto step = [&] { return forward_range(run); };
     bool ok;
     if (use_graphs_ && !timing_) {
         // one graph per (B, state pointers, logits pointer): a decode loop alternating two state
@@ -307,10 +301,11 @@ bool Engine::generate_slots(size_t Q, const BatchSamplingParams & p, size_t n, u
         // without a table draws at counter_r + counter, a lane at counter_r + its sequence's length
         a.counter = i;
         a.step = (uint32_t)i;
-        if (timing_) g_klt = this;
-        ok = (!qc || turnover(i, cur)) && (!lp || launch_logprobs(stream_, a)) && launch_sample(stream_, a) &&
-             launch_gen_snapshot(stream_, g, (uint32_t)i, cur, glogits_, gsnap_state_, gsnap_logits_);
-        g_klt = nullptr;
+        {
+            const LaunchTimerScope timed(this, timing_);
+            ok = (!qc || turnover(i, cur)) && (!lp || launch_logprobs(stream_, a)) && launch_sample(stream_, a) &&
+                 launch_gen_snapshot(stream_, g, (uint32_t)i, cur, glogits_, gsnap_state_, gsnap_logits_);
+        }
         ok = ok && eval_batch(nullptr, rows, cur, gstate_[(steps & 1) ^ 1], glogits_, true);
         if (!ok) return fail();
         steps++;

@@ -21,7 +21,8 @@ struct DecodeRun {
     const float * sin;
     float * sout;
     uint32_t l0, l1;
-    MaaDec emaa;           // v6, emb_in: layer 0's maa launch with the embedding LayerNorm inside
+    TokArg tok;            // the step's token id, for the launch that embeds it
+    MaaDec emaa;          // v6, emb_in: layer 0's maa launch with the embedding LayerNorm inside
     bool emb_in = false;   // layer 0's first launch computes the embedding LayerNorm itself
     bool emb4_in = false;  // ... and it is v4's fused attention launch (with Wo: the Wo rows store x)
     bool maa_done = false; // this layer's maa ran in the previous layer's channel-mix launch (k_sig_maa)
@@ -110,9 +111,9 @@ bool Engine::mv(MVGroup & g, hipStream_t st) {
 }
 
 // v5/v6 attention core arguments of layer L (k_att6_dec; also Att6Fused::att), state slices si / so:
-// fp32 y into y_ until the caller asks for an emission (yq).  Used by the decode program and, with
-// nb / bs added, by the batched step (batch_att_tail).
-Att6Dec Engine::att6_args(const DLayer & L, const float * si, float * so) const {
+// fp32 y into y_ until the caller asks for an emission (yq).  Used by the decode program (bs == 0)
+// and, with nb / bs added, by the batched step (batch_att_tail; bs = its state stride).
+Att6Dec Engine::att6_args(const DLayer & L, const float * si, float * so, size_t bs) const {
     const int C = (int)m_->n_embed;
     Att6Dec a;
     memset(&a, 0, sizeof(a));
@@ -138,8 +139,8 @@ Att6Dec Engine::att6_args(const DLayer & L, const float * si, float * so) const 
         a.decay = L.decay6;
         a.eps = 64e-5f;
         // tanh(Wd1 . xw): one token's in dsmall_[0]; the batched step's, a row per context, in lora_
-        a.dl = bs_ ? lora_ : dsmall_[0];
-        a.ldd = bs_ ? L.decay_w1.M : 0;
+        a.dl = bs ? lora_ : dsmall_[0];
+        a.ldd = bs ? L.decay_w1.M : 0;
     }
     return a;
 }
@@ -186,7 +187,7 @@ bool Engine::decode_att_v4(DecodeRun & d, uint32_t l) {
         memset(&wf, 0, sizeof(wf));
         const bool wo_in = (fuse_ & FUSE_WO4) && L.att_o.type == L.att_r.type && C % 8 == 0;
         if (wo_in && d.emb4_in && l == 0) {
-            wf.tok = tok_arg();
+            wf.tok = d.tok;
             wf.emb = m_->emb;
             wf.ln0w = m_->ln0_w;
             wf.ln0b = m_->ln0_b;
@@ -234,7 +235,7 @@ bool Engine::decode_att_v5(DecodeRun & d, uint32_t l) {
     mix(b.add(L.att_v, v_, EPI_STORE), L.att_mix_v);
     if (m_->minor >= 2) mix(b.add(L.att_g, g_, EPI_SILU), L.att_mix_g);
     if (!mv(b.g)) return false;
-    Att6Dec a = att6_args(L, si, so);
+    Att6Dec a = att6_args(L, si, so, 0);
     MV c_wo = wo_after(a, L.att_o, A(6, L.att_o), x_);
     return launch_att6_dec(stream_, a) && mv(c_wo.g);
 }
@@ -276,7 +277,7 @@ bool Engine::decode_att_v6(DecodeRun & d, uint32_t l) {
     float * ys[5] = {r_, k_, v_, g_, dsmall_[0]};
     const DMat * Ws[5] = {&L.att_r, &L.att_k, &L.att_v, &L.att_g, &L.decay_w1};
     const int epis[5] = {EPI_STORE, EPI_STORE, EPI_STORE, EPI_SILU, EPI_TANH};
-    Att6Dec a = att6_args(L, si, so);
+    Att6Dec a = att6_args(L, si, so, 0);
     MV c_wo = wo_after(a, L.att_o, A(6, L.att_o), x_);
     // r, k, v, g, Wd1 rows and the per-head attention in one launch (mv_att6f.hip), else
     // the k_mva group + k_att6_dec pair (the same bits)
@@ -521,13 +522,14 @@ bool Engine::decode_ffn(DecodeRun & d, uint32_t l) {
 }
 
 // Layers [l0, l1) (embedding when l0 == 0, head when l1 == n_layer and logits).
-bool Engine::forward_decode(const float * sin, float * sout, bool logits, uint32_t l0, uint32_t l1) {
+bool Engine::forward_decode(const float * sin, float * sout, bool logits, const TokArg & tok, uint32_t l0, uint32_t l1) {
     const int C = (int)m_->n_embed;
     DecodeRun d;
     d.sin = sin;
     d.sout = sout;
     d.l0 = l0;
     d.l1 = std::min(l1, m_->n_layer);
+    d.tok = tok;
     const bool emb_layer = l0 == 0 && d.l1 > 0 && (fuse_ & FUSE_EMBMAA);
     // v6: layer 0's maa launch computes the embedding LayerNorm itself (k_v6_maa_dec4 EMB: the same
     // bits as k_embed_ln; one launch and one boundary less per token)
@@ -536,7 +538,7 @@ bool Engine::forward_decode(const float * sin, float * sout, bool logits, uint32
         const ActBuf o0[5] = {A(1, F.decay_w1), A(2, F.att_k), A(3, F.att_v), A(4, F.att_r), A(5, F.att_g)};
         v6_maa_dec_args(d.emaa, C, m_->maa_D, F.maa_w1, x_, sin + C, sout + C, F.ln1_w, F.ln1_b, F.maa_x, F.maa_w2t,
                         F.maa, o0);
-        d.emaa.tok = tok_arg();
+        d.emaa.tok = tok;
         d.emaa.emb = m_->emb;
         d.emaa.ln0w = m_->ln0_w;
         d.emaa.ln0b = m_->ln0_b;
@@ -550,7 +552,7 @@ bool Engine::forward_decode(const float * sin, float * sout, bool logits, uint32
                     C % 8 == 0 && (m_->emb.type == W_F16 || m_->emb.type == W_F32) && (int)m_->emb.K == C;
         d.emb_in = d.emb4_in;
     }
-    if (l0 == 0 && !d.emb_in && !launch_embed_ln(stream_, tok_arg(), 1, m_->emb, m_->ln0_w, m_->ln0_b, x_)) return false;
+    if (l0 == 0 && !d.emb_in && !launch_embed_ln(stream_, tok, 1, m_->emb, m_->ln0_w, m_->ln0_b, x_)) return false;
     v7_fused_lora_ = false;
     for (uint32_t l = d.l0; l < d.l1; l++) {
         bool ok;

@@ -115,9 +115,10 @@ bool Engine::generate(const SamplingParams & p, size_t n, uint32_t * tokens_out,
             a.lp_top_ids = lp_ids_ + i * K;
             a.lp_top = lp_top_ + i * K;
         }
-        if (timing_) g_klt = this;
-        ok = (!lp || launch_logprobs(stream_, a)) && launch_sample(stream_, a);
-        g_klt = nullptr;
+        {
+            const LaunchTimerScope timed(this, timing_);
+            ok = (!lp || launch_logprobs(stream_, a)) && launch_sample(stream_, a);
+        }
         ok = ok && run_tokens(nullptr, 1, true);
     }
     if (ok) {
@@ -149,19 +150,19 @@ bool Engine::score_buffers(size_t T) {
 
 // After the layers of tokens [done, done + n) of a score() call: x_ holds their n final residual
 // rows (n > 1), or the decode program's head has written logits_ (n == 1).
-bool Engine::score_chunk(size_t done, size_t n, bool last) {
+bool Engine::score_chunk(const ScoreRun & score, size_t done, size_t n, bool last) {
     const size_t C = m_->n_embed, V = m_->n_vocab;
-    const bool want_loss = score_->targets != nullptr;
+    const bool want_loss = score.targets != nullptr;
     if (want_loss)
-        HIP_OK(hipMemcpyAsync(score_targets_ + done, score_->targets + done, n * 4, hipMemcpyHostToDevice, stream_));
+        HIP_OK(hipMemcpyAsync(score_targets_ + done, score.targets + done, n * 4, hipMemcpyHostToDevice, stream_));
     auto reduce = [&](const float * lg, size_t row0, int rows) {
         const size_t at = done + row0;
         if (!launch_xent(stream_, lg, rows, (int)V, want_loss ? score_targets_ + at : nullptr,
                          want_loss ? score_loss_ + at : nullptr, score_argmax_ + at))
             return false;
-        if (score_->logits_out) {
+        if (score.logits_out) {
             // the next tile (or step) overwrites lg: the copy has landed before it is enqueued
-            HIP_OK(hipMemcpyAsync(score_->logits_out + at * V, lg, (size_t)rows * V * 4, hipMemcpyDeviceToHost, stream_));
+            HIP_OK(hipMemcpyAsync(score.logits_out + at * V, lg, (size_t)rows * V * 4, hipMemcpyDeviceToHost, stream_));
             HIP_OK(hipStreamSynchronize(stream_));
         }
         return true;
@@ -172,10 +173,8 @@ bool Engine::score_chunk(size_t done, size_t n, bool last) {
         // the head over `rows` rows as batched decode runs it over that many contexts (mm_dispatch:
         // k_fmm, k_mvb or k_mm, each row the bits of its one-token head); never the sequence GEMM,
         // for which the head has no tile records (upload_mat)
-        bs_ = m_->state_len;
-        const bool ok = head_rows(x_ + row0 * C, rows, score_tile_);
-        bs_ = 0;
-        if (!ok || !reduce(score_tile_, row0, rows)) return false;
+        if (!head_rows(rows_run(rows, 0, nullptr, nullptr, score_tile_), x_ + row0 * C) || !reduce(score_tile_, row0, rows))
+            return false;
         if (last && row0 + rows == n)
             HIP_OK(hipMemcpyAsync(logits_, score_tile_ + (size_t)(rows - 1) * V, V * 4, hipMemcpyDeviceToDevice, stream_));
     }
@@ -186,12 +185,9 @@ bool Engine::score(const uint32_t * tokens, size_t T, const uint32_t * targets, 
                    uint32_t * argmax_out, float * logits_out) {
     HIP_OK(hipSetDevice(m_->device));
     if (!tokens || T == 0 || (targets != nullptr) != (losses_out != nullptr) || !score_buffers(T)) return false;
-    ScoreRun run{targets, logits_out};
+    const ScoreRun run{targets, logits_out};
     co_retry_ = false;
-    score_ = &run;
-    const bool ok = run_tokens(tokens, T, true);
-    score_ = nullptr;
-    if (!ok) return false;
+    if (!run_tokens(tokens, T, true, &run)) return false;
     if (losses_out) HIP_OK(hipMemcpyAsync(losses_out, score_loss_, T * 8, hipMemcpyDeviceToHost, stream_));
     if (argmax_out) HIP_OK(hipMemcpyAsync(argmax_out, score_argmax_, T * 4, hipMemcpyDeviceToHost, stream_));
     HIP_OK(hipStreamSynchronize(stream_));

@@ -23,7 +23,7 @@ __global__ __launch_bounds__(256) void k_prefill_clear(const uint32_t * slot, si
 
 // The sequence path runs every per-token stage position-independently, so a chunk of tokens packed
 // from several prompts is one forward_range call; only the token shift (k_ln_mix) and the WKV
-// recurrences see that it is cut into segments, through seg_.  States: every segment reads and
+// recurrences see that it is cut into segments, through SeqRun::seg.  States: every segment reads and
 // writes a state in gstates_ -- [2][slots] and the fresh state -- at offsets from gstates_ itself, so
 // the layer functions get gstates_ as both state pointers.  A segment never writes the state it
 // reads (k_ln_mix: the workgroup of a segment's last token writes the carry its first token's
@@ -110,12 +110,7 @@ bool Engine::prefill_batch(size_t n_rows, const uint32_t * slots, const uint32_t
         !grow(pend_x_, (size_t)kBatchMax * C, (size_t)kBatchMax * C, GRAPHS_NONE))
         return false;
     // from here on a failure leaves the slots of the call undefined
-    auto fail = [&] {
-        seg_ = nullptr;
-        bs_ = 0;
-        g_klt = nullptr;
-        return slots_fail(n_rows, slots);
-    };
+    auto fail = [&] { return slots_fail(n_rows, slots); };
     for (size_t i = 0; i < n_rows; i++)
         if (!(cont && cont[i])) gvalid_[slots[i]] = 0;
     if (hipMemcpyAsync(ptokens_, tokens, N * 4, hipMemcpyHostToDevice, stream_) != hipSuccess ||
@@ -128,22 +123,15 @@ bool Engine::prefill_batch(size_t n_rows, const uint32_t * slots, const uint32_t
 
     for (size_t c = 0; c < n_chunks; c++) {
         const size_t s0 = chunk_seg0[c], t0 = chunk_tok0[c], T = chunk_tok0[c + 1] - t0;
-        SegTab sg;
-        sg.n = (int)(chunk_seg0[c + 1] - s0);
-        sg.begin = d_begin + s0;
-        sg.len = d_len + s0;
-        sg.sin_off = d_sin + s0;
-        sg.sout_off = d_sin + nseg + s0;
-        sg.seg_of = d_seg_of + t0;
+        // in the order of SegTab's members: n, begin, len, sin_off, sout_off, seg_of
+        const SegTab sg{(int)(chunk_seg0[c + 1] - s0), d_begin + s0, d_len + s0, d_sin + s0, d_sin + nseg + s0, d_seg_of + t0};
         if (hipMemcpyAsync(dtokens_, ptokens_ + t0, T * 4, hipMemcpyDeviceToDevice, stream_) != hipSuccess) return fail();
         // eager, as the sequence path: with kernel timing on, a one-token chunk's launches carry their
         // event pairs and the matmul groups theirs (mm_launch)
-        if (timing_ && T == 1) g_klt = this;
-        seg_ = &sg;
-        const bool ok = forward_range((int)T, gstates_, gstates_, 0, m_->n_layer, false);
-        seg_ = nullptr;
-        g_klt = nullptr;
-        if (!ok) return fail();
+        {
+            const LaunchTimerScope timed(this, timing_ && T == 1);
+            if (!forward_range(packed_run((int)T, &sg, gstates_))) return fail();
+        }
         // the residual rows of the tokens that end a row in this chunk, to the rows' places in pend_x_
         const uint32_t e0 = chunk_end0[c], ne = chunk_end0[c + 1] - e0;
         if (!launch_copy_rows(stream_, x_, d_end_src + e0, pend_x_ + (size_t)e0 * C, nullptr, (int)ne, C)) return fail();
@@ -151,10 +139,9 @@ bool Engine::prefill_batch(size_t n_rows, const uint32_t * slots, const uint32_t
     // the head over the rows' last tokens as batched decode runs it over that many contexts (each row
     // the bits of its one-token head, as score_chunk), into the snapshot area -- free between
     // generate_batch calls -- and from there to the rows' slots
-    bs_ = n;
-    const bool hok = head_rows(pend_x_, (int)n_rows, gsnap_logits_);
-    bs_ = 0;
-    if (!hok || !launch_copy_rows(stream_, gsnap_logits_, nullptr, glogits_, d_slot, (int)n_rows, V)) return fail();
+    if (!head_rows(rows_run((int)n_rows, 0, nullptr, nullptr, gsnap_logits_), pend_x_) ||
+        !launch_copy_rows(stream_, gsnap_logits_, nullptr, glogits_, d_slot, (int)n_rows, V))
+        return fail();
     if (!launch_copy_rows(stream_, gstate_[1], d_back, gstate_[0], d_back, (int)n_back, n)) return fail();
     // a new sequence in every slot: no token counted yet, not finished
     RK_LAUNCH(k_prefill_clear, dim3((unsigned)std::min<size_t>((V + 255) / 256, 256), (unsigned)n_rows), dim3(256), 0, stream_,

@@ -14,6 +14,10 @@ Cases, per BASELINE configuration (test_gpu_configs.CONFIGS at 2 layers, V = 409
   batched   one rwkv_mi355x_eval_batch step at B = 2 and B = 16 (the two sides of the batched GEMM
             threshold)
   sequence  one evaluation at T = 2 and T = 33 (the two sides of the 32-token float-matmul threshold)
+  prefill   one rwkv_mi355x_prefill_batch of rows of 1, 2 and 33 tokens at the default packing cap, and
+            one of rows of 1 and 3 tokens with the debug knob prefill_chunk = 1 (one-token chunks)
+  score     one rwkv_mi355x_score_sequence with targets at T = 1 (the decode step and k_xent), 34 (one
+            head tile) and 130 (two head tiles, 128 + 2 rows)
 
 Names, their order and the launch counts must match exactly; bytes and flops to a relative 1e-9
 (the order of additions in a formula may change, nothing else).  tools/record_decode_program.py
@@ -37,6 +41,9 @@ MASKS = (-1, 0, 1023, 127)
 DECODE_TOKENS = (17, 4000, 321, 9)
 BATCHES = (2, 16)
 SEQ_LENS = (2, 33)
+PREFILL_ROWS = (1, 2, 33)
+PREFILL_ROWS_1 = (1, 3)
+SCORE_LENS = (1, 34, 130)
 
 
 def model_file(model_dir, name):
@@ -110,6 +117,19 @@ def collect(name, model_dir):
             assert lib.rwkv_mi355x_eval_device(ptr, arr, T, True, None, True)
 
         out[f'sequence T={T}'] = timed(lib, ptr, run)
+    m.batch_reserve(len(PREFILL_ROWS))
+    for rows, chunk in ((PREFILL_ROWS, 0), (PREFILL_ROWS_1, 1)):
+        prompts = [[int(t) for t in rng.integers(0, VOCAB, n)] for n in rows]
+        assert lib.rwkv_mi355x_debug_set(ptr, b'prefill_chunk', chunk)
+        try:
+            out[f'prefill rows={rows} chunk={chunk}'] = timed(lib, ptr, lambda: m.prefill_batch(prompts))
+        finally:
+            assert lib.rwkv_mi355x_debug_set(ptr, b'prefill_chunk', 0)
+    for T in SCORE_LENS:
+        toks = [int(t) for t in rng.integers(0, VOCAB, T)]
+        targets = [int(t) for t in rng.integers(0, VOCAB, T)]
+        m.reset_state()
+        out[f'score T={T}'] = timed(lib, ptr, lambda: m.score(toks, targets))
     m.free()
     if CONFIGS[name][0] == 6:
         os.environ['RWKV_MI355X_SPLIT_MAA'] = '1'
