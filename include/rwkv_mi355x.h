@@ -249,6 +249,58 @@ RWKV_API bool rwkv_mi355x_generate_queue_logprobs(struct rwkv_context * ctx, siz
                                                   uint32_t * lane_out /* [Q] */, uint32_t * start_out /* [Q] */,
                                                   uint32_t * steps_out, const struct rwkv_mi355x_logprobs * lp);
 
+/* The rest of the sampler: top-k, min-p and locally typical sampling, on the device, in front of
+ * top-p.  They decide which tokens are kept; the row l the token is drawn from, and so every
+ * log-probability above, is untouched.
+ *
+ * Per draw take l, m = max l and e_i = expf(l_i - m) as rwkv_mi355x_sample forms them (float32,
+ * penalties and bias included; e_max == 1.0f).  Temperature 0 is still the argmax and ignores every
+ * filter.  The kept set is built in this order; every rule keeps all ties at its cutoff, as top_p does:
+ *   1. top_k = K: keep every i with e_i >= e_(K), the K-th largest e.  Exact: integer counts.  K == 0 or
+ *      K >= n_vocab: off.
+ *   2. min_p = q: among those, keep e_i >= q, a float32 compare (p_i >= q p_max).  q == 0: off.
+ *   3. typical_p = t: over the set F kept so far, S_F = sum_F e_i and A = sum_F e_i (m - l_i), every
+ *      product and sum in double, one fixed association; g = A / S_F (the mean of -log p over F up to
+ *      the constant that cancels); d_i = (float)|((double)m - (double)l_i) - g|.  Keep d_i <= d_c, the
+ *      smallest d with mass{i in F, d_i <= d_c} > t * mass{F}, the masses being the sampler's float32
+ *      sums of e (one fixed association each).  t == 0 or t == 1: off.
+ *   4. top_p, as in rwkv_mi355x_sample, with the mass of the set kept so far in place of sum e.
+ * A token whose e underflows to 0 (l_i < m - 103) is kept by no draw in which a filter is on.
+ * The weights of the kept tokens, their prefix sums and the draw are those of rwkv_mi355x_sample.
+ * rwkv_cpp.sampling.kept_mask restates the rules in float64 numpy.  A call is a pure function of its
+ * inputs; non-finite logits may give any token < n_vocab and cannot hang or fault a call.
+ * Each array is host [rows], or NULL (that filter off); rows = 1 for sample and generate, B for
+ * generate_batch, Q for generate_queue, where the values are indexed by sequence and follow it into
+ * its lane, as temperature does. */
+struct rwkv_mi355x_filters {
+    const uint32_t * top_k;
+    const float    * min_p;      /* each in [0, 1] */
+    const float    * typical_p;  /* each in [0, 1] */
+};
+/* Each is its _logprobs sibling above plus f, with lp still optional; f == NULL is that call.  Besides
+ * the sibling's errors: a min_p or typical_p that is NaN or outside [0, 1] fails with RWKV_ERROR_ARGS
+ * before anything is enqueued (slots, state and logits untouched).  A call in which every value of
+ * every row is off runs exactly what the sibling runs. */
+RWKV_API bool rwkv_mi355x_sample_filtered(struct rwkv_context * ctx, const struct rwkv_mi355x_sampling * params,
+                                          uint32_t * token_out, const struct rwkv_mi355x_logprobs * lp,
+                                          const struct rwkv_mi355x_filters * f);
+RWKV_API bool rwkv_mi355x_generate_filtered(struct rwkv_context * ctx, const struct rwkv_mi355x_sampling * params,
+                                            size_t n, uint32_t * tokens_out, float * logits_out,
+                                            const struct rwkv_mi355x_logprobs * lp,
+                                            const struct rwkv_mi355x_filters * f);
+RWKV_API bool rwkv_mi355x_generate_batch_filtered(struct rwkv_context * ctx, size_t B,
+                                                  const struct rwkv_mi355x_batch_sampling * params, size_t n,
+                                                  uint32_t * tokens_out /* [B][n] */, uint32_t * lengths_out /* [B] */,
+                                                  uint32_t * steps_out, const struct rwkv_mi355x_logprobs * lp,
+                                                  const struct rwkv_mi355x_filters * f);
+RWKV_API bool rwkv_mi355x_generate_queue_filtered(struct rwkv_context * ctx, size_t Q, size_t lanes,
+                                                  const struct rwkv_mi355x_batch_sampling * params,
+                                                  const uint32_t * max_tokens /* host [Q] */, size_t n,
+                                                  uint32_t * tokens_out /* [Q][n] */, uint32_t * lengths_out /* [Q] */,
+                                                  uint32_t * lane_out /* [Q] */, uint32_t * start_out /* [Q] */,
+                                                  uint32_t * steps_out, const struct rwkv_mi355x_logprobs * lp,
+                                                  const struct rwkv_mi355x_filters * f);
+
 /* Batched prefill: n_rows prompts, concatenated in `tokens` (lengths[i] >= 1 tokens each), are
  * evaluated together in packed sequence passes and land in slots[i] (distinct, each < the reserved
  * slots).  cont == NULL or cont[i] == 0: row i starts from the fresh state (the slot need not have
@@ -616,6 +668,21 @@ RWKV_API bool rwkv_mi355x_selftest_sample_rows_logprobs(const float * logits, in
                                                         uint32_t * kept, float * cutoff, uint32_t * lengths,
                                                         uint32_t * active, uint32_t top_k, double * token_logprob,
                                                         uint32_t * top_ids, double * top_logprobs);
+
+/* The first two self-tests above with filters (NULL: those self-tests), as the rwkv_mi355x_*_filtered
+ * calls launch the sampler: filters' arrays hold one value for all rows (selftest_sample_filtered, as
+ * params does) or one per row (selftest_sample_rows_filtered); a min_p or typical_p outside [0, 1]
+ * fails.  kept and cutoff are the final count and the smallest kept e / sum e. */
+RWKV_API bool rwkv_mi355x_selftest_sample_filtered(const float * logits, int rows, int V,
+                                                   const struct rwkv_mi355x_sampling * params, const float * u,
+                                                   uint32_t * tokens, uint32_t * kept, float * cutoff,
+                                                   const struct rwkv_mi355x_filters * filters);
+RWKV_API bool rwkv_mi355x_selftest_sample_rows_filtered(const float * logits, int rows, int V,
+                                                        const struct rwkv_mi355x_batch_sampling * params,
+                                                        const float * u, uint32_t step, uint32_t * counts,
+                                                        uint32_t * done, uint32_t * tokens, uint32_t * decode_tokens,
+                                                        uint32_t * kept, float * cutoff, uint32_t * lengths,
+                                                        uint32_t * active, const struct rwkv_mi355x_filters * filters);
 
 /* The turnover kernel of rwkv_mi355x_generate_queue (k_gen_turnover) on host operands, as before step
  * `step`: lane_seq [lanes] (a sequence id < Q or 0xFFFFFFFF: idle), done / lane / start [Q], *next

@@ -117,6 +117,7 @@ struct GenSlots {
     DevBuf<uint32_t> gcounts_;
     DevBuf<float> gparams_;      // temperature, top_p, presence, frequency: [4][kBatchMax]
     DevBuf<uint64_t> gstreams_;  // seed, offset: [2][kBatchMax]
+    DevBuf<uint32_t> gfilters_;  // top_k, the bits of min_p, the bits of typical_p: [3][kBatchMax]
     DevBuf<uint32_t> gwords_;
     GenWords gw_;  // views of gwords_
     bool alloc(size_t n_slots, size_t state_len, size_t n_vocab, size_t batch_max);
@@ -225,6 +226,13 @@ struct LogprobsOut {
     double * top_logprobs = nullptr;   // top_k per column
 };
 
+// rwkv_mi355x_filters, checked by the caller (include/rwkv_mi355x.h): host arrays of one value per row
+// (sample, generate: one row) or sequence; NULL: that filter is off
+struct FilterParams {
+    const uint32_t * top_k = nullptr;
+    const float *min_p = nullptr, *typical_p = nullptr;
+};
+
 class Engine : public KLaunchTimer, private Workspace, private GenSlots {
   public:
     explicit Engine(DeviceModel * m) : m_(m) {}
@@ -249,9 +257,13 @@ class Engine : public KLaunchTimer, private Workspace, private GenSlots {
     // lp != NULL (all four generation calls): k_logprobs runs in front of every sampler launch and the
     // sampler's LP form writes the drawn token's log-probability; the device arrays start as 0xFF bytes
     // and are copied out with the tokens.  lp == NULL: the call as it was.
-    bool sample(const SamplingParams & p, uint32_t * token_out, const LogprobsOut * lp = nullptr);
+    // f != NULL with some filter on in some row (all four calls): the sampler launches are those of
+    // sample_filter.hip, the per-sequence values uploaded beside the other per-sequence parameters.
+    // f == NULL, or every value off: the call as it was.
+    bool sample(const SamplingParams & p, uint32_t * token_out, const LogprobsOut * lp = nullptr,
+                const FilterParams * f = nullptr);
     bool generate(const SamplingParams & p, size_t n, uint32_t * tokens_out, float * logits_out,
-                  const LogprobsOut * lp = nullptr);
+                  const LogprobsOut * lp = nullptr, const FilterParams * f = nullptr);
     // The device arrays of a call with log-probabilities: rows * n columns of 8 + 12 top_k bytes and one
     // logZ word per row, grown here and never inside a loop.  Enqueues nothing; the callers of the four
     // calls run it first, so that a failed allocation fails the call before anything else happens.
@@ -285,7 +297,7 @@ class Engine : public KLaunchTimer, private Workspace, private GenSlots {
     bool batch_store(size_t slot);
     bool batch_load(size_t slot);
     bool generate_batch(size_t B, const BatchSamplingParams & p, size_t n, uint32_t * tokens_out, uint32_t * lengths_out,
-                        uint32_t * steps_out, const LogprobsOut * lp = nullptr);
+                        uint32_t * steps_out, const LogprobsOut * lp = nullptr, const FilterParams * f = nullptr);
     // A queue of Q sequences (slots [0, Q)) over L = min(lanes, Q) decode rows
     // (rwkv_mi355x_generate_queue): per step k_gen_turnover frees the lanes of ended
     // sequences and admits the waiting ones, k_gen_move copies a capped sequence's result out of its
@@ -293,7 +305,7 @@ class Engine : public KLaunchTimer, private Workspace, private GenSlots {
     // lanes as in generate_batch.  Every per-row array of p is [Q]; max_tokens[s] in [1, n].
     bool generate_queue(size_t Q, size_t lanes, const BatchSamplingParams & p, const uint32_t * max_tokens, size_t n,
                         uint32_t * tokens_out, uint32_t * lengths_out, uint32_t * lane_out, uint32_t * start_out,
-                        uint32_t * steps_out, const LogprobsOut * lp = nullptr);
+                        uint32_t * steps_out, const LogprobsOut * lp = nullptr, const FilterParams * f = nullptr);
     // Batched prefill (rwkv_mi355x_prefill_batch; engine_prefill.hip): n_rows prompts, concatenated in
     // tokens, are packed into chunks of at most prefill_chunk_ tokens (prefill_plan.hpp) and each chunk
     // runs as one sequence pass whose token shift and WKV kernels follow a segment table (SegTab);
@@ -451,6 +463,11 @@ class Engine : public KLaunchTimer, private Workspace, private GenSlots {
     // the copies out at the end of the call
     bool lp_begin(const LogprobsOut * lp, size_t rows, size_t n, SampleArgs & a);
     bool lp_copy_out(const LogprobsOut * lp, size_t rows, size_t n);
+    // The filters of `rows` rows as the kernels take them, off values as 0 (top_k >= n_vocab, typical_p
+    // 1).  upload: the values go to gfilters_ in stream order and sf points there; else rows == 1 and
+    // they are sf's scalars.  Nothing on in any row leaves sf unset: launch_sample then runs what it
+    // runs without filters.
+    bool filters_begin(const FilterParams * f, size_t rows, bool upload, SampleFilters & sf);
     DevBuf<float> dstate_[2];
     int cur_ = 0;
     unsigned * herr_h_ = nullptr;  // hand-off timeout flag, host-mapped (herr_d_ = its device address)
@@ -553,6 +570,7 @@ class Engine : public KLaunchTimer, private Workspace, private GenSlots {
     DevBuf<uint32_t> gtokens_;  // the drawn tokens [B][n] of a call
     std::vector<float> gparams_h_;   // the host copies the uploads read
     std::vector<uint64_t> gstreams_h_;
+    std::vector<uint32_t> gfilters_h_;
     std::vector<uint32_t> gqueue_h_;  // max_tokens up, start down (generate_queue)
     void free_slots();
     // generate_batch and generate_queue are one driver (engine_batch.hip): sequences [0, Q) over the
@@ -563,7 +581,7 @@ class Engine : public KLaunchTimer, private Workspace, private GenSlots {
         uint32_t *lane_out, *start_out;
     };
     bool generate_slots(size_t Q, const BatchSamplingParams & p, size_t n, uint32_t * tokens_out, uint32_t * lengths_out,
-                        uint32_t * steps_out, const LogprobsOut * lp, const QueueCall * qc);
+                        uint32_t * steps_out, const LogprobsOut * lp, const FilterParams * f, const QueueCall * qc);
     // the per-sequence arrays of Q sequences to the device and the token buffer [Q][n] set to
     // 0xFFFFFFFF; the sampler's arguments for `rows` rows
     bool gen_upload(size_t Q, const BatchSamplingParams & p, size_t n);

@@ -106,7 +106,7 @@ bool GenSlots::alloc(size_t n_slots, size_t state_len, size_t n_vocab, size_t ba
     gfresh_ = gstates_ + 2 * n_slots * state_len;
     if (!(gsnap_state_.alloc(n_slots * state_len) && glogits_.alloc(n_slots * n_vocab) &&
           gsnap_logits_.alloc(n_slots * n_vocab) && gcounts_.alloc(n_slots * n_vocab) && gparams_.alloc(4 * batch_max) &&
-          gstreams_.alloc(2 * batch_max) && gwords_.alloc(GenWords().bind(nullptr, batch_max))))
+          gstreams_.alloc(2 * batch_max) && gfilters_.alloc(3 * batch_max) && gwords_.alloc(GenWords().bind(nullptr, batch_max))))
         return false;
     gw_.bind(gwords_, batch_max);
     return true;
@@ -210,15 +210,15 @@ SampleArgs Engine::gen_sample_args(size_t rows, const BatchSamplingParams & p, s
 }
 
 bool Engine::generate_batch(size_t B, const BatchSamplingParams & p, size_t n, uint32_t * tokens_out,
-                            uint32_t * lengths_out, uint32_t * steps_out, const LogprobsOut * lp) {
-    return generate_slots(B, p, n, tokens_out, lengths_out, steps_out, lp, nullptr);
+                            uint32_t * lengths_out, uint32_t * steps_out, const LogprobsOut * lp, const FilterParams * f) {
+    return generate_slots(B, p, n, tokens_out, lengths_out, steps_out, lp, f, nullptr);
 }
 
 bool Engine::generate_queue(size_t Q, size_t lanes, const BatchSamplingParams & p, const uint32_t * max_tokens, size_t n,
                             uint32_t * tokens_out, uint32_t * lengths_out, uint32_t * lane_out, uint32_t * start_out,
-                            uint32_t * steps_out, const LogprobsOut * lp) {
+                            uint32_t * steps_out, const LogprobsOut * lp, const FilterParams * f) {
     const QueueCall qc{lanes, max_tokens, lane_out, start_out};
-    return generate_slots(Q, p, n, tokens_out, lengths_out, steps_out, lp, &qc);
+    return generate_slots(Q, p, n, tokens_out, lengths_out, steps_out, lp, f, &qc);
 }
 
 // The driver of both calls.  Per step one sampler launch over the rows' logits (per-sequence
@@ -235,7 +235,7 @@ bool Engine::generate_queue(size_t Q, size_t lanes, const BatchSamplingParams & 
 // snapshot (row s of gsnap_*), taken by k_gen_snapshot at a stop and by k_gen_move at its cap.
 // done[s] == 1 from then on, so the restore needs no table.  What the queue adds is under `qc`.
 bool Engine::generate_slots(size_t Q, const BatchSamplingParams & p, size_t n, uint32_t * tokens_out, uint32_t * lengths_out,
-                            uint32_t * steps_out, const LogprobsOut * lp, const QueueCall * qc) {
+                            uint32_t * steps_out, const LogprobsOut * lp, const FilterParams * f, const QueueCall * qc) {
     HIP_OK(hipSetDevice(m_->device));
     // ---- the arguments; the per-sequence values of p are the caller's to check (BatchSamplingParams)
     if (Q == 0 || Q > gslots_ || n == 0 || !tokens_out || !lengths_out || !p.temperature || !p.top_p || !p.seed ||
@@ -268,7 +268,8 @@ bool Engine::generate_slots(size_t Q, const BatchSamplingParams & p, size_t n, u
 
     // ---- the start of the call: uploads and fills that do not depend on one another
     SampleArgs a = gen_sample_args(rows, p, n);
-    bool ok = gen_upload(Q, p, n) && (p.keep_counts || hipMemsetAsync(gcounts_, 0, Q * V * 4, stream_) == hipSuccess);
+    SampleFilters sf;  // per sequence, as the other parameters: they follow a sequence into its lane
+    bool ok = gen_upload(Q, p, n) && filters_begin(f, Q, true, sf) && (p.keep_counts || hipMemsetAsync(gcounts_, 0, Q * V * 4, stream_) == hipSuccess);
     // the queue's argument block, in the order of GenQueue's members (launched under qc only)
     const GenQueue q{(int)rows,  (int)Q,    gw_.lane_seq,  gw_.done,       gw_.length, gw_.max_tokens,
                      gw_.lane,   gw_.start, gw_.retire_to, gw_.admit_from, gw_.next,   gw_.active};
@@ -303,7 +304,7 @@ bool Engine::generate_slots(size_t Q, const BatchSamplingParams & p, size_t n, u
         a.step = (uint32_t)i;
         {
             const LaunchTimerScope timed(this, timing_);
-            ok = (!qc || turnover(i, cur)) && (!lp || launch_logprobs(stream_, a)) && launch_sample(stream_, a) &&
+            ok = (!qc || turnover(i, cur)) && (!lp || launch_logprobs(stream_, a)) && launch_sample(stream_, a, &sf) &&
                  launch_gen_snapshot(stream_, g, (uint32_t)i, cur, glogits_, gsnap_state_, gsnap_logits_);
         }
         ok = ok && eval_batch(nullptr, rows, cur, gstate_[(steps & 1) ^ 1], glogits_, true);

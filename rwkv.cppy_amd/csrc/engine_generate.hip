@@ -79,14 +79,45 @@ bool Engine::lp_copy_out(const LogprobsOut * lp, size_t rows, size_t n) {
     return true;
 }
 
-bool Engine::sample(const SamplingParams & p, uint32_t * token_out, const LogprobsOut * lp) {
+bool Engine::filters_begin(const FilterParams * f, size_t rows, bool upload, SampleFilters & sf) {
+    memset(&sf, 0, sizeof(sf));
+    if (!f) return true;
+    const size_t K = (size_t)kBatchMax;
+    if (rows > K || (!upload && rows != 1)) return false;
+    gfilters_h_.assign(3 * K, 0);
+    bool on = false;
+    for (size_t r = 0; r < rows; r++) {
+        const uint32_t k = f->top_k && f->top_k[r] < m_->n_vocab ? f->top_k[r] : 0u;
+        const float q = f->min_p ? f->min_p[r] : 0.0f;
+        const float t = f->typical_p && f->typical_p[r] < 1.0f ? f->typical_p[r] : 0.0f;
+        gfilters_h_[r] = k;
+        memcpy(&gfilters_h_[K + r], &q, 4);
+        memcpy(&gfilters_h_[2 * K + r], &t, 4);
+        on = on || k != 0u || q != 0.0f || t != 0.0f;
+    }
+    if (!on) return true;
+    if (!upload) {
+        sf.top_k = gfilters_h_[0];
+        memcpy(&sf.min_p, &gfilters_h_[K], 4);
+        memcpy(&sf.typical_p, &gfilters_h_[2 * K], 4);
+        return true;
+    }
+    HIP_OK(hipMemcpyAsync(gfilters_, gfilters_h_.data(), 3 * K * 4, hipMemcpyHostToDevice, stream_));
+    sf.top_k_r = gfilters_;
+    sf.min_p_r = (const float *)(gfilters_ + K);
+    sf.typical_p_r = (const float *)(gfilters_ + 2 * K);
+    return true;
+}
+
+bool Engine::sample(const SamplingParams & p, uint32_t * token_out, const LogprobsOut * lp, const FilterParams * f) {
     HIP_OK(hipSetDevice(m_->device));
     if (!logits_valid_ || !token_out) return false;
     SampleArgs a;
+    SampleFilters sf;
     if (lp && !lp_reserve(1, 1, lp->top_k)) return false;
-    if (!sampler_buffers(p, 1, a) || !lp_begin(lp, 1, 1, a)) return false;
+    if (!sampler_buffers(p, 1, a) || !filters_begin(f, 1, false, sf) || !lp_begin(lp, 1, 1, a)) return false;
     if (lp && !launch_logprobs(stream_, a)) return false;
-    if (!launch_sample(stream_, a)) return false;
+    if (!launch_sample(stream_, a, &sf)) return false;
     HIP_OK(hipMemcpyAsync(token_out, gen_tokens_, 4, hipMemcpyDeviceToHost, stream_));
     if (!lp_copy_out(lp, 1, 1)) return false;
     HIP_OK(hipStreamSynchronize(stream_));
@@ -94,12 +125,15 @@ bool Engine::sample(const SamplingParams & p, uint32_t * token_out, const Logpro
 }
 
 bool Engine::generate(const SamplingParams & p, size_t n, uint32_t * tokens_out, float * logits_out,
-                      const LogprobsOut * lp) {
+                      const LogprobsOut * lp, const FilterParams * f) {
     HIP_OK(hipSetDevice(m_->device));
     if (!logits_valid_ || !tokens_out || n == 0) return false;
     SampleArgs a;
+    SampleFilters sf;
     // dtokens_ moves when the workspace grows (the graphs are dropped with it): settle it first
-    if (!ensure_workspace(1) || (lp && !lp_reserve(1, n, lp->top_k)) || !sampler_buffers(p, n, a)) return false;
+    if (!ensure_workspace(1) || (lp && !lp_reserve(1, n, lp->top_k)) || !sampler_buffers(p, n, a) ||
+        !filters_begin(f, 1, false, sf))
+        return false;
     const int cur0 = cur_;
     co_retry_ = false;
     bool ok = lp_begin(lp, 1, n, a);
@@ -117,7 +151,7 @@ bool Engine::generate(const SamplingParams & p, size_t n, uint32_t * tokens_out,
         }
         {
             const LaunchTimerScope timed(this, timing_);
-            ok = (!lp || launch_logprobs(stream_, a)) && launch_sample(stream_, a);
+            ok = (!lp || launch_logprobs(stream_, a)) && launch_sample(stream_, a, &sf);
         }
         ok = ok && run_tokens(nullptr, 1, true);
     }

@@ -268,8 +268,23 @@ struct SampleArgs {
 };
 constexpr int SAMPLE_MAX_STOP = 16;
 constexpr int LOGPROBS_MAX_TOP = 20;  // RWKV_MI355X_MAX_TOP_LOGPROBS
-// One workgroup per row: bias, greedy or top-p / temperature sampling (rwkv_mi355x.h).
-bool launch_sample(hipStream_t st, const SampleArgs & a);
+// The truncation rules in front of top-p (rwkv_mi355x_filters; sample_filter.hip), the second argument
+// of the filtered sampler kernels: SampleArgs and the four kernels that take it alone stay as they are.
+struct SampleFilters {
+    uint32_t top_k;               // 0 or >= V: off
+    float min_p, typical_p;       // in [0, 1]; 0 (typical_p: or 1): off
+    // device [rows], indexed like temperature_r (by sequence under lane_seq); each replaces its scalar
+    const uint32_t * top_k_r;
+    const float * min_p_r;
+    const float * typical_p_r;
+    bool per_row() const { return top_k_r || min_p_r || typical_p_r; }
+    bool set() const { return top_k != 0 || min_p != 0.0f || (typical_p != 0.0f && typical_p != 1.0f) || per_row(); }
+};
+// One workgroup per row: bias, greedy or top-p / temperature sampling (rwkv_mi355x.h).  f == NULL or
+// nothing set in it: the kernels of sample.hip; else those of sample_filter.hip.
+bool launch_sample(hipStream_t st, const SampleArgs & a, const SampleFilters * f = nullptr);
+// launch_sample's second half for a set f: `rows` and `lp` pick the kernel as they do in sample.hip
+bool launch_sample_filtered(hipStream_t st, const SampleArgs & a, const SampleFilters & f, bool rows, bool lp);
 // One workgroup per row (logprobs.hip): logZ and the leading lp_k elements of the row the sampler is
 // about to draw from.  A row the sampler skips (finished, idle) writes nothing.  Needs lp_logz.
 bool launch_logprobs(hipStream_t st, const SampleArgs & a);

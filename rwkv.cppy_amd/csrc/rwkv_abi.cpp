@@ -844,6 +844,110 @@ RWKV_API bool rwkv_mi355x_generate_queue(struct rwkv_context * ctx, size_t Q, si
                                                steps_out, nullptr);
 }
 
+// ---- the four calls with filters: each is its _logprobs sibling, check for check, plus filters_ok
+// The checks of a rwkv_mi355x_filters over `rows` rows, before any GPU call
+static bool filters_ok(struct rwkv_context * ctx, const struct rwkv_mi355x_filters * f, size_t rows, FilterParams & out) {
+    for (size_t r = 0; r < rows; r++) {
+        CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, !f->min_p || (f->min_p[r] >= 0.0f && f->min_p[r] <= 1.0f),
+                  "Row %zu: min_p %f is outside [0, 1]", r, f->min_p[r]);
+        CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, !f->typical_p || (f->typical_p[r] >= 0.0f && f->typical_p[r] <= 1.0f),
+                  "Row %zu: typical_p %f is outside [0, 1]", r, f->typical_p[r]);
+    }
+    out.top_k = f->top_k;
+    out.min_p = f->min_p;
+    out.typical_p = f->typical_p;
+    return true;
+}
+
+RWKV_API bool rwkv_mi355x_sample_filtered(struct rwkv_context * ctx, const struct rwkv_mi355x_sampling * params,
+                                          uint32_t * token_out, const struct rwkv_mi355x_logprobs * lp,
+                                          const struct rwkv_mi355x_filters * f) {
+    if (!f) return rwkv_mi355x_sample_logprobs(ctx, params, token_out, lp);
+    if (!ctx || !ctx->engine) return false;
+    ctx->last_error = RWKV_ERROR_NONE;
+    SamplingParams sp;
+    LogprobsOut lo;
+    FilterParams fp;
+    if (!logprobs_ok(ctx, lp, lo) || !sampling_ok(ctx, params, sp) || !filters_ok(ctx, f, 1, fp)) return false;
+    CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, token_out != nullptr, "NULL token_out");
+    if (!logprobs_reserve(ctx, lp, 1, 1)) return false;
+    use_device(ctx);
+    CTX_CHECK(ctx, RWKV_ERROR_CTX, false, ctx->engine->sample(sp, token_out, lp ? &lo : nullptr, &fp), "GPU sampling failed");
+    return true;
+}
+
+RWKV_API bool rwkv_mi355x_generate_filtered(struct rwkv_context * ctx, const struct rwkv_mi355x_sampling * params,
+                                            size_t n, uint32_t * tokens_out, float * logits_out,
+                                            const struct rwkv_mi355x_logprobs * lp, const struct rwkv_mi355x_filters * f) {
+    if (!f) return rwkv_mi355x_generate_logprobs(ctx, params, n, tokens_out, logits_out, lp);
+    if (!ctx || !ctx->engine) return false;
+    ctx->last_error = RWKV_ERROR_NONE;
+    SamplingParams sp;
+    LogprobsOut lo;
+    FilterParams fp;
+    if (!logprobs_ok(ctx, lp, lo) || !sampling_ok(ctx, params, sp) || !filters_ok(ctx, f, 1, fp)) return false;
+    CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, n > 0 && n <= 65536, "Token count %zu is outside [1, 65536]", n);
+    CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, tokens_out != nullptr, "NULL tokens_out");
+    if (!logprobs_reserve(ctx, lp, 1, n)) return false;
+    use_device(ctx);
+    CTX_CHECK(ctx, RWKV_ERROR_CTX, false, ctx->engine->generate(sp, n, tokens_out, logits_out, lp ? &lo : nullptr, &fp),
+              "GPU generation failed");
+    return true;
+}
+
+RWKV_API bool rwkv_mi355x_generate_batch_filtered(struct rwkv_context * ctx, size_t B,
+                                                  const struct rwkv_mi355x_batch_sampling * p, size_t n,
+                                                  uint32_t * tokens_out, uint32_t * lengths_out, uint32_t * steps_out,
+                                                  const struct rwkv_mi355x_logprobs * lp,
+                                                  const struct rwkv_mi355x_filters * f) {
+    if (!f) return rwkv_mi355x_generate_batch_logprobs(ctx, B, p, n, tokens_out, lengths_out, steps_out, lp);
+    if (!ctx || !ctx->engine) return false;
+    ctx->last_error = RWKV_ERROR_NONE;
+    LogprobsOut lo;
+    BatchSamplingParams bp;
+    FilterParams fp;
+    if (!batch_call_ok(ctx, lp, lo, B, B, n, tokens_out, lengths_out) || !batch_sampling_ok(ctx, B, p, bp) ||
+        !filters_ok(ctx, f, B, fp))
+        return false;
+    if (!logprobs_reserve(ctx, lp, B, n)) return false;
+    use_device(ctx);
+    CTX_CHECK(ctx, RWKV_ERROR_CTX, false,
+              ctx->engine->generate_batch(B, bp, n, tokens_out, lengths_out, steps_out, lp ? &lo : nullptr, &fp),
+              "GPU batched generation failed");
+    return true;
+}
+
+RWKV_API bool rwkv_mi355x_generate_queue_filtered(struct rwkv_context * ctx, size_t Q, size_t lanes,
+                                                  const struct rwkv_mi355x_batch_sampling * p,
+                                                  const uint32_t * max_tokens, size_t n, uint32_t * tokens_out,
+                                                  uint32_t * lengths_out, uint32_t * lane_out, uint32_t * start_out,
+                                                  uint32_t * steps_out, const struct rwkv_mi355x_logprobs * lp,
+                                                  const struct rwkv_mi355x_filters * f) {
+    if (!f)
+        return rwkv_mi355x_generate_queue_logprobs(ctx, Q, lanes, p, max_tokens, n, tokens_out, lengths_out, lane_out,
+                                                   start_out, steps_out, lp);
+    if (!ctx || !ctx->engine) return false;
+    ctx->last_error = RWKV_ERROR_NONE;
+    LogprobsOut lo;
+    BatchSamplingParams bp;
+    FilterParams fp;
+    if (!batch_call_ok(ctx, lp, lo, Q, lanes, n, tokens_out, lengths_out)) return false;
+    CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, max_tokens != nullptr, "NULL max_tokens");
+    for (size_t s = 0; s < Q; s++)
+        CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, max_tokens[s] > 0 && max_tokens[s] <= n, "Sequence %zu: max_tokens %" PRIu32 " is outside [1, %zu]",
+                  s, max_tokens[s], n);
+    if (!batch_sampling_ok(ctx, Q, p, bp) || !filters_ok(ctx, f, Q, fp)) return false;
+    CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, !bp.keep_counts,
+              "keep_counts is not supported by the queue (continue a capped sequence with rwkv_mi355x_generate_batch)");
+    if (!logprobs_reserve(ctx, lp, Q, n)) return false;
+    use_device(ctx);
+    CTX_CHECK(ctx, RWKV_ERROR_CTX, false,
+              ctx->engine->generate_queue(Q, lanes, bp, max_tokens, n, tokens_out, lengths_out, lane_out, start_out, steps_out,
+                                          lp ? &lo : nullptr, &fp),
+              "GPU queued generation failed");
+    return true;
+}
+
 RWKV_API bool rwkv_mi355x_prefill_batch(struct rwkv_context * ctx, size_t n_rows, const uint32_t * slots,
                                         const uint32_t * tokens, const size_t * lengths, const uint8_t * cont) {
     if (!ctx || !ctx->engine) return false;

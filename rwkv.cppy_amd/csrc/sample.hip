@@ -528,17 +528,22 @@ __global__ __launch_bounds__(GEN_THREADS) void k_gen_move(const GenQueue q, size
 
 }  // namespace
 
-bool launch_sample(hipStream_t st, const SampleArgs & a) {
+bool launch_sample(hipStream_t st, const SampleArgs & a, const SampleFilters * f) {
     if (!a.logits || !a.tok || a.rows < 1 || a.V < 1 || a.V > SAMPLE_MAX_VOCAB) return false;
     if (a.n_bias < 0 || a.n_bias > SAMPLE_MAX_BIAS || (a.n_bias && (!a.bias_ids || !a.bias_vals))) return false;
     if (a.n_stop < 0 || a.n_stop > SAMPLE_MAX_STOP) return false;
+    const bool filtered = f && f->set();  // the kernels of sample_filter.hip; nothing set: those below, as ever
     const bool rows = a.temperature_r || a.top_p_r || a.seed_r || a.counter_r || a.presence_r || a.frequency_r ||
-                      a.counts || a.n_stop || a.done || a.length || a.fin_step || a.active || a.tok_stride || a.lane_seq;
+                      a.counts || a.n_stop || a.done || a.length || a.fin_step || a.active || a.tok_stride || a.lane_seq ||
+                      (filtered && f->per_row());
     const bool lp = a.lp_token != nullptr;
     if (lp && !a.lp_logz) return false;  // k_logprobs leaves the row's logZ there
     if (rows) {
         if ((a.seed_r == nullptr) != (a.counter_r == nullptr)) return false;
         if (a.lane_seq && !a.length) return false;  // a queue's draw index is the sequence's length
+    }
+    if (filtered) return launch_sample_filtered(st, a, *f, rows, lp);
+    if (rows) {
         if (lp) RK_LAUNCH(k_sample_rows_lp, dim3((unsigned)a.rows), dim3(SM_THREADS), 0, st, a);
         else RK_LAUNCH(k_sample_rows, dim3((unsigned)a.rows), dim3(SM_THREADS), 0, st, a);
     } else {

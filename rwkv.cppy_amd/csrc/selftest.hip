@@ -679,10 +679,42 @@ struct SelftestLogprobs {
     }
 };
 
-// The sampler kernel (sample.hip) on host logits with the uniform draws given: what
-// rwkv_mi355x_sample / _generate launch, one workgroup per row.
+// The filters of a self-test (NULL: none) as the engine hands them to launch_sample: off values as 0
+// (top_k >= V, typical_p 1); per_row: device copies of the [rows] values, else entry 0 as the scalars.
+static bool selftest_filters(const struct rwkv_mi355x_filters * f, int rows, int V, bool per_row, DevBufs & b,
+                             SampleFilters & sf) {
+    memset(&sf, 0, sizeof(sf));
+    if (!f) return true;
+    const size_t R = per_row ? (size_t)rows : 1;
+    std::vector<uint32_t> k(R, 0u);
+    std::vector<float> q(R, 0.0f), t(R, 0.0f);
+    for (size_t r = 0; r < R; r++) {
+        if (f->min_p && !(f->min_p[r] >= 0.0f && f->min_p[r] <= 1.0f)) return false;
+        if (f->typical_p && !(f->typical_p[r] >= 0.0f && f->typical_p[r] <= 1.0f)) return false;
+        k[r] = f->top_k && f->top_k[r] < (uint32_t)V ? f->top_k[r] : 0u;
+        q[r] = f->min_p ? f->min_p[r] : 0.0f;
+        t[r] = f->typical_p && f->typical_p[r] < 1.0f ? f->typical_p[r] : 0.0f;
+    }
+    if (!per_row) {
+        sf.top_k = k[0], sf.min_p = q[0], sf.typical_p = t[0];
+        return true;
+    }
+    uint32_t * dk = (uint32_t *)b.alloc(R * 4);
+    float * dq = (float *)b.alloc(R * 4);
+    float * dt = (float *)b.alloc(R * 4);
+    if (!dk || !dq || !dt || hipMemcpy(dk, k.data(), R * 4, hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemcpy(dq, q.data(), R * 4, hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemcpy(dt, t.data(), R * 4, hipMemcpyHostToDevice) != hipSuccess)
+        return false;
+    sf.top_k_r = dk, sf.min_p_r = dq, sf.typical_p_r = dt;
+    return true;
+}
+
+// The sampler kernel (sample.hip; sample_filter.hip with filters) on host logits with the uniform draws
+// given: what rwkv_mi355x_sample / _generate launch, one workgroup per row.
 static bool selftest_sample(const float * logits, int rows, int V, const struct rwkv_mi355x_sampling * p, const float * u,
-                            uint32_t * tokens, uint32_t * kept, float * cutoff, const SelftestLogprobs * lp) {
+                            uint32_t * tokens, uint32_t * kept, float * cutoff, const SelftestLogprobs * lp,
+                            const struct rwkv_mi355x_filters * f = nullptr) {
     if (!logits || !p || !u || !tokens || rows < 1 || V < 1 || V > SAMPLE_MAX_VOCAB || (lp && !lp->ok(V))) return false;
     if (!(p->temperature >= 0.0f) || !(p->top_p >= 0.0f && p->top_p <= 1.0f) || p->n_bias > (uint32_t)SAMPLE_MAX_BIAS)
         return false;
@@ -716,8 +748,10 @@ static bool selftest_sample(const float * logits, int rows, int V, const struct 
     a.bias_ids = bi;
     a.bias_vals = bv;
     a.u = du;
+    SampleFilters sf;
+    if (!selftest_filters(f, rows, V, false, b, sf)) return false;
     if (lp && (!lp->up(b, rows, a) || !launch_logprobs(nullptr, a))) return false;
-    if (!launch_sample(nullptr, a) || hipDeviceSynchronize() != hipSuccess) return false;
+    if (!launch_sample(nullptr, a, &sf) || hipDeviceSynchronize() != hipSuccess) return false;
     if (hipMemcpy(tokens, a.tok, (size_t)rows * 4, hipMemcpyDeviceToHost) != hipSuccess) return false;
     if (kept && hipMemcpy(kept, a.kept, (size_t)rows * 4, hipMemcpyDeviceToHost) != hipSuccess) return false;
     if (cutoff && hipMemcpy(cutoff, a.cutoff, (size_t)rows * 4, hipMemcpyDeviceToHost) != hipSuccess) return false;
@@ -739,12 +773,20 @@ extern "C" RWKV_API bool rwkv_mi355x_selftest_sample_logprobs(const float * logi
     return selftest_sample(logits, rows, V, p, u, tokens, kept, cutoff, &lp);
 }
 
+extern "C" RWKV_API bool rwkv_mi355x_selftest_sample_filtered(const float * logits, int rows, int V,
+                                                             const struct rwkv_mi355x_sampling * p, const float * u,
+                                                             uint32_t * tokens, uint32_t * kept, float * cutoff,
+                                                             const struct rwkv_mi355x_filters * filters) {
+    return selftest_sample(logits, rows, V, p, u, tokens, kept, cutoff, nullptr, filters);
+}
+
 // The batched sampler kernel (sample.hip, k_sample_rows) on host operands: what
 // rwkv_mi355x_generate_batch launches per step, with the uniform draws given.
 static bool selftest_sample_rows(const float * logits, int rows, int V, const struct rwkv_mi355x_batch_sampling * p,
                                  const float * u, uint32_t step, uint32_t * counts, uint32_t * done, uint32_t * tokens,
                                  uint32_t * decode_tokens, uint32_t * kept, float * cutoff, uint32_t * lengths,
-                                 uint32_t * active, const SelftestLogprobs * lp) {
+                                 uint32_t * active, const SelftestLogprobs * lp,
+                                 const struct rwkv_mi355x_filters * f = nullptr) {
     if (!logits || !p || !u || !done || !tokens || !decode_tokens || !kept || !cutoff || !lengths || !active) return false;
     if (lp && (V < 1 || !lp->ok(V))) return false;
     if (rows < 1 || V < 1 || V > SAMPLE_MAX_VOCAB || !p->temperature || !p->top_p) return false;
@@ -792,8 +834,10 @@ static bool selftest_sample_rows(const float * logits, int rows, int V, const st
     a.n_stop = (int)p->n_stop;
     for (uint32_t i = 0; i < p->n_stop; i++) a.stop[i] = p->stop_tokens[i];
     a.step = step;
+    SampleFilters sf;
+    if (!selftest_filters(f, rows, V, true, b, sf)) return false;
     if (lp && (!lp->up(b, rows, a) || !launch_logprobs(nullptr, a))) return false;
-    if (!launch_sample(nullptr, a) || hipDeviceSynchronize() != hipSuccess) return false;
+    if (!launch_sample(nullptr, a, &sf) || hipDeviceSynchronize() != hipSuccess) return false;
     const std::pair<void *, const void *> down[] = {{done, a.done},     {tokens, a.tok},     {decode_tokens, a.tok2},
                                                     {kept, a.kept},     {cutoff, a.cutoff}, {lengths, a.length}};
     for (const auto & d : down)
@@ -820,6 +864,14 @@ extern "C" RWKV_API bool rwkv_mi355x_selftest_sample_rows_logprobs(
     const SelftestLogprobs lp{top_k, token_logprob, top_ids, top_logprobs};
     return selftest_sample_rows(logits, rows, V, p, u, step, counts, done, tokens, decode_tokens, kept, cutoff, lengths,
                                 active, &lp);
+}
+
+extern "C" RWKV_API bool rwkv_mi355x_selftest_sample_rows_filtered(
+    const float * logits, int rows, int V, const struct rwkv_mi355x_batch_sampling * p, const float * u, uint32_t step,
+    uint32_t * counts, uint32_t * done, uint32_t * tokens, uint32_t * decode_tokens, uint32_t * kept, float * cutoff,
+    uint32_t * lengths, uint32_t * active, const struct rwkv_mi355x_filters * filters) {
+    return selftest_sample_rows(logits, rows, V, p, u, step, counts, done, tokens, decode_tokens, kept, cutoff, lengths,
+                                active, nullptr, filters);
 }
 
 // The queue's turnover kernel (sample.hip, k_gen_turnover) on host operands: what

@@ -22,6 +22,11 @@ def _is_torch(t) -> bool:
     return type(t).__module__.startswith('torch')
 
 
+def _filter_kwargs(top_k, min_p, typical_p) -> dict:
+    """The filters that are set, as keyword arguments of the library's methods; none set: none passed."""
+    return {k: v for k, v in (('top_k', top_k), ('min_p', min_p), ('typical_p', typical_p)) if v is not None}
+
+
 class RWKVModel:
     def __init__(self, shared_library: 'rwkv_cpp_shared_library.RWKVSharedLibrary', model_path: str,
                  thread_count: int = max(1, multiprocessing.cpu_count() // 2), gpu_layer_count: int = 0,
@@ -149,22 +154,27 @@ class RWKVModel:
         return logits, states
 
     def sample(self, temperature: float = 1.0, top_p: float = 0.8, logit_bias=None, seed: int = 0,
-               offset: int = 0, logprobs: Optional[int] = None):
+               offset: int = 0, logprobs: Optional[int] = None, top_k=None, min_p=None, typical_p=None):
         """MI355X extension (rwkv_mi355x_sample): draws one token on the device from the logits of the
         last evaluation on this model (sampling.sample_logits semantics; draw `offset` of the stream
         `seed`, sampling.uniform).  The state is untouched.
 
         logprobs=K (0 <= K <= 20): returns (token, Logprobs(token_logprob, top_ids, top_logprobs)), the
         token's log-probability under softmax(logits + bias) and the K most likely tokens with theirs
-        (sampling.logprobs), taken on the device inside the sampling step."""
+        (sampling.logprobs), taken on the device inside the sampling step.
+
+        top_k, min_p, typical_p (each None: off): the filters in front of top_p, on the device
+        (rwkv_mi355x_sample_filtered; sampling.kept_mask)."""
         if not self._valid:
             raise ValueError('Model was freed')
-        if logprobs is None:
-            return self._library.rwkv_mi355x_sample(self._ctx, temperature, top_p, logit_bias, seed, offset)
-        return self._library.rwkv_mi355x_sample(self._ctx, temperature, top_p, logit_bias, seed, offset, logprobs=logprobs)
+        extra = _filter_kwargs(top_k, min_p, typical_p)
+        if logprobs is not None:
+            extra['logprobs'] = logprobs
+        return self._library.rwkv_mi355x_sample(self._ctx, temperature, top_p, logit_bias, seed, offset, **extra)
 
     def generate(self, n: int, temperature: float = 1.0, top_p: float = 0.8, logit_bias=None, seed: int = 0,
-                 offset: int = 0, stop_tokens=(), block: int = 16, logprobs: Optional[int] = None):
+                 offset: int = 0, stop_tokens=(), block: int = 16, logprobs: Optional[int] = None, top_k=None,
+                 min_p=None, typical_p=None):
         """MI355X extension (rwkv_mi355x_generate): generates up to n tokens on the device, continuing
         from the state and logits the last evaluation on this model left there (eval, eval_sequence, or
         an earlier generate).  Sampling and decoding run back to back on the GPU in blocks of `block`
@@ -176,11 +186,15 @@ class RWKVModel:
 
         logprobs=K (0 <= K <= 20): returns (tokens, Logprobs) with one entry per returned token, cut
         where the tokens are cut: token_logprob float64 [len], top_ids uint32 and top_logprobs float64
-        [len, K] (sampling.logprobs of every draw, taken on the device)."""
+        [len, K] (sampling.logprobs of every draw, taken on the device).
+
+        top_k, min_p, typical_p (each None: off): the filters in front of top_p, on the device
+        (rwkv_mi355x_generate_filtered; sampling.kept_mask)."""
         if not self._valid:
             raise ValueError('Model was freed')
         if not block > 0:
             raise ValueError('block must be > 0')
+        filters = _filter_kwargs(top_k, min_p, typical_p)
         stop = set(stop_tokens)
         out: List[int] = []
         parts = []
@@ -199,10 +213,10 @@ class RWKVModel:
             lp = None
             if logprobs is None:  # the call as it always was
                 tokens = self._library.rwkv_mi355x_generate(self._ctx, m, temperature, top_p, logit_bias, seed,
-                                                            offset + len(out))
+                                                            offset + len(out), **filters)
             else:
                 tokens, lp = self._library.rwkv_mi355x_generate(self._ctx, m, temperature, top_p, logit_bias, seed,
-                                                                offset + len(out), logprobs=logprobs)
+                                                                offset + len(out), logprobs=logprobs, **filters)
             for i, t in enumerate(tokens):
                 if t in stop:
                     cut = None if lp is None else rwkv_cpp_shared_library.Logprobs(*(x[:i + 1] for x in lp))
@@ -265,7 +279,8 @@ class RWKVModel:
 
     def generate_batch(self, prompts: List[List[int]], n: int, temperature=1.0, top_p=0.8, presence_penalty=0.0,
                        frequency_penalty=0.0, logit_bias=None, seeds=None, stop_tokens=(),
-                       check_every: int = 16, batched_prefill: bool = False, logprobs: Optional[int] = None):
+                       check_every: int = 16, batched_prefill: bool = False, logprobs: Optional[int] = None,
+                       top_k=None, min_p=None, typical_p=None):
         """MI355X extension (rwkv_mi355x_generate_batch): generates up to n tokens for every prompt, all
         rows together on the device: sampling, penalties over the tokens a row has drawn, exact stops
         and one batched decode step per token, with only the tokens coming back.  temperature, top_p,
@@ -279,7 +294,10 @@ class RWKVModel:
         logprobs=K (0 <= K <= 20): returns (token lists, [Logprobs per prompt]); prompt i's Logprobs
         has one entry per token of its list, the stop token included: token_logprob float64 [len],
         top_ids uint32 and top_logprobs float64 [len, K], of the penalised and biased distribution each
-        token was drawn from (sampling.logprobs)."""
+        token was drawn from (sampling.logprobs).
+
+        top_k, min_p, typical_p (each None: off; a scalar or one value per prompt): the filters in front
+        of top_p, on the device (rwkv_mi355x_generate_batch_filtered; sampling.kept_mask)."""
         if not self._valid:
             raise ValueError('Model was freed')
         rows = len(prompts)
@@ -300,10 +318,11 @@ class RWKVModel:
             self.reset_state()
             self._library.rwkv_mi355x_eval_device(self._ctx, list(prompt))
             self._library.rwkv_mi355x_batch_store(self._ctx, slot)
-        if logprobs is None:  # the call as it always was
-            out = self._library.rwkv_mi355x_generate_batch(self._ctx, rows, n, params)
+        filters = _filter_kwargs(top_k, min_p, typical_p)
+        if logprobs is None:  # without filters: the call as it always was
+            out = self._library.rwkv_mi355x_generate_batch(self._ctx, rows, n, params, **filters)
         else:
-            out = self._library.rwkv_mi355x_generate_batch(self._ctx, rows, n, params, logprobs=logprobs)
+            out = self._library.rwkv_mi355x_generate_batch(self._ctx, rows, n, params, logprobs=logprobs, **filters)
         tokens, lengths = out[0], out[1]
         lists = [[int(t) for t in tokens[r][:int(lengths[r])]] for r in range(rows)]
         if logprobs is None:
@@ -312,7 +331,7 @@ class RWKVModel:
 
     def generate_queue(self, prompts: List[List[int]], max_tokens, lanes: int = 32, temperature=1.0, top_p=0.8,
                        presence_penalty=0.0, frequency_penalty=0.0, logit_bias=None, seeds=None, stop_tokens=(),
-                       check_every: int = 16, logprobs: Optional[int] = None):
+                       check_every: int = 16, logprobs: Optional[int] = None, top_k=None, min_p=None, typical_p=None):
         """MI355X extension (rwkv_mi355x_generate_queue): continuous batching.  Up to 256 prompts are
         evaluated together (prefill_batch) into slots 0 .. Q-1 and generated through a queue over
         `lanes` decode rows: a row whose sequence has ended -- a stop token, or its max_tokens (a scalar
@@ -320,7 +339,7 @@ class RWKVModel:
         stay full.  The other parameters are those of generate_batch, per prompt.  Returns one token
         list per prompt, each exactly what that prompt generates alone; slot i holds its final state
         and logits, and batch_load(i) continues from there.  logprobs=K: as generate_batch, (token
-        lists, [Logprobs per prompt])."""
+        lists, [Logprobs per prompt]).  top_k, min_p, typical_p: as generate_batch, per prompt."""
         if not self._valid:
             raise ValueError('Model was freed')
         rows = len(prompts)
@@ -339,7 +358,9 @@ class RWKVModel:
         if self._library.rwkv_mi355x_batch_slots(self._ctx) < rows:
             self._library.rwkv_mi355x_batch_reserve(self._ctx, rows)
         self._library.rwkv_mi355x_prefill_batch(self._ctx, [list(p) for p in prompts], list(range(rows)), None)
-        extra = {} if logprobs is None else {'logprobs': logprobs}
+        extra = _filter_kwargs(top_k, min_p, typical_p)
+        if logprobs is not None:
+            extra['logprobs'] = logprobs
         out = self._library.rwkv_mi355x_generate_queue(
             self._ctx, caps, lanes, temperature, top_p, presence_penalty, frequency_penalty, logit_bias, seeds, 0,
             stop_tokens, check_every, **extra)

@@ -65,6 +65,32 @@ class RWKVLogprobs(ctypes.Structure):
                 ('top_ids', ctypes.POINTER(ctypes.c_uint32)), ('top_logprobs', ctypes.POINTER(ctypes.c_double))]
 
 
+class RWKVFilters(ctypes.Structure):
+    """struct rwkv_mi355x_filters (include/rwkv_mi355x.h)."""
+    _fields_ = [('top_k', ctypes.POINTER(ctypes.c_uint32)), ('min_p', P_FLOAT), ('typical_p', P_FLOAT)]
+
+
+def make_filters(rows: int, top_k=None, min_p=None, typical_p=None) -> Optional[RWKVFilters]:
+    """An RWKVFilters for `rows` rows: each of top_k, min_p, typical_p is None (that filter off: a NULL
+    array), a scalar (every row) or a sequence of `rows` values.  All three None: None, and the caller
+    makes the call without filters.  The arrays stay referenced by the returned structure."""
+    if top_k is None and min_p is None and typical_p is None:
+        return None
+    keep = []
+
+    def array(value, ctype, cast, name):
+        if value is None:
+            return None
+        arr = (ctype * rows)(*[cast(v) for v in _per_row(value, rows, name)])
+        keep.append(arr)
+        return arr
+
+    f = RWKVFilters(array(top_k, ctypes.c_uint32, int, 'top_k'), array(min_p, ctypes.c_float, float, 'min_p'),
+                    array(typical_p, ctypes.c_float, float, 'typical_p'))
+    f._keep = keep
+    return f
+
+
 # What a call with logprobs=K returns besides its tokens: the drawn tokens' log-probabilities
 # (float64 [n]) and the K most likely alternatives of every draw (uint32 / float64 [n, K]).
 Logprobs = collections.namedtuple('Logprobs', ('token_logprob', 'top_ids', 'top_logprobs'))
@@ -294,6 +320,15 @@ class RWKVSharedLibrary:
             u32, P_DOUBLE, P_U32, P_DOUBLE]
         for name in ('sample', 'generate', 'generate_batch', 'generate_queue', 'selftest_sample', 'selftest_sample_rows'):
             getattr(L, f'rwkv_mi355x_{name}_logprobs').restype = ctypes.c_bool
+        P_F = ctypes.POINTER(RWKVFilters)
+        for name in ('sample', 'generate', 'generate_batch', 'generate_queue'):
+            fn = getattr(L, f'rwkv_mi355x_{name}_filtered')
+            fn.argtypes = getattr(L, f'rwkv_mi355x_{name}').argtypes + [P_LP, P_F]
+            fn.restype = ctypes.c_bool
+        for name in ('selftest_sample', 'selftest_sample_rows'):
+            fn = getattr(L, f'rwkv_mi355x_{name}_filtered')
+            fn.argtypes = getattr(L, f'rwkv_mi355x_{name}').argtypes + [P_F]
+            fn.restype = ctypes.c_bool
         L.rwkv_mi355x_score_sequence.argtypes = [vp, P_U32, sz, P_U32, P_DOUBLE, P_U32, P_FLOAT]
         L.rwkv_mi355x_score_sequence.restype = ctypes.c_bool
         L.rwkv_mi355x_selftest_xent.argtypes = [P_FLOAT, ctypes.c_int, ctypes.c_int, P_U32, P_DOUBLE, P_U32]
@@ -392,12 +427,23 @@ class RWKVSharedLibrary:
 
     # ---- additive: sampling and the generation loop on the device ---------------------------
     def rwkv_mi355x_sample(self, ctx: RWKVContext, temperature: float = 1.0, top_p: float = 0.8, logit_bias=None,
-                           seed: int = 0, offset: int = 0, logprobs: Optional[int] = None):
+                           seed: int = 0, offset: int = 0, logprobs: Optional[int] = None, top_k=None, min_p=None,
+                           typical_p=None):
         """One token drawn on the device from the context's logits (draw `offset` of stream `seed`);
         the state is untouched.  logprobs=K (rwkv_mi355x_sample_logprobs): returns (token, Logprobs)
-        with the token's log-probability (a float) and the K most likely alternatives ([K] arrays)."""
+        with the token's log-probability (a float) and the K most likely alternatives ([K] arrays).
+        top_k / min_p / typical_p (rwkv_mi355x_sample_filtered): the filters in front of top_p."""
         token = ctypes.c_uint32(0)
         p = make_sampling(temperature, top_p, logit_bias, seed, offset)
+        filters = make_filters(1, top_k, min_p, typical_p)
+        if filters is not None:
+            lp, out = make_logprobs(1, 1, logprobs) if logprobs is not None else (None, None)
+            if not self.library.rwkv_mi355x_sample_filtered(ctx.ptr, ctypes.byref(p), ctypes.byref(token),
+                                                            lp and ctypes.byref(lp), ctypes.byref(filters)):
+                raise ValueError('rwkv_mi355x_sample_filtered failed, check stderr')
+            if lp is None:
+                return token.value
+            return token.value, Logprobs(float(out.token_logprob[0, 0]), out.top_ids[0, 0], out.top_logprobs[0, 0])
         if logprobs is None:
             if not self.library.rwkv_mi355x_sample(ctx.ptr, ctypes.byref(p), ctypes.byref(token)):
                 raise ValueError('rwkv_mi355x_sample failed, check stderr')
@@ -409,13 +455,24 @@ class RWKVSharedLibrary:
 
     def rwkv_mi355x_generate(self, ctx: RWKVContext, n: int, temperature: float = 1.0, top_p: float = 0.8,
                              logit_bias=None, seed: int = 0, offset: int = 0,
-                             logits_out_address: Optional[int] = None, logprobs: Optional[int] = None):
+                             logits_out_address: Optional[int] = None, logprobs: Optional[int] = None, top_k=None,
+                             min_p=None, typical_p=None):
         """n times (draw a token on the device, evaluate it) without a host round trip; returns the
         tokens.  Draw i uses counter offset + i, so a call with offset + n continues the stream.
-        logprobs=K (rwkv_mi355x_generate_logprobs): returns (tokens, Logprobs of [n] / [n, K] arrays)."""
+        logprobs=K (rwkv_mi355x_generate_logprobs): returns (tokens, Logprobs of [n] / [n, K] arrays).
+        top_k / min_p / typical_p (rwkv_mi355x_generate_filtered): the filters in front of top_p."""
         tokens = (ctypes.c_uint32 * max(1, n))()
         p = make_sampling(temperature, top_p, logit_bias, seed, offset)
         logits_out = ctypes.cast(logits_out_address or 0, P_FLOAT)
+        filters = make_filters(1, top_k, min_p, typical_p)
+        if filters is not None:
+            lp, out = make_logprobs(1, max(1, n), logprobs) if logprobs is not None else (None, None)
+            if not self.library.rwkv_mi355x_generate_filtered(ctx.ptr, ctypes.byref(p), n, tokens, logits_out,
+                                                              lp and ctypes.byref(lp), ctypes.byref(filters)):
+                raise ValueError('rwkv_mi355x_generate_filtered failed, check stderr')
+            if lp is None:
+                return list(tokens[:n])
+            return list(tokens[:n]), Logprobs(*(x[0, :n] for x in out))
         if logprobs is None:
             if not self.library.rwkv_mi355x_generate(ctx.ptr, ctypes.byref(p), n, tokens, logits_out):
                 raise ValueError('rwkv_mi355x_generate failed, check stderr')
@@ -427,11 +484,13 @@ class RWKVSharedLibrary:
         return list(tokens[:n]), Logprobs(*(x[0, :n] for x in out))
 
     def rwkv_mi355x_selftest_sample(self, logits, u, temperature: float = 1.0, top_p: float = 0.8, logit_bias=None,
-                                    logprobs: Optional[int] = None, fill: int = 0xA5):
+                                    logprobs: Optional[int] = None, fill: int = 0xA5, filters: Optional[dict] = None):
         """The sampler kernel on host logits [rows][V] (float32 numpy) with the draws u [rows] given.
         Returns (tokens, kept, cutoff) numpy arrays [rows].  logprobs=K
         (rwkv_mi355x_selftest_sample_logprobs): a fourth element, Logprobs of [rows] / [rows, K] arrays
-        that start as bytes of `fill`, so an entry the kernels do not write keeps them."""
+        that start as bytes of `fill`, so an entry the kernels do not write keeps them.  filters: None,
+        or a dict of make_filters' top_k / min_p / typical_p, one value each for all rows
+        (rwkv_mi355x_selftest_sample_filtered; not together with logprobs)."""
         import numpy as np
         logits = np.ascontiguousarray(logits, dtype=np.float32)
         if logits.ndim == 1:
@@ -443,6 +502,11 @@ class RWKVSharedLibrary:
         P_U32 = ctypes.POINTER(ctypes.c_uint32)
         args = (logits.ctypes.data_as(P_FLOAT), rows, V, ctypes.byref(p), u.ctypes.data_as(P_FLOAT),
                 tokens.ctypes.data_as(P_U32), kept.ctypes.data_as(P_U32), cutoff.ctypes.data_as(P_FLOAT))
+        if filters is not None:
+            f = make_filters(1, **filters)
+            if not self.library.rwkv_mi355x_selftest_sample_filtered(*args, f and ctypes.byref(f)):
+                raise ValueError('rwkv_mi355x_selftest_sample_filtered failed')
+            return tokens, kept, cutoff
         if logprobs is None:
             if not self.library.rwkv_mi355x_selftest_sample(*args):
                 raise ValueError('rwkv_mi355x_selftest_sample failed')
@@ -492,10 +556,10 @@ class RWKVSharedLibrary:
             raise ValueError('rwkv_mi355x_batch_load failed, check stderr')
 
     def _generate_slots(self, name: str, ctx: RWKVContext, rows: int, n: int, logprobs: Optional[int], head: tuple,
-                        extra: tuple = ()):
+                        extra: tuple = (), filters: Optional[RWKVFilters] = None):
         """What rwkv_mi355x_generate_batch and rwkv_mi355x_generate_queue share: the output arrays of
-        `rows` sequences and the plain / _logprobs entry point `name`, called with (ctx, *head, n,
-        tokens, lengths, *extra, steps[, logprobs]).  Returns (tokens [rows, n], lengths [rows], steps,
+        `rows` sequences and the plain / _logprobs / _filtered entry point `name`, called with (ctx, *head,
+        n, tokens, lengths, *extra, steps[, logprobs[, filters]]).  Returns (tokens [rows, n], lengths [rows], steps,
         Logprobs of [rows, n] / [rows, n, K] arrays or None)."""
         import numpy as np
         tokens = np.zeros((rows, max(1, n)), np.uint32)
@@ -504,34 +568,42 @@ class RWKVSharedLibrary:
         P_U32 = ctypes.POINTER(ctypes.c_uint32)
         args = (ctx.ptr, *head, n, tokens.ctypes.data_as(P_U32), lengths.ctypes.data_as(P_U32),
                 *(x.ctypes.data_as(P_U32) for x in extra), ctypes.byref(steps))
-        out = None
+        out = lp = None
         if logprobs is not None:
-            name += '_logprobs'
             lp, out = make_logprobs(rows, max(1, n), logprobs)
+        if filters is not None:
+            name += '_filtered'
+            args += (lp and ctypes.byref(lp), ctypes.byref(filters))
+        elif lp is not None:
+            name += '_logprobs'
             args += (ctypes.byref(lp),)
         if not getattr(self.library, name)(*args):
             raise ValueError(f'{name} failed, check stderr')
         return tokens[:, :n], lengths, steps.value, out and Logprobs(*(x[:, :n] for x in out))
 
     def rwkv_mi355x_generate_batch(self, ctx: RWKVContext, rows: int, n: int, params: RWKVBatchSampling,
-                                   logprobs: Optional[int] = None):
+                                   logprobs: Optional[int] = None, top_k=None, min_p=None, typical_p=None):
         """Up to n tokens for each of slots [0, rows) (make_batch_sampling).  Returns (tokens uint32
         [rows, n], 0xFFFFFFFF after a row's last token; lengths uint32 [rows]; the decode steps run).
         logprobs=K (rwkv_mi355x_generate_batch_logprobs): a fourth element, Logprobs of [rows, n] /
-        [rows, n, K] arrays whose columns past a row's length hold the fill (NaN, 0xFFFFFFFF)."""
-        out = self._generate_slots('rwkv_mi355x_generate_batch', ctx, rows, n, logprobs, (rows, ctypes.byref(params)))
+        [rows, n, K] arrays whose columns past a row's length hold the fill (NaN, 0xFFFFFFFF).
+        top_k / min_p / typical_p, scalars or per row (rwkv_mi355x_generate_batch_filtered): the filters
+        in front of top_p."""
+        out = self._generate_slots('rwkv_mi355x_generate_batch', ctx, rows, n, logprobs, (rows, ctypes.byref(params)),
+                                   filters=make_filters(rows, top_k, min_p, typical_p))
         return out if logprobs is not None else out[:3]
 
     def rwkv_mi355x_generate_queue(self, ctx: RWKVContext, max_tokens, lanes: int, temperature=1.0, top_p=0.8,
                                    presence=None, frequency=None, logit_bias=None, seeds=None, offsets=0,
                                    stop_tokens=(), check_every: int = 0, n: Optional[int] = None,
-                                   logprobs: Optional[int] = None):
+                                   logprobs: Optional[int] = None, top_k=None, min_p=None, typical_p=None):
         """The sequences in slots [0, len(max_tokens)) through a queue over `lanes` decode rows, at most
         max_tokens[s] tokens each (make_batch_sampling over the sequences, keep_counts false).  Returns
         a dict: tokens uint32 [Q, n] (n: max(max_tokens) unless given; 0xFFFFFFFF after a sequence's
         last token), lengths, lane, start uint32 [Q] and steps, the decode steps that were needed.
         logprobs=K (rwkv_mi355x_generate_queue_logprobs) adds 'logprobs': Logprobs of [Q, n] / [Q, n, K]
-        arrays."""
+        arrays.  top_k / min_p / typical_p, scalars or per sequence (rwkv_mi355x_generate_queue_filtered):
+        the filters in front of top_p."""
         import numpy as np
         caps = np.ascontiguousarray(max_tokens, dtype=np.uint32)
         Q = int(caps.size)
@@ -541,7 +613,8 @@ class RWKVSharedLibrary:
         out = {k: np.zeros(Q, np.uint32) for k in ('lane', 'start')}
         head = (Q, lanes, ctypes.byref(params), caps.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)))
         out['tokens'], out['lengths'], out['steps'], lp = self._generate_slots(
-            'rwkv_mi355x_generate_queue', ctx, Q, n, logprobs, head, (out['lane'], out['start']))
+            'rwkv_mi355x_generate_queue', ctx, Q, n, logprobs, head, (out['lane'], out['start']),
+            make_filters(Q, top_k, min_p, typical_p))
         if logprobs is not None:
             out['logprobs'] = lp
         return out
@@ -602,14 +675,17 @@ class RWKVSharedLibrary:
     def rwkv_mi355x_selftest_sample_rows(self, logits, u, temperature, top_p, presence=None, frequency=None,
                                          counts=None, done=None, logit_bias=None, stop_tokens=(), step: int = 0,
                                          fill: int = 0xFFFFFFFF, active: Optional[int] = None,
-                                         logprobs: Optional[int] = None, lp_fill: int = 0xA5):
+                                         logprobs: Optional[int] = None, lp_fill: int = 0xA5,
+                                         filters: Optional[dict] = None):
         """The batched sampler kernel on host logits [rows][V] with the draws u [rows] given and
         per-row parameters (scalars or [rows]).  counts (uint32 [rows][V]) and done (uint32 [rows]) are
         updated in place when given.  Every output starts as `fill` (cutoff: its bits), so an entry
         the kernel does not write keeps it.  Returns a dict: tokens, decode_tokens, kept, cutoff,
         lengths, done [rows] and active (the live rows, starting from `active`, default rows).
         logprobs=K (rwkv_mi355x_selftest_sample_rows_logprobs) adds 'logprobs': Logprobs of [rows] /
-        [rows, K] arrays that start as bytes of `lp_fill`."""
+        [rows, K] arrays that start as bytes of `lp_fill`.  filters: None, or a dict of make_filters'
+        top_k / min_p / typical_p, scalars or [rows] (rwkv_mi355x_selftest_sample_rows_filtered; not
+        together with logprobs)."""
         import numpy as np
         logits = np.ascontiguousarray(logits, dtype=np.float32)
         rows, V = logits.shape
@@ -628,7 +704,11 @@ class RWKVSharedLibrary:
                 out['tokens'].ctypes.data_as(P_U32), out['decode_tokens'].ctypes.data_as(P_U32),
                 out['kept'].ctypes.data_as(P_U32), out['cutoff'].ctypes.data_as(P_FLOAT),
                 out['lengths'].ctypes.data_as(P_U32), act.ctypes.data_as(P_U32))
-        if logprobs is None:
+        if filters is not None:
+            f = make_filters(rows, **filters)
+            if not self.library.rwkv_mi355x_selftest_sample_rows_filtered(*args, f and ctypes.byref(f)):
+                raise ValueError('rwkv_mi355x_selftest_sample_rows_filtered failed')
+        elif logprobs is None:
             if not self.library.rwkv_mi355x_selftest_sample_rows(*args):
                 raise ValueError('rwkv_mi355x_selftest_sample_rows failed')
         else:

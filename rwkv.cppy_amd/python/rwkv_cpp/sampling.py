@@ -112,6 +112,53 @@ def logprobs(l, top_k: int):
         return float(log_z), top.astype(np.uint32), ld[top] - log_z
 
 
+def _cutoff(key, mass, target: float) -> float:
+    """The first key, in ascending order, at which the mass of all elements with a key <= it exceeds
+    target (ties are one step)."""
+    order = np.argsort(key, kind='stable')
+    k, cum = key[order], np.cumsum(mass[order])
+    step_end = np.append(k[1:] != k[:-1], True)
+    return float(k[np.argmax((cum > target) & step_end)])
+
+
+def kept_mask(l, top_k: int = 0, min_p: float = 0.0, typical_p: float = 0.0, top_p: float = 0.0) -> np.ndarray:
+    """The tokens librwkv.so's sampler keeps for one draw (rwkv_mi355x_filters, then top_p), in float64
+    numpy; the specification the device kernels are measured against.
+
+    l is the float32 row the sampler samples from (logits, penalize(), bias).  With m = max l and
+    e = exp(l - m), in this order and every rule keeping all ties at its cutoff:
+      top_k      keep e >= the top_k-th largest e                       (0 or >= len(l): off)
+      min_p      among those, keep e >= min_p, i.e. p >= min_p * p_max  (0: off)
+      typical_p  over the set F kept so far: g = sum_F e (m - l) / sum_F e, d = |(m - l) - g|; keep
+                 d <= d_c, the smallest d with sum{e in F, d <= d_c} > typical_p * sum_F e  (0, 1: off)
+      top_p      over the set G kept so far: keep e >= e_c, the largest e with
+                 sum{e in G, e >= e_c} > top_p * sum_G e                 (0, 1: off)
+    Returns a bool array.  The device forms e in float32 and d as one float32 rounding of a float64
+    value, and sums the masses in float32: where a cutoff falls between two tie groups whose masses (and,
+    for typical_p, distances) differ by more than those errors, it keeps exactly this set."""
+    ld = np.asarray(l, dtype=np.float32).astype(np.float64)
+    if ld.ndim != 1 or ld.size == 0:
+        raise ValueError('one row of logits')
+    if not 0.0 <= min_p <= 1.0 or not 0.0 <= typical_p <= 1.0 or not 0.0 <= top_p <= 1.0:
+        raise ValueError('min_p, typical_p and top_p are in [0, 1]')
+    x = ld.max() - ld
+    e = np.exp(-x)
+    keep = np.ones(ld.size, bool)
+    if 0 < top_k < ld.size:
+        keep &= e >= np.sort(e)[-int(top_k)]
+    if min_p > 0.0:
+        keep &= e >= float(np.float32(min_p))
+    if 0.0 < typical_p < 1.0:
+        f = np.flatnonzero(keep)
+        total = e[f].sum()
+        d = np.abs(x - (e[f] * x[f]).sum() / total)
+        keep &= d <= _cutoff(d[f], e[f], typical_p * total)
+    if 0.0 < top_p < 1.0:
+        g = np.flatnonzero(keep)
+        keep &= -e <= _cutoff(-e[g], e[g], top_p * e[g].sum())
+    return keep
+
+
 def queue_schedule(lengths, lanes: int):
     """The schedule of librwkv.so's queue (rwkv_mi355x_generate_queue) on plain integers: sequence s
     occupies a lane for lengths[s] >= 1 steps.  Before step i the lanes whose sequence has had its
