@@ -301,6 +301,78 @@ RWKV_API bool rwkv_mi355x_generate_queue_filtered(struct rwkv_context * ctx, siz
                                                   uint32_t * steps_out, const struct rwkv_mi355x_logprobs * lp,
                                                   const struct rwkv_mi355x_filters * f);
 
+/* Grammar-constrained generation: a byte-level DFA decides, per draw, which tokens may be drawn, on
+ * the device, in all four calls.  Tokens are byte strings, so a DFA over bytes describes a constraint
+ * exactly (a set of strings, a JSON shape, a number format); building one is the caller's business
+ * (rwkv_cpp.constraint.from_choices builds the simplest kind).
+ *
+ * rwkv_mi355x_vocab_bytes tells the model its tokens' bytes, once: token t is bytes[offsets[t] ..
+ * offsets[t + 1]), offsets [n_vocab + 1] non-decreasing (else RWKV_ERROR_ARGS).  The copy belongs to
+ * the model and is shared by its clones on the same GPU.
+ *
+ * One table serves all rows: next [n_states][256], 0xFFFF = dead, any other entry < n_states.
+ * Automata for different requests are disjoint state sets of one table with different start states.
+ * One draw of a live row in state q:
+ *   1. Token t with n >= 1 bytes is allowed iff walking its bytes from q through next never reaches
+ *      dead.  A token with no bytes is not allowed.
+ *   2. A stop token (params->stop_tokens) is allowed iff accepting[q], whatever its bytes.
+ *   3. No token allowed: the row is finished before the draw; nothing is drawn, and its length, counts,
+ *      slot state and logits are as the previous step left them.  ended = 2.  rwkv_mi355x_sample then
+ *      returns token 0xFFFFFFFF; rwkv_mi355x_generate leaves 0xFFFFFFFF in tokens_out from that draw
+ *      on, and the context's state and logits are those after the last drawn token.
+ *   4. Otherwise l'_i = allowed_i ? logits_i : -inf in float32, and everything the _filtered call does
+ *      (penalties, bias, filters, top-p, the draw, log-probabilities) is done on l', bit for bit as
+ *      the unconstrained call would on those logits.  The slot's own logits stay unmasked.
+ *   5. After a non-stop token t, q = walk(q, t).  A stop token ends the row as ever (ended = 1).
+ *   6. With keep_counts != 0, a second call that passes the returned state continues the derivation.
+ * rows = 1 for sample and generate, B for generate_batch, Q for generate_queue, where state and ended
+ * are indexed by sequence.
+ *
+ * The table is compressed on the host (bytes whose columns are equal in every state form one class,
+ * n_cls <= 256 of them) and must fit one workgroup's LDS: n_states * n_cls * 2 bytes, rounded up to 16,
+ * plus 272 bytes, at most the device's LDS per workgroup (hipDeviceAttributeMaxSharedMemoryPerBlock;
+ * 160 KiB on the MI355X: n_states * n_cls <= 81784, which rwkv_mi355x_constraint_max_entries() returns
+ * for the current device: 319 states at 256 classes, 2044 at 40).  There is no larger path. */
+RWKV_API bool rwkv_mi355x_vocab_bytes(struct rwkv_context * ctx, const uint32_t * offsets /* [n_vocab + 1] */,
+                                      const uint8_t * bytes);
+RWKV_API uint32_t rwkv_mi355x_constraint_max_entries(void);
+struct rwkv_mi355x_constraint {
+    uint32_t n_states;          /* >= 1, < 0xFFFF */
+    const uint16_t * next;      /* host [n_states][256]; 0xFFFF = dead */
+    const uint8_t  * accepting; /* host [n_states] */
+    uint32_t * state;           /* host [rows], in: the start state of each row / sequence; out: its state on return */
+    uint32_t * ended;           /* host [rows] out, may be NULL: 0 not ended (cap reached / still live),
+                                   1 drew a stop token, 2 no token was allowed */
+};
+/* Each is its _filtered sibling above plus c, with lp and f still optional; c == NULL is that call.
+ * Besides the sibling's errors, all RWKV_ERROR_ARGS before anything is enqueued: no vocabulary bytes
+ * on the context; n_states == 0 or >= 0xFFFF; a NULL next / accepting / state; a next entry >=
+ * n_states that is not 0xFFFF; a start state >= n_states; a table over the limit above.  A failed
+ * allocation is RWKV_ERROR_ALLOC, also with nothing enqueued. */
+RWKV_API bool rwkv_mi355x_sample_constrained(struct rwkv_context * ctx, const struct rwkv_mi355x_sampling * params,
+                                             uint32_t * token_out, const struct rwkv_mi355x_logprobs * lp,
+                                             const struct rwkv_mi355x_filters * f,
+                                             const struct rwkv_mi355x_constraint * c);
+RWKV_API bool rwkv_mi355x_generate_constrained(struct rwkv_context * ctx, const struct rwkv_mi355x_sampling * params,
+                                               size_t n, uint32_t * tokens_out, float * logits_out,
+                                               const struct rwkv_mi355x_logprobs * lp,
+                                               const struct rwkv_mi355x_filters * f,
+                                               const struct rwkv_mi355x_constraint * c);
+RWKV_API bool rwkv_mi355x_generate_batch_constrained(struct rwkv_context * ctx, size_t B,
+                                                     const struct rwkv_mi355x_batch_sampling * params, size_t n,
+                                                     uint32_t * tokens_out /* [B][n] */, uint32_t * lengths_out /* [B] */,
+                                                     uint32_t * steps_out, const struct rwkv_mi355x_logprobs * lp,
+                                                     const struct rwkv_mi355x_filters * f,
+                                                     const struct rwkv_mi355x_constraint * c);
+RWKV_API bool rwkv_mi355x_generate_queue_constrained(struct rwkv_context * ctx, size_t Q, size_t lanes,
+                                                     const struct rwkv_mi355x_batch_sampling * params,
+                                                     const uint32_t * max_tokens /* host [Q] */, size_t n,
+                                                     uint32_t * tokens_out /* [Q][n] */, uint32_t * lengths_out /* [Q] */,
+                                                     uint32_t * lane_out /* [Q] */, uint32_t * start_out /* [Q] */,
+                                                     uint32_t * steps_out, const struct rwkv_mi355x_logprobs * lp,
+                                                     const struct rwkv_mi355x_filters * f,
+                                                     const struct rwkv_mi355x_constraint * c);
+
 /* Batched prefill: n_rows prompts, concatenated in `tokens` (lengths[i] >= 1 tokens each), are
  * evaluated together in packed sequence passes and land in slots[i] (distinct, each < the reserved
  * slots).  cont == NULL or cont[i] == 0: row i starts from the fresh state (the slot need not have
@@ -683,6 +755,20 @@ RWKV_API bool rwkv_mi355x_selftest_sample_rows_filtered(const float * logits, in
                                                         uint32_t * done, uint32_t * tokens, uint32_t * decode_tokens,
                                                         uint32_t * kept, float * cutoff, uint32_t * lengths,
                                                         uint32_t * active, const struct rwkv_mi355x_filters * filters);
+
+/* k_dfa_mask (rwkv_mi355x_constraint's mask kernel) on host operands, as the generation calls launch it
+ * over `rows` <= 256 rows, row r being sequence r in state c->state[r].  offsets / bytes: the vocabulary
+ * of V tokens, as rwkv_mi355x_vocab_bytes takes it.  c->ended (may be NULL) marks on entry the rows that
+ * are already finished (nonzero: the row is skipped, its masked row untouched) and holds 2 on return for
+ * a live row with no allowed token.  stop [n_stop <= 16]: the stop tokens.  masked [rows][V] is uploaded
+ * first and downloaded after; n_allowed [rows] counts from 0. */
+RWKV_API bool rwkv_mi355x_selftest_dfa_mask(const float * logits, int rows, int V, const uint32_t * offsets,
+                                            const uint8_t * bytes, const struct rwkv_mi355x_constraint * c,
+                                            const uint32_t * stop, int n_stop, float * masked, uint32_t * n_allowed);
+/* k_dfa_advance on host operands: states [rows <= 256] (each < n_states) walk tokens [rows] (each < V). */
+RWKV_API bool rwkv_mi355x_selftest_dfa_advance(uint32_t * states, const uint32_t * tokens, int rows, int V,
+                                               const uint32_t * offsets, const uint8_t * bytes, uint32_t n_states,
+                                               const uint16_t * next /* [n_states][256] */);
 
 /* The turnover kernel of rwkv_mi355x_generate_queue (k_gen_turnover) on host operands, as before step
  * `step`: lane_seq [lanes] (a sequence id < Q or 0xFFFFFFFF: idle), done / lane / start [Q], *next

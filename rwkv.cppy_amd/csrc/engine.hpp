@@ -53,6 +53,9 @@ struct DeviceModel {
     double head_weight_bytes = 0;
     double layer_flops = 0, head_flops = 0;  // 2*M*K per token
     double small_param_bytes = 0;    // fp32 vectors read per token
+    // the tokens' bytes (rwkv_mi355x_vocab_bytes; dfa_pack_vocab's layout), shared by the clones
+    DevBuf<uint8_t> vocab_head, vocab_tail;
+    DevBuf<uint32_t> vocab_meta;
 };
 
 bool upload_model(const ModelFile & mf, DeviceModel & dm, uint32_t layer_begin = 0, uint32_t layer_end = UINT32_MAX);
@@ -233,6 +236,16 @@ struct FilterParams {
     const float *min_p = nullptr, *typical_p = nullptr;
 };
 
+// rwkv_mi355x_constraint (include/rwkv_mi355x.h): one table for all rows, a start state per row or
+// sequence.  Engine::constraint_reserve checks it.
+struct ConstraintParams {
+    uint32_t n_states = 0;
+    const uint16_t * next = nullptr;
+    const uint8_t * accepting = nullptr;
+    uint32_t * state = nullptr;
+    uint32_t * ended = nullptr;
+};
+
 class Engine : public KLaunchTimer, private Workspace, private GenSlots {
   public:
     explicit Engine(DeviceModel * m) : m_(m) {}
@@ -260,10 +273,24 @@ class Engine : public KLaunchTimer, private Workspace, private GenSlots {
     // f != NULL with some filter on in some row (all four calls): the sampler launches are those of
     // sample_filter.hip, the per-sequence values uploaded beside the other per-sequence parameters.
     // f == NULL, or every value off: the call as it was.
+    // c != NULL (all four calls; constraint_reserve(c, ...) has passed): k_dfa_mask in front of every
+    // k_logprobs / sampler launch, which read its masked rows, and k_dfa_advance behind the sampler
+    // (constrain.hip).  A row with no allowed token ends before its draw.  sample and
+    // generate then run the sampler's rows form over one row (the same arithmetic): a finished row
+    // needs its done word.  c == NULL: the call as it was.
     bool sample(const SamplingParams & p, uint32_t * token_out, const LogprobsOut * lp = nullptr,
-                const FilterParams * f = nullptr);
+                const FilterParams * f = nullptr, const ConstraintParams * c = nullptr);
     bool generate(const SamplingParams & p, size_t n, uint32_t * tokens_out, float * logits_out,
-                  const LogprobsOut * lp = nullptr, const FilterParams * f = nullptr);
+                  const LogprobsOut * lp = nullptr, const FilterParams * f = nullptr,
+                  const ConstraintParams * c = nullptr);
+    // The vocabulary's bytes to the model (shared by its clones).  0: done, 1: offsets decrease, 2: allocation
+    int vocab_bytes(const uint32_t * offsets, const uint8_t * bytes);
+    // The checks and the allocations of a constrained call over Q sequences in `rows` rows, before
+    // anything is enqueued: the table is compressed (dfa_compress) and kept for the call that follows.
+    // 0: passed; 1: the arguments (no vocabulary bytes, a bad entry or start state, a table over
+    // dfa_lds_limit); 2: an allocation failed
+    int constraint_reserve(const ConstraintParams & c, size_t Q, size_t rows);
+    size_t constraint_lds_limit() const { return dfa_lds_limit(m_->device); }
     // The device arrays of a call with log-probabilities: rows * n columns of 8 + 12 top_k bytes and one
     // logZ word per row, grown here and never inside a loop.  Enqueues nothing; the callers of the four
     // calls run it first, so that a failed allocation fails the call before anything else happens.
@@ -297,7 +324,8 @@ class Engine : public KLaunchTimer, private Workspace, private GenSlots {
     bool batch_store(size_t slot);
     bool batch_load(size_t slot);
     bool generate_batch(size_t B, const BatchSamplingParams & p, size_t n, uint32_t * tokens_out, uint32_t * lengths_out,
-                        uint32_t * steps_out, const LogprobsOut * lp = nullptr, const FilterParams * f = nullptr);
+                        uint32_t * steps_out, const LogprobsOut * lp = nullptr, const FilterParams * f = nullptr,
+                        const ConstraintParams * c = nullptr);
     // A queue of Q sequences (slots [0, Q)) over L = min(lanes, Q) decode rows
     // (rwkv_mi355x_generate_queue): per step k_gen_turnover frees the lanes of ended
     // sequences and admits the waiting ones, k_gen_move copies a capped sequence's result out of its
@@ -305,7 +333,8 @@ class Engine : public KLaunchTimer, private Workspace, private GenSlots {
     // lanes as in generate_batch.  Every per-row array of p is [Q]; max_tokens[s] in [1, n].
     bool generate_queue(size_t Q, size_t lanes, const BatchSamplingParams & p, const uint32_t * max_tokens, size_t n,
                         uint32_t * tokens_out, uint32_t * lengths_out, uint32_t * lane_out, uint32_t * start_out,
-                        uint32_t * steps_out, const LogprobsOut * lp = nullptr, const FilterParams * f = nullptr);
+                        uint32_t * steps_out, const LogprobsOut * lp = nullptr, const FilterParams * f = nullptr,
+                        const ConstraintParams * c = nullptr);
     // Batched prefill (rwkv_mi355x_prefill_batch; engine_prefill.hip): n_rows prompts, concatenated in
     // tokens, are packed into chunks of at most prefill_chunk_ tokens (prefill_plan.hpp) and each chunk
     // runs as one sequence pass whose token shift and WKV kernels follow a segment table (SegTab);
@@ -468,6 +497,18 @@ class Engine : public KLaunchTimer, private Workspace, private GenSlots {
     // they are sf's scalars.  Nothing on in any row leaves sf unset: launch_sample then runs what it
     // runs without filters.
     bool filters_begin(const FilterParams * f, size_t rows, bool upload, SampleFilters & sf);
+    // The start of a constrained call, in stream order: table, accepting and the Q start states up,
+    // ended / counts / ticket cleared; d is filled for `rows` rows except for what belongs to the
+    // sampler's words.  dfa_copy_out: state and ended to the caller (before the call's synchronise).
+    bool dfa_begin(const ConstraintParams & c, size_t Q, size_t rows, DfaArgs & d);
+    bool dfa_copy_out(const ConstraintParams & c, size_t Q);
+    DfaTable dfa_tab_;           // the table of the call being made (constraint_reserve)
+    DevBuf<uint8_t> dfa_blob_, dfa_accept_;
+    DevBuf<float> dfa_masked_;   // [rows][V]
+    DevBuf<float> dfa_snap_;     // generate: state_len + V floats (DfaSnap)
+    // state, ended, n_allowed [kBatchMax] each; then ticket, and sample / generate's done and fin_step
+    DevBuf<uint32_t> dfa_words_;
+    std::vector<uint32_t> dfa_h_;
     DevBuf<float> dstate_[2];
     int cur_ = 0;
     unsigned * herr_h_ = nullptr;  // hand-off timeout flag, host-mapped (herr_d_ = its device address)
@@ -581,7 +622,8 @@ class Engine : public KLaunchTimer, private Workspace, private GenSlots {
         uint32_t *lane_out, *start_out;
     };
     bool generate_slots(size_t Q, const BatchSamplingParams & p, size_t n, uint32_t * tokens_out, uint32_t * lengths_out,
-                        uint32_t * steps_out, const LogprobsOut * lp, const FilterParams * f, const QueueCall * qc);
+                        uint32_t * steps_out, const LogprobsOut * lp, const FilterParams * f, const ConstraintParams * c,
+                        const QueueCall * qc);
     // the per-sequence arrays of Q sequences to the device and the token buffer [Q][n] set to
     // 0xFFFFFFFF; the sampler's arguments for `rows` rows
     bool gen_upload(size_t Q, const BatchSamplingParams & p, size_t n);

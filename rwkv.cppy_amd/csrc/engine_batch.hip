@@ -210,15 +210,16 @@ SampleArgs Engine::gen_sample_args(size_t rows, const BatchSamplingParams & p, s
 }
 
 bool Engine::generate_batch(size_t B, const BatchSamplingParams & p, size_t n, uint32_t * tokens_out,
-                            uint32_t * lengths_out, uint32_t * steps_out, const LogprobsOut * lp, const FilterParams * f) {
-    return generate_slots(B, p, n, tokens_out, lengths_out, steps_out, lp, f, nullptr);
+                            uint32_t * lengths_out, uint32_t * steps_out, const LogprobsOut * lp, const FilterParams * f,
+                            const ConstraintParams * c) {
+    return generate_slots(B, p, n, tokens_out, lengths_out, steps_out, lp, f, c, nullptr);
 }
 
 bool Engine::generate_queue(size_t Q, size_t lanes, const BatchSamplingParams & p, const uint32_t * max_tokens, size_t n,
                             uint32_t * tokens_out, uint32_t * lengths_out, uint32_t * lane_out, uint32_t * start_out,
-                            uint32_t * steps_out, const LogprobsOut * lp, const FilterParams * f) {
+                            uint32_t * steps_out, const LogprobsOut * lp, const FilterParams * f, const ConstraintParams * c) {
     const QueueCall qc{lanes, max_tokens, lane_out, start_out};
-    return generate_slots(Q, p, n, tokens_out, lengths_out, steps_out, lp, f, &qc);
+    return generate_slots(Q, p, n, tokens_out, lengths_out, steps_out, lp, f, c, &qc);
 }
 
 // The driver of both calls.  Per step one sampler launch over the rows' logits (per-sequence
@@ -234,8 +235,13 @@ bool Engine::generate_queue(size_t Q, size_t lanes, const BatchSamplingParams & 
 // lanes writes rows [0, L) of the state buffers and of glogits_ only), runs in a lane, and ends in its
 // snapshot (row s of gsnap_*), taken by k_gen_snapshot at a stop and by k_gen_move at its cap.
 // done[s] == 1 from then on, so the restore needs no table.  What the queue adds is under `qc`.
+// A constraint (c): k_dfa_mask in front of k_logprobs and the sampler, which read its masked rows in
+// place of glogits_, and k_dfa_advance behind the sampler.  A row with no allowed token is finished by
+// the mask as a stop token finishes one, at this step: the snapshot that follows takes the state and
+// the (unmasked) logits the previous step left.
 bool Engine::generate_slots(size_t Q, const BatchSamplingParams & p, size_t n, uint32_t * tokens_out, uint32_t * lengths_out,
-                            uint32_t * steps_out, const LogprobsOut * lp, const FilterParams * f, const QueueCall * qc) {
+                            uint32_t * steps_out, const LogprobsOut * lp, const FilterParams * f, const ConstraintParams * c,
+                            const QueueCall * qc) {
     HIP_OK(hipSetDevice(m_->device));
     // ---- the arguments; the per-sequence values of p are the caller's to check (BatchSamplingParams)
     if (Q == 0 || Q > gslots_ || n == 0 || !tokens_out || !lengths_out || !p.temperature || !p.top_p || !p.seed ||
@@ -285,6 +291,16 @@ bool Engine::generate_slots(size_t Q, const BatchSamplingParams & p, size_t n, u
     }
     ok = ok && lp_begin(lp, Q, n, a) &&
          launch_gen_begin(stream_, (int)Q, p.keep_counts ? 1 : 0, a.done, a.length, a.fin_step, a.active);
+    DfaArgs d{};
+    if (c) {
+        ok = ok && dfa_begin(*c, Q, rows, d);
+        d.logits = a.logits;
+        a.logits = d.masked;
+        d.tokens = a.tok2;
+        d.lane_seq = a.lane_seq, d.done = a.done, d.fin_step = a.fin_step, d.active = a.active;
+        d.n_stop = a.n_stop;
+        memcpy(d.stop, a.stop, sizeof(d.stop));
+    }
     if (!ok) return fail();
     const GenRows g{(int)rows, S, V, a.done, a.fin_step, a.lane_seq};
     // the queue's turnover and move in front of step `step`, on the live rows that step reads
@@ -304,8 +320,10 @@ bool Engine::generate_slots(size_t Q, const BatchSamplingParams & p, size_t n, u
         a.step = (uint32_t)i;
         {
             const LaunchTimerScope timed(this, timing_);
-            ok = (!qc || turnover(i, cur)) && (!lp || launch_logprobs(stream_, a)) && launch_sample(stream_, a, &sf) &&
-                 launch_gen_snapshot(stream_, g, (uint32_t)i, cur, glogits_, gsnap_state_, gsnap_logits_);
+            d.step = (uint32_t)i;
+            ok = (!qc || turnover(i, cur)) && (!c || launch_dfa_mask(stream_, d, constraint_lds_limit())) &&
+                 (!lp || launch_logprobs(stream_, a)) && launch_sample(stream_, a, &sf) &&
+                 (!c || launch_dfa_advance(stream_, d)) && launch_gen_snapshot(stream_, g, (uint32_t)i, cur, glogits_, gsnap_state_, gsnap_logits_);
         }
         ok = ok && eval_batch(nullptr, rows, cur, gstate_[(steps & 1) ^ 1], glogits_, true);
         if (!ok) return fail();
@@ -335,7 +353,7 @@ bool Engine::generate_slots(size_t Q, const BatchSamplingParams & p, size_t n, u
                  hipSuccess &&
              hipMemcpyAsync(start_h, gw_.start, Q * 4, hipMemcpyDeviceToHost, stream_) == hipSuccess;
     }
-    ok = ok && lp_copy_out(lp, Q, n);
+    ok = ok && lp_copy_out(lp, Q, n) && (!c || dfa_copy_out(*c, Q));
     if (!ok || hipStreamSynchronize(stream_) != hipSuccess || !handoff_check()) return fail();
     size_t used = steps;
     if (qc) {

@@ -109,15 +109,98 @@ bool Engine::filters_begin(const FilterParams * f, size_t rows, bool upload, Sam
     return true;
 }
 
-bool Engine::sample(const SamplingParams & p, uint32_t * token_out, const LogprobsOut * lp, const FilterParams * f) {
+int Engine::vocab_bytes(const uint32_t * offsets, const uint8_t * bytes) {
+    if (hipSetDevice(m_->device) != hipSuccess) return 2;
+    std::vector<uint8_t> head, tail;
+    std::vector<uint32_t> meta;
+    if (!dfa_pack_vocab(offsets, bytes, m_->n_vocab, head, meta, tail)) return 1;
+    // queued work of this context may still read the old copy
+    if (hipStreamSynchronize(stream_) != hipSuccess) return 2;
+    DevBuf<uint8_t> dh, dt;
+    DevBuf<uint32_t> dm;
+    if (!dh.alloc(head.size()) || !dt.alloc(tail.size()) || !dm.alloc(meta.size())) return 2;
+    if (hipMemcpy(dh, head.data(), head.size(), hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemcpy(dm, meta.data(), meta.size() * 4, hipMemcpyHostToDevice) != hipSuccess ||
+        (!tail.empty() && hipMemcpy(dt, tail.data(), tail.size(), hipMemcpyHostToDevice) != hipSuccess))
+        return 2;
+    m_->vocab_head = std::move(dh);
+    m_->vocab_tail = std::move(dt);
+    m_->vocab_meta = std::move(dm);
+    return 0;
+}
+
+int Engine::constraint_reserve(const ConstraintParams & c, size_t Q, size_t rows) {
+    if (hipSetDevice(m_->device) != hipSuccess) return 2;
+    const size_t K = (size_t)kBatchMax, V = m_->n_vocab;
+    if (!m_->vocab_head.get() || !c.next || !c.accepting || !c.state || Q == 0 || Q > K || rows == 0 || rows > Q) return 1;
+    if (!dfa_compress(c.next, c.n_states, dfa_tab_)) return 1;
+    for (size_t s = 0; s < Q; s++)
+        if (c.state[s] >= c.n_states) return 1;
+    if (dfa_lds_bytes(dfa_tab_.n_states, dfa_tab_.n_cls) > constraint_lds_limit()) return 1;
+    const size_t blob = dfa_tab_.blob.size(), tile = rows * V;
+    if (!grow(dfa_blob_, blob, doubled(4096, blob), GRAPHS_NONE) ||
+        !grow(dfa_accept_, c.n_states, doubled(256, c.n_states), GRAPHS_NONE) ||
+        !grow(dfa_masked_, tile, doubled(V, tile), GRAPHS_NONE) || !grow(dfa_words_, 3 * K + 3, 3 * K + 3, GRAPHS_NONE) ||
+        !grow(dfa_snap_, m_->state_len + V, m_->state_len + V, GRAPHS_NONE))
+        return 2;
+    return 0;
+}
+
+bool Engine::dfa_begin(const ConstraintParams & c, size_t Q, size_t rows, DfaArgs & d) {
+    const size_t K = (size_t)kBatchMax;
+    if (dfa_tab_.n_states != c.n_states || dfa_tab_.blob.empty() || dfa_masked_.size() < rows * m_->n_vocab) return false;
+    dfa_h_.assign(3 * K + 3, 0);
+    for (size_t s = 0; s < Q; s++) dfa_h_[s] = c.state[s];
+    HIP_OK(hipMemcpyAsync(dfa_blob_, dfa_tab_.blob.data(), dfa_tab_.blob.size(), hipMemcpyHostToDevice, stream_));
+    HIP_OK(hipMemcpyAsync(dfa_accept_, c.accepting, c.n_states, hipMemcpyHostToDevice, stream_));
+    HIP_OK(hipMemcpyAsync(dfa_words_, dfa_h_.data(), (3 * K + 3) * 4, hipMemcpyHostToDevice, stream_));
+    memset(&d, 0, sizeof(d));
+    d.head = (const uint4 *)m_->vocab_head.get();
+    d.meta = (const uint2 *)m_->vocab_meta.get();
+    d.tail = m_->vocab_tail;
+    d.V = (int)m_->n_vocab;
+    d.tab = (const uint16_t *)dfa_blob_.get();
+    d.accepting = dfa_accept_;
+    d.n_states = dfa_tab_.n_states;
+    d.n_cls = dfa_tab_.n_cls;
+    d.rows = (int)rows;
+    d.masked = dfa_masked_;
+    d.state = dfa_words_;
+    d.ended = dfa_words_ + K;
+    d.n_allowed = dfa_words_ + 2 * K;
+    d.ticket = dfa_words_ + 3 * K;
+    return true;
+}
+
+bool Engine::dfa_copy_out(const ConstraintParams & c, size_t Q) {
+    const size_t K = (size_t)kBatchMax;
+    HIP_OK(hipMemcpyAsync(c.state, dfa_words_, Q * 4, hipMemcpyDeviceToHost, stream_));
+    if (c.ended) HIP_OK(hipMemcpyAsync(c.ended, dfa_words_ + K, Q * 4, hipMemcpyDeviceToHost, stream_));
+    return true;
+}
+
+bool Engine::sample(const SamplingParams & p, uint32_t * token_out, const LogprobsOut * lp, const FilterParams * f,
+                    const ConstraintParams * c) {
     HIP_OK(hipSetDevice(m_->device));
     if (!logits_valid_ || !token_out) return false;
     SampleArgs a;
     SampleFilters sf;
+    DfaArgs d{};
     if (lp && !lp_reserve(1, 1, lp->top_k)) return false;
     if (!sampler_buffers(p, 1, a) || !filters_begin(f, 1, false, sf) || !lp_begin(lp, 1, 1, a)) return false;
+    if (c) {
+        // no draw (no token allowed): the token stays 0xFFFFFFFF
+        if (!dfa_begin(*c, 1, 1, d) || hipMemsetAsync(gen_tokens_, 0xff, 4, stream_) != hipSuccess) return false;
+        d.logits = a.logits;
+        d.done = a.done = dfa_words_ + 3 * (size_t)kBatchMax + 1;
+        d.fin_step = a.fin_step = d.done + 1;
+        d.tokens = a.tok;
+        a.logits = d.masked;
+        if (!launch_dfa_mask(stream_, d, constraint_lds_limit())) return false;
+    }
     if (lp && !launch_logprobs(stream_, a)) return false;
     if (!launch_sample(stream_, a, &sf)) return false;
+    if (c && !(launch_dfa_advance(stream_, d) && dfa_copy_out(*c, 1))) return false;
     HIP_OK(hipMemcpyAsync(token_out, gen_tokens_, 4, hipMemcpyDeviceToHost, stream_));
     if (!lp_copy_out(lp, 1, 1)) return false;
     HIP_OK(hipStreamSynchronize(stream_));
@@ -125,7 +208,7 @@ bool Engine::sample(const SamplingParams & p, uint32_t * token_out, const Logpro
 }
 
 bool Engine::generate(const SamplingParams & p, size_t n, uint32_t * tokens_out, float * logits_out,
-                      const LogprobsOut * lp, const FilterParams * f) {
+                      const LogprobsOut * lp, const FilterParams * f, const ConstraintParams * c) {
     HIP_OK(hipSetDevice(m_->device));
     if (!logits_valid_ || !tokens_out || n == 0) return false;
     SampleArgs a;
@@ -138,6 +221,19 @@ bool Engine::generate(const SamplingParams & p, size_t n, uint32_t * tokens_out,
     co_retry_ = false;
     bool ok = lp_begin(lp, 1, n, a);
     const size_t K = lp ? lp->top_k : 0;
+    DfaArgs d{};
+    DfaSnap snap{};
+    const float * const lg = a.logits;
+    if (c) {
+        // a draw that does not happen (no token allowed) leaves 0xFFFFFFFF, as do the draws after it
+        ok = ok && dfa_begin(*c, 1, 1, d) && hipMemsetAsync(gen_tokens_, 0xff, n * 4, stream_) == hipSuccess;
+        d.logits = lg;
+        d.done = a.done = dfa_words_ + 3 * (size_t)kBatchMax + 1;
+        d.fin_step = a.fin_step = d.done + 1;
+        d.tokens = dtokens_;
+        a.logits = d.masked;
+        snap = DfaSnap{nullptr, lg, dfa_snap_, dfa_snap_ + m_->state_len, m_->state_len};
+    }
     for (size_t i = 0; ok && i < n; i++) {
         // the counter is a kernel argument of an eager launch between the decode graphs' replays:
         // nothing per step is baked into a captured node
@@ -151,9 +247,25 @@ bool Engine::generate(const SamplingParams & p, size_t n, uint32_t * tokens_out,
         }
         {
             const LaunchTimerScope timed(this, timing_);
-            ok = (!lp || launch_logprobs(stream_, a)) && launch_sample(stream_, a, &sf);
+            if (c) {
+                a.step = d.step = (uint32_t)i;
+                snap.state_from = dstate_[cur_];
+                ok = launch_dfa_mask(stream_, d, constraint_lds_limit());
+            }
+            ok = ok && (!lp || launch_logprobs(stream_, a)) && launch_sample(stream_, a, &sf) &&
+                 (!c || launch_dfa_advance(stream_, d, &snap));
         }
         ok = ok && run_tokens(nullptr, 1, true);
+    }
+    if (ok && c) {
+        // a sequence that ended without a draw: the state and logits it ended with come back
+        uint32_t ended = 0;
+        ok = dfa_copy_out(*c, 1) &&
+             hipMemcpyAsync(&ended, d.ended, 4, hipMemcpyDeviceToHost, stream_) == hipSuccess &&
+             hipStreamSynchronize(stream_) == hipSuccess;
+        if (ok && ended == 2u)
+            ok = hipMemcpyAsync(dstate_[cur_], snap.state_to, m_->state_len * 4, hipMemcpyDeviceToDevice, stream_) == hipSuccess &&
+                 hipMemcpyAsync(logits_, snap.logits_to, (size_t)m_->n_vocab * 4, hipMemcpyDeviceToDevice, stream_) == hipSuccess;
     }
     if (ok) {
         ok = hipMemcpyAsync(tokens_out, gen_tokens_, n * 4, hipMemcpyDeviceToHost, stream_) == hipSuccess;

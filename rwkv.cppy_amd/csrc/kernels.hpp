@@ -1,6 +1,8 @@
 // kernels.hpp -- host launchers for the gfx950 kernels (kernels.hip, wkv_serial.hip).
 #pragma once
 
+#include <vector>
+
 #include "common.hpp"
 
 namespace rwkvmi {
@@ -288,6 +290,66 @@ bool launch_sample_filtered(hipStream_t st, const SampleArgs & a, const SampleFi
 // One workgroup per row (logprobs.hip): logZ and the leading lp_k elements of the row the sampler is
 // about to draw from.  A row the sampler skips (finished, idle) writes nothing.  Needs lp_logz.
 bool launch_logprobs(hipStream_t st, const SampleArgs & a);
+
+// ---- byte-DFA token masks (constrain.hip; rwkv_mi355x_constraint) --------------------
+constexpr int DFA_THREADS = 256;  // tokens of a k_dfa_mask workgroup: 256 workgroups at V = 65536
+// A constraint's table as the kernels read it: byte columns that are equal in every state are one
+// class.  blob = uint16 tab[n_states][n_cls], padded to 16 bytes, then uint8 cls[256].
+struct DfaTable {
+    uint32_t n_states = 0, n_cls = 0;
+    uint8_t cls[256];
+    std::vector<uint8_t> blob;
+};
+// false: n_states == 0 or >= 0xFFFF, or an entry that is neither < n_states nor 0xFFFF (dead)
+bool dfa_compress(const uint16_t * next /* [n_states][256] */, uint32_t n_states, DfaTable & out);
+// The LDS k_dfa_mask takes for a table (blob + 16 bytes of its own) and what a workgroup may take on
+// `device` (the device attribute; 0: the query failed).  A table over the limit is not launched.
+size_t dfa_lds_bytes(uint32_t n_states, uint32_t n_cls);
+size_t dfa_lds_limit(int device);
+// The vocabulary as the kernels read it: head [V][16] (a token's first 16 bytes, zero padded, one
+// aligned vector), meta [V][2] (its length, the offset of its byte 16 in tail), tail (the bytes from
+// 16 on of the longer tokens, concatenated).  false: offsets decrease somewhere.
+bool dfa_pack_vocab(const uint32_t * offsets, const uint8_t * bytes, size_t V, std::vector<uint8_t> & head,
+                    std::vector<uint32_t> & meta, std::vector<uint8_t> & tail);
+struct DfaArgs {
+    const uint4 * head;          // the vocabulary (dfa_pack_vocab), device
+    const uint2 * meta;
+    const uint8_t * tail;
+    int V;
+    const uint16_t * tab;        // DfaTable::blob, device (16-byte aligned)
+    const uint8_t * accepting;   // [n_states]
+    uint32_t n_states, n_cls;
+    int rows;
+    const float * logits;        // [rows][V]
+    float * masked;              // [rows][V]: l' of the live rows
+    uint32_t * state;            // [sequences]: the DFA state, < n_states
+    uint32_t * n_allowed;        // [rows]: 0 before k_dfa_mask, the row's allowed tokens after it
+    uint32_t * ticket;           // one word, 0 between launches; NULL: the mask alone, no row is finished
+    uint32_t * ended;            // [sequences], optional: 1 a stop token, 2 no token was allowed
+    const uint32_t * tokens;     // k_dfa_advance: the token row r drew (the sampler's tok2, or tok)
+    // the sampler's words, indexed as SampleArgs indexes them; a row with done set or an idle lane is skipped
+    const uint32_t * lane_seq;
+    uint32_t * done;
+    uint32_t * fin_step;
+    uint32_t * active;
+    uint32_t step;
+    int n_stop;                  // a stop token is allowed iff accepting[state], whatever its bytes
+    uint32_t stop[16];
+};
+// rows == 1 without slots (rwkv_mi355x_generate): where the state and logits of a row that ended
+// without a draw at this step are kept while the loop decodes on
+struct DfaSnap {
+    const float * state_from;
+    const float * logits_from;   // [V]
+    float * state_to;
+    float * logits_to;
+    size_t state_len;
+};
+// masked[r][t] = allowed ? logits[r][t] : -inf for every live row, n_allowed[r] += the allowed tokens,
+// and (ticket set) a live row with none is finished: done = 1, fin_step = step, *active -= 1, ended = 2.
+bool launch_dfa_mask(hipStream_t st, const DfaArgs & a, size_t lds_limit);
+// Behind the sampler: n_allowed = 0; a live row's state walks tokens[r]; a row stopped at `step`: ended = 1.
+bool launch_dfa_advance(hipStream_t st, const DfaArgs & a, const DfaSnap * snap = nullptr);
 
 // Batched generation (Engine::generate_batch; sample.hip).  Row r of a [rows][n] buffer is at r * n.
 struct GenRows {

@@ -948,6 +948,136 @@ RWKV_API bool rwkv_mi355x_generate_queue_filtered(struct rwkv_context * ctx, siz
     return true;
 }
 
+// ---- the four calls with a constraint: each is its _filtered sibling, check for check, plus constraint_ok
+RWKV_API bool rwkv_mi355x_vocab_bytes(struct rwkv_context * ctx, const uint32_t * offsets, const uint8_t * bytes) {
+    if (!ctx || !ctx->engine) return false;
+    ctx->last_error = RWKV_ERROR_NONE;
+    CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, offsets != nullptr, "NULL offsets");
+    std::lock_guard<std::mutex> lock(g_model_mutex);
+    const int e = ctx->engine->vocab_bytes(offsets, bytes);
+    CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, e != 1, "Token offsets must not decrease (and bytes must not be NULL)");
+    CTX_CHECK(ctx, RWKV_ERROR_CTX | RWKV_ERROR_ALLOC, false, e == 0, "Vocabulary upload failed");
+    return true;
+}
+
+// The checks and allocations of a rwkv_mi355x_constraint over Q sequences in `rows` rows, before anything is enqueued
+static bool constraint_ok(struct rwkv_context * ctx, const struct rwkv_mi355x_constraint * c, size_t Q, size_t rows,
+                          ConstraintParams & out) {
+    CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, c->n_states > 0 && c->next && c->accepting && c->state,
+              "A constraint needs n_states >= 1, next, accepting and state");
+    out.n_states = c->n_states;
+    out.next = c->next;
+    out.accepting = c->accepting;
+    out.state = c->state;
+    out.ended = c->ended;
+    use_device(ctx);
+    const int e = ctx->engine->constraint_reserve(out, Q, rows);
+    CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, e != 1,
+              "Constraint rejected: no vocabulary bytes set, a next entry or start state >= n_states, or a table over the "
+              "LDS limit (%zu bytes)", ctx->engine->constraint_lds_limit());
+    CTX_CHECK(ctx, RWKV_ERROR_CTX | RWKV_ERROR_ALLOC, false, e == 0, "Constraint buffer allocation failed");
+    return true;
+}
+static const FilterParams * filters_of(const struct rwkv_mi355x_filters * f, const FilterParams & fp) { return f ? &fp : nullptr; }
+
+RWKV_API bool rwkv_mi355x_sample_constrained(struct rwkv_context * ctx, const struct rwkv_mi355x_sampling * params,
+                                             uint32_t * token_out, const struct rwkv_mi355x_logprobs * lp,
+                                             const struct rwkv_mi355x_filters * f, const struct rwkv_mi355x_constraint * c) {
+    if (!c) return rwkv_mi355x_sample_filtered(ctx, params, token_out, lp, f);
+    if (!ctx || !ctx->engine) return false;
+    ctx->last_error = RWKV_ERROR_NONE;
+    SamplingParams sp;
+    LogprobsOut lo;
+    FilterParams fp;
+    ConstraintParams cp;
+    if (!logprobs_ok(ctx, lp, lo) || !sampling_ok(ctx, params, sp) || (f && !filters_ok(ctx, f, 1, fp))) return false;
+    CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, token_out != nullptr, "NULL token_out");
+    if (!constraint_ok(ctx, c, 1, 1, cp) || !logprobs_reserve(ctx, lp, 1, 1)) return false;
+    use_device(ctx);
+    CTX_CHECK(ctx, RWKV_ERROR_CTX, false, ctx->engine->sample(sp, token_out, lp ? &lo : nullptr, filters_of(f, fp), &cp),
+              "GPU sampling failed");
+    return true;
+}
+
+RWKV_API bool rwkv_mi355x_generate_constrained(struct rwkv_context * ctx, const struct rwkv_mi355x_sampling * params,
+                                               size_t n, uint32_t * tokens_out, float * logits_out,
+                                               const struct rwkv_mi355x_logprobs * lp, const struct rwkv_mi355x_filters * f,
+                                               const struct rwkv_mi355x_constraint * c) {
+    if (!c) return rwkv_mi355x_generate_filtered(ctx, params, n, tokens_out, logits_out, lp, f);
+    if (!ctx || !ctx->engine) return false;
+    ctx->last_error = RWKV_ERROR_NONE;
+    SamplingParams sp;
+    LogprobsOut lo;
+    FilterParams fp;
+    ConstraintParams cp;
+    if (!logprobs_ok(ctx, lp, lo) || !sampling_ok(ctx, params, sp) || (f && !filters_ok(ctx, f, 1, fp))) return false;
+    CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, n > 0 && n <= 65536, "Token count %zu is outside [1, 65536]", n);
+    CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, tokens_out != nullptr, "NULL tokens_out");
+    if (!constraint_ok(ctx, c, 1, 1, cp) || !logprobs_reserve(ctx, lp, 1, n)) return false;
+    use_device(ctx);
+    CTX_CHECK(ctx, RWKV_ERROR_CTX, false,
+              ctx->engine->generate(sp, n, tokens_out, logits_out, lp ? &lo : nullptr, filters_of(f, fp), &cp),
+              "GPU generation failed");
+    return true;
+}
+
+RWKV_API bool rwkv_mi355x_generate_batch_constrained(struct rwkv_context * ctx, size_t B,
+                                                     const struct rwkv_mi355x_batch_sampling * p, size_t n,
+                                                     uint32_t * tokens_out, uint32_t * lengths_out, uint32_t * steps_out,
+                                                     const struct rwkv_mi355x_logprobs * lp,
+                                                     const struct rwkv_mi355x_filters * f,
+                                                     const struct rwkv_mi355x_constraint * c) {
+    if (!c) return rwkv_mi355x_generate_batch_filtered(ctx, B, p, n, tokens_out, lengths_out, steps_out, lp, f);
+    if (!ctx || !ctx->engine) return false;
+    ctx->last_error = RWKV_ERROR_NONE;
+    LogprobsOut lo;
+    BatchSamplingParams bp;
+    FilterParams fp;
+    ConstraintParams cp;
+    if (!batch_call_ok(ctx, lp, lo, B, B, n, tokens_out, lengths_out) || !batch_sampling_ok(ctx, B, p, bp) ||
+        (f && !filters_ok(ctx, f, B, fp)) || !constraint_ok(ctx, c, B, B, cp))
+        return false;
+    if (!logprobs_reserve(ctx, lp, B, n)) return false;
+    use_device(ctx);
+    CTX_CHECK(ctx, RWKV_ERROR_CTX, false,
+              ctx->engine->generate_batch(B, bp, n, tokens_out, lengths_out, steps_out, lp ? &lo : nullptr, filters_of(f, fp), &cp),
+              "GPU batched generation failed");
+    return true;
+}
+
+RWKV_API bool rwkv_mi355x_generate_queue_constrained(struct rwkv_context * ctx, size_t Q, size_t lanes,
+                                                     const struct rwkv_mi355x_batch_sampling * p,
+                                                     const uint32_t * max_tokens, size_t n, uint32_t * tokens_out,
+                                                     uint32_t * lengths_out, uint32_t * lane_out, uint32_t * start_out,
+                                                     uint32_t * steps_out, const struct rwkv_mi355x_logprobs * lp,
+                                                     const struct rwkv_mi355x_filters * f,
+                                                     const struct rwkv_mi355x_constraint * c) {
+    if (!c)
+        return rwkv_mi355x_generate_queue_filtered(ctx, Q, lanes, p, max_tokens, n, tokens_out, lengths_out, lane_out,
+                                                   start_out, steps_out, lp, f);
+    if (!ctx || !ctx->engine) return false;
+    ctx->last_error = RWKV_ERROR_NONE;
+    LogprobsOut lo;
+    BatchSamplingParams bp;
+    FilterParams fp;
+    ConstraintParams cp;
+    if (!batch_call_ok(ctx, lp, lo, Q, lanes, n, tokens_out, lengths_out)) return false;
+    CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, max_tokens != nullptr, "NULL max_tokens");
+    for (size_t s = 0; s < Q; s++)
+        CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, max_tokens[s] > 0 && max_tokens[s] <= n, "Sequence %zu: max_tokens %" PRIu32 " is outside [1, %zu]",
+                  s, max_tokens[s], n);
+    if (!batch_sampling_ok(ctx, Q, p, bp) || (f && !filters_ok(ctx, f, Q, fp))) return false;
+    CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, !bp.keep_counts,
+              "keep_counts is not supported by the queue (continue a capped sequence with rwkv_mi355x_generate_batch)");
+    if (!constraint_ok(ctx, c, Q, std::min(lanes, Q), cp) || !logprobs_reserve(ctx, lp, Q, n)) return false;
+    use_device(ctx);
+    CTX_CHECK(ctx, RWKV_ERROR_CTX, false,
+              ctx->engine->generate_queue(Q, lanes, bp, max_tokens, n, tokens_out, lengths_out, lane_out, start_out, steps_out,
+                                          lp ? &lo : nullptr, filters_of(f, fp), &cp),
+              "GPU queued generation failed");
+    return true;
+}
+
 RWKV_API bool rwkv_mi355x_prefill_batch(struct rwkv_context * ctx, size_t n_rows, const uint32_t * slots,
                                         const uint32_t * tokens, const size_t * lengths, const uint8_t * cont) {
     if (!ctx || !ctx->engine) return false;

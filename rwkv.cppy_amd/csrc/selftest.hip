@@ -1024,3 +1024,105 @@ extern "C" RWKV_API bool rwkv_mi355x_selftest_wave_sums(int n, const float * p, 
     return hipMemcpy(sums, ds, 64 * 4, hipMemcpyDeviceToHost) == hipSuccess &&
            hipMemcpy(ref, dr, (size_t)slots * 4, hipMemcpyDeviceToHost) == hipSuccess;
 }
+
+// ---- byte-DFA token masks (constrain.hip) ----------------------------------------------------
+// A self-test's vocabulary and table on the device, as Engine::vocab_bytes and Engine::dfa_begin leave them
+static bool selftest_dfa_setup(DevBufs & b, int V, const uint32_t * offsets, const uint8_t * bytes, uint32_t n_states,
+                               const uint16_t * next, const uint8_t * accepting, DfaArgs & d) {
+    std::vector<uint8_t> head, tail;
+    std::vector<uint32_t> meta;
+    DfaTable tab;
+    if (V < 1 || !dfa_pack_vocab(offsets, bytes, (size_t)V, head, meta, tail) || !dfa_compress(next, n_states, tab)) return false;
+    bool ok = true;
+    auto up = [&](const void * h, size_t bytes_) -> void * {
+        void * p = b.alloc(bytes_);
+        ok = ok && p && (bytes_ == 0 || hipMemcpy(p, h, bytes_, hipMemcpyHostToDevice) == hipSuccess);
+        return p;
+    };
+    memset(&d, 0, sizeof(d));
+    d.head = (const uint4 *)up(head.data(), head.size());
+    d.meta = (const uint2 *)up(meta.data(), meta.size() * 4);
+    d.tail = (const uint8_t *)up(tail.data(), tail.size());
+    d.V = V;
+    d.tab = (const uint16_t *)up(tab.blob.data(), tab.blob.size());
+    d.accepting = (const uint8_t *)(accepting ? up(accepting, n_states) : b.alloc(n_states));
+    d.n_states = tab.n_states;
+    d.n_cls = tab.n_cls;
+    return ok;
+}
+
+extern "C" RWKV_API uint32_t rwkv_mi355x_constraint_max_entries(void) {
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess) return 0;
+    const size_t lim = dfa_lds_limit(dev), fixed = dfa_lds_bytes(0, 0);
+    return lim > fixed ? (uint32_t)((lim - fixed) / 2) : 0u;
+}
+
+// k_dfa_mask on host operands, as the generation calls launch it over `rows` rows (row r is sequence
+// r).  c->state [rows] are the rows' states; c->ended [rows] (may be NULL) marks on entry the rows
+// that are already finished (nonzero: skipped) and holds 2 on return for a live row with no allowed
+// token.  masked is uploaded first and downloaded after; n_allowed starts at 0.
+extern "C" RWKV_API bool rwkv_mi355x_selftest_dfa_mask(const float * logits, int rows, int V, const uint32_t * offsets,
+                                                      const uint8_t * bytes, const struct rwkv_mi355x_constraint * c,
+                                                      const uint32_t * stop, int n_stop, float * masked,
+                                                      uint32_t * n_allowed) {
+    if (!logits || rows < 1 || rows > 256 || !c || !c->next || !c->accepting || !c->state || !masked || !n_allowed ||
+        n_stop < 0 || n_stop > SAMPLE_MAX_STOP || (n_stop && !stop))
+        return false;
+    for (int r = 0; r < rows; r++)
+        if (c->state[r] >= c->n_states) return false;
+    DevBufs b;
+    DfaArgs d;
+    if (!selftest_dfa_setup(b, V, offsets, bytes, c->n_states, c->next, c->accepting, d)) return false;
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess) return false;
+    const size_t RB = (size_t)rows * 4, LB = (size_t)rows * V * 4;
+    std::vector<uint32_t> done(rows, 0u);
+    for (int r = 0; r < rows; r++) done[r] = c->ended && c->ended[r] != 0 ? 1u : 0u;
+    float * dl = (float *)b.alloc(LB);
+    d.masked = (float *)b.alloc(LB);
+    d.state = (uint32_t *)b.alloc(RB);
+    d.done = (uint32_t *)b.alloc(RB);
+    d.ended = (uint32_t *)b.alloc(RB);
+    d.fin_step = (uint32_t *)b.alloc(RB);
+    d.n_allowed = (uint32_t *)b.alloc(RB);  // zeroed (DevBufs)
+    d.ticket = (uint32_t *)b.alloc(4);
+    if (!dl || !d.masked || !d.state || !d.done || !d.ended || !d.fin_step || !d.n_allowed || !d.ticket) return false;
+    d.logits = dl;
+    d.rows = rows;
+    d.n_stop = n_stop;
+    for (int j = 0; j < n_stop; j++) d.stop[j] = stop[j];
+    if (hipMemcpy(dl, logits, LB, hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemcpy(d.masked, masked, LB, hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemcpy(d.state, c->state, RB, hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemcpy(d.done, done.data(), RB, hipMemcpyHostToDevice) != hipSuccess ||
+        (c->ended && hipMemcpy(d.ended, c->ended, RB, hipMemcpyHostToDevice) != hipSuccess))
+        return false;
+    if (!launch_dfa_mask(nullptr, d, dfa_lds_limit(dev)) || hipDeviceSynchronize() != hipSuccess) return false;
+    return hipMemcpy(masked, d.masked, LB, hipMemcpyDeviceToHost) == hipSuccess &&
+           hipMemcpy(n_allowed, d.n_allowed, RB, hipMemcpyDeviceToHost) == hipSuccess &&
+           (!c->ended || hipMemcpy(c->ended, d.ended, RB, hipMemcpyDeviceToHost) == hipSuccess);
+}
+
+// k_dfa_advance on host operands: states [rows] (each < n_states) walk tokens [rows] (each < V) through
+// next; a walk that dies leaves its state as it was.
+extern "C" RWKV_API bool rwkv_mi355x_selftest_dfa_advance(uint32_t * states, const uint32_t * tokens, int rows, int V,
+                                                         const uint32_t * offsets, const uint8_t * bytes,
+                                                         uint32_t n_states, const uint16_t * next) {
+    if (!states || !tokens || rows < 1 || rows > 256) return false;
+    for (int r = 0; r < rows; r++)
+        if (states[r] >= n_states || tokens[r] >= (uint32_t)V) return false;
+    DevBufs b;
+    DfaArgs d;
+    if (!selftest_dfa_setup(b, V, offsets, bytes, n_states, next, nullptr, d)) return false;
+    const size_t RB = (size_t)rows * 4;
+    d.state = (uint32_t *)b.alloc(RB);
+    uint32_t * dt = (uint32_t *)b.alloc(RB);
+    if (!d.state || !dt || hipMemcpy(d.state, states, RB, hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemcpy(dt, tokens, RB, hipMemcpyHostToDevice) != hipSuccess)
+        return false;
+    d.tokens = dt;
+    d.rows = rows;
+    if (!launch_dfa_advance(nullptr, d) || hipDeviceSynchronize() != hipSuccess) return false;
+    return hipMemcpy(states, d.state, RB, hipMemcpyDeviceToHost) == hipSuccess;
+}

@@ -30,7 +30,10 @@ def _filter_kwargs(top_k, min_p, typical_p) -> dict:
 class RWKVModel:
     def __init__(self, shared_library: 'rwkv_cpp_shared_library.RWKVSharedLibrary', model_path: str,
                  thread_count: int = max(1, multiprocessing.cpu_count() // 2), gpu_layer_count: int = 0,
-                 **kwargs) -> None:
+                 vocab_bytes=None, **kwargs) -> None:
+        """vocab_bytes: None, a sequence of n_vocab bytes objects, or a tokenizer with index_to_token
+        (WorldTokenizer): the tokens' bytes, which the dfa= argument of the generation calls needs
+        (set_vocab_bytes sets them later)."""
         if 'gpu_layers_count' in kwargs:
             gpu_layer_count = kwargs['gpu_layers_count']
         if not os.path.isfile(model_path):
@@ -44,6 +47,21 @@ class RWKVModel:
         self._state_buffer_element_count = self._library.rwkv_get_state_buffer_element_count(self._ctx)
         self._logits_buffer_element_count = self._library.rwkv_get_logits_buffer_element_count(self._ctx)
         self._valid = True
+        if vocab_bytes is not None:
+            self.set_vocab_bytes(vocab_bytes)
+
+    def set_vocab_bytes(self, vocab) -> None:
+        """MI355X extension (rwkv_mi355x_vocab_bytes): the bytes of every token, as a sequence of n_vocab
+        bytes objects or a tokenizer whose index_to_token maps ids to bytes (ids it lacks: no bytes,
+        never allowed under a constraint).  Shared by the clones of this model."""
+        if not self._valid:
+            raise ValueError('Model was freed')
+        table = getattr(vocab, 'index_to_token', None)
+        if table is not None:
+            vocab = [bytes(table.get(i, b'')) for i in range(self.n_vocab)]
+        if len(vocab) != self.n_vocab:
+            raise ValueError(f'{len(vocab)} tokens for a vocabulary of {self.n_vocab}')
+        self._library.rwkv_mi355x_vocab_bytes(self._ctx, vocab)
 
     @property
     def n_vocab(self) -> int:
@@ -154,7 +172,7 @@ class RWKVModel:
         return logits, states
 
     def sample(self, temperature: float = 1.0, top_p: float = 0.8, logit_bias=None, seed: int = 0,
-               offset: int = 0, logprobs: Optional[int] = None, top_k=None, min_p=None, typical_p=None):
+               offset: int = 0, logprobs: Optional[int] = None, top_k=None, min_p=None, typical_p=None, dfa=None):
         """MI355X extension (rwkv_mi355x_sample): draws one token on the device from the logits of the
         last evaluation on this model (sampling.sample_logits semantics; draw `offset` of the stream
         `seed`, sampling.uniform).  The state is untouched.
@@ -164,17 +182,23 @@ class RWKVModel:
         (sampling.logprobs), taken on the device inside the sampling step.
 
         top_k, min_p, typical_p (each None: off): the filters in front of top_p, on the device
-        (rwkv_mi355x_sample_filtered; sampling.kept_mask)."""
+        (rwkv_mi355x_sample_filtered; sampling.kept_mask).
+
+        dfa (constraint.Dfa; needs the vocabulary's bytes): only a token its start state allows is drawn
+        (rwkv_mi355x_sample_constrained; constraint.allowed_mask); dfa.state and dfa.ended are set, and
+        the token is 0xFFFFFFFF when none was allowed."""
         if not self._valid:
             raise ValueError('Model was freed')
         extra = _filter_kwargs(top_k, min_p, typical_p)
+        if dfa is not None:
+            extra['dfa'] = dfa
         if logprobs is not None:
             extra['logprobs'] = logprobs
         return self._library.rwkv_mi355x_sample(self._ctx, temperature, top_p, logit_bias, seed, offset, **extra)
 
     def generate(self, n: int, temperature: float = 1.0, top_p: float = 0.8, logit_bias=None, seed: int = 0,
                  offset: int = 0, stop_tokens=(), block: int = 16, logprobs: Optional[int] = None, top_k=None,
-                 min_p=None, typical_p=None):
+                 min_p=None, typical_p=None, dfa=None):
         """MI355X extension (rwkv_mi355x_generate): generates up to n tokens on the device, continuing
         from the state and logits the last evaluation on this model left there (eval, eval_sequence, or
         an earlier generate).  Sampling and decoding run back to back on the GPU in blocks of `block`
@@ -189,12 +213,19 @@ class RWKVModel:
         [len, K] (sampling.logprobs of every draw, taken on the device).
 
         top_k, min_p, typical_p (each None: off): the filters in front of top_p, on the device
-        (rwkv_mi355x_generate_filtered; sampling.kept_mask)."""
+        (rwkv_mi355x_generate_filtered; sampling.kept_mask).
+
+        dfa (constraint.Dfa): every draw is constrained (rwkv_mi355x_generate_constrained), the state
+        carried from block to block; generation also ends, exactly, when no token is allowed any more
+        (dfa.ended[0] == 2: the grammar is complete, or at a dead end).  dfa.state is the final state."""
         if not self._valid:
             raise ValueError('Model was freed')
         if not block > 0:
             raise ValueError('block must be > 0')
         filters = _filter_kwargs(top_k, min_p, typical_p)
+        if dfa is not None:
+            import copy
+            filters['dfa'] = live = copy.copy(dfa)  # its start moves along with the blocks
         stop = set(stop_tokens)
         out: List[int] = []
         parts = []
@@ -217,6 +248,13 @@ class RWKVModel:
             else:
                 tokens, lp = self._library.rwkv_mi355x_generate(self._ctx, m, temperature, top_p, logit_bias, seed,
                                                                 offset + len(out), logprobs=logprobs, **filters)
+            if dfa is not None:
+                dfa.state, dfa.ended = live.state, live.ended
+                live.start = int(live.state[0])
+                if int(live.ended[0]) == 2:  # ended before draw `drawn` of this block
+                    drawn = tokens.index(0xFFFFFFFF)
+                    cut = None if lp is None else rwkv_cpp_shared_library.Logprobs(*(x[:drawn] for x in lp))
+                    return result(out + tokens[:drawn], cut)
             for i, t in enumerate(tokens):
                 if t in stop:
                     cut = None if lp is None else rwkv_cpp_shared_library.Logprobs(*(x[:i + 1] for x in lp))
@@ -280,7 +318,7 @@ class RWKVModel:
     def generate_batch(self, prompts: List[List[int]], n: int, temperature=1.0, top_p=0.8, presence_penalty=0.0,
                        frequency_penalty=0.0, logit_bias=None, seeds=None, stop_tokens=(),
                        check_every: int = 16, batched_prefill: bool = False, logprobs: Optional[int] = None,
-                       top_k=None, min_p=None, typical_p=None):
+                       top_k=None, min_p=None, typical_p=None, dfa=None):
         """MI355X extension (rwkv_mi355x_generate_batch): generates up to n tokens for every prompt, all
         rows together on the device: sampling, penalties over the tokens a row has drawn, exact stops
         and one batched decode step per token, with only the tokens coming back.  temperature, top_p,
@@ -297,7 +335,11 @@ class RWKVModel:
         token was drawn from (sampling.logprobs).
 
         top_k, min_p, typical_p (each None: off; a scalar or one value per prompt): the filters in front
-        of top_p, on the device (rwkv_mi355x_generate_batch_filtered; sampling.kept_mask)."""
+        of top_p, on the device (rwkv_mi355x_generate_batch_filtered; sampling.kept_mask).
+
+        dfa (constraint.Dfa, start: one state or one per prompt): every row's draws are constrained
+        (rwkv_mi355x_generate_batch_constrained); a stop token is allowed only in an accepting state, and
+        a row also ends when nothing is allowed.  dfa.state and dfa.ended hold one entry per prompt."""
         if not self._valid:
             raise ValueError('Model was freed')
         rows = len(prompts)
@@ -319,6 +361,8 @@ class RWKVModel:
             self._library.rwkv_mi355x_eval_device(self._ctx, list(prompt))
             self._library.rwkv_mi355x_batch_store(self._ctx, slot)
         filters = _filter_kwargs(top_k, min_p, typical_p)
+        if dfa is not None:
+            filters['dfa'] = dfa
         if logprobs is None:  # without filters: the call as it always was
             out = self._library.rwkv_mi355x_generate_batch(self._ctx, rows, n, params, **filters)
         else:
@@ -331,7 +375,8 @@ class RWKVModel:
 
     def generate_queue(self, prompts: List[List[int]], max_tokens, lanes: int = 32, temperature=1.0, top_p=0.8,
                        presence_penalty=0.0, frequency_penalty=0.0, logit_bias=None, seeds=None, stop_tokens=(),
-                       check_every: int = 16, logprobs: Optional[int] = None, top_k=None, min_p=None, typical_p=None):
+                       check_every: int = 16, logprobs: Optional[int] = None, top_k=None, min_p=None, typical_p=None,
+                       dfa=None):
         """MI355X extension (rwkv_mi355x_generate_queue): continuous batching.  Up to 256 prompts are
         evaluated together (prefill_batch) into slots 0 .. Q-1 and generated through a queue over
         `lanes` decode rows: a row whose sequence has ended -- a stop token, or its max_tokens (a scalar
@@ -339,7 +384,7 @@ class RWKVModel:
         stay full.  The other parameters are those of generate_batch, per prompt.  Returns one token
         list per prompt, each exactly what that prompt generates alone; slot i holds its final state
         and logits, and batch_load(i) continues from there.  logprobs=K: as generate_batch, (token
-        lists, [Logprobs per prompt]).  top_k, min_p, typical_p: as generate_batch, per prompt."""
+        lists, [Logprobs per prompt]).  top_k, min_p, typical_p, dfa: as generate_batch, per prompt."""
         if not self._valid:
             raise ValueError('Model was freed')
         rows = len(prompts)
@@ -359,6 +404,8 @@ class RWKVModel:
             self._library.rwkv_mi355x_batch_reserve(self._ctx, rows)
         self._library.rwkv_mi355x_prefill_batch(self._ctx, [list(p) for p in prompts], list(range(rows)), None)
         extra = _filter_kwargs(top_k, min_p, typical_p)
+        if dfa is not None:
+            extra['dfa'] = dfa
         if logprobs is not None:
             extra['logprobs'] = logprobs
         out = self._library.rwkv_mi355x_generate_queue(

@@ -91,6 +91,34 @@ def make_filters(rows: int, top_k=None, min_p=None, typical_p=None) -> Optional[
     return f
 
 
+class RWKVConstraint(ctypes.Structure):
+    """struct rwkv_mi355x_constraint (include/rwkv_mi355x.h)."""
+    _fields_ = [('n_states', ctypes.c_uint32), ('next', ctypes.POINTER(ctypes.c_uint16)),
+                ('accepting', ctypes.POINTER(ctypes.c_uint8)), ('state', ctypes.POINTER(ctypes.c_uint32)),
+                ('ended', ctypes.POINTER(ctypes.c_uint32))]
+
+
+def make_constraint(rows: int, dfa) -> Optional[RWKVConstraint]:
+    """An RWKVConstraint for `rows` rows from an object with next [n_states, 256], accepting [n_states]
+    and start (a state, or one per row), e.g. rwkv_cpp.constraint.Dfa; None: None.  The call's outputs
+    are left on the object: dfa.state and dfa.ended, uint32 [rows]."""
+    if dfa is None:
+        return None
+    import numpy as np
+    nxt = np.ascontiguousarray(dfa.next, dtype=np.uint16).reshape(-1, 256)
+    acc = np.ascontiguousarray(dfa.accepting, dtype=np.uint8)
+    if acc.size != nxt.shape[0]:
+        raise ValueError('one accepting flag per state')
+    dfa.state = np.array([int(v) for v in _per_row(dfa.start, rows, 'start')], dtype=np.uint32)
+    dfa.ended = np.zeros(rows, np.uint32)
+    c = RWKVConstraint(nxt.shape[0], nxt.ctypes.data_as(ctypes.POINTER(ctypes.c_uint16)),
+                       acc.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8)),
+                       dfa.state.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)),
+                       dfa.ended.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)))
+    c._keep = (nxt, acc, dfa.state, dfa.ended)
+    return c
+
+
 # What a call with logprobs=K returns besides its tokens: the drawn tokens' log-probabilities
 # (float64 [n]) and the K most likely alternatives of every draw (uint32 / float64 [n, K]).
 Logprobs = collections.namedtuple('Logprobs', ('token_logprob', 'top_ids', 'top_logprobs'))
@@ -329,6 +357,21 @@ class RWKVSharedLibrary:
             fn = getattr(L, f'rwkv_mi355x_{name}_filtered')
             fn.argtypes = getattr(L, f'rwkv_mi355x_{name}').argtypes + [P_F]
             fn.restype = ctypes.c_bool
+        P_C, P_U8 = ctypes.POINTER(RWKVConstraint), ctypes.POINTER(ctypes.c_uint8)
+        for name in ('sample', 'generate', 'generate_batch', 'generate_queue'):
+            fn = getattr(L, f'rwkv_mi355x_{name}_constrained')
+            fn.argtypes = getattr(L, f'rwkv_mi355x_{name}').argtypes + [P_LP, P_F, P_C]
+            fn.restype = ctypes.c_bool
+        L.rwkv_mi355x_vocab_bytes.argtypes = [vp, P_U32, P_U8]
+        L.rwkv_mi355x_vocab_bytes.restype = ctypes.c_bool
+        L.rwkv_mi355x_constraint_max_entries.argtypes = []
+        L.rwkv_mi355x_constraint_max_entries.restype = ctypes.c_uint32
+        L.rwkv_mi355x_selftest_dfa_mask.argtypes = [P_FLOAT, ctypes.c_int, ctypes.c_int, P_U32, P_U8, P_C, P_U32,
+                                                    ctypes.c_int, P_FLOAT, P_U32]
+        L.rwkv_mi355x_selftest_dfa_mask.restype = ctypes.c_bool
+        L.rwkv_mi355x_selftest_dfa_advance.argtypes = [P_U32, P_U32, ctypes.c_int, ctypes.c_int, P_U32, P_U8, u32,
+                                                       ctypes.POINTER(ctypes.c_uint16)]
+        L.rwkv_mi355x_selftest_dfa_advance.restype = ctypes.c_bool
         L.rwkv_mi355x_score_sequence.argtypes = [vp, P_U32, sz, P_U32, P_DOUBLE, P_U32, P_FLOAT]
         L.rwkv_mi355x_score_sequence.restype = ctypes.c_bool
         L.rwkv_mi355x_selftest_xent.argtypes = [P_FLOAT, ctypes.c_int, ctypes.c_int, P_U32, P_DOUBLE, P_U32]
@@ -428,19 +471,23 @@ class RWKVSharedLibrary:
     # ---- additive: sampling and the generation loop on the device ---------------------------
     def rwkv_mi355x_sample(self, ctx: RWKVContext, temperature: float = 1.0, top_p: float = 0.8, logit_bias=None,
                            seed: int = 0, offset: int = 0, logprobs: Optional[int] = None, top_k=None, min_p=None,
-                           typical_p=None):
+                           typical_p=None, dfa=None):
         """One token drawn on the device from the context's logits (draw `offset` of stream `seed`);
         the state is untouched.  logprobs=K (rwkv_mi355x_sample_logprobs): returns (token, Logprobs)
         with the token's log-probability (a float) and the K most likely alternatives ([K] arrays).
-        top_k / min_p / typical_p (rwkv_mi355x_sample_filtered): the filters in front of top_p."""
+        top_k / min_p / typical_p (rwkv_mi355x_sample_filtered): the filters in front of top_p.
+        dfa (rwkv_mi355x_sample_constrained; make_constraint): only tokens its state allows are drawn;
+        its state and ended are left on it, and the token is 0xFFFFFFFF when none was allowed."""
         token = ctypes.c_uint32(0)
         p = make_sampling(temperature, top_p, logit_bias, seed, offset)
         filters = make_filters(1, top_k, min_p, typical_p)
-        if filters is not None:
+        c = make_constraint(1, dfa)
+        if filters is not None or c is not None:
             lp, out = make_logprobs(1, 1, logprobs) if logprobs is not None else (None, None)
-            if not self.library.rwkv_mi355x_sample_filtered(ctx.ptr, ctypes.byref(p), ctypes.byref(token),
-                                                            lp and ctypes.byref(lp), ctypes.byref(filters)):
-                raise ValueError('rwkv_mi355x_sample_filtered failed, check stderr')
+            if not self.library.rwkv_mi355x_sample_constrained(ctx.ptr, ctypes.byref(p), ctypes.byref(token),
+                                                               lp and ctypes.byref(lp), filters and ctypes.byref(filters),
+                                                               c and ctypes.byref(c)):
+                raise ValueError('rwkv_mi355x_sample_filtered / _constrained failed, check stderr')
             if lp is None:
                 return token.value
             return token.value, Logprobs(float(out.token_logprob[0, 0]), out.top_ids[0, 0], out.top_logprobs[0, 0])
@@ -456,20 +503,24 @@ class RWKVSharedLibrary:
     def rwkv_mi355x_generate(self, ctx: RWKVContext, n: int, temperature: float = 1.0, top_p: float = 0.8,
                              logit_bias=None, seed: int = 0, offset: int = 0,
                              logits_out_address: Optional[int] = None, logprobs: Optional[int] = None, top_k=None,
-                             min_p=None, typical_p=None):
+                             min_p=None, typical_p=None, dfa=None):
         """n times (draw a token on the device, evaluate it) without a host round trip; returns the
         tokens.  Draw i uses counter offset + i, so a call with offset + n continues the stream.
         logprobs=K (rwkv_mi355x_generate_logprobs): returns (tokens, Logprobs of [n] / [n, K] arrays).
-        top_k / min_p / typical_p (rwkv_mi355x_generate_filtered): the filters in front of top_p."""
+        top_k / min_p / typical_p (rwkv_mi355x_generate_filtered): the filters in front of top_p.
+        dfa (rwkv_mi355x_generate_constrained; make_constraint): every draw is constrained; when the
+        sequence ends early (dfa.ended[0] == 2) the tokens from that draw on are 0xFFFFFFFF."""
         tokens = (ctypes.c_uint32 * max(1, n))()
         p = make_sampling(temperature, top_p, logit_bias, seed, offset)
         logits_out = ctypes.cast(logits_out_address or 0, P_FLOAT)
         filters = make_filters(1, top_k, min_p, typical_p)
-        if filters is not None:
+        c = make_constraint(1, dfa)
+        if filters is not None or c is not None:
             lp, out = make_logprobs(1, max(1, n), logprobs) if logprobs is not None else (None, None)
-            if not self.library.rwkv_mi355x_generate_filtered(ctx.ptr, ctypes.byref(p), n, tokens, logits_out,
-                                                              lp and ctypes.byref(lp), ctypes.byref(filters)):
-                raise ValueError('rwkv_mi355x_generate_filtered failed, check stderr')
+            if not self.library.rwkv_mi355x_generate_constrained(ctx.ptr, ctypes.byref(p), n, tokens, logits_out,
+                                                                 lp and ctypes.byref(lp), filters and ctypes.byref(filters),
+                                                                 c and ctypes.byref(c)):
+                raise ValueError('rwkv_mi355x_generate_filtered / _constrained failed, check stderr')
             if lp is None:
                 return list(tokens[:n])
             return list(tokens[:n]), Logprobs(*(x[0, :n] for x in out))
@@ -556,7 +607,7 @@ class RWKVSharedLibrary:
             raise ValueError('rwkv_mi355x_batch_load failed, check stderr')
 
     def _generate_slots(self, name: str, ctx: RWKVContext, rows: int, n: int, logprobs: Optional[int], head: tuple,
-                        extra: tuple = (), filters: Optional[RWKVFilters] = None):
+                        extra: tuple = (), filters: Optional[RWKVFilters] = None, dfa=None):
         """What rwkv_mi355x_generate_batch and rwkv_mi355x_generate_queue share: the output arrays of
         `rows` sequences and the plain / _logprobs / _filtered entry point `name`, called with (ctx, *head,
         n, tokens, lengths, *extra, steps[, logprobs[, filters]]).  Returns (tokens [rows, n], lengths [rows], steps,
@@ -571,7 +622,11 @@ class RWKVSharedLibrary:
         out = lp = None
         if logprobs is not None:
             lp, out = make_logprobs(rows, max(1, n), logprobs)
-        if filters is not None:
+        c = make_constraint(rows, dfa)
+        if c is not None:
+            name += '_constrained'
+            args += (lp and ctypes.byref(lp), filters and ctypes.byref(filters), ctypes.byref(c))
+        elif filters is not None:
             name += '_filtered'
             args += (lp and ctypes.byref(lp), ctypes.byref(filters))
         elif lp is not None:
@@ -582,28 +637,30 @@ class RWKVSharedLibrary:
         return tokens[:, :n], lengths, steps.value, out and Logprobs(*(x[:, :n] for x in out))
 
     def rwkv_mi355x_generate_batch(self, ctx: RWKVContext, rows: int, n: int, params: RWKVBatchSampling,
-                                   logprobs: Optional[int] = None, top_k=None, min_p=None, typical_p=None):
+                                   logprobs: Optional[int] = None, top_k=None, min_p=None, typical_p=None, dfa=None):
         """Up to n tokens for each of slots [0, rows) (make_batch_sampling).  Returns (tokens uint32
         [rows, n], 0xFFFFFFFF after a row's last token; lengths uint32 [rows]; the decode steps run).
         logprobs=K (rwkv_mi355x_generate_batch_logprobs): a fourth element, Logprobs of [rows, n] /
         [rows, n, K] arrays whose columns past a row's length hold the fill (NaN, 0xFFFFFFFF).
         top_k / min_p / typical_p, scalars or per row (rwkv_mi355x_generate_batch_filtered): the filters
-        in front of top_p."""
+        in front of top_p.  dfa (rwkv_mi355x_generate_batch_constrained; make_constraint): the rows'
+        constraint; their states and ended flags are left on it."""
         out = self._generate_slots('rwkv_mi355x_generate_batch', ctx, rows, n, logprobs, (rows, ctypes.byref(params)),
-                                   filters=make_filters(rows, top_k, min_p, typical_p))
+                                   filters=make_filters(rows, top_k, min_p, typical_p), dfa=dfa)
         return out if logprobs is not None else out[:3]
 
     def rwkv_mi355x_generate_queue(self, ctx: RWKVContext, max_tokens, lanes: int, temperature=1.0, top_p=0.8,
                                    presence=None, frequency=None, logit_bias=None, seeds=None, offsets=0,
                                    stop_tokens=(), check_every: int = 0, n: Optional[int] = None,
-                                   logprobs: Optional[int] = None, top_k=None, min_p=None, typical_p=None):
+                                   logprobs: Optional[int] = None, top_k=None, min_p=None, typical_p=None, dfa=None):
         """The sequences in slots [0, len(max_tokens)) through a queue over `lanes` decode rows, at most
         max_tokens[s] tokens each (make_batch_sampling over the sequences, keep_counts false).  Returns
         a dict: tokens uint32 [Q, n] (n: max(max_tokens) unless given; 0xFFFFFFFF after a sequence's
         last token), lengths, lane, start uint32 [Q] and steps, the decode steps that were needed.
         logprobs=K (rwkv_mi355x_generate_queue_logprobs) adds 'logprobs': Logprobs of [Q, n] / [Q, n, K]
         arrays.  top_k / min_p / typical_p, scalars or per sequence (rwkv_mi355x_generate_queue_filtered):
-        the filters in front of top_p."""
+        the filters in front of top_p.  dfa (rwkv_mi355x_generate_queue_constrained): as generate_batch,
+        per sequence."""
         import numpy as np
         caps = np.ascontiguousarray(max_tokens, dtype=np.uint32)
         Q = int(caps.size)
@@ -614,10 +671,62 @@ class RWKVSharedLibrary:
         head = (Q, lanes, ctypes.byref(params), caps.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)))
         out['tokens'], out['lengths'], out['steps'], lp = self._generate_slots(
             'rwkv_mi355x_generate_queue', ctx, Q, n, logprobs, head, (out['lane'], out['start']),
-            make_filters(Q, top_k, min_p, typical_p))
+            make_filters(Q, top_k, min_p, typical_p), dfa)
         if logprobs is not None:
             out['logprobs'] = lp
         return out
+
+    # ---- additive: byte-DFA constraints ----------------------------------------------------
+    def rwkv_mi355x_vocab_bytes(self, ctx: RWKVContext, vocab) -> None:
+        """Tells the model its tokens' bytes (a sequence of n_vocab bytes objects), once per model."""
+        from .constraint import pack_vocab
+        offsets, data = pack_vocab(vocab)
+        if not self.library.rwkv_mi355x_vocab_bytes(ctx.ptr, offsets.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)),
+                                                    data.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8))):
+            raise ValueError('rwkv_mi355x_vocab_bytes failed, check stderr')
+
+    def rwkv_mi355x_constraint_max_entries(self) -> int:
+        """The largest n_states * n_cls a constraint's compressed table may have on the current device."""
+        return int(self.library.rwkv_mi355x_constraint_max_entries())
+
+    def rwkv_mi355x_selftest_dfa_mask(self, logits, vocab, dfa, stop_tokens=(), finished=None, fill: float = 7.0):
+        """k_dfa_mask on host operands: logits float32 [rows, V], vocab (V bytes objects), dfa (start: the
+        rows' states), finished (None, or one flag per row: the row is skipped).  Returns (masked [rows,
+        V], which starts as `fill`; n_allowed [rows]; ended [rows])."""
+        import numpy as np
+        from .constraint import pack_vocab
+        logits = np.ascontiguousarray(logits, dtype=np.float32)
+        rows, V = logits.shape
+        offsets, data = pack_vocab(vocab)
+        c = make_constraint(rows, dfa)
+        if finished is not None:
+            dfa.ended[:] = np.asarray(finished, dtype=np.uint32)
+        masked = np.full((rows, V), fill, np.float32)
+        n_allowed = np.zeros(rows, np.uint32)
+        stops = np.array(list(stop_tokens) or [0], np.uint32)
+        P_U32 = ctypes.POINTER(ctypes.c_uint32)
+        if not self.library.rwkv_mi355x_selftest_dfa_mask(
+                logits.ctypes.data_as(P_FLOAT), rows, V, offsets.ctypes.data_as(P_U32),
+                data.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8)), ctypes.byref(c), stops.ctypes.data_as(P_U32),
+                len(stop_tokens), masked.ctypes.data_as(P_FLOAT), n_allowed.ctypes.data_as(P_U32)):
+            raise ValueError('rwkv_mi355x_selftest_dfa_mask failed')
+        return masked, n_allowed, dfa.ended.copy()
+
+    def rwkv_mi355x_selftest_dfa_advance(self, states, tokens, vocab, next):
+        """k_dfa_advance on host operands; returns the states [rows] after each walked its token."""
+        import numpy as np
+        from .constraint import pack_vocab
+        states = np.array(states, dtype=np.uint32, copy=True)
+        tokens = np.ascontiguousarray(tokens, dtype=np.uint32)
+        nxt = np.ascontiguousarray(next, dtype=np.uint16).reshape(-1, 256)
+        offsets, data = pack_vocab(vocab)
+        P_U32 = ctypes.POINTER(ctypes.c_uint32)
+        if not self.library.rwkv_mi355x_selftest_dfa_advance(
+                states.ctypes.data_as(P_U32), tokens.ctypes.data_as(P_U32), states.size, len(vocab),
+                offsets.ctypes.data_as(P_U32), data.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8)), nxt.shape[0],
+                nxt.ctypes.data_as(ctypes.POINTER(ctypes.c_uint16))):
+            raise ValueError('rwkv_mi355x_selftest_dfa_advance failed')
+        return states
 
     def rwkv_mi355x_selftest_gen_turnover(self, lane_seq, done, length, max_tokens, next_seq: int, step: int = 0,
                                           fill: int = 0xFFFFFFFE):
