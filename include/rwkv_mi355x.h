@@ -329,21 +329,37 @@ RWKV_API bool rwkv_mi355x_generate_queue_filtered(struct rwkv_context * ctx, siz
  * are indexed by sequence.
  *
  * The table is compressed on the host (bytes whose columns are equal in every state form one class,
- * n_cls <= 256 of them) and must fit one workgroup's LDS: n_states * n_cls * 2 bytes, rounded up to 16,
- * plus 272 bytes, at most the device's LDS per workgroup (hipDeviceAttributeMaxSharedMemoryPerBlock;
- * 160 KiB on the MI355X: n_states * n_cls <= 81784, which rwkv_mi355x_constraint_max_entries() returns
- * for the current device: 319 states at 256 classes, 2044 at 40).  There is no larger path. */
+ * n_cls <= 256 of them).  A table passed with the call must fit one workgroup's LDS: n_states * n_cls * 2
+ * bytes, rounded up to 16, plus 272 bytes, at most the device's LDS per workgroup
+ * (hipDeviceAttributeMaxSharedMemoryPerBlock; 160 KiB on the MI355X: n_states * n_cls <= 81784, which
+ * rwkv_mi355x_constraint_max_entries() returns for the current device: 319 states at 256 classes, 2044
+ * at 40).  A resident table (rwkv_mi355x_constraint_table, below) need not: it is walked from device
+ * memory when it does not fit, and gives the same bits either way. */
 RWKV_API bool rwkv_mi355x_vocab_bytes(struct rwkv_context * ctx, const uint32_t * offsets /* [n_vocab + 1] */,
                                       const uint8_t * bytes);
 RWKV_API uint32_t rwkv_mi355x_constraint_max_entries(void);
 struct rwkv_mi355x_constraint {
     uint32_t n_states;          /* >= 1, < 0xFFFF */
     const uint16_t * next;      /* host [n_states][256]; 0xFFFF = dead */
-    const uint8_t  * accepting; /* host [n_states] */
+    const uint8_t  * accepting; /* host [n_states]; next and accepting both NULL: the resident table */
     uint32_t * state;           /* host [rows], in: the start state of each row / sequence; out: its state on return */
     uint32_t * ended;           /* host [rows] out, may be NULL: 0 not ended (cap reached / still live),
                                    1 drew a stop token, 2 no token was allowed */
 };
+/* Gives the context a constraint table that stays on the device: compressed once, uploaded once,
+ * used by every later _constrained call whose constraint has next == NULL and accepting == NULL and
+ * n_states equal to the resident table's.  1 <= n_states < 0xFFFF; there is no LDS limit.
+ * n_states == 0 frees it.  Replacing or freeing waits for the context's queued work.
+ * The table belongs to the context (rwkv_clone_context does not copy it).  Errors, all before anything
+ * changes, the table set before staying in place: RWKV_ERROR_ARGS for n_states >= 0xFFFF, a NULL array
+ * with n_states > 0, or an entry that is neither < n_states nor 0xFFFF; RWKV_ERROR_ALLOC for a failed
+ * allocation; RWKV_ERROR_CTX | RWKV_ERROR_UNSUPPORTED on a pipeline or stage context.
+ * A constraint with both arrays NULL and no resident table, or another n_states than the resident
+ * table's, or only one array NULL, is RWKV_ERROR_ARGS in the _constrained calls. */
+RWKV_API bool rwkv_mi355x_constraint_table(struct rwkv_context * ctx, uint32_t n_states,
+                                           const uint16_t * next /* host [n_states][256] */,
+                                           const uint8_t * accepting /* host [n_states] */);
+RWKV_API uint32_t rwkv_mi355x_constraint_table_states(const struct rwkv_context * ctx); /* 0: none */
 /* Each is its _filtered sibling above plus c, with lp and f still optional; c == NULL is that call.
  * Besides the sibling's errors, all RWKV_ERROR_ARGS before anything is enqueued: no vocabulary bytes
  * on the context; n_states == 0 or >= 0xFFFF; a NULL next / accepting / state; a next entry >=
@@ -765,6 +781,11 @@ RWKV_API bool rwkv_mi355x_selftest_sample_rows_filtered(const float * logits, in
 RWKV_API bool rwkv_mi355x_selftest_dfa_mask(const float * logits, int rows, int V, const uint32_t * offsets,
                                             const uint8_t * bytes, const struct rwkv_mi355x_constraint * c,
                                             const uint32_t * stop, int n_stop, float * masked, uint32_t * n_allowed);
+/* The same through k_dfa_mask_mem (the kernel of a resident table over the LDS limit), whatever the
+ * table's size: n_states up to 65534. */
+RWKV_API bool rwkv_mi355x_selftest_dfa_mask_mem(const float * logits, int rows, int V, const uint32_t * offsets,
+                                                const uint8_t * bytes, const struct rwkv_mi355x_constraint * c,
+                                                const uint32_t * stop, int n_stop, float * masked, uint32_t * n_allowed);
 /* k_dfa_advance on host operands: states [rows <= 256] (each < n_states) walk tokens [rows] (each < V). */
 RWKV_API bool rwkv_mi355x_selftest_dfa_advance(uint32_t * states, const uint32_t * tokens, int rows, int V,
                                                const uint32_t * offsets, const uint8_t * bytes, uint32_t n_states,

@@ -32,6 +32,28 @@ __device__ __forceinline__ uint32_t dfa_row_seq(const DfaArgs & a, int r) {
     return seq;
 }
 
+// The end of both mask kernels.  The workgroup that finishes last sees every count: a live row with no
+// allowed token is finished before its draw, as the sampler finishes a row at a stop token (done,
+// fin_step, *active).  `last` is one LDS word.
+__device__ __forceinline__ void dfa_finish_rows(const DfaArgs & a, uint32_t * last, int tid) {
+    if (!a.ticket) return;
+    __threadfence();
+    __syncthreads();
+    if (tid == 0) *last = atomicAdd(a.ticket, 1u) == gridDim.x - 1u ? 1u : 0u;
+    __syncthreads();
+    if (*last == 0u) return;
+    __threadfence();
+    for (int r = tid; r < a.rows; r += DFA_THREADS) {
+        const uint32_t seq = dfa_row_seq(a, r);
+        if (seq == GEN_NONE || atomicAdd(a.n_allowed + r, 0u) != 0u) continue;
+        if (a.done) a.done[seq] = 1u;
+        if (a.fin_step) a.fin_step[seq] = a.step;
+        if (a.active) atomicSub(a.active, 1u);
+        if (a.ended) a.ended[seq] = 2u;
+    }
+    if (tid == 0) *a.ticket = 0u;
+}
+
 // grid: ceil(V / DFA_THREADS) workgroups; dynamic LDS: dfa_lds_bytes(n_states, n_cls)
 __global__ __launch_bounds__(DFA_THREADS) void k_dfa_mask(const DfaArgs a) {
     extern __shared__ uint4 lds4[];
@@ -103,24 +125,133 @@ __global__ __launch_bounds__(DFA_THREADS) void k_dfa_mask(const DfaArgs a) {
         if (lane == 0 && b != 0ull) atomicAdd(a.n_allowed + r, (uint32_t)__popcll(b));
     }
 
-    // the workgroup that finishes last sees every count: a live row with no allowed token is finished
-    // before its draw, as the sampler finishes a row at a stop token (done, fin_step, *active)
-    if (!a.ticket) return;
-    __threadfence();
-    __syncthreads();
-    if (tid == 0) *last = atomicAdd(a.ticket, 1u) == gridDim.x - 1u ? 1u : 0u;
-    __syncthreads();
-    if (*last == 0u) return;
-    __threadfence();
-    for (int r = tid; r < a.rows; r += DFA_THREADS) {
-        const uint32_t seq = dfa_row_seq(a, r);
-        if (seq == GEN_NONE || atomicAdd(a.n_allowed + r, 0u) != 0u) continue;
-        if (a.done) a.done[seq] = 1u;
-        if (a.fin_step) a.fin_step[seq] = a.step;
-        if (a.active) atomicSub(a.active, 1u);
-        if (a.ended) a.ended[seq] = 2u;
+    dfa_finish_rows(a, last, tid);
+}
+
+// ---- a resident table that does not fit the LDS (rwkv_mi355x_constraint_table) ---------
+// k_dfa_mask_mem has k_dfa_mask's contract and split, and reads the table from memory.  Its LDS holds
+// what the walks need beside it: the class map; one word per row, resolved by thread r in parallel
+// (lane_seq -> done -> state -> accepting happen once per workgroup, not once per row in series); and
+// the compacted list of the live rows.  The walks of four rows run in lockstep: the four loads of a
+// byte are independent and in flight together.  (Staging the table rows of the rows' states in LDS for
+// the first byte was measured and not kept: DESIGN 4v.)
+constexpr uint32_t DFA_ROW_SKIP = 0xffffffffu;  // a row's word: state | accepting << 16, or no draw
+constexpr uint32_t DFA_MEM_FIXED = 256 + 4 * DFA_THREADS + DFA_THREADS + 32;  // cls, words, live list, counts
+
+// One byte (class ci) of up to four walks.  A walk that is not going reads entry 0 and keeps its state,
+// so the four loads are unconditional and the compiler waits for them once.
+__device__ __forceinline__ void dfa_step4(const uint16_t * __restrict__ tab, uint32_t n_cls, uint32_t ci, const bool (&go)[4],
+                                          uint32_t (&s)[4], bool (&alive)[4]) {
+    uint32_t x[4];
+#pragma unroll
+    for (int j = 0; j < 4; j++) x[j] = tab[go[j] ? s[j] * n_cls + ci : 0u];
+#pragma unroll
+    for (int j = 0; j < 4; j++)
+        if (go[j]) {
+            s[j] = x[j];
+            alive[j] = x[j] != DFA_DEAD;
+        }
+}
+
+// grid: ceil(V / DFA_THREADS) workgroups; dynamic LDS: DFA_MEM_FIXED bytes; rows <= DFA_THREADS
+__global__ __launch_bounds__(DFA_THREADS) void k_dfa_mask_mem(const DfaArgs a) {
+    extern __shared__ uint4 lds4[];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const uint32_t n_cls = a.n_cls;
+    uint8_t * cls = (uint8_t *)lds4;
+    uint32_t * word = (uint32_t *)(cls + 256);             // [DFA_THREADS]
+    uint8_t * live = (uint8_t *)(word + DFA_THREADS);      // [DFA_THREADS]: the live rows, in order
+    uint32_t * wave_n = (uint32_t *)(live + DFA_THREADS);  // [4], then the epilogue's word
+    uint32_t * last = wave_n + 4;
+    const uint16_t * __restrict__ tab = a.tab;
+
+    // the class map behind the table, and row tid's word
+    if (tid < 16) ((uint4 *)cls)[tid] = ((const uint4 *)((const uint8_t *)a.tab + dfa_pad16(a.n_states * n_cls * 2u)))[tid];
+    uint32_t w = DFA_ROW_SKIP;
+    if (tid < a.rows) {
+        const uint32_t seq = dfa_row_seq(a, tid);
+        if (seq != GEN_NONE) {
+            const uint32_t q = a.state[seq];
+            if (q < a.n_states) w = q | (a.accepting[q] != 0 ? 0x10000u : 0u);
+        }
     }
-    if (tid == 0) *a.ticket = 0u;
+    word[tid] = w;
+    const unsigned long long mine = __ballot(w != DFA_ROW_SKIP);
+    if (lane == 0) wave_n[wave] = (uint32_t)__popcll(mine);
+
+    // this thread's token, as in k_dfa_mask
+    const int t = blockIdx.x * DFA_THREADS + tid;
+    const bool in = t < a.V;
+    const int tc = min(t, a.V - 1);
+    const uint4 h = a.head[tc];
+    const uint2 m = a.meta[tc];
+    const int len = in ? (int)m.x : 0;
+    bool is_stop = false;
+#pragma unroll
+    for (int j = 0; j < SAMPLE_MAX_STOP; j++) is_stop = is_stop || (j < a.n_stop && a.stop[j] == (uint32_t)t);
+    __syncthreads();
+
+    uint32_t at = (uint32_t)__popcll(mine & ((1ull << lane) - 1ull)), n = 0;
+#pragma unroll
+    for (int v = 0; v < DFA_THREADS / 64; v++) {
+        if (v < wave) at += wave_n[v];
+        n += wave_n[v];
+    }
+    if (w != DFA_ROW_SKIP) live[at] = (uint8_t)tid;
+    const uint32_t hw[4] = {h.x, h.y, h.z, h.w};
+    uint32_t c[4];
+#pragma unroll
+    for (int v = 0; v < 4; v++)
+        c[v] = (uint32_t)cls[hw[v] & 255u] | (uint32_t)cls[(hw[v] >> 8) & 255u] << 8 |
+               (uint32_t)cls[(hw[v] >> 16) & 255u] << 16 | (uint32_t)cls[hw[v] >> 24] << 24;
+    __syncthreads();
+
+    const float NEG_INF = __int_as_float(0xff800000);
+    const uint8_t * tl = a.tail + m.y;
+    for (uint32_t j0 = 0; j0 < n; j0 += 4) {
+        uint32_t row[4], s[4];
+        bool acc[4], alive[4], go[4];
+#pragma unroll
+        for (int j = 0; j < 4; j++) {  // uniform; a slot past the last live row repeats it and stays idle
+            row[j] = __builtin_amdgcn_readfirstlane((uint32_t)live[min(j0 + j, n - 1u)]);
+            const uint32_t wj = __builtin_amdgcn_readfirstlane(word[row[j]]);
+            s[j] = wj & 0xffffu;
+            acc[j] = (wj & 0x10000u) != 0u;
+            alive[j] = len > 0 && j0 + j < n;
+        }
+        // a wave with no walk still going in any of the four rows leaves, mostly after the first byte:
+        // the vocabulary is sorted by bytes, so its 64 tokens tend to die together
+#pragma unroll
+        for (int i = 0; i < 16; i++) {
+            bool any = false;
+#pragma unroll
+            for (int j = 0; j < 4; j++) {
+                go[j] = alive[j] && i < len;
+                any = any || go[j];
+            }
+            if (__ballot(any) == 0ull) break;
+            dfa_step4(tab, n_cls, (c[i >> 2] >> (8 * (i & 3))) & 255u, go, s, alive);
+        }
+        if (len > 16) {  // a long token: its tail comes from memory
+            for (int i = 16; i < len && (alive[0] || alive[1] || alive[2] || alive[3]); i++) {
+#pragma unroll
+                for (int j = 0; j < 4; j++) go[j] = alive[j];
+                dfa_step4(tab, n_cls, cls[tl[i - 16]], go, s, alive);
+            }
+        }
+#pragma unroll
+        for (int j = 0; j < 4; j++) {
+            if (j0 + j >= n) break;
+            const bool allowed = in && (is_stop ? acc[j] : alive[j]);
+            if (in) {
+                const size_t o = (size_t)row[j] * (size_t)a.V + (size_t)t;
+                a.masked[o] = allowed ? a.logits[o] : NEG_INF;
+            }
+            const unsigned long long b = __ballot(allowed);
+            if (lane == 0 && b != 0ull) atomicAdd(a.n_allowed + row[j], (uint32_t)__popcll(b));
+        }
+    }
+    dfa_finish_rows(a, last, tid);
 }
 
 // Behind the sampler.  Workgroup 0, thread r = row r: the row's count is cleared for the next mask; a
@@ -235,6 +366,13 @@ bool launch_dfa_mask(hipStream_t st, const DfaArgs & a, size_t lds_limit) {
     if (lds > 48 * 1024)
         HIP_OK(hipFuncSetAttribute((const void *)k_dfa_mask, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     RK_LAUNCH(k_dfa_mask, dim3((unsigned)((a.V + DFA_THREADS - 1) / DFA_THREADS)), dim3(DFA_THREADS), (unsigned)lds, st, a);
+    HIP_OK(hipGetLastError());
+    return true;
+}
+
+bool launch_dfa_mask_mem(hipStream_t st, const DfaArgs & a) {
+    if (!dfa_args_ok(a) || !a.logits || !a.masked || !a.n_allowed || a.rows > DFA_THREADS || a.n_states >= DFA_DEAD) return false;
+    RK_LAUNCH(k_dfa_mask_mem, dim3((unsigned)((a.V + DFA_THREADS - 1) / DFA_THREADS)), dim3(DFA_THREADS), DFA_MEM_FIXED, st, a);
     HIP_OK(hipGetLastError());
     return true;
 }

@@ -289,7 +289,14 @@ class Engine : public KLaunchTimer, private Workspace, private GenSlots {
     // anything is enqueued: the table is compressed (dfa_compress) and kept for the call that follows.
     // 0: passed; 1: the arguments (no vocabulary bytes, a bad entry or start state, a table over
     // dfa_lds_limit); 2: an allocation failed
+    // c.next == NULL and c.accepting == NULL: the resident table (constraint_table), which must be set
+    // and have c.n_states states; nothing is compressed and no table is uploaded by the call.
     int constraint_reserve(const ConstraintParams & c, size_t Q, size_t rows);
+    // The context's resident table (rwkv_mi355x_constraint_table): compressed and uploaded
+    // once, of any size below 0xFFFF states; n_states == 0 frees it.  Waits for the stream before the
+    // old one goes.  0: done; 1: the arguments (the old table stays); 2: allocation or copy (it stays)
+    int constraint_table(uint32_t n_states, const uint16_t * next, const uint8_t * accepting);
+    uint32_t constraint_table_states() const { return res_states_; }
     size_t constraint_lds_limit() const { return dfa_lds_limit(m_->device); }
     // The device arrays of a call with log-probabilities: rows * n columns of 8 + 12 top_k bytes and one
     // logZ word per row, grown here and never inside a loop.  Enqueues nothing; the callers of the four
@@ -502,6 +509,12 @@ class Engine : public KLaunchTimer, private Workspace, private GenSlots {
     // sampler's words.  dfa_copy_out: state and ended to the caller (before the call's synchronise).
     bool dfa_begin(const ConstraintParams & c, size_t Q, size_t rows, DfaArgs & d);
     bool dfa_copy_out(const ConstraintParams & c, size_t Q);
+    // The mask launch of the call dfa_begin started: k_dfa_mask for a table passed with the call and for
+    // a resident one that fits the LDS, k_dfa_mask_mem for a resident one that does not
+    bool dfa_mask(const DfaArgs & d);
+    DevBuf<uint8_t> res_blob_, res_accept_;  // the resident table: DfaTable::blob and accepting
+    uint32_t res_states_ = 0, res_cls_ = 0;
+    bool dfa_resident_ = false, dfa_mem_ = false;  // the call being made: resident table; k_dfa_mask_mem
     DfaTable dfa_tab_;           // the table of the call being made (constraint_reserve)
     DevBuf<uint8_t> dfa_blob_, dfa_accept_;
     DevBuf<float> dfa_masked_;   // [rows][V]

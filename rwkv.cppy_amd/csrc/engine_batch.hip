@@ -321,7 +321,7 @@ bool Engine::generate_slots(size_t Q, const BatchSamplingParams & p, size_t n, u
         {
             const LaunchTimerScope timed(this, timing_);
             d.step = (uint32_t)i;
-            ok = (!qc || turnover(i, cur)) && (!c || launch_dfa_mask(stream_, d, constraint_lds_limit())) &&
+            ok = (!qc || turnover(i, cur)) && (!c || dfa_mask(d)) &&
                  (!lp || launch_logprobs(stream_, a)) && launch_sample(stream_, a, &sf) &&
                  (!c || launch_dfa_advance(stream_, d)) && launch_gen_snapshot(stream_, g, (uint32_t)i, cur, glogits_, gsnap_state_, gsnap_logits_);
         }

@@ -129,18 +129,48 @@ int Engine::vocab_bytes(const uint32_t * offsets, const uint8_t * bytes) {
     return 0;
 }
 
+int Engine::constraint_table(uint32_t n_states, const uint16_t * next, const uint8_t * accepting) {
+    if (hipSetDevice(m_->device) != hipSuccess) return 2;
+    DfaTable t;
+    DevBuf<uint8_t> blob, accept;
+    if (n_states != 0) {
+        if (!next || !accepting || !dfa_compress(next, n_states, t)) return 1;
+        if (!blob.alloc(t.blob.size()) || !accept.alloc(n_states)) return 2;
+        if (hipMemcpy(blob, t.blob.data(), t.blob.size(), hipMemcpyHostToDevice) != hipSuccess ||
+            hipMemcpy(accept, accepting, n_states, hipMemcpyHostToDevice) != hipSuccess)
+            return 2;
+    }
+    // queued work of this context may still read the old table
+    if (hipStreamSynchronize(stream_) != hipSuccess) return 2;
+    res_blob_ = std::move(blob);
+    res_accept_ = std::move(accept);
+    res_states_ = n_states;
+    res_cls_ = n_states ? t.n_cls : 0;
+    return 0;
+}
+
 int Engine::constraint_reserve(const ConstraintParams & c, size_t Q, size_t rows) {
     if (hipSetDevice(m_->device) != hipSuccess) return 2;
     const size_t K = (size_t)kBatchMax, V = m_->n_vocab;
-    if (!m_->vocab_head.get() || !c.next || !c.accepting || !c.state || Q == 0 || Q > K || rows == 0 || rows > Q) return 1;
-    if (!dfa_compress(c.next, c.n_states, dfa_tab_)) return 1;
+    dfa_resident_ = !c.next && !c.accepting;
+    if (!m_->vocab_head.get() || (!dfa_resident_ && (!c.next || !c.accepting)) || !c.state || Q == 0 || Q > K || rows == 0 || rows > Q)
+        return 1;
+    if (dfa_resident_) {
+        if (res_states_ == 0 || c.n_states != res_states_) return 1;
+    } else if (!dfa_compress(c.next, c.n_states, dfa_tab_)) {
+        return 1;
+    }
     for (size_t s = 0; s < Q; s++)
         if (c.state[s] >= c.n_states) return 1;
-    if (dfa_lds_bytes(dfa_tab_.n_states, dfa_tab_.n_cls) > constraint_lds_limit()) return 1;
-    const size_t blob = dfa_tab_.blob.size(), tile = rows * V;
-    if (!grow(dfa_blob_, blob, doubled(4096, blob), GRAPHS_NONE) ||
-        !grow(dfa_accept_, c.n_states, doubled(256, c.n_states), GRAPHS_NONE) ||
-        !grow(dfa_masked_, tile, doubled(V, tile), GRAPHS_NONE) || !grow(dfa_words_, 3 * K + 3, 3 * K + 3, GRAPHS_NONE) ||
+    const size_t tile = rows * V;
+    if (!dfa_resident_) {
+        if (dfa_lds_bytes(dfa_tab_.n_states, dfa_tab_.n_cls) > constraint_lds_limit()) return 1;
+        const size_t blob = dfa_tab_.blob.size();
+        if (!grow(dfa_blob_, blob, doubled(4096, blob), GRAPHS_NONE) ||
+            !grow(dfa_accept_, c.n_states, doubled(256, c.n_states), GRAPHS_NONE))
+            return 2;
+    }
+    if (!grow(dfa_masked_, tile, doubled(V, tile), GRAPHS_NONE) || !grow(dfa_words_, 3 * K + 3, 3 * K + 3, GRAPHS_NONE) ||
         !grow(dfa_snap_, m_->state_len + V, m_->state_len + V, GRAPHS_NONE))
         return 2;
     return 0;
@@ -148,28 +178,38 @@ int Engine::constraint_reserve(const ConstraintParams & c, size_t Q, size_t rows
 
 bool Engine::dfa_begin(const ConstraintParams & c, size_t Q, size_t rows, DfaArgs & d) {
     const size_t K = (size_t)kBatchMax;
-    if (dfa_tab_.n_states != c.n_states || dfa_tab_.blob.empty() || dfa_masked_.size() < rows * m_->n_vocab) return false;
+    if (dfa_resident_ != (!c.next && !c.accepting) || dfa_masked_.size() < rows * m_->n_vocab) return false;
+    if (dfa_resident_ ? res_states_ != c.n_states || res_states_ == 0 : dfa_tab_.n_states != c.n_states || dfa_tab_.blob.empty())
+        return false;
     dfa_h_.assign(3 * K + 3, 0);
     for (size_t s = 0; s < Q; s++) dfa_h_[s] = c.state[s];
-    HIP_OK(hipMemcpyAsync(dfa_blob_, dfa_tab_.blob.data(), dfa_tab_.blob.size(), hipMemcpyHostToDevice, stream_));
-    HIP_OK(hipMemcpyAsync(dfa_accept_, c.accepting, c.n_states, hipMemcpyHostToDevice, stream_));
+    if (!dfa_resident_) {
+        HIP_OK(hipMemcpyAsync(dfa_blob_, dfa_tab_.blob.data(), dfa_tab_.blob.size(), hipMemcpyHostToDevice, stream_));
+        HIP_OK(hipMemcpyAsync(dfa_accept_, c.accepting, c.n_states, hipMemcpyHostToDevice, stream_));
+    }
     HIP_OK(hipMemcpyAsync(dfa_words_, dfa_h_.data(), (3 * K + 3) * 4, hipMemcpyHostToDevice, stream_));
     memset(&d, 0, sizeof(d));
     d.head = (const uint4 *)m_->vocab_head.get();
     d.meta = (const uint2 *)m_->vocab_meta.get();
     d.tail = m_->vocab_tail;
     d.V = (int)m_->n_vocab;
-    d.tab = (const uint16_t *)dfa_blob_.get();
-    d.accepting = dfa_accept_;
-    d.n_states = dfa_tab_.n_states;
-    d.n_cls = dfa_tab_.n_cls;
+    d.tab = (const uint16_t *)(dfa_resident_ ? res_blob_ : dfa_blob_).get();
+    d.accepting = dfa_resident_ ? res_accept_ : dfa_accept_;
+    d.n_states = c.n_states;
+    d.n_cls = dfa_resident_ ? res_cls_ : dfa_tab_.n_cls;
     d.rows = (int)rows;
     d.masked = dfa_masked_;
     d.state = dfa_words_;
     d.ended = dfa_words_ + K;
     d.n_allowed = dfa_words_ + 2 * K;
     d.ticket = dfa_words_ + 3 * K;
+    // a table passed with the call, or a resident one that fits the LDS: k_dfa_mask; else k_dfa_mask_mem
+    dfa_mem_ = dfa_resident_ && dfa_lds_bytes(d.n_states, d.n_cls) > constraint_lds_limit();
     return true;
+}
+
+bool Engine::dfa_mask(const DfaArgs & d) {
+    return dfa_mem_ ? launch_dfa_mask_mem(stream_, d) : launch_dfa_mask(stream_, d, constraint_lds_limit());
 }
 
 bool Engine::dfa_copy_out(const ConstraintParams & c, size_t Q) {
@@ -196,7 +236,7 @@ bool Engine::sample(const SamplingParams & p, uint32_t * token_out, const Logpro
         d.fin_step = a.fin_step = d.done + 1;
         d.tokens = a.tok;
         a.logits = d.masked;
-        if (!launch_dfa_mask(stream_, d, constraint_lds_limit())) return false;
+        if (!dfa_mask(d)) return false;
     }
     if (lp && !launch_logprobs(stream_, a)) return false;
     if (!launch_sample(stream_, a, &sf)) return false;
@@ -250,7 +290,7 @@ bool Engine::generate(const SamplingParams & p, size_t n, uint32_t * tokens_out,
             if (c) {
                 a.step = d.step = (uint32_t)i;
                 snap.state_from = dstate_[cur_];
-                ok = launch_dfa_mask(stream_, d, constraint_lds_limit());
+                ok = dfa_mask(d);
             }
             ok = ok && (!lp || launch_logprobs(stream_, a)) && launch_sample(stream_, a, &sf) &&
                  (!c || launch_dfa_advance(stream_, d, &snap));

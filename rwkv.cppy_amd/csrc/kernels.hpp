@@ -348,6 +348,10 @@ struct DfaSnap {
 // masked[r][t] = allowed ? logits[r][t] : -inf for every live row, n_allowed[r] += the allowed tokens,
 // and (ticket set) a live row with none is finished: done = 1, fin_step = step, *active -= 1, ended = 2.
 bool launch_dfa_mask(hipStream_t st, const DfaArgs & a, size_t lds_limit);
+// The same for a table of any size below the 16-bit numbering's end (a resident one): the
+// table is read from memory, the LDS (1.5 KiB) holds the class map and the rows' words.  rows <=
+// DFA_THREADS.  Bit for bit what launch_dfa_mask writes.
+bool launch_dfa_mask_mem(hipStream_t st, const DfaArgs & a);
 // Behind the sampler: n_allowed = 0; a live row's state walks tokens[r]; a row stopped at `step`: ended = 1.
 bool launch_dfa_advance(hipStream_t st, const DfaArgs & a, const DfaSnap * snap = nullptr);
 

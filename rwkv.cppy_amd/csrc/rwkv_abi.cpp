@@ -960,11 +960,34 @@ RWKV_API bool rwkv_mi355x_vocab_bytes(struct rwkv_context * ctx, const uint32_t 
     return true;
 }
 
+RWKV_API bool rwkv_mi355x_constraint_table(struct rwkv_context * ctx, uint32_t n_states, const uint16_t * next,
+                                           const uint8_t * accepting) {
+    if (!ctx || !ctx->engine) return false;
+    ctx->last_error = RWKV_ERROR_NONE;
+    CTX_CHECK(ctx, RWKV_ERROR_CTX | RWKV_ERROR_UNSUPPORTED, false, ctx->pipe == nullptr && !ctx->model->dm.partial(),
+              "A resident constraint table is not available on a pipeline or stage context");
+    CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, n_states < 0xFFFFu && (n_states == 0 || (next && accepting)),
+              "A resident table needs n_states < 0xFFFF, next and accepting");
+    use_device(ctx);
+    const int e = ctx->engine->constraint_table(n_states, next, accepting);
+    CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, e != 1, "A next entry is neither < n_states nor 0xFFFF");
+    CTX_CHECK(ctx, RWKV_ERROR_CTX | RWKV_ERROR_ALLOC, false, e == 0, "Resident table allocation failed");
+    return true;
+}
+
+RWKV_API uint32_t rwkv_mi355x_constraint_table_states(const struct rwkv_context * ctx) {
+    return ctx && ctx->engine ? ctx->engine->constraint_table_states() : 0u;
+}
+
 // The checks and allocations of a rwkv_mi355x_constraint over Q sequences in `rows` rows, before anything is enqueued
 static bool constraint_ok(struct rwkv_context * ctx, const struct rwkv_mi355x_constraint * c, size_t Q, size_t rows,
                           ConstraintParams & out) {
-    CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, c->n_states > 0 && c->next && c->accepting && c->state,
-              "A constraint needs n_states >= 1, next, accepting and state");
+    const bool resident = !c->next && !c->accepting && ctx->engine->constraint_table_states() != 0;
+    CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, c->n_states > 0 && ((c->next && c->accepting) || resident) && c->state,
+              "A constraint needs n_states >= 1, next and accepting (both NULL: the resident table, which must be set) and state");
+    CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, !resident || c->n_states == ctx->engine->constraint_table_states(),
+              "The resident table has %" PRIu32 " states, the constraint names %" PRIu32,
+              ctx->engine->constraint_table_states(), c->n_states);
     out.n_states = c->n_states;
     out.next = c->next;
     out.accepting = c->accepting;

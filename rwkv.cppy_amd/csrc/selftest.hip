@@ -1062,10 +1062,10 @@ extern "C" RWKV_API uint32_t rwkv_mi355x_constraint_max_entries(void) {
 // r).  c->state [rows] are the rows' states; c->ended [rows] (may be NULL) marks on entry the rows
 // that are already finished (nonzero: skipped) and holds 2 on return for a live row with no allowed
 // token.  masked is uploaded first and downloaded after; n_allowed starts at 0.
-extern "C" RWKV_API bool rwkv_mi355x_selftest_dfa_mask(const float * logits, int rows, int V, const uint32_t * offsets,
-                                                      const uint8_t * bytes, const struct rwkv_mi355x_constraint * c,
-                                                      const uint32_t * stop, int n_stop, float * masked,
-                                                      uint32_t * n_allowed) {
+// mem: k_dfa_mask_mem, whatever the table's size
+static bool selftest_dfa_mask(bool mem, const float * logits, int rows, int V, const uint32_t * offsets, const uint8_t * bytes,
+                              const struct rwkv_mi355x_constraint * c, const uint32_t * stop, int n_stop, float * masked,
+                              uint32_t * n_allowed) {
     if (!logits || rows < 1 || rows > 256 || !c || !c->next || !c->accepting || !c->state || !masked || !n_allowed ||
         n_stop < 0 || n_stop > SAMPLE_MAX_STOP || (n_stop && !stop))
         return false;
@@ -1098,10 +1098,24 @@ extern "C" RWKV_API bool rwkv_mi355x_selftest_dfa_mask(const float * logits, int
         hipMemcpy(d.done, done.data(), RB, hipMemcpyHostToDevice) != hipSuccess ||
         (c->ended && hipMemcpy(d.ended, c->ended, RB, hipMemcpyHostToDevice) != hipSuccess))
         return false;
-    if (!launch_dfa_mask(nullptr, d, dfa_lds_limit(dev)) || hipDeviceSynchronize() != hipSuccess) return false;
+    if (!(mem ? launch_dfa_mask_mem(nullptr, d) : launch_dfa_mask(nullptr, d, dfa_lds_limit(dev))) ||
+        hipDeviceSynchronize() != hipSuccess)
+        return false;
     return hipMemcpy(masked, d.masked, LB, hipMemcpyDeviceToHost) == hipSuccess &&
            hipMemcpy(n_allowed, d.n_allowed, RB, hipMemcpyDeviceToHost) == hipSuccess &&
            (!c->ended || hipMemcpy(c->ended, d.ended, RB, hipMemcpyDeviceToHost) == hipSuccess);
+}
+extern "C" RWKV_API bool rwkv_mi355x_selftest_dfa_mask(const float * logits, int rows, int V, const uint32_t * offsets,
+                                                      const uint8_t * bytes, const struct rwkv_mi355x_constraint * c,
+                                                      const uint32_t * stop, int n_stop, float * masked,
+                                                      uint32_t * n_allowed) {
+    return selftest_dfa_mask(false, logits, rows, V, offsets, bytes, c, stop, n_stop, masked, n_allowed);
+}
+extern "C" RWKV_API bool rwkv_mi355x_selftest_dfa_mask_mem(const float * logits, int rows, int V, const uint32_t * offsets,
+                                                          const uint8_t * bytes, const struct rwkv_mi355x_constraint * c,
+                                                          const uint32_t * stop, int n_stop, float * masked,
+                                                          uint32_t * n_allowed) {
+    return selftest_dfa_mask(true, logits, rows, V, offsets, bytes, c, stop, n_stop, masked, n_allowed);
 }
 
 // k_dfa_advance on host operands: states [rows] (each < n_states) walk tokens [rows] (each < V) through

@@ -27,6 +27,17 @@ class Dfa:
         self.ended: Optional[np.ndarray] = None
 
 
+class ResidentDfa(Dfa):
+    """A Dfa whose table is resident on the model's context (RWKVModel.set_constraint_table): it carries
+    n_states and the start states and no arrays.  state and ended come back as for any Dfa."""
+
+    def __init__(self, n_states: int, start=0):
+        self.next = self.accepting = None
+        self.n_states = int(n_states)
+        self.start = start
+        self.state = self.ended = None
+
+
 def walk(next, q: int, data: bytes) -> int:
     """The state after the bytes of data from q, or DEAD."""
     for b in data:

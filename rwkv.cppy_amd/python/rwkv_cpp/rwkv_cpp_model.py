@@ -63,6 +63,18 @@ class RWKVModel:
             raise ValueError(f'{len(vocab)} tokens for a vocabulary of {self.n_vocab}')
         self._library.rwkv_mi355x_vocab_bytes(self._ctx, vocab)
 
+    def set_constraint_table(self, next, accepting=None, start=0):
+        """MI355X extension (rwkv_mi355x_constraint_table): keeps a constraint's table on the device,
+        compressed and uploaded once, with no limit on its size but the 16-bit state numbers (a table
+        passed with a call must fit the LDS).  Returns a constraint.ResidentDfa, which dfa= of sample,
+        generate, generate_batch and generate_queue takes like any Dfa; set its start per call.  The
+        table belongs to this context; setting another replaces it, next=None frees it (returns None)."""
+        if not self._valid:
+            raise ValueError('Model was freed')
+        from .constraint import ResidentDfa
+        n = self._library.rwkv_mi355x_constraint_table(self._ctx, next, accepting)
+        return ResidentDfa(n, start) if n else None
+
     @property
     def n_vocab(self) -> int:
         return self._library.rwkv_get_n_vocab(self._ctx)

@@ -100,17 +100,23 @@ class RWKVConstraint(ctypes.Structure):
 
 def make_constraint(rows: int, dfa) -> Optional[RWKVConstraint]:
     """An RWKVConstraint for `rows` rows from an object with next [n_states, 256], accepting [n_states]
-    and start (a state, or one per row), e.g. rwkv_cpp.constraint.Dfa; None: None.  The call's outputs
+    and start (a state, or one per row), e.g. rwkv_cpp.constraint.Dfa; None: None.  next and accepting
+    both None with n_states (constraint.ResidentDfa): the context's resident table.  The call's outputs
     are left on the object: dfa.state and dfa.ended, uint32 [rows]."""
     if dfa is None:
         return None
     import numpy as np
+    dfa.state = np.array([int(v) for v in _per_row(dfa.start, rows, 'start')], dtype=np.uint32)
+    dfa.ended = np.zeros(rows, np.uint32)
+    if dfa.next is None and dfa.accepting is None:  # the context's resident table (constraint.ResidentDfa)
+        c = RWKVConstraint(int(dfa.n_states), None, None, dfa.state.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)),
+                           dfa.ended.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)))
+        c._keep = (dfa.state, dfa.ended)
+        return c
     nxt = np.ascontiguousarray(dfa.next, dtype=np.uint16).reshape(-1, 256)
     acc = np.ascontiguousarray(dfa.accepting, dtype=np.uint8)
     if acc.size != nxt.shape[0]:
         raise ValueError('one accepting flag per state')
-    dfa.state = np.array([int(v) for v in _per_row(dfa.start, rows, 'start')], dtype=np.uint32)
-    dfa.ended = np.zeros(rows, np.uint32)
     c = RWKVConstraint(nxt.shape[0], nxt.ctypes.data_as(ctypes.POINTER(ctypes.c_uint16)),
                        acc.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8)),
                        dfa.state.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)),
@@ -369,6 +375,12 @@ class RWKVSharedLibrary:
         L.rwkv_mi355x_selftest_dfa_mask.argtypes = [P_FLOAT, ctypes.c_int, ctypes.c_int, P_U32, P_U8, P_C, P_U32,
                                                     ctypes.c_int, P_FLOAT, P_U32]
         L.rwkv_mi355x_selftest_dfa_mask.restype = ctypes.c_bool
+        L.rwkv_mi355x_selftest_dfa_mask_mem.argtypes = L.rwkv_mi355x_selftest_dfa_mask.argtypes
+        L.rwkv_mi355x_selftest_dfa_mask_mem.restype = ctypes.c_bool
+        L.rwkv_mi355x_constraint_table.argtypes = [vp, u32, ctypes.POINTER(ctypes.c_uint16), P_U8]
+        L.rwkv_mi355x_constraint_table.restype = ctypes.c_bool
+        L.rwkv_mi355x_constraint_table_states.argtypes = [vp]
+        L.rwkv_mi355x_constraint_table_states.restype = ctypes.c_uint32
         L.rwkv_mi355x_selftest_dfa_advance.argtypes = [P_U32, P_U32, ctypes.c_int, ctypes.c_int, P_U32, P_U8, u32,
                                                        ctypes.POINTER(ctypes.c_uint16)]
         L.rwkv_mi355x_selftest_dfa_advance.restype = ctypes.c_bool
@@ -689,10 +701,32 @@ class RWKVSharedLibrary:
         """The largest n_states * n_cls a constraint's compressed table may have on the current device."""
         return int(self.library.rwkv_mi355x_constraint_max_entries())
 
-    def rwkv_mi355x_selftest_dfa_mask(self, logits, vocab, dfa, stop_tokens=(), finished=None, fill: float = 7.0):
+    def rwkv_mi355x_constraint_table(self, ctx: RWKVContext, next, accepting) -> int:
+        """Sets the context's resident constraint table (next [n_states, 256] uint16, accepting
+        [n_states]); next None frees it.  Returns the number of states now resident."""
+        import numpy as np
+        if next is None:
+            n, p_next, p_acc = 0, None, None
+        else:
+            nxt = np.ascontiguousarray(next, dtype=np.uint16).reshape(-1, 256)
+            acc = np.ascontiguousarray(accepting, dtype=np.uint8)
+            if acc.size != nxt.shape[0]:
+                raise ValueError('one accepting flag per state')
+            n, p_next = nxt.shape[0], nxt.ctypes.data_as(ctypes.POINTER(ctypes.c_uint16))
+            p_acc = acc.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8))
+        if not self.library.rwkv_mi355x_constraint_table(ctx.ptr, n, p_next, p_acc):
+            raise ValueError('rwkv_mi355x_constraint_table failed, check stderr')
+        return int(self.library.rwkv_mi355x_constraint_table_states(ctx.ptr))
+
+    def rwkv_mi355x_selftest_dfa_mask_mem(self, logits, vocab, dfa, stop_tokens=(), finished=None, fill: float = 7.0):
+        """rwkv_mi355x_selftest_dfa_mask through k_dfa_mask_mem, whatever the table's size."""
+        return self.rwkv_mi355x_selftest_dfa_mask(logits, vocab, dfa, stop_tokens, finished, fill, mem=True)
+
+    def rwkv_mi355x_selftest_dfa_mask(self, logits, vocab, dfa, stop_tokens=(), finished=None, fill: float = 7.0,
+                                      mem: bool = False):
         """k_dfa_mask on host operands: logits float32 [rows, V], vocab (V bytes objects), dfa (start: the
         rows' states), finished (None, or one flag per row: the row is skipped).  Returns (masked [rows,
-        V], which starts as `fill`; n_allowed [rows]; ended [rows])."""
+        V], which starts as `fill`; n_allowed [rows]; ended [rows]).  mem: k_dfa_mask_mem instead."""
         import numpy as np
         from .constraint import pack_vocab
         logits = np.ascontiguousarray(logits, dtype=np.float32)
@@ -705,7 +739,8 @@ class RWKVSharedLibrary:
         n_allowed = np.zeros(rows, np.uint32)
         stops = np.array(list(stop_tokens) or [0], np.uint32)
         P_U32 = ctypes.POINTER(ctypes.c_uint32)
-        if not self.library.rwkv_mi355x_selftest_dfa_mask(
+        fn = self.library.rwkv_mi355x_selftest_dfa_mask_mem if mem else self.library.rwkv_mi355x_selftest_dfa_mask
+        if not fn(
                 logits.ctypes.data_as(P_FLOAT), rows, V, offsets.ctypes.data_as(P_U32),
                 data.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8)), ctypes.byref(c), stops.ctypes.data_as(P_U32),
                 len(stop_tokens), masked.ctypes.data_as(P_FLOAT), n_allowed.ctypes.data_as(P_U32)):
