@@ -627,9 +627,9 @@ struct rwkv_mi355x_selftest_mm_entry {
 /* Runs a whole group of n <= 8 entries over x [T][K] (host, shared by the entries, in entry 0's
  * activation format) through one launcher: form 0 = launch_mm_group (k_mm / k_mm_small, or k_fmm where
  * it applies), 1 = launch_mvb_group (k_mvb), 2 = launch_qgemm (token-tile input; emitting entries with
- * out_tiled), 3 = launch_fmm_group.  split (0, 1, 4, 8) is MMGroup::split.  *launched = 1 when the
- * launcher took the group, 0 when forms 1 / 3 declined it (the outputs are then untouched).  false only
- * on an error. */
+ * out_tiled), 3 = launch_fmm_group, 4 = launch_mvt_group (k_mvt: quantized weights, 2 <= T <= 16).
+ * split (0, 1, 4, 8) is MMGroup::split.  *launched = 1 when the launcher took the group, 0 when forms
+ * 1 / 3 / 4 declined it (the outputs are then untouched).  false only on an error. */
 RWKV_API bool rwkv_mi355x_selftest_matmul_group(int form, int split, int T, int K, const float * x, int n,
                                                 struct rwkv_mi355x_selftest_mm_entry * entries, int * launched);
 

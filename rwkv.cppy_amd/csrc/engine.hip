@@ -145,6 +145,8 @@ bool Engine::init() {
     fuse_ = df ? (unsigned)strtoul(df, nullptr, 0) & FUSE_ALL : FUSE_DEFAULT | (m_->major == 4 ? FUSE_FFNCO : 0u);
     const char * wc = getenv("RWKV_MI355X_WKV_CHUNK");  // 1: chunk-parallel wkv6 (not bit-exact)
     wkv_chunk_ = wc && wc[0] == '1';
+    const char * bm = getenv("RWKV_MI355X_BATCH_MMA_MIN");  // batched decode: contexts from which k_mvt runs (17: never)
+    if (bm) batch_mma_min_ = std::max(2, atoi(bm));
     // the fused decode prologues hold LayerNorm inputs in registers up to n_embed 4096
     if (m_->n_embed > 4096 || m_->n_embed % 64) generic_decode_ = true;
     return ensure_workspace(1) && init_state(dstate_[0]);
@@ -534,7 +536,10 @@ bool Engine::debug_set(const char * name, long long value) {
     else if (n == "wo_prepoll") wo_prepoll_ = value != 0;
     else if (n == "ffn_wdelay" && value >= -1 && value <= 10000) ffn_wdelay_ = (int)value;
     else if (n == "ffn_prepoll") ffn_prepoll_ = value != 0;
-    else return false;
+    else if (n == "batch_mma_min" && value >= 2) {  // 17 or more: the route is off
+        batch_mma_min_ = (int)std::min<long long>(value, 1 << 20);
+        drop_batch_graphs();  // they captured the other matvec
+    } else return false;
     // the decode graphs captured the old values; the new decode program may lack a hand-off
     // (GranuleMem::clear_tagged)
     (void)hipStreamSynchronize(stream_);

@@ -596,6 +596,7 @@ class Engine : public KLaunchTimer, private Workspace, private GenSlots {
     enum MMRoute { MM_QGEMM, MM_ROWS, MM_KMM };  // the sequence GEMM; rows as contexts; k_mm
     MMRoute mm_route(int T, int wtype, bool rows, bool tile_acts) const;
     bool mm_dispatch(MMGroup & g, int wtype, MMRoute route);
+    bool rows_mvt(const MMGroup & g, int wtype) const;
     bool mm_launch(MMGroup & g, int wtype, MMRoute route);
     // the GEMM scratch, grown to the exact size a group needs (captured batched graphs point at it)
     DevBuf<float> gy_;    // scratch y of emit-only GEMM entries
@@ -607,6 +608,10 @@ class Engine : public KLaunchTimer, private Workspace, private GenSlots {
     DevBuf<uint64_t> ptab_;             // its segment tables and row lists
     DevBuf<float> pend_x_;              // [kBatchMax][C] the residual rows that end its prompts
     int batch_gemm_min_ = 16;  // batched decode: contexts from which the quantized matmuls take the sequence GEMM
+    // batched decode: contexts from which (up to batch_gemm_min_) the quantized matmuls take k_mvt, the
+    // int8-MFMA tile matvec, instead of k_mvb; 17 or more: never.  RWKV_MI355X_BATCH_MMA_MIN /
+    // rwkv_mi355x_debug_set "batch_mma_min"; the default is measured
+    int batch_mma_min_ = 17;
     // batched decode (eval_batch): the engine-owned staging buffers / graphs
     DevBuf<float> bstate_[2], blogits_;  // staging of host states / logits: a power of two >= B rows
     struct BatchGraph {

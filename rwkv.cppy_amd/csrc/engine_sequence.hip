@@ -84,6 +84,11 @@ Engine::MMRoute Engine::mm_route(int T, int wtype, bool rows, bool tile_acts) co
     return T < 2 || !wtype_quantized(wtype) || use_mm_ ? MM_KMM : MM_QGEMM;
 }
 
+// A rows-as-contexts group of the k_mvt range: batch_mma_min_ <= T < batch_gemm_min_, a shape it covers
+bool Engine::rows_mvt(const MMGroup & g, int wtype) const {
+    return g.T >= batch_mma_min_ && g.T < batch_gemm_min_ && mvt_covers(g, wtype);
+}
+
 // Sequence matmuls on quantized weights go to the int8-MFMA GEMM; entries that only emit get
 // a scratch y, and emission is a separate quantization pass (same bits as k_mm's epilogue).
 bool Engine::mm_dispatch(MMGroup & g, int wtype, MMRoute route) {
@@ -107,11 +112,15 @@ bool Engine::mm_dispatch(MMGroup & g, int wtype, MMRoute route) {
         }
     }
     if (route == MM_ROWS) {
-        // k_mvb; float weights (the F16 head, LoRA) over 16+ contexts: the f32-MFMA form; k_mm for
-        // the shapes neither covers -- the same bits
+        // k_mvt (quantized weights from batch_mma_min_ contexts on) or k_mvb; float weights (the F16
+        // head, LoRA) over 16+ contexts: the f32-MFMA form; k_mm for the shapes none covers -- the same bits
         bool launched = false;
         if (!launch_fmm_group(stream_, g, wtype, &launched)) return false;
         if (launched) return true;
+        if (rows_mvt(g, wtype)) {
+            if (!launch_mvt_group(stream_, g, wtype, &launched)) return false;
+            if (launched) return true;
+        }
         if (!launch_mvb_group(stream_, g, wtype, &launched)) return false;
         if (launched) return true;
     }
@@ -176,9 +185,9 @@ bool Engine::mm_launch(MMGroup & g, int wtype, MMRoute route) {
         flops += 2.0 * e.W.M * e.W.K * g.T;
     }
     // kernel class = the template instantiation rocprofv3 reports: k_mm<WF, RPW, NT>; every launch of
-    // the rows-as-contexts route goes by k_mvb's name
+    // the rows-as-contexts route goes by k_mvb's name, or k_mvt's where that kernel takes the group
     const std::string name = route == MM_QGEMM ? "k_qgemm<" + std::to_string(wtype) + ">"
-                           : route == MM_ROWS ? "k_mvb<" + std::to_string(wtype) + ">"
+                           : route == MM_ROWS ? (rows_mvt(g, wtype) ? "k_mvt<" : "k_mvb<") + std::to_string(wtype) + ">"
                                               : "k_mm<" + std::to_string(wtype) + ", " + (emit ? "8" : "2") + ", " + (g.T == 1 ? "1" : "4") + ">";
     const int si = add_stat(name);
     hipEvent_t a, b;  // a pair from the pool, as a timed RK_LAUNCH takes one

@@ -25,6 +25,10 @@ extern int kQgCUs;
 // Batched decode matvec (mv_batch.hip): the T rows are T independent contexts; same results as
 // launch_mm_group.  *launched = false (and nothing enqueued) for shapes it does not cover.
 bool launch_mvb_group(hipStream_t st, MMGroup & g, int wtype, bool * launched);
+// The same over 2..16 contexts on the int8 MFMA (mv_tile.hip, k_mvt): quantized weights only, the
+// same bits; *launched = false (and nothing enqueued) for everything else.
+bool launch_mvt_group(hipStream_t st, MMGroup & g, int wtype, bool * launched);
+bool mvt_covers(const MMGroup & g, int wtype);  // the groups launch_mvt_group takes
 
 // ---- elementwise / recurrence kernels -----------------------------------------------------
 // x[t] = LN(emb[tokens[t]]; w, b)   (rwkv_graph.inc:654-658); tokens.imm needs T == 1

@@ -204,7 +204,7 @@ extern "C" RWKV_API bool rwkv_mi355x_selftest_matmul_group(int form, int split, 
                                                            struct rwkv_mi355x_selftest_mm_entry * ent, int * launched) {
     if (!launched) return false;
     *launched = 0;
-    if (form < 0 || form > 3 || (split != 0 && split != 1 && split != 4 && split != 8)) return false;
+    if (form < 0 || form > 4 || (split != 0 && split != 1 && split != 4 && split != 8)) return false;
     if (T <= 0 || K <= 0 || K % 32 || !x || n < 1 || n > MM_MAX_ENTRIES || !ent) return false;
     const int wtype = ent[0].wtype;
     if (form == 2 && (!wtype_quantized(wtype) || T < 2)) return false;
@@ -292,7 +292,8 @@ extern "C" RWKV_API bool rwkv_mi355x_selftest_matmul_group(int form, int split, 
             case 0: ok = launch_mm_group(nullptr, g, wtype); break;
             case 1: ok = launch_mvb_group(nullptr, g, wtype, &ran); break;
             case 2: ok = launch_qgemm(nullptr, g, wtype); break;
-            default: ok = launch_fmm_group(nullptr, g, wtype, &ran); break;
+            case 4: ok = launch_mvt_group(nullptr, g, wtype, &ran); break;
+            default: ok = launch_fmm_group(nullptr, g, wtype, &ran); break;  // form 3
         }
     }
     ok = ok && hipDeviceSynchronize() == hipSuccess;
