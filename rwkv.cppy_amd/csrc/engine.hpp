@@ -246,6 +246,13 @@ struct ConstraintParams {
     uint32_t * ended = nullptr;
 };
 
+// The optional parts of a generation call, each NULL or checked by the caller as its type says
+struct GenExtras {
+    const LogprobsOut * lp = nullptr;
+    const FilterParams * f = nullptr;
+    const ConstraintParams * c = nullptr;
+};
+
 class Engine : public KLaunchTimer, private Workspace, private GenSlots {
   public:
     explicit Engine(DeviceModel * m) : m_(m) {}
@@ -267,22 +274,19 @@ class Engine : public KLaunchTimer, private Workspace, private GenSlots {
     // n tokens (and, logits_out != NULL, of the final logits) and one synchronisation at the end.  A
     // hand-off timeout anywhere in the chain fails the call (no re-run: the state has moved on).
     // Both need logits_valid().
-    // lp != NULL (all four generation calls): k_logprobs runs in front of every sampler launch and the
+    // x.lp != NULL (all four generation calls): k_logprobs runs in front of every sampler launch and the
     // sampler's LP form writes the drawn token's log-probability; the device arrays start as 0xFF bytes
-    // and are copied out with the tokens.  lp == NULL: the call as it was.
-    // f != NULL with some filter on in some row (all four calls): the sampler launches are those of
+    // and are copied out with the tokens.  x.lp == NULL: the call as it was.
+    // x.f != NULL with some filter on in some row (all four calls): the sampler launches are those of
     // sample_filter.hip, the per-sequence values uploaded beside the other per-sequence parameters.
-    // f == NULL, or every value off: the call as it was.
-    // c != NULL (all four calls; constraint_reserve(c, ...) has passed): k_dfa_mask in front of every
+    // x.f == NULL, or every value off: the call as it was.
+    // x.c != NULL (all four calls; constraint_reserve(*x.c, ...) has passed): k_dfa_mask in front of every
     // k_logprobs / sampler launch, which read its masked rows, and k_dfa_advance behind the sampler
     // (constrain.hip).  A row with no allowed token ends before its draw.  sample and
     // generate then run the sampler's rows form over one row (the same arithmetic): a finished row
-    // needs its done word.  c == NULL: the call as it was.
-    bool sample(const SamplingParams & p, uint32_t * token_out, const LogprobsOut * lp = nullptr,
-                const FilterParams * f = nullptr, const ConstraintParams * c = nullptr);
-    bool generate(const SamplingParams & p, size_t n, uint32_t * tokens_out, float * logits_out,
-                  const LogprobsOut * lp = nullptr, const FilterParams * f = nullptr,
-                  const ConstraintParams * c = nullptr);
+    // needs its done word.  x.c == NULL: the call as it was.
+    bool sample(const SamplingParams & p, uint32_t * token_out, const GenExtras & x);
+    bool generate(const SamplingParams & p, size_t n, uint32_t * tokens_out, float * logits_out, const GenExtras & x);
     // The vocabulary's bytes to the model (shared by its clones).  0: done, 1: offsets decrease, 2: allocation
     int vocab_bytes(const uint32_t * offsets, const uint8_t * bytes);
     // The checks and the allocations of a constrained call over Q sequences in `rows` rows, before
@@ -331,8 +335,7 @@ class Engine : public KLaunchTimer, private Workspace, private GenSlots {
     bool batch_store(size_t slot);
     bool batch_load(size_t slot);
     bool generate_batch(size_t B, const BatchSamplingParams & p, size_t n, uint32_t * tokens_out, uint32_t * lengths_out,
-                        uint32_t * steps_out, const LogprobsOut * lp = nullptr, const FilterParams * f = nullptr,
-                        const ConstraintParams * c = nullptr);
+                        uint32_t * steps_out, const GenExtras & x);
     // A queue of Q sequences (slots [0, Q)) over L = min(lanes, Q) decode rows
     // (rwkv_mi355x_generate_queue): per step k_gen_turnover frees the lanes of ended
     // sequences and admits the waiting ones, k_gen_move copies a capped sequence's result out of its
@@ -340,8 +343,7 @@ class Engine : public KLaunchTimer, private Workspace, private GenSlots {
     // lanes as in generate_batch.  Every per-row array of p is [Q]; max_tokens[s] in [1, n].
     bool generate_queue(size_t Q, size_t lanes, const BatchSamplingParams & p, const uint32_t * max_tokens, size_t n,
                         uint32_t * tokens_out, uint32_t * lengths_out, uint32_t * lane_out, uint32_t * start_out,
-                        uint32_t * steps_out, const LogprobsOut * lp = nullptr, const FilterParams * f = nullptr,
-                        const ConstraintParams * c = nullptr);
+                        uint32_t * steps_out, const GenExtras & x);
     // Batched prefill (rwkv_mi355x_prefill_batch; engine_prefill.hip): n_rows prompts, concatenated in
     // tokens, are packed into chunks of at most prefill_chunk_ tokens (prefill_plan.hpp) and each chunk
     // runs as one sequence pass whose token shift and WKV kernels follow a segment table (SegTab);
@@ -640,8 +642,7 @@ class Engine : public KLaunchTimer, private Workspace, private GenSlots {
         uint32_t *lane_out, *start_out;
     };
     bool generate_slots(size_t Q, const BatchSamplingParams & p, size_t n, uint32_t * tokens_out, uint32_t * lengths_out,
-                        uint32_t * steps_out, const LogprobsOut * lp, const FilterParams * f, const ConstraintParams * c,
-                        const QueueCall * qc);
+                        uint32_t * steps_out, const GenExtras & x, const QueueCall * qc);
     // the per-sequence arrays of Q sequences to the device and the token buffer [Q][n] set to
     // 0xFFFFFFFF; the sampler's arguments for `rows` rows
     bool gen_upload(size_t Q, const BatchSamplingParams & p, size_t n);

@@ -210,16 +210,15 @@ SampleArgs Engine::gen_sample_args(size_t rows, const BatchSamplingParams & p, s
 }
 
 bool Engine::generate_batch(size_t B, const BatchSamplingParams & p, size_t n, uint32_t * tokens_out,
-                            uint32_t * lengths_out, uint32_t * steps_out, const LogprobsOut * lp, const FilterParams * f,
-                            const ConstraintParams * c) {
-    return generate_slots(B, p, n, tokens_out, lengths_out, steps_out, lp, f, c, nullptr);
+                            uint32_t * lengths_out, uint32_t * steps_out, const GenExtras & x) {
+    return generate_slots(B, p, n, tokens_out, lengths_out, steps_out, x, nullptr);
 }
 
 bool Engine::generate_queue(size_t Q, size_t lanes, const BatchSamplingParams & p, const uint32_t * max_tokens, size_t n,
                             uint32_t * tokens_out, uint32_t * lengths_out, uint32_t * lane_out, uint32_t * start_out,
-                            uint32_t * steps_out, const LogprobsOut * lp, const FilterParams * f, const ConstraintParams * c) {
+                            uint32_t * steps_out, const GenExtras & x) {
     const QueueCall qc{lanes, max_tokens, lane_out, start_out};
-    return generate_slots(Q, p, n, tokens_out, lengths_out, steps_out, lp, f, c, &qc);
+    return generate_slots(Q, p, n, tokens_out, lengths_out, steps_out, x, &qc);
 }
 
 // The driver of both calls.  Per step one sampler launch over the rows' logits (per-sequence
@@ -240,8 +239,8 @@ bool Engine::generate_queue(size_t Q, size_t lanes, const BatchSamplingParams & 
 // the mask as a stop token finishes one, at this step: the snapshot that follows takes the state and
 // the (unmasked) logits the previous step left.
 bool Engine::generate_slots(size_t Q, const BatchSamplingParams & p, size_t n, uint32_t * tokens_out, uint32_t * lengths_out,
-                            uint32_t * steps_out, const LogprobsOut * lp, const FilterParams * f, const ConstraintParams * c,
-                            const QueueCall * qc) {
+                            uint32_t * steps_out, const GenExtras & x, const QueueCall * qc) {
+    const auto [lp, f, c] = x;
     HIP_OK(hipSetDevice(m_->device));
     // ---- the arguments; the per-sequence values of p are the caller's to check (BatchSamplingParams)
     if (Q == 0 || Q > gslots_ || n == 0 || !tokens_out || !lengths_out || !p.temperature || !p.top_p || !p.seed ||

@@ -219,8 +219,8 @@ bool Engine::dfa_copy_out(const ConstraintParams & c, size_t Q) {
     return true;
 }
 
-bool Engine::sample(const SamplingParams & p, uint32_t * token_out, const LogprobsOut * lp, const FilterParams * f,
-                    const ConstraintParams * c) {
+bool Engine::sample(const SamplingParams & p, uint32_t * token_out, const GenExtras & x) {
+    const auto [lp, f, c] = x;
     HIP_OK(hipSetDevice(m_->device));
     if (!logits_valid_ || !token_out) return false;
     SampleArgs a;
@@ -247,8 +247,8 @@ bool Engine::sample(const SamplingParams & p, uint32_t * token_out, const Logpro
     return handoff_check();
 }
 
-bool Engine::generate(const SamplingParams & p, size_t n, uint32_t * tokens_out, float * logits_out,
-                      const LogprobsOut * lp, const FilterParams * f, const ConstraintParams * c) {
+bool Engine::generate(const SamplingParams & p, size_t n, uint32_t * tokens_out, float * logits_out, const GenExtras & x) {
+    const auto [lp, f, c] = x;
     HIP_OK(hipSetDevice(m_->device));
     if (!logits_valid_ || !tokens_out || n == 0) return false;
     SampleArgs a;

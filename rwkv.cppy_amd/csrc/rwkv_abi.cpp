@@ -615,9 +615,17 @@ static bool sampling_ok(struct rwkv_context * ctx, const struct rwkv_mi355x_samp
     return true;
 }
 
+// The optional parts of a generation call as the engine takes them: each *_ok below that is given
+// its part fills the conversion and points the GenExtras at it.  On the stack of the call's body.
+struct Extras : GenExtras {
+    LogprobsOut lo;
+    FilterParams fp;
+    ConstraintParams cp;
+};
+
 // The checks of a rwkv_mi355x_logprobs (NULL: none asked for), the first of a call's argument checks:
 // they need nothing but the model's vocabulary.
-static bool logprobs_ok(struct rwkv_context * ctx, const struct rwkv_mi355x_logprobs * lp, LogprobsOut & out) {
+static bool logprobs_ok(struct rwkv_context * ctx, const struct rwkv_mi355x_logprobs * lp, Extras & x) {
     if (!lp) return true;
     CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, lp->top_k <= RWKV_MI355X_MAX_TOP_LOGPROBS, "top_k %" PRIu32 " is above %d",
               lp->top_k, RWKV_MI355X_MAX_TOP_LOGPROBS);
@@ -626,10 +634,11 @@ static bool logprobs_ok(struct rwkv_context * ctx, const struct rwkv_mi355x_logp
     CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, lp->token_logprob != nullptr, "NULL token_logprob");
     CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, lp->top_k == 0 || (lp->top_ids != nullptr && lp->top_logprobs != nullptr),
               "NULL top_ids or top_logprobs with top_k > 0");
-    out.top_k = lp->top_k;
-    out.token_logprob = lp->token_logprob;
-    out.top_ids = lp->top_ids;
-    out.top_logprobs = lp->top_logprobs;
+    x.lo.top_k = lp->top_k;
+    x.lo.token_logprob = lp->token_logprob;
+    x.lo.top_ids = lp->top_ids;
+    x.lo.top_logprobs = lp->top_logprobs;
+    x.lp = &x.lo;
     return true;
 }
 
@@ -643,45 +652,119 @@ static bool logprobs_reserve(struct rwkv_context * ctx, const struct rwkv_mi355x
     return true;
 }
 
-RWKV_API bool rwkv_mi355x_sample_logprobs(struct rwkv_context * ctx, const struct rwkv_mi355x_sampling * params,
-                                          uint32_t * token_out, const struct rwkv_mi355x_logprobs * lp) {
+// The checks of a rwkv_mi355x_filters (NULL: none) over `rows` rows, before any GPU call
+static bool filters_ok(struct rwkv_context * ctx, const struct rwkv_mi355x_filters * f, size_t rows, Extras & x) {
+    if (!f) return true;
+    for (size_t r = 0; r < rows; r++) {
+        CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, !f->min_p || (f->min_p[r] >= 0.0f && f->min_p[r] <= 1.0f),
+                  "Row %zu: min_p %f is outside [0, 1]", r, f->min_p[r]);
+        CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, !f->typical_p || (f->typical_p[r] >= 0.0f && f->typical_p[r] <= 1.0f),
+                  "Row %zu: typical_p %f is outside [0, 1]", r, f->typical_p[r]);
+    }
+    x.fp.top_k = f->top_k;
+    x.fp.min_p = f->min_p;
+    x.fp.typical_p = f->typical_p;
+    x.f = &x.fp;
+    return true;
+}
+
+// The checks and allocations of a rwkv_mi355x_constraint (NULL: none) over Q sequences in `rows` rows,
+// before anything is enqueued: the last of a call's argument checks and the first step that may allocate
+static bool constraint_ok(struct rwkv_context * ctx, const struct rwkv_mi355x_constraint * c, size_t Q, size_t rows,
+                          Extras & x) {
+    if (!c) return true;
+    const bool resident = !c->next && !c->accepting && ctx->engine->constraint_table_states() != 0;
+    CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, c->n_states > 0 && ((c->next && c->accepting) || resident) && c->state,
+              "A constraint needs n_states >= 1, next and accepting (both NULL: the resident table, which must be set) and state");
+    CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, !resident || c->n_states == ctx->engine->constraint_table_states(),
+              "The resident table has %" PRIu32 " states, the constraint names %" PRIu32,
+              ctx->engine->constraint_table_states(), c->n_states);
+    x.cp.n_states = c->n_states;
+    x.cp.next = c->next;
+    x.cp.accepting = c->accepting;
+    x.cp.state = c->state;
+    x.cp.ended = c->ended;
+    use_device(ctx);
+    const int e = ctx->engine->constraint_reserve(x.cp, Q, rows);
+    CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, e != 1,
+              "Constraint rejected: no vocabulary bytes set, a next entry or start state >= n_states, or a table over the "
+              "LDS limit (%zu bytes)", ctx->engine->constraint_lds_limit());
+    CTX_CHECK(ctx, RWKV_ERROR_CTX | RWKV_ERROR_ALLOC, false, e == 0, "Constraint buffer allocation failed");
+    x.c = &x.cp;
+    return true;
+}
+
+// ---- sample and generate: one body each; lp, f and c may each be NULL.  The exported plain,
+// _logprobs, _filtered and _constrained calls are forwards that name the parts they take.
+static bool sample_call(struct rwkv_context * ctx, const struct rwkv_mi355x_sampling * params, uint32_t * token_out,
+                        const struct rwkv_mi355x_logprobs * lp, const struct rwkv_mi355x_filters * f,
+                        const struct rwkv_mi355x_constraint * c) {
     if (!ctx || !ctx->engine) return false;
     ctx->last_error = RWKV_ERROR_NONE;
     SamplingParams sp;
-    LogprobsOut lo;
-    if (!logprobs_ok(ctx, lp, lo) || !sampling_ok(ctx, params, sp)) return false;
+    Extras x;
+    if (!logprobs_ok(ctx, lp, x) || !sampling_ok(ctx, params, sp) || !filters_ok(ctx, f, 1, x)) return false;
     CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, token_out != nullptr, "NULL token_out");
-    if (!logprobs_reserve(ctx, lp, 1, 1)) return false;
+    if (!constraint_ok(ctx, c, 1, 1, x) || !logprobs_reserve(ctx, lp, 1, 1)) return false;
     use_device(ctx);
-    CTX_CHECK(ctx, RWKV_ERROR_CTX, false, ctx->engine->sample(sp, token_out, lp ? &lo : nullptr), "GPU sampling failed");
+    CTX_CHECK(ctx, RWKV_ERROR_CTX, false, ctx->engine->sample(sp, token_out, x), "GPU sampling failed");
+    return true;
+}
+
+static bool generate_call(struct rwkv_context * ctx, const struct rwkv_mi355x_sampling * params, size_t n,
+                          uint32_t * tokens_out, float * logits_out, const struct rwkv_mi355x_logprobs * lp,
+                          const struct rwkv_mi355x_filters * f, const struct rwkv_mi355x_constraint * c) {
+    if (!ctx || !ctx->engine) return false;
+    ctx->last_error = RWKV_ERROR_NONE;
+    SamplingParams sp;
+    Extras x;
+    if (!logprobs_ok(ctx, lp, x) || !sampling_ok(ctx, params, sp) || !filters_ok(ctx, f, 1, x)) return false;
+    CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, n > 0 && n <= 65536, "Token count %zu is outside [1, 65536]", n);
+    CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, tokens_out != nullptr, "NULL tokens_out");
+    if (!constraint_ok(ctx, c, 1, 1, x) || !logprobs_reserve(ctx, lp, 1, n)) return false;
+    use_device(ctx);
+    CTX_CHECK(ctx, RWKV_ERROR_CTX, false, ctx->engine->generate(sp, n, tokens_out, logits_out, x), "GPU generation failed");
     return true;
 }
 
 RWKV_API bool rwkv_mi355x_sample(struct rwkv_context * ctx, const struct rwkv_mi355x_sampling * params,
                                  uint32_t * token_out) {
-    return rwkv_mi355x_sample_logprobs(ctx, params, token_out, nullptr);
+    return sample_call(ctx, params, token_out, nullptr, nullptr, nullptr);
 }
-
-RWKV_API bool rwkv_mi355x_generate_logprobs(struct rwkv_context * ctx, const struct rwkv_mi355x_sampling * params,
-                                            size_t n, uint32_t * tokens_out, float * logits_out,
-                                            const struct rwkv_mi355x_logprobs * lp) {
-    if (!ctx || !ctx->engine) return false;
-    ctx->last_error = RWKV_ERROR_NONE;
-    SamplingParams sp;
-    LogprobsOut lo;
-    if (!logprobs_ok(ctx, lp, lo) || !sampling_ok(ctx, params, sp)) return false;
-    CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, n > 0 && n <= 65536, "Token count %zu is outside [1, 65536]", n);
-    CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, tokens_out != nullptr, "NULL tokens_out");
-    if (!logprobs_reserve(ctx, lp, 1, n)) return false;
-    use_device(ctx);
-    CTX_CHECK(ctx, RWKV_ERROR_CTX, false, ctx->engine->generate(sp, n, tokens_out, logits_out, lp ? &lo : nullptr),
-              "GPU generation failed");
-    return true;
+RWKV_API bool rwkv_mi355x_sample_logprobs(struct rwkv_context * ctx, const struct rwkv_mi355x_sampling * params,
+                                          uint32_t * token_out, const struct rwkv_mi355x_logprobs * lp) {
+    return sample_call(ctx, params, token_out, lp, nullptr, nullptr);
+}
+RWKV_API bool rwkv_mi355x_sample_filtered(struct rwkv_context * ctx, const struct rwkv_mi355x_sampling * params,
+                                          uint32_t * token_out, const struct rwkv_mi355x_logprobs * lp,
+                                          const struct rwkv_mi355x_filters * f) {
+    return sample_call(ctx, params, token_out, lp, f, nullptr);
+}
+RWKV_API bool rwkv_mi355x_sample_constrained(struct rwkv_context * ctx, const struct rwkv_mi355x_sampling * params,
+                                             uint32_t * token_out, const struct rwkv_mi355x_logprobs * lp,
+                                             const struct rwkv_mi355x_filters * f, const struct rwkv_mi355x_constraint * c) {
+    return sample_call(ctx, params, token_out, lp, f, c);
 }
 
 RWKV_API bool rwkv_mi355x_generate(struct rwkv_context * ctx, const struct rwkv_mi355x_sampling * params, size_t n,
                                    uint32_t * tokens_out, float * logits_out) {
-    return rwkv_mi355x_generate_logprobs(ctx, params, n, tokens_out, logits_out, nullptr);
+    return generate_call(ctx, params, n, tokens_out, logits_out, nullptr, nullptr, nullptr);
+}
+RWKV_API bool rwkv_mi355x_generate_logprobs(struct rwkv_context * ctx, const struct rwkv_mi355x_sampling * params,
+                                            size_t n, uint32_t * tokens_out, float * logits_out,
+                                            const struct rwkv_mi355x_logprobs * lp) {
+    return generate_call(ctx, params, n, tokens_out, logits_out, lp, nullptr, nullptr);
+}
+RWKV_API bool rwkv_mi355x_generate_filtered(struct rwkv_context * ctx, const struct rwkv_mi355x_sampling * params,
+                                            size_t n, uint32_t * tokens_out, float * logits_out,
+                                            const struct rwkv_mi355x_logprobs * lp, const struct rwkv_mi355x_filters * f) {
+    return generate_call(ctx, params, n, tokens_out, logits_out, lp, f, nullptr);
+}
+RWKV_API bool rwkv_mi355x_generate_constrained(struct rwkv_context * ctx, const struct rwkv_mi355x_sampling * params,
+                                               size_t n, uint32_t * tokens_out, float * logits_out,
+                                               const struct rwkv_mi355x_logprobs * lp, const struct rwkv_mi355x_filters * f,
+                                               const struct rwkv_mi355x_constraint * c) {
+    return generate_call(ctx, params, n, tokens_out, logits_out, lp, f, c);
 }
 
 // ---- batched generation: every check returns before any GPU call
@@ -774,9 +857,9 @@ static bool batch_sampling_ok(struct rwkv_context * ctx, size_t rows, const stru
 // What the two batched generation calls check alike, in this order: the log-probability arrays, the
 // context, `rows` sequences in valid slots [0, rows) over `lanes` decode rows (generate_batch: its rows),
 // n, and the two arrays every call fills.
-static bool batch_call_ok(struct rwkv_context * ctx, const struct rwkv_mi355x_logprobs * lp, LogprobsOut & lo, size_t rows,
+static bool batch_call_ok(struct rwkv_context * ctx, const struct rwkv_mi355x_logprobs * lp, Extras & x, size_t rows,
                           size_t lanes, size_t n, const uint32_t * tokens_out, const uint32_t * lengths_out) {
-    if (!logprobs_ok(ctx, lp, lo) || !batch_ctx_ok(ctx)) return false;
+    if (!logprobs_ok(ctx, lp, x) || !batch_ctx_ok(ctx)) return false;
     CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, rows > 0 && rows <= ctx->engine->batch_slots(), "%zu sequences with %zu slots reserved",
               rows, ctx->engine->batch_slots());
     CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, lanes > 0 && lanes <= (size_t)Engine::kBatchMax, "%zu lanes (1 to %d)", lanes,
@@ -788,167 +871,111 @@ static bool batch_call_ok(struct rwkv_context * ctx, const struct rwkv_mi355x_lo
     return true;
 }
 
-RWKV_API bool rwkv_mi355x_generate_batch_logprobs(struct rwkv_context * ctx, size_t B,
-                                                  const struct rwkv_mi355x_batch_sampling * p, size_t n,
-                                                  uint32_t * tokens_out, uint32_t * lengths_out, uint32_t * steps_out,
-                                                  const struct rwkv_mi355x_logprobs * lp) {
+// ---- generate_batch and generate_queue: one body each, as sample and generate above
+static bool generate_batch_call(struct rwkv_context * ctx, size_t B, const struct rwkv_mi355x_batch_sampling * p, size_t n,
+                                uint32_t * tokens_out, uint32_t * lengths_out, uint32_t * steps_out,
+                                const struct rwkv_mi355x_logprobs * lp, const struct rwkv_mi355x_filters * f,
+                                const struct rwkv_mi355x_constraint * c) {
     if (!ctx || !ctx->engine) return false;
     ctx->last_error = RWKV_ERROR_NONE;
-    LogprobsOut lo;
     BatchSamplingParams bp;
-    if (!batch_call_ok(ctx, lp, lo, B, B, n, tokens_out, lengths_out) || !batch_sampling_ok(ctx, B, p, bp)) return false;
-    if (!logprobs_reserve(ctx, lp, B, n)) return false;
+    Extras x;
+    if (!batch_call_ok(ctx, lp, x, B, B, n, tokens_out, lengths_out) || !batch_sampling_ok(ctx, B, p, bp) ||
+        !filters_ok(ctx, f, B, x) || !constraint_ok(ctx, c, B, B, x) || !logprobs_reserve(ctx, lp, B, n))
+        return false;
+    use_device(ctx);
+    CTX_CHECK(ctx, RWKV_ERROR_CTX, false, ctx->engine->generate_batch(B, bp, n, tokens_out, lengths_out, steps_out, x),
+              "GPU batched generation failed");
+    return true;
+}
+
+static bool generate_queue_call(struct rwkv_context * ctx, size_t Q, size_t lanes, const struct rwkv_mi355x_batch_sampling * p,
+                                const uint32_t * max_tokens, size_t n, uint32_t * tokens_out, uint32_t * lengths_out,
+                                uint32_t * lane_out, uint32_t * start_out, uint32_t * steps_out,
+                                const struct rwkv_mi355x_logprobs * lp, const struct rwkv_mi355x_filters * f,
+                                const struct rwkv_mi355x_constraint * c) {
+    if (!ctx || !ctx->engine) return false;
+    ctx->last_error = RWKV_ERROR_NONE;
+    BatchSamplingParams bp;
+    Extras x;
+    if (!batch_call_ok(ctx, lp, x, Q, lanes, n, tokens_out, lengths_out)) return false;
+    CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, max_tokens != nullptr, "NULL max_tokens");
+    for (size_t s = 0; s < Q; s++)
+        CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, max_tokens[s] > 0 && max_tokens[s] <= n, "Sequence %zu: max_tokens %" PRIu32 " is outside [1, %zu]",
+                  s, max_tokens[s], n);
+    if (!batch_sampling_ok(ctx, Q, p, bp) || !filters_ok(ctx, f, Q, x)) return false;
+    CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, !bp.keep_counts,
+              "keep_counts is not supported by the queue (continue a capped sequence with rwkv_mi355x_generate_batch)");
+    if (!constraint_ok(ctx, c, Q, std::min(lanes, Q), x) || !logprobs_reserve(ctx, lp, Q, n)) return false;
     use_device(ctx);
     CTX_CHECK(ctx, RWKV_ERROR_CTX, false,
-              ctx->engine->generate_batch(B, bp, n, tokens_out, lengths_out, steps_out, lp ? &lo : nullptr),
-              "GPU batched generation failed");
+              ctx->engine->generate_queue(Q, lanes, bp, max_tokens, n, tokens_out, lengths_out, lane_out, start_out, steps_out, x),
+              "GPU queued generation failed");
     return true;
 }
 
 RWKV_API bool rwkv_mi355x_generate_batch(struct rwkv_context * ctx, size_t B, const struct rwkv_mi355x_batch_sampling * p,
                                          size_t n, uint32_t * tokens_out, uint32_t * lengths_out, uint32_t * steps_out) {
-    return rwkv_mi355x_generate_batch_logprobs(ctx, B, p, n, tokens_out, lengths_out, steps_out, nullptr);
+    return generate_batch_call(ctx, B, p, n, tokens_out, lengths_out, steps_out, nullptr, nullptr, nullptr);
 }
-
-RWKV_API bool rwkv_mi355x_generate_queue_logprobs(struct rwkv_context * ctx, size_t Q, size_t lanes,
-                                                  const struct rwkv_mi355x_batch_sampling * p,
-                                                  const uint32_t * max_tokens, size_t n, uint32_t * tokens_out,
-                                                  uint32_t * lengths_out, uint32_t * lane_out, uint32_t * start_out,
-                                                  uint32_t * steps_out, const struct rwkv_mi355x_logprobs * lp) {
-    if (!ctx || !ctx->engine) return false;
-    ctx->last_error = RWKV_ERROR_NONE;
-    LogprobsOut lo;
-    BatchSamplingParams bp;
-    if (!batch_call_ok(ctx, lp, lo, Q, lanes, n, tokens_out, lengths_out)) return false;
-    CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, max_tokens != nullptr, "NULL max_tokens");
-    for (size_t s = 0; s < Q; s++)
-        CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, max_tokens[s] > 0 && max_tokens[s] <= n, "Sequence %zu: max_tokens %" PRIu32 " is outside [1, %zu]",
-                  s, max_tokens[s], n);
-    if (!batch_sampling_ok(ctx, Q, p, bp)) return false;
-    CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, !bp.keep_counts,
-              "keep_counts is not supported by the queue (continue a capped sequence with rwkv_mi355x_generate_batch)");
-    if (!logprobs_reserve(ctx, lp, Q, n)) return false;
-    use_device(ctx);
-    CTX_CHECK(ctx, RWKV_ERROR_CTX, false,
-              ctx->engine->generate_queue(Q, lanes, bp, max_tokens, n, tokens_out, lengths_out, lane_out, start_out, steps_out,
-                                          lp ? &lo : nullptr),
-              "GPU queued generation failed");
-    return true;
+RWKV_API bool rwkv_mi355x_generate_batch_logprobs(struct rwkv_context * ctx, size_t B,
+                                                  const struct rwkv_mi355x_batch_sampling * p, size_t n,
+                                                  uint32_t * tokens_out, uint32_t * lengths_out, uint32_t * steps_out,
+                                                  const struct rwkv_mi355x_logprobs * lp) {
+    return generate_batch_call(ctx, B, p, n, tokens_out, lengths_out, steps_out, lp, nullptr, nullptr);
+}
+RWKV_API bool rwkv_mi355x_generate_batch_filtered(struct rwkv_context * ctx, size_t B,
+                                                  const struct rwkv_mi355x_batch_sampling * p, size_t n,
+                                                  uint32_t * tokens_out, uint32_t * lengths_out, uint32_t * steps_out,
+                                                  const struct rwkv_mi355x_logprobs * lp,
+                                                  const struct rwkv_mi355x_filters * f) {
+    return generate_batch_call(ctx, B, p, n, tokens_out, lengths_out, steps_out, lp, f, nullptr);
+}
+RWKV_API bool rwkv_mi355x_generate_batch_constrained(struct rwkv_context * ctx, size_t B,
+                                                     const struct rwkv_mi355x_batch_sampling * p, size_t n,
+                                                     uint32_t * tokens_out, uint32_t * lengths_out, uint32_t * steps_out,
+                                                     const struct rwkv_mi355x_logprobs * lp,
+                                                     const struct rwkv_mi355x_filters * f,
+                                                     const struct rwkv_mi355x_constraint * c) {
+    return generate_batch_call(ctx, B, p, n, tokens_out, lengths_out, steps_out, lp, f, c);
 }
 
 RWKV_API bool rwkv_mi355x_generate_queue(struct rwkv_context * ctx, size_t Q, size_t lanes,
                                          const struct rwkv_mi355x_batch_sampling * p, const uint32_t * max_tokens, size_t n,
                                          uint32_t * tokens_out, uint32_t * lengths_out, uint32_t * lane_out,
                                          uint32_t * start_out, uint32_t * steps_out) {
-    return rwkv_mi355x_generate_queue_logprobs(ctx, Q, lanes, p, max_tokens, n, tokens_out, lengths_out, lane_out, start_out,
-                                               steps_out, nullptr);
+    return generate_queue_call(ctx, Q, lanes, p, max_tokens, n, tokens_out, lengths_out, lane_out, start_out, steps_out,
+                               nullptr, nullptr, nullptr);
 }
-
-// ---- the four calls with filters: each is its _logprobs sibling, check for check, plus filters_ok
-// The checks of a rwkv_mi355x_filters over `rows` rows, before any GPU call
-static bool filters_ok(struct rwkv_context * ctx, const struct rwkv_mi355x_filters * f, size_t rows, FilterParams & out) {
-    for (size_t r = 0; r < rows; r++) {
-        CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, !f->min_p || (f->min_p[r] >= 0.0f && f->min_p[r] <= 1.0f),
-                  "Row %zu: min_p %f is outside [0, 1]", r, f->min_p[r]);
-        CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, !f->typical_p || (f->typical_p[r] >= 0.0f && f->typical_p[r] <= 1.0f),
-                  "Row %zu: typical_p %f is outside [0, 1]", r, f->typical_p[r]);
-    }
-    out.top_k = f->top_k;
-    out.min_p = f->min_p;
-    out.typical_p = f->typical_p;
-    return true;
+RWKV_API bool rwkv_mi355x_generate_queue_logprobs(struct rwkv_context * ctx, size_t Q, size_t lanes,
+                                                  const struct rwkv_mi355x_batch_sampling * p,
+                                                  const uint32_t * max_tokens, size_t n, uint32_t * tokens_out,
+                                                  uint32_t * lengths_out, uint32_t * lane_out, uint32_t * start_out,
+                                                  uint32_t * steps_out, const struct rwkv_mi355x_logprobs * lp) {
+    return generate_queue_call(ctx, Q, lanes, p, max_tokens, n, tokens_out, lengths_out, lane_out, start_out, steps_out, lp,
+                               nullptr, nullptr);
 }
-
-RWKV_API bool rwkv_mi355x_sample_filtered(struct rwkv_context * ctx, const struct rwkv_mi355x_sampling * params,
-                                          uint32_t * token_out, const struct rwkv_mi355x_logprobs * lp,
-                                          const struct rwkv_mi355x_filters * f) {
-    if (!f) return rwkv_mi355x_sample_logprobs(ctx, params, token_out, lp);
-    if (!ctx || !ctx->engine) return false;
-    ctx->last_error = RWKV_ERROR_NONE;
-    SamplingParams sp;
-    LogprobsOut lo;
-    FilterParams fp;
-    if (!logprobs_ok(ctx, lp, lo) || !sampling_ok(ctx, params, sp) || !filters_ok(ctx, f, 1, fp)) return false;
-    CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, token_out != nullptr, "NULL token_out");
-    if (!logprobs_reserve(ctx, lp, 1, 1)) return false;
-    use_device(ctx);
-    CTX_CHECK(ctx, RWKV_ERROR_CTX, false, ctx->engine->sample(sp, token_out, lp ? &lo : nullptr, &fp), "GPU sampling failed");
-    return true;
-}
-
-RWKV_API bool rwkv_mi355x_generate_filtered(struct rwkv_context * ctx, const struct rwkv_mi355x_sampling * params,
-                                            size_t n, uint32_t * tokens_out, float * logits_out,
-                                            const struct rwkv_mi355x_logprobs * lp, const struct rwkv_mi355x_filters * f) {
-    if (!f) return rwkv_mi355x_generate_logprobs(ctx, params, n, tokens_out, logits_out, lp);
-    if (!ctx || !ctx->engine) return false;
-    ctx->last_error = RWKV_ERROR_NONE;
-    SamplingParams sp;
-    LogprobsOut lo;
-    FilterParams fp;
-    if (!logprobs_ok(ctx, lp, lo) || !sampling_ok(ctx, params, sp) || !filters_ok(ctx, f, 1, fp)) return false;
-    CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, n > 0 && n <= 65536, "Token count %zu is outside [1, 65536]", n);
-    CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, tokens_out != nullptr, "NULL tokens_out");
-    if (!logprobs_reserve(ctx, lp, 1, n)) return false;
-    use_device(ctx);
-    CTX_CHECK(ctx, RWKV_ERROR_CTX, false, ctx->engine->generate(sp, n, tokens_out, logits_out, lp ? &lo : nullptr, &fp),
-              "GPU generation failed");
-    return true;
-}
-
-RWKV_API bool rwkv_mi355x_generate_batch_filtered(struct rwkv_context * ctx, size_t B,
-                                                  const struct rwkv_mi355x_batch_sampling * p, size_t n,
-                                                  uint32_t * tokens_out, uint32_t * lengths_out, uint32_t * steps_out,
-                                                  const struct rwkv_mi355x_logprobs * lp,
-                                                  const struct rwkv_mi355x_filters * f) {
-    if (!f) return rwkv_mi355x_generate_batch_logprobs(ctx, B, p, n, tokens_out, lengths_out, steps_out, lp);
-    if (!ctx || !ctx->engine) return false;
-    ctx->last_error = RWKV_ERROR_NONE;
-    LogprobsOut lo;
-    BatchSamplingParams bp;
-    FilterParams fp;
-    if (!batch_call_ok(ctx, lp, lo, B, B, n, tokens_out, lengths_out) || !batch_sampling_ok(ctx, B, p, bp) ||
-        !filters_ok(ctx, f, B, fp))
-        return false;
-    if (!logprobs_reserve(ctx, lp, B, n)) return false;
-    use_device(ctx);
-    CTX_CHECK(ctx, RWKV_ERROR_CTX, false,
-              ctx->engine->generate_batch(B, bp, n, tokens_out, lengths_out, steps_out, lp ? &lo : nullptr, &fp),
-              "GPU batched generation failed");
-    return true;
-}
-
 RWKV_API bool rwkv_mi355x_generate_queue_filtered(struct rwkv_context * ctx, size_t Q, size_t lanes,
                                                   const struct rwkv_mi355x_batch_sampling * p,
                                                   const uint32_t * max_tokens, size_t n, uint32_t * tokens_out,
                                                   uint32_t * lengths_out, uint32_t * lane_out, uint32_t * start_out,
                                                   uint32_t * steps_out, const struct rwkv_mi355x_logprobs * lp,
                                                   const struct rwkv_mi355x_filters * f) {
-    if (!f)
-        return rwkv_mi355x_generate_queue_logprobs(ctx, Q, lanes, p, max_tokens, n, tokens_out, lengths_out, lane_out,
-                                                   start_out, steps_out, lp);
-    if (!ctx || !ctx->engine) return false;
-    ctx->last_error = RWKV_ERROR_NONE;
-    LogprobsOut lo;
-    BatchSamplingParams bp;
-    FilterParams fp;
-    if (!batch_call_ok(ctx, lp, lo, Q, lanes, n, tokens_out, lengths_out)) return false;
-    CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, max_tokens != nullptr, "NULL max_tokens");
-    for (size_t s = 0; s < Q; s++)
-        CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, max_tokens[s] > 0 && max_tokens[s] <= n, "Sequence %zu: max_tokens %" PRIu32 " is outside [1, %zu]",
-                  s, max_tokens[s], n);
-    if (!batch_sampling_ok(ctx, Q, p, bp) || !filters_ok(ctx, f, Q, fp)) return false;
-    CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, !bp.keep_counts,
-              "keep_counts is not supported by the queue (continue a capped sequence with rwkv_mi355x_generate_batch)");
-    if (!logprobs_reserve(ctx, lp, Q, n)) return false;
-    use_device(ctx);
-    CTX_CHECK(ctx, RWKV_ERROR_CTX, false,
-              ctx->engine->generate_queue(Q, lanes, bp, max_tokens, n, tokens_out, lengths_out, lane_out, start_out, steps_out,
-                                          lp ? &lo : nullptr, &fp),
-              "GPU queued generation failed");
-    return true;
+    return generate_queue_call(ctx, Q, lanes, p, max_tokens, n, tokens_out, lengths_out, lane_out, start_out, steps_out, lp,
+                               f, nullptr);
+}
+RWKV_API bool rwkv_mi355x_generate_queue_constrained(struct rwkv_context * ctx, size_t Q, size_t lanes,
+                                                     const struct rwkv_mi355x_batch_sampling * p,
+                                                     const uint32_t * max_tokens, size_t n, uint32_t * tokens_out,
+                                                     uint32_t * lengths_out, uint32_t * lane_out, uint32_t * start_out,
+                                                     uint32_t * steps_out, const struct rwkv_mi355x_logprobs * lp,
+                                                     const struct rwkv_mi355x_filters * f,
+                                                     const struct rwkv_mi355x_constraint * c) {
+    return generate_queue_call(ctx, Q, lanes, p, max_tokens, n, tokens_out, lengths_out, lane_out, start_out, steps_out, lp,
+                               f, c);
 }
 
-// ---- the four calls with a constraint: each is its _filtered sibling, check for check, plus constraint_ok
+// ---- the tables of a constrained call: the vocabulary's bytes and the context's resident table
 RWKV_API bool rwkv_mi355x_vocab_bytes(struct rwkv_context * ctx, const uint32_t * offsets, const uint8_t * bytes) {
     if (!ctx || !ctx->engine) return false;
     ctx->last_error = RWKV_ERROR_NONE;
@@ -979,127 +1006,6 @@ RWKV_API uint32_t rwkv_mi355x_constraint_table_states(const struct rwkv_context 
     return ctx && ctx->engine ? ctx->engine->constraint_table_states() : 0u;
 }
 
-// The checks and allocations of a rwkv_mi355x_constraint over Q sequences in `rows` rows, before anything is enqueued
-static bool constraint_ok(struct rwkv_context * ctx, const struct rwkv_mi355x_constraint * c, size_t Q, size_t rows,
-                          ConstraintParams & out) {
-    const bool resident = !c->next && !c->accepting && ctx->engine->constraint_table_states() != 0;
-    CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, c->n_states > 0 && ((c->next && c->accepting) || resident) && c->state,
-              "A constraint needs n_states >= 1, next and accepting (both NULL: the resident table, which must be set) and state");
-    CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, !resident || c->n_states == ctx->engine->constraint_table_states(),
-              "The resident table has %" PRIu32 " states, the constraint names %" PRIu32,
-              ctx->engine->constraint_table_states(), c->n_states);
-    out.n_states = c->n_states;
-    out.next = c->next;
-    out.accepting = c->accepting;
-    out.state = c->state;
-    out.ended = c->ended;
-    use_device(ctx);
-    const int e = ctx->engine->constraint_reserve(out, Q, rows);
-    CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, e != 1,
-              "Constraint rejected: no vocabulary bytes set, a next entry or start state >= n_states, or a table over the "
-              "LDS limit (%zu bytes)", ctx->engine->constraint_lds_limit());
-    CTX_CHECK(ctx, RWKV_ERROR_CTX | RWKV_ERROR_ALLOC, false, e == 0, "Constraint buffer allocation failed");
-    return true;
-}
-static const FilterParams * filters_of(const struct rwkv_mi355x_filters * f, const FilterParams & fp) { return f ? &fp : nullptr; }
-
-RWKV_API bool rwkv_mi355x_sample_constrained(struct rwkv_context * ctx, const struct rwkv_mi355x_sampling * params,
-                                             uint32_t * token_out, const struct rwkv_mi355x_logprobs * lp,
-                                             const struct rwkv_mi355x_filters * f, const struct rwkv_mi355x_constraint * c) {
-    if (!c) return rwkv_mi355x_sample_filtered(ctx, params, token_out, lp, f);
-    if (!ctx || !ctx->engine) return false;
-    ctx->last_error = RWKV_ERROR_NONE;
-    SamplingParams sp;
-    LogprobsOut lo;
-    FilterParams fp;
-    ConstraintParams cp;
-    if (!logprobs_ok(ctx, lp, lo) || !sampling_ok(ctx, params, sp) || (f && !filters_ok(ctx, f, 1, fp))) return false;
-    CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, token_out != nullptr, "NULL token_out");
-    if (!constraint_ok(ctx, c, 1, 1, cp) || !logprobs_reserve(ctx, lp, 1, 1)) return false;
-    use_device(ctx);
-    CTX_CHECK(ctx, RWKV_ERROR_CTX, false, ctx->engine->sample(sp, token_out, lp ? &lo : nullptr, filters_of(f, fp), &cp),
-              "GPU sampling failed");
-    return true;
-}
-
-RWKV_API bool rwkv_mi355x_generate_constrained(struct rwkv_context * ctx, const struct rwkv_mi355x_sampling * params,
-                                               size_t n, uint32_t * tokens_out, float * logits_out,
-                                               const struct rwkv_mi355x_logprobs * lp, const struct rwkv_mi355x_filters * f,
-                                               const struct rwkv_mi355x_constraint * c) {
-    if (!c) return rwkv_mi355x_generate_filtered(ctx, params, n, tokens_out, logits_out, lp, f);
-    if (!ctx || !ctx->engine) return false;
-    ctx->last_error = RWKV_ERROR_NONE;
-    SamplingParams sp;
-    LogprobsOut lo;
-    FilterParams fp;
-    ConstraintParams cp;
-    if (!logprobs_ok(ctx, lp, lo) || !sampling_ok(ctx, params, sp) || (f && !filters_ok(ctx, f, 1, fp))) return false;
-    CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, n > 0 && n <= 65536, "Token count %zu is outside [1, 65536]", n);
-    CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, tokens_out != nullptr, "NULL tokens_out");
-    if (!constraint_ok(ctx, c, 1, 1, cp) || !logprobs_reserve(ctx, lp, 1, n)) return false;
-    use_device(ctx);
-    CTX_CHECK(ctx, RWKV_ERROR_CTX, false,
-              ctx->engine->generate(sp, n, tokens_out, logits_out, lp ? &lo : nullptr, filters_of(f, fp), &cp),
-              "GPU generation failed");
-    return true;
-}
-
-RWKV_API bool rwkv_mi355x_generate_batch_constrained(struct rwkv_context * ctx, size_t B,
-                                                     const struct rwkv_mi355x_batch_sampling * p, size_t n,
-                                                     uint32_t * tokens_out, uint32_t * lengths_out, uint32_t * steps_out,
-                                                     const struct rwkv_mi355x_logprobs * lp,
-                                                     const struct rwkv_mi355x_filters * f,
-                                                     const struct rwkv_mi355x_constraint * c) {
-    if (!c) return rwkv_mi355x_generate_batch_filtered(ctx, B, p, n, tokens_out, lengths_out, steps_out, lp, f);
-    if (!ctx || !ctx->engine) return false;
-    ctx->last_error = RWKV_ERROR_NONE;
-    LogprobsOut lo;
-    BatchSamplingParams bp;
-    FilterParams fp;
-    ConstraintParams cp;
-    if (!batch_call_ok(ctx, lp, lo, B, B, n, tokens_out, lengths_out) || !batch_sampling_ok(ctx, B, p, bp) ||
-        (f && !filters_ok(ctx, f, B, fp)) || !constraint_ok(ctx, c, B, B, cp))
-        return false;
-    if (!logprobs_reserve(ctx, lp, B, n)) return false;
-    use_device(ctx);
-    CTX_CHECK(ctx, RWKV_ERROR_CTX, false,
-              ctx->engine->generate_batch(B, bp, n, tokens_out, lengths_out, steps_out, lp ? &lo : nullptr, filters_of(f, fp), &cp),
-              "GPU batched generation failed");
-    return true;
-}
-
-RWKV_API bool rwkv_mi355x_generate_queue_constrained(struct rwkv_context * ctx, size_t Q, size_t lanes,
-                                                     const struct rwkv_mi355x_batch_sampling * p,
-                                                     const uint32_t * max_tokens, size_t n, uint32_t * tokens_out,
-                                                     uint32_t * lengths_out, uint32_t * lane_out, uint32_t * start_out,
-                                                     uint32_t * steps_out, const struct rwkv_mi355x_logprobs * lp,
-                                                     const struct rwkv_mi355x_filters * f,
-                                                     const struct rwkv_mi355x_constraint * c) {
-    if (!c)
-        return rwkv_mi355x_generate_queue_filtered(ctx, Q, lanes, p, max_tokens, n, tokens_out, lengths_out, lane_out,
-                                                   start_out, steps_out, lp, f);
-    if (!ctx || !ctx->engine) return false;
-    ctx->last_error = RWKV_ERROR_NONE;
-    LogprobsOut lo;
-    BatchSamplingParams bp;
-    FilterParams fp;
-    ConstraintParams cp;
-    if (!batch_call_ok(ctx, lp, lo, Q, lanes, n, tokens_out, lengths_out)) return false;
-    CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, max_tokens != nullptr, "NULL max_tokens");
-    for (size_t s = 0; s < Q; s++)
-        CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, max_tokens[s] > 0 && max_tokens[s] <= n, "Sequence %zu: max_tokens %" PRIu32 " is outside [1, %zu]",
-                  s, max_tokens[s], n);
-    if (!batch_sampling_ok(ctx, Q, p, bp) || (f && !filters_ok(ctx, f, Q, fp))) return false;
-    CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, !bp.keep_counts,
-              "keep_counts is not supported by the queue (continue a capped sequence with rwkv_mi355x_generate_batch)");
-    if (!constraint_ok(ctx, c, Q, std::min(lanes, Q), cp) || !logprobs_reserve(ctx, lp, Q, n)) return false;
-    use_device(ctx);
-    CTX_CHECK(ctx, RWKV_ERROR_CTX, false,
-              ctx->engine->generate_queue(Q, lanes, bp, max_tokens, n, tokens_out, lengths_out, lane_out, start_out, steps_out,
-                                          lp ? &lo : nullptr, filters_of(f, fp), &cp),
-              "GPU queued generation failed");
-    return true;
-}
 
 RWKV_API bool rwkv_mi355x_prefill_batch(struct rwkv_context * ctx, size_t n_rows, const uint32_t * slots,
                                         const uint32_t * tokens, const size_t * lengths, const uint8_t * cont) {

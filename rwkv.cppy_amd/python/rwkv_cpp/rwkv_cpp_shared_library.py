@@ -159,6 +159,21 @@ def _per_row(value, rows: int, name: str) -> list:
     return [value] * rows
 
 
+def _gen_extras(rows: int, n: int, logprobs: Optional[int], top_k, min_p, typical_p, dfa):
+    """The optional parts of a generation call over `rows` rows of n tokens: (lp, out, filters,
+    constraint), each None where its arguments are (make_logprobs, make_filters, make_constraint)."""
+    filters = make_filters(rows, top_k, min_p, typical_p)
+    constraint = make_constraint(rows, dfa)
+    lp, out = make_logprobs(rows, max(1, n), logprobs) if logprobs is not None else (None, None)
+    return lp, out, filters, constraint
+
+
+def _or_null(*parts) -> tuple:
+    """The trailing arguments of a _constrained entry point: a reference to each part, NULL for None,
+    which the library defines as the call without that part."""
+    return tuple(x and ctypes.byref(x) for x in parts)
+
+
 def make_batch_sampling(rows: int, temperature=1.0, top_p=0.8, presence=None, frequency=None, logit_bias=None,
                         seeds=None, offsets=0, stop_tokens=(), keep_counts: bool = False,
                         check_every: int = 0) -> RWKVBatchSampling:
@@ -313,14 +328,21 @@ class RWKVSharedLibrary:
         L.rwkv_mi355x_debug_set.argtypes = [vp, ctypes.c_char_p, ctypes.c_longlong]
         L.rwkv_mi355x_debug_set.restype = ctypes.c_bool
         P_SAMPLING, P_U32 = ctypes.POINTER(RWKVSampling), ctypes.POINTER(ctypes.c_uint32)
-        L.rwkv_mi355x_sample.argtypes = [vp, P_SAMPLING, P_U32]
-        L.rwkv_mi355x_sample.restype = ctypes.c_bool
-        L.rwkv_mi355x_generate.argtypes = [vp, P_SAMPLING, sz, P_U32, P_FLOAT]
-        L.rwkv_mi355x_generate.restype = ctypes.c_bool
+        P_BATCH, P_LP = ctypes.POINTER(RWKVBatchSampling), ctypes.POINTER(RWKVLogprobs)
+        P_F, P_C = ctypes.POINTER(RWKVFilters), ctypes.POINTER(RWKVConstraint)
+        # the four generation families: the plain call's arguments, and what each variant adds to them
+        families = {'sample': [vp, P_SAMPLING, P_U32], 'generate': [vp, P_SAMPLING, sz, P_U32, P_FLOAT],
+                    'generate_batch': [vp, sz, P_BATCH, sz, P_U32, P_U32, P_U32],
+                    'generate_queue': [vp, sz, sz, P_BATCH, P_U32, sz, P_U32, P_U32, P_U32, P_U32, P_U32]}
+        for name, base in families.items():
+            for suffix, extra in (('', []), ('_logprobs', [P_LP]), ('_filtered', [P_LP, P_F]),
+                                  ('_constrained', [P_LP, P_F, P_C])):
+                fn = getattr(L, f'rwkv_mi355x_{name}{suffix}')
+                fn.argtypes = base + extra
+                fn.restype = ctypes.c_bool
         L.rwkv_mi355x_selftest_sample.argtypes = [P_FLOAT, ctypes.c_int, ctypes.c_int, P_SAMPLING, P_FLOAT, P_U32, P_U32,
                                                   P_FLOAT]
         L.rwkv_mi355x_selftest_sample.restype = ctypes.c_bool
-        P_BATCH = ctypes.POINTER(RWKVBatchSampling)
         L.rwkv_mi355x_batch_reserve.argtypes = [vp, sz]
         L.rwkv_mi355x_batch_reserve.restype = ctypes.c_bool
         L.rwkv_mi355x_batch_slots.argtypes = [vp]
@@ -329,10 +351,6 @@ class RWKVSharedLibrary:
         L.rwkv_mi355x_batch_store.restype = ctypes.c_bool
         L.rwkv_mi355x_batch_load.argtypes = [vp, sz]
         L.rwkv_mi355x_batch_load.restype = ctypes.c_bool
-        L.rwkv_mi355x_generate_batch.argtypes = [vp, sz, P_BATCH, sz, P_U32, P_U32, P_U32]
-        L.rwkv_mi355x_generate_batch.restype = ctypes.c_bool
-        L.rwkv_mi355x_generate_queue.argtypes = [vp, sz, sz, P_BATCH, P_U32, sz, P_U32, P_U32, P_U32, P_U32, P_U32]
-        L.rwkv_mi355x_generate_queue.restype = ctypes.c_bool
         L.rwkv_mi355x_selftest_gen_turnover.argtypes = [ctypes.c_int, ctypes.c_int, u32] + [P_U32] * 10
         L.rwkv_mi355x_selftest_gen_turnover.restype = ctypes.c_bool
         P_SIZE = ctypes.POINTER(sz)
@@ -343,31 +361,18 @@ class RWKVSharedLibrary:
         L.rwkv_mi355x_selftest_sample_rows.argtypes = [P_FLOAT, ctypes.c_int, ctypes.c_int, P_BATCH, P_FLOAT, u32, P_U32,
                                                        P_U32, P_U32, P_U32, P_U32, P_FLOAT, P_U32, P_U32]
         L.rwkv_mi355x_selftest_sample_rows.restype = ctypes.c_bool
-        P_DOUBLE, P_LP = ctypes.POINTER(ctypes.c_double), ctypes.POINTER(RWKVLogprobs)
-        L.rwkv_mi355x_sample_logprobs.argtypes = L.rwkv_mi355x_sample.argtypes + [P_LP]
-        L.rwkv_mi355x_generate_logprobs.argtypes = L.rwkv_mi355x_generate.argtypes + [P_LP]
-        L.rwkv_mi355x_generate_batch_logprobs.argtypes = L.rwkv_mi355x_generate_batch.argtypes + [P_LP]
-        L.rwkv_mi355x_generate_queue_logprobs.argtypes = L.rwkv_mi355x_generate_queue.argtypes + [P_LP]
+        P_DOUBLE = ctypes.POINTER(ctypes.c_double)
         L.rwkv_mi355x_selftest_sample_logprobs.argtypes = L.rwkv_mi355x_selftest_sample.argtypes + [
             u32, P_DOUBLE, P_U32, P_DOUBLE]
         L.rwkv_mi355x_selftest_sample_rows_logprobs.argtypes = L.rwkv_mi355x_selftest_sample_rows.argtypes + [
             u32, P_DOUBLE, P_U32, P_DOUBLE]
-        for name in ('sample', 'generate', 'generate_batch', 'generate_queue', 'selftest_sample', 'selftest_sample_rows'):
+        for name in ('selftest_sample', 'selftest_sample_rows'):
             getattr(L, f'rwkv_mi355x_{name}_logprobs').restype = ctypes.c_bool
-        P_F = ctypes.POINTER(RWKVFilters)
-        for name in ('sample', 'generate', 'generate_batch', 'generate_queue'):
-            fn = getattr(L, f'rwkv_mi355x_{name}_filtered')
-            fn.argtypes = getattr(L, f'rwkv_mi355x_{name}').argtypes + [P_LP, P_F]
-            fn.restype = ctypes.c_bool
         for name in ('selftest_sample', 'selftest_sample_rows'):
             fn = getattr(L, f'rwkv_mi355x_{name}_filtered')
             fn.argtypes = getattr(L, f'rwkv_mi355x_{name}').argtypes + [P_F]
             fn.restype = ctypes.c_bool
-        P_C, P_U8 = ctypes.POINTER(RWKVConstraint), ctypes.POINTER(ctypes.c_uint8)
-        for name in ('sample', 'generate', 'generate_batch', 'generate_queue'):
-            fn = getattr(L, f'rwkv_mi355x_{name}_constrained')
-            fn.argtypes = getattr(L, f'rwkv_mi355x_{name}').argtypes + [P_LP, P_F, P_C]
-            fn.restype = ctypes.c_bool
+        P_U8 = ctypes.POINTER(ctypes.c_uint8)
         L.rwkv_mi355x_vocab_bytes.argtypes = [vp, P_U32, P_U8]
         L.rwkv_mi355x_vocab_bytes.restype = ctypes.c_bool
         L.rwkv_mi355x_constraint_max_entries.argtypes = []
@@ -492,24 +497,12 @@ class RWKVSharedLibrary:
         its state and ended are left on it, and the token is 0xFFFFFFFF when none was allowed."""
         token = ctypes.c_uint32(0)
         p = make_sampling(temperature, top_p, logit_bias, seed, offset)
-        filters = make_filters(1, top_k, min_p, typical_p)
-        c = make_constraint(1, dfa)
-        if filters is not None or c is not None:
-            lp, out = make_logprobs(1, 1, logprobs) if logprobs is not None else (None, None)
-            if not self.library.rwkv_mi355x_sample_constrained(ctx.ptr, ctypes.byref(p), ctypes.byref(token),
-                                                               lp and ctypes.byref(lp), filters and ctypes.byref(filters),
-                                                               c and ctypes.byref(c)):
-                raise ValueError('rwkv_mi355x_sample_filtered / _constrained failed, check stderr')
-            if lp is None:
-                return token.value
-            return token.value, Logprobs(float(out.token_logprob[0, 0]), out.top_ids[0, 0], out.top_logprobs[0, 0])
-        if logprobs is None:
-            if not self.library.rwkv_mi355x_sample(ctx.ptr, ctypes.byref(p), ctypes.byref(token)):
-                raise ValueError('rwkv_mi355x_sample failed, check stderr')
+        lp, out, filters, c = _gen_extras(1, 1, logprobs, top_k, min_p, typical_p, dfa)
+        if not self.library.rwkv_mi355x_sample_constrained(ctx.ptr, ctypes.byref(p), ctypes.byref(token),
+                                                           *_or_null(lp, filters, c)):
+            raise ValueError('rwkv_mi355x_sample failed, check stderr')
+        if lp is None:
             return token.value
-        lp, out = make_logprobs(1, 1, logprobs)
-        if not self.library.rwkv_mi355x_sample_logprobs(ctx.ptr, ctypes.byref(p), ctypes.byref(token), ctypes.byref(lp)):
-            raise ValueError('rwkv_mi355x_sample_logprobs failed, check stderr')
         return token.value, Logprobs(float(out.token_logprob[0, 0]), out.top_ids[0, 0], out.top_logprobs[0, 0])
 
     def rwkv_mi355x_generate(self, ctx: RWKVContext, n: int, temperature: float = 1.0, top_p: float = 0.8,
@@ -525,25 +518,12 @@ class RWKVSharedLibrary:
         tokens = (ctypes.c_uint32 * max(1, n))()
         p = make_sampling(temperature, top_p, logit_bias, seed, offset)
         logits_out = ctypes.cast(logits_out_address or 0, P_FLOAT)
-        filters = make_filters(1, top_k, min_p, typical_p)
-        c = make_constraint(1, dfa)
-        if filters is not None or c is not None:
-            lp, out = make_logprobs(1, max(1, n), logprobs) if logprobs is not None else (None, None)
-            if not self.library.rwkv_mi355x_generate_constrained(ctx.ptr, ctypes.byref(p), n, tokens, logits_out,
-                                                                 lp and ctypes.byref(lp), filters and ctypes.byref(filters),
-                                                                 c and ctypes.byref(c)):
-                raise ValueError('rwkv_mi355x_generate_filtered / _constrained failed, check stderr')
-            if lp is None:
-                return list(tokens[:n])
-            return list(tokens[:n]), Logprobs(*(x[0, :n] for x in out))
-        if logprobs is None:
-            if not self.library.rwkv_mi355x_generate(ctx.ptr, ctypes.byref(p), n, tokens, logits_out):
-                raise ValueError('rwkv_mi355x_generate failed, check stderr')
+        lp, out, filters, c = _gen_extras(1, n, logprobs, top_k, min_p, typical_p, dfa)
+        if not self.library.rwkv_mi355x_generate_constrained(ctx.ptr, ctypes.byref(p), n, tokens, logits_out,
+                                                             *_or_null(lp, filters, c)):
+            raise ValueError('rwkv_mi355x_generate failed, check stderr')
+        if lp is None:
             return list(tokens[:n])
-        lp, out = make_logprobs(1, max(1, n), logprobs)
-        if not self.library.rwkv_mi355x_generate_logprobs(ctx.ptr, ctypes.byref(p), n, tokens, logits_out,
-                                                          ctypes.byref(lp)):
-            raise ValueError('rwkv_mi355x_generate_logprobs failed, check stderr')
         return list(tokens[:n]), Logprobs(*(x[0, :n] for x in out))
 
     def rwkv_mi355x_selftest_sample(self, logits, u, temperature: float = 1.0, top_p: float = 0.8, logit_bias=None,
@@ -618,33 +598,21 @@ class RWKVSharedLibrary:
         if not self.library.rwkv_mi355x_batch_load(ctx.ptr, slot):
             raise ValueError('rwkv_mi355x_batch_load failed, check stderr')
 
-    def _generate_slots(self, name: str, ctx: RWKVContext, rows: int, n: int, logprobs: Optional[int], head: tuple,
-                        extra: tuple = (), filters: Optional[RWKVFilters] = None, dfa=None):
+    def _generate_slots(self, name: str, ctx: RWKVContext, rows: int, n: int, head: tuple, extra: tuple, logprobs, top_k,
+                        min_p, typical_p, dfa):
         """What rwkv_mi355x_generate_batch and rwkv_mi355x_generate_queue share: the output arrays of
-        `rows` sequences and the plain / _logprobs / _filtered entry point `name`, called with (ctx, *head,
-        n, tokens, lengths, *extra, steps[, logprobs[, filters]]).  Returns (tokens [rows, n], lengths [rows], steps,
-        Logprobs of [rows, n] / [rows, n, K] arrays or None)."""
+        `rows` sequences and the family's _constrained entry point, called with (ctx, *head, n, tokens,
+        lengths, *extra, steps, logprobs, filters, constraint).  Returns (tokens [rows, n], lengths [rows],
+        steps, Logprobs of [rows, n] / [rows, n, K] arrays or None)."""
         import numpy as np
         tokens = np.zeros((rows, max(1, n)), np.uint32)
         lengths = np.zeros(rows, np.uint32)
         steps = ctypes.c_uint32(0)
         P_U32 = ctypes.POINTER(ctypes.c_uint32)
-        args = (ctx.ptr, *head, n, tokens.ctypes.data_as(P_U32), lengths.ctypes.data_as(P_U32),
-                *(x.ctypes.data_as(P_U32) for x in extra), ctypes.byref(steps))
-        out = lp = None
-        if logprobs is not None:
-            lp, out = make_logprobs(rows, max(1, n), logprobs)
-        c = make_constraint(rows, dfa)
-        if c is not None:
-            name += '_constrained'
-            args += (lp and ctypes.byref(lp), filters and ctypes.byref(filters), ctypes.byref(c))
-        elif filters is not None:
-            name += '_filtered'
-            args += (lp and ctypes.byref(lp), ctypes.byref(filters))
-        elif lp is not None:
-            name += '_logprobs'
-            args += (ctypes.byref(lp),)
-        if not getattr(self.library, name)(*args):
+        lp, out, filters, c = _gen_extras(rows, n, logprobs, top_k, min_p, typical_p, dfa)
+        if not getattr(self.library, name + '_constrained')(
+                ctx.ptr, *head, n, tokens.ctypes.data_as(P_U32), lengths.ctypes.data_as(P_U32),
+                *(x.ctypes.data_as(P_U32) for x in extra), ctypes.byref(steps), *_or_null(lp, filters, c)):
             raise ValueError(f'{name} failed, check stderr')
         return tokens[:, :n], lengths, steps.value, out and Logprobs(*(x[:, :n] for x in out))
 
@@ -657,8 +625,8 @@ class RWKVSharedLibrary:
         top_k / min_p / typical_p, scalars or per row (rwkv_mi355x_generate_batch_filtered): the filters
         in front of top_p.  dfa (rwkv_mi355x_generate_batch_constrained; make_constraint): the rows'
         constraint; their states and ended flags are left on it."""
-        out = self._generate_slots('rwkv_mi355x_generate_batch', ctx, rows, n, logprobs, (rows, ctypes.byref(params)),
-                                   filters=make_filters(rows, top_k, min_p, typical_p), dfa=dfa)
+        out = self._generate_slots('rwkv_mi355x_generate_batch', ctx, rows, n, (rows, ctypes.byref(params)), (), logprobs,
+                                   top_k, min_p, typical_p, dfa)
         return out if logprobs is not None else out[:3]
 
     def rwkv_mi355x_generate_queue(self, ctx: RWKVContext, max_tokens, lanes: int, temperature=1.0, top_p=0.8,
@@ -682,8 +650,8 @@ class RWKVSharedLibrary:
         out = {k: np.zeros(Q, np.uint32) for k in ('lane', 'start')}
         head = (Q, lanes, ctypes.byref(params), caps.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)))
         out['tokens'], out['lengths'], out['steps'], lp = self._generate_slots(
-            'rwkv_mi355x_generate_queue', ctx, Q, n, logprobs, head, (out['lane'], out['start']),
-            make_filters(Q, top_k, min_p, typical_p), dfa)
+            'rwkv_mi355x_generate_queue', ctx, Q, n, head, (out['lane'], out['start']), logprobs, top_k, min_p, typical_p,
+            dfa)
         if logprobs is not None:
             out['logprobs'] = lp
         return out
