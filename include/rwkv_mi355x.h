@@ -389,6 +389,50 @@ RWKV_API bool rwkv_mi355x_generate_queue_constrained(struct rwkv_context * ctx, 
                                                      const struct rwkv_mi355x_filters * f,
                                                      const struct rwkv_mi355x_constraint * c);
 
+/* Beam search on the device: the W best continuations of the context, by summed log-probability.
+ * Candidates are scored, the best W kept exactly, the recurrent states moved to follow their parents
+ * and the history kept, all between two batched decode steps; nothing but the results crosses PCIe.
+ *
+ * Start.  The call starts from the context's device state and device logits (the logits must follow the
+ * state, as for rwkv_mi355x_sample) and works in slots [0, W), which it overwrites; other slots, the
+ * context's own state and its logits are untouched.  Beam 0 begins with score 0 and length 0; beams
+ * 1 .. W-1 are empty before step 0 and contribute no candidate.
+ * Step i.  A live beam b with float32 logits row l: m = max l (exact), S = sum exp((double)l -
+ * (double)m), logZ_b = (double)m + log(S) -- the words rwkv_mi355x_logprobs forms, in the same
+ * association -- and candidate (b, v) scores s_b + ((double)l_v - logZ_b) in double; a NaN element is
+ * no candidate.  A finished beam has one candidate: itself, score unchanged.  The new beams are the W
+ * first candidates in the order: larger score first (doubles, compared exactly), then lower b, then
+ * lower v (a finished beam's candidate sorts as v = 0).  New beam j takes its parent's history and
+ * state and appends its token, if it has one; a stop token finishes it: the stop token is its last
+ * token and is not evaluated.  Then one batched decode step over the W rows (rows of finished beams
+ * decode token 0 and their result is ignored).  The call ends when every beam is finished (looked at
+ * every check_every steps, as in rwkv_mi355x_batch_sampling; the results do not depend on it), or
+ * after n steps.
+ * Return.  Beams come back ranked by score / max(len, 1)^length_penalty, descending (0: the raw score),
+ * ties to the lower working row.  tokens_out[j] is 0xFFFFFFFF past lengths_out[j]; scores_out[j] is the
+ * raw sum of log-probabilities; row_out[j] is the slot that holds beam j's state and logits: for an
+ * unfinished beam the state has consumed all of its tokens and the logits follow it, so
+ * rwkv_mi355x_batch_load(row_out[j]) continues it.  Slots of finished beams are invalid on return.
+ * steps_out (may be NULL): the decode steps that ran.  rwkv_cpp.sampling.beam_step restates a step in
+ * float64 numpy.  A call is a pure function of its inputs; with non-finite logits the result is
+ * unspecified, but the call cannot hang, fault or index outside a row.
+ * Errors before anything is enqueued (RWKV_ERROR_ARGS; slots, state and logits untouched): width 0,
+ * above 16, above the reserved slots or above n_vocab; n == 0 or > 65536; a NULL required pointer;
+ * n_stop > 16 or a stop id >= n_vocab; a negative, infinite or NaN length_penalty; device logits that do not
+ * follow the state.  A pipeline or stage context: RWKV_ERROR_CTX | RWKV_ERROR_UNSUPPORTED.  A failure
+ * after the first enqueue (RWKV_ERROR_CTX) leaves slots [0, W) invalid. */
+struct rwkv_mi355x_beam {
+    uint32_t width;                 /* W: 1 .. 16, <= the reserved slots, <= n_vocab */
+    uint32_t n_stop;                /* <= 16, each < n_vocab */
+    const uint32_t * stop_tokens;
+    float    length_penalty;        /* alpha >= 0 and finite, used for the final ranking only */
+    uint32_t check_every;           /* as in rwkv_mi355x_batch_sampling */
+};
+RWKV_API bool rwkv_mi355x_generate_beam(struct rwkv_context * ctx, const struct rwkv_mi355x_beam * p, size_t n,
+                                        uint32_t * tokens_out /* [W][n] */, uint32_t * lengths_out /* [W] */,
+                                        double * scores_out /* [W] */, uint32_t * finished_out /* [W] */,
+                                        uint32_t * row_out /* [W] */, uint32_t * steps_out);
+
 /* Batched prefill: n_rows prompts, concatenated in `tokens` (lengths[i] >= 1 tokens each), are
  * evaluated together in packed sequence passes and land in slots[i] (distinct, each < the reserved
  * slots).  cont == NULL or cont[i] == 0: row i starts from the fresh state (the slot need not have
@@ -790,6 +834,14 @@ RWKV_API bool rwkv_mi355x_selftest_dfa_mask_mem(const float * logits, int rows, 
 RWKV_API bool rwkv_mi355x_selftest_dfa_advance(uint32_t * states, const uint32_t * tokens, int rows, int V,
                                                const uint32_t * offsets, const uint8_t * bytes, uint32_t n_states,
                                                const uint16_t * next /* [n_states][256] */);
+
+/* One step of rwkv_mi355x_generate_beam on host operands: k_beam_rows and k_beam_select over W <= 16
+ * beams with logits [W][V] (V >= W), scores [W] and finished [W] (0 live, 1 finished; lengths are 0).
+ * parent, token, score_out and finished_out [W] start on the device as 0xA5 bytes.  A beam that
+ * continues a finished one has token 0xFFFFFFFF. */
+RWKV_API bool rwkv_mi355x_selftest_beam_step(const float * logits /* [W][V] */, const double * scores, const uint32_t * finished,
+                                             int W, int V, uint32_t n_stop, const uint32_t * stop_tokens,
+                                             uint32_t * parent, uint32_t * token, double * score_out, uint32_t * finished_out);
 
 /* The turnover kernel of rwkv_mi355x_generate_queue (k_gen_turnover) on host operands, as before step
  * `step`: lane_seq [lanes] (a sequence id < Q or 0xFFFFFFFF: idle), done / lane / start [Q], *next

@@ -220,6 +220,21 @@ struct BatchSamplingParams {
     uint32_t check_every = 0;
 };
 
+// rwkv_mi355x_beam, checked by the caller (include/rwkv_mi355x.h)
+struct BeamParams {
+    uint32_t width = 1;
+    uint32_t n_stop = 0;
+    const uint32_t * stop_tokens = nullptr;
+    double length_penalty = 0.0;
+    uint32_t check_every = 0;
+};
+// what a beam call returns, host arrays of `width` entries in rank order (tokens: [width][n])
+struct BeamOut {
+    uint32_t *tokens, *lengths;
+    double * scores;
+    uint32_t *finished, *rows, *steps;  // steps: one word, may be NULL
+};
+
 // rwkv_mi355x_logprobs, checked by the caller (include/rwkv_mi355x.h): the host arrays that receive
 // the log-probabilities of a call's draws, [rows][n] columns with the rows n apart, as tokens_out
 struct LogprobsOut {
@@ -344,6 +359,12 @@ class Engine : public KLaunchTimer, private Workspace, private GenSlots {
     bool generate_queue(size_t Q, size_t lanes, const BatchSamplingParams & p, const uint32_t * max_tokens, size_t n,
                         uint32_t * tokens_out, uint32_t * lengths_out, uint32_t * lane_out, uint32_t * start_out,
                         uint32_t * steps_out, const GenExtras & x);
+    // Beam search (rwkv_mi355x_generate_beam; engine_beam.hip) over slots [0, width): the
+    // context's state and logits go into slot 0, then n times { k_beam_rows, k_beam_select,
+    // k_beam_gather gstate_[0] -> gstate_[1], one batched decode step gstate_[1] -> gstate_[0] }; the
+    // history is walked back on the device, the final ranking is the host's.  A live beam's slot holds
+    // its state and logits on return; a failed call leaves slots [0, width) invalid.
+    bool generate_beam(const BeamParams & p, size_t n, const BeamOut & out);
     // Batched prefill (rwkv_mi355x_prefill_batch; engine_prefill.hip): n_rows prompts, concatenated in
     // tokens, are packed into chunks of at most prefill_chunk_ tokens (prefill_plan.hpp) and each chunk
     // runs as one sequence pass whose token shift and WKV kernels follow a segment table (SegTab);
@@ -633,6 +654,11 @@ class Engine : public KLaunchTimer, private Workspace, private GenSlots {
     std::vector<uint64_t> gstreams_h_;
     std::vector<uint32_t> gfilters_h_;
     std::vector<uint32_t> gqueue_h_;  // max_tokens up, start down (generate_queue)
+    // generate_beam: the beams' words (BeamArgs; doubles first, one allocation), the history [n][W]
+    // pairs, and the host's unranked copy of what comes back
+    DevBuf<double> beam_words_;
+    DevBuf<uint32_t> beam_hist_;
+    std::vector<uint32_t> beam_h_;
     void free_slots();
     // generate_batch and generate_queue are one driver (engine_batch.hip): sequences [0, Q) over the
     // rows of a batched step; with a QueueCall the rows are lanes the sequences pass through

@@ -409,6 +409,47 @@ bool launch_gen_turnover(hipStream_t st, const GenQueue & q, uint32_t step);
 bool launch_gen_move(hipStream_t st, const GenQueue & q, size_t state_len, size_t V, float * state, float * logits,
                      const float * slot_state, float * snap_state, float * snap_logits);
 
+// ---- beam search (beam.hip; rwkv_mi355x_generate_beam) -------------------------------
+constexpr int BEAM_MAX_WIDTH = 16;
+enum : uint32_t { BEAM_LIVE = 0, BEAM_FINISHED = 1, BEAM_EMPTY = 2 };  // a beam's word in `finished`
+struct BeamRec {  // one candidate: 16 bytes
+    double score;
+    uint32_t b, v;
+};
+// The words of a call's W beams, all device memory.  One step: launch_beam_rows (reads logits, score,
+// finished; writes rec, nrec), launch_beam_select (reads rec, nrec, score, finished, length; writes
+// the rest), launch_beam_gather.  score_out / finished_out / length_out may be score / finished /
+// length themselves (the engine's are): k_beam_select has read every old word before it writes one.
+struct BeamArgs {
+    const float * logits;        // [W][V]
+    int W, V;
+    const double * score;        // [W]
+    const uint32_t * finished;   // [W]: BEAM_LIVE, BEAM_FINISHED or BEAM_EMPTY (no beam yet)
+    const uint32_t * length;     // [W]
+    BeamRec * rec;               // [W][BEAM_MAX_WIDTH]: row b's nrec[b] <= W best candidates, in order
+    uint32_t * nrec;             // [W]
+    uint32_t * parent;           // [W]: the beam new beam j continues (j itself where no candidate reached j)
+    uint32_t * token;            // [W]: its token; GEN_NONE for a beam that was finished already
+    double * score_out;          // [W]
+    uint32_t * finished_out;     // [W]
+    uint32_t * length_out;       // [W]
+    uint2 * hist;                // [steps][W]: (parent, token) of every step, line `step` written
+    uint32_t * dtok;             // [W]: the decode step's tokens; 0 for a beam that is not live
+    uint32_t * live;             // one word: the live beams after the step
+    uint32_t step;
+    int n_stop;                  // <= 16
+    uint32_t stop[16];
+};
+// The start of a call, into score_out / finished_out / length_out: score 0, beam 0 live, beams
+// 1 .. W - 1 empty, lengths 0
+bool launch_beam_begin(hipStream_t st, const BeamArgs & a);
+bool launch_beam_rows(hipStream_t st, const BeamArgs & a);
+bool launch_beam_select(hipStream_t st, const BeamArgs & a);
+// dst row j = src row parent[j] (state_len floats each) for every j with finished_out[j] == BEAM_LIVE
+bool launch_beam_gather(hipStream_t st, const BeamArgs & a, const float * src, float * dst, size_t state_len);
+// tokens [W][n]: beam j's length_out[j] tokens, walked back through `steps` lines of hist, then GEN_NONE
+bool launch_beam_finish(hipStream_t st, const BeamArgs & a, uint32_t steps, uint32_t * tokens, size_t n);
+
 // One workgroup per row of logits [rows][V] (xent.hip): loss[r] = -log softmax(row r)[targets[r]]
 // with the exponentials and their sum in fp64, argmax[r] = the lowest index of the row's maximum.
 // loss (with targets) and argmax may each be NULL; targets beyond the row are clamped to V - 1.

@@ -1,6 +1,7 @@
 // rwkv_abi.cpp -- the rwkv.h C ABI (reference rwkv.h:70-224, rwkv.cpp:70-258, rwkv_eval.inc:37-241)
 // on top of the MI355X engine.  Error, ownership and NULL-argument semantics follow the
 // reference; evaluation always runs on the GPU (see include/rwkv.h notes).
+#include <float.h>
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -938,6 +939,43 @@ RWKV_API bool rwkv_mi355x_generate_batch_constrained(struct rwkv_context * ctx, 
                                                      const struct rwkv_mi355x_filters * f,
                                                      const struct rwkv_mi355x_constraint * c) {
     return generate_batch_call(ctx, B, p, n, tokens_out, lengths_out, steps_out, lp, f, c);
+}
+
+// ---- beam search: one checked body, every check before any GPU call
+RWKV_API bool rwkv_mi355x_generate_beam(struct rwkv_context * ctx, const struct rwkv_mi355x_beam * p, size_t n,
+                                        uint32_t * tokens_out, uint32_t * lengths_out, double * scores_out,
+                                        uint32_t * finished_out, uint32_t * row_out, uint32_t * steps_out) {
+    if (!ctx || !ctx->engine) return false;
+    ctx->last_error = RWKV_ERROR_NONE;
+    if (!batch_ctx_ok(ctx)) return false;
+    const uint32_t V = ctx->model->dm.n_vocab;
+    CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, p != nullptr, "NULL beam parameters");
+    CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, p->width >= 1 && p->width <= (uint32_t)BEAM_MAX_WIDTH, "Beam width %" PRIu32 " is outside [1, %d]",
+              p->width, BEAM_MAX_WIDTH);
+    CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, p->width <= ctx->engine->batch_slots() && p->width <= V,
+              "Beam width %" PRIu32 " with %zu slots reserved and %" PRIu32 " tokens", p->width, ctx->engine->batch_slots(), V);
+    CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, n > 0 && n <= 65536, "Token count %zu is outside [1, 65536]", n);
+    CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, tokens_out && lengths_out && scores_out && finished_out && row_out,
+              "NULL tokens_out, lengths_out, scores_out, finished_out or row_out");
+    CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, p->n_stop <= (uint32_t)SAMPLE_MAX_STOP, "More than %d stop tokens", SAMPLE_MAX_STOP);
+    CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, p->n_stop == 0 || p->stop_tokens != nullptr, "NULL stop token array");
+    for (uint32_t i = 0; i < p->n_stop; i++)
+        CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, p->stop_tokens[i] < V, "Stop token %u out of range", p->stop_tokens[i]);
+    CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, p->length_penalty >= 0.0f && p->length_penalty <= FLT_MAX,
+              "Length penalty %f is negative, infinite or NaN", p->length_penalty);
+    CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, ctx->engine->logits_valid(),
+              "The device logits do not follow the device state (evaluate with logits first)");
+    BeamParams bp;
+    bp.width = p->width;
+    bp.n_stop = p->n_stop;
+    bp.stop_tokens = p->stop_tokens;
+    bp.length_penalty = (double)p->length_penalty;
+    bp.check_every = p->check_every;
+    use_device(ctx);
+    CTX_CHECK(ctx, RWKV_ERROR_CTX, false,
+              ctx->engine->generate_beam(bp, n, BeamOut{tokens_out, lengths_out, scores_out, finished_out, row_out, steps_out}),
+              "GPU beam search failed");
+    return true;
 }
 
 RWKV_API bool rwkv_mi355x_generate_queue(struct rwkv_context * ctx, size_t Q, size_t lanes,

@@ -919,6 +919,55 @@ extern "C" RWKV_API bool rwkv_mi355x_selftest_gen_turnover(int lanes, int Q, uin
     return true;
 }
 
+// One beam step (beam.hip: k_beam_rows, then k_beam_select) on host operands, as step 0 of a call whose
+// beams all have length 0.  What k_beam_select writes starts as 0xA5 bytes.
+extern "C" RWKV_API bool rwkv_mi355x_selftest_beam_step(const float * logits, const double * scores, const uint32_t * finished,
+                                                       int W, int V, uint32_t n_stop, const uint32_t * stop_tokens,
+                                                       uint32_t * parent, uint32_t * token, double * score_out,
+                                                       uint32_t * finished_out) {
+    if (!logits || !scores || !finished || W < 1 || W > BEAM_MAX_WIDTH || V < W || n_stop > 16u || (n_stop && !stop_tokens) ||
+        !parent || !token || !score_out || !finished_out)
+        return false;
+    for (int b = 0; b < W; b++)
+        if (finished[b] > 1u) return false;
+    for (uint32_t i = 0; i < n_stop; i++)
+        if (stop_tokens[i] >= (uint32_t)V) return false;
+    const size_t WB = (size_t)W * 4, n = (size_t)W * V;
+    DevBufs b;
+    BeamArgs a;
+    memset(&a, 0, sizeof(a));
+    a.W = W, a.V = V;
+    float * dl = (float *)b.alloc(n * 4);
+    double * ds = (double *)b.alloc((size_t)W * 8);
+    uint32_t * df = (uint32_t *)b.alloc(WB);
+    a.logits = dl, a.score = ds, a.finished = df;
+    a.length = (uint32_t *)b.alloc(WB);  // zeros
+    a.rec = (BeamRec *)alloc_poison(b, sizeof(BeamRec) * BEAM_MAX_WIDTH * BEAM_MAX_WIDTH);
+    a.nrec = (uint32_t *)alloc_poison(b, WB);
+    a.parent = (uint32_t *)alloc_poison(b, WB);
+    a.token = (uint32_t *)alloc_poison(b, WB);
+    a.score_out = (double *)alloc_poison(b, (size_t)W * 8);
+    a.finished_out = (uint32_t *)alloc_poison(b, WB);
+    a.length_out = (uint32_t *)alloc_poison(b, WB);
+    a.hist = (uint2 *)alloc_poison(b, WB * 2);
+    a.dtok = (uint32_t *)alloc_poison(b, WB);
+    a.live = (uint32_t *)alloc_poison(b, 4);
+    a.n_stop = (int)n_stop;
+    for (uint32_t i = 0; i < n_stop; i++) a.stop[i] = stop_tokens[i];
+    if (!dl || !ds || !df || !a.length || !a.rec || !a.nrec || !a.parent || !a.token || !a.score_out || !a.finished_out ||
+        !a.length_out || !a.hist || !a.dtok || !a.live)
+        return false;
+    if (hipMemcpy(dl, logits, n * 4, hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemcpy(ds, scores, (size_t)W * 8, hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemcpy(df, finished, WB, hipMemcpyHostToDevice) != hipSuccess)
+        return false;
+    if (!launch_beam_rows(nullptr, a) || !launch_beam_select(nullptr, a) || hipDeviceSynchronize() != hipSuccess) return false;
+    return hipMemcpy(parent, a.parent, WB, hipMemcpyDeviceToHost) == hipSuccess &&
+           hipMemcpy(token, a.token, WB, hipMemcpyDeviceToHost) == hipSuccess &&
+           hipMemcpy(score_out, a.score_out, (size_t)W * 8, hipMemcpyDeviceToHost) == hipSuccess &&
+           hipMemcpy(finished_out, a.finished_out, WB, hipMemcpyDeviceToHost) == hipSuccess;
+}
+
 // The scoring kernel (xent.hip) on host operands: what rwkv_mi355x_score_sequence launches per head
 // tile, one workgroup per row.  Targets beyond the row are refused here (the kernel clamps them).
 extern "C" RWKV_API bool rwkv_mi355x_selftest_xent(const float * logits, int rows, int V, const uint32_t * targets,

@@ -385,6 +385,31 @@ class RWKVModel:
             return lists
         return lists, [rwkv_cpp_shared_library.Logprobs(*(x[r, :int(lengths[r])] for x in out[3])) for r in range(rows)]
 
+    def generate_beam(self, width: int, max_tokens: int, stop_tokens=(), length_penalty: float = 0.0,
+                      check_every: int = 16):
+        """MI355X extension (rwkv_mi355x_generate_beam): beam search of `width` <= 16 beams for up to
+        max_tokens tokens, continuing from the state and logits the last evaluation on this model left
+        on the device.  Scoring, the exact selection of the best `width` candidates, the reorder of the
+        recurrent states and the history all stay on the device (sampling.beam_step restates a step).
+        A beam that draws one of stop_tokens is finished; the stop token is its last token.  Returns the
+        beams, best first by score / max(len, 1) ** length_penalty, as (tokens, score, finished, row)
+        tuples: score is the sum of the tokens' log-probabilities, and for an unfinished beam
+        batch_load(row) continues it.  Works in slots [0, width), which it overwrites.  With fewer than
+        `width` slots reserved it calls batch_reserve(width), which drops every slot stored before: reserve
+        enough slots first to keep them.  The model's own state and logits are untouched."""
+        if not self._valid:
+            raise ValueError('Model was freed')
+        if not 0 < width <= 16:
+            raise ValueError(f'width {width} (1 to 16)')
+        if not max_tokens > 0:
+            raise ValueError('max_tokens must be > 0')
+        if self._library.rwkv_mi355x_batch_slots(self._ctx) < width:
+            self._library.rwkv_mi355x_batch_reserve(self._ctx, width)
+        out = self._library.rwkv_mi355x_generate_beam(self._ctx, width, max_tokens, list(stop_tokens), length_penalty,
+                                                      check_every)
+        return [([int(t) for t in out['tokens'][j][:int(out['lengths'][j])]], float(out['scores'][j]),
+                 bool(out['finished'][j]), int(out['rows'][j])) for j in range(width)]
+
     def generate_queue(self, prompts: List[List[int]], max_tokens, lanes: int = 32, temperature=1.0, top_p=0.8,
                        presence_penalty=0.0, frequency_penalty=0.0, logit_bias=None, seeds=None, stop_tokens=(),
                        check_every: int = 16, logprobs: Optional[int] = None, top_k=None, min_p=None, typical_p=None,

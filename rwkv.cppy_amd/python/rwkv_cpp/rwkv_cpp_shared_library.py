@@ -59,6 +59,12 @@ class RWKVBatchSampling(ctypes.Structure):
                 ('keep_counts', ctypes.c_uint32), ('check_every', ctypes.c_uint32)]
 
 
+class RWKVBeam(ctypes.Structure):
+    """struct rwkv_mi355x_beam (include/rwkv_mi355x.h)."""
+    _fields_ = [('width', ctypes.c_uint32), ('n_stop', ctypes.c_uint32), ('stop_tokens', ctypes.POINTER(ctypes.c_uint32)),
+                ('length_penalty', ctypes.c_float), ('check_every', ctypes.c_uint32)]
+
+
 class RWKVLogprobs(ctypes.Structure):
     """struct rwkv_mi355x_logprobs (include/rwkv_mi355x.h)."""
     _fields_ = [('top_k', ctypes.c_uint32), ('token_logprob', ctypes.POINTER(ctypes.c_double)),
@@ -393,6 +399,11 @@ class RWKVSharedLibrary:
         L.rwkv_mi355x_score_sequence.restype = ctypes.c_bool
         L.rwkv_mi355x_selftest_xent.argtypes = [P_FLOAT, ctypes.c_int, ctypes.c_int, P_U32, P_DOUBLE, P_U32]
         L.rwkv_mi355x_selftest_xent.restype = ctypes.c_bool
+        L.rwkv_mi355x_generate_beam.argtypes = [vp, ctypes.POINTER(RWKVBeam), sz, P_U32, P_U32, P_DOUBLE, P_U32, P_U32, P_U32]
+        L.rwkv_mi355x_generate_beam.restype = ctypes.c_bool
+        L.rwkv_mi355x_selftest_beam_step.argtypes = [P_FLOAT, P_DOUBLE, P_U32, ctypes.c_int, ctypes.c_int, u32, P_U32,
+                                                     P_U32, P_U32, P_DOUBLE, P_U32]
+        L.rwkv_mi355x_selftest_beam_step.restype = ctypes.c_bool
         L.rwkv_mi355x_selftest_wkv_layouts.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int, P_U32, ctypes.c_int,
                                                        ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint64)]
         L.rwkv_mi355x_selftest_wkv_layouts.restype = ctypes.c_bool
@@ -655,6 +666,48 @@ class RWKVSharedLibrary:
         if logprobs is not None:
             out['logprobs'] = lp
         return out
+
+    # ---- additive: beam search ------------------------------------------------------------------
+    def rwkv_mi355x_generate_beam(self, ctx: RWKVContext, width: int, n: int, stop_tokens=(), length_penalty: float = 0.0,
+                                  check_every: int = 0):
+        """Beam search of `width` beams for up to n steps from the context's device state and logits, in
+        slots [0, width).  Returns a dict, beams in rank order: tokens uint32 [width, n] (0xFFFFFFFF after
+        a beam's last token), lengths uint32, scores float64, finished uint32, rows uint32 [width] (the
+        slot that holds the beam's state and logits; valid for an unfinished beam), and steps."""
+        import numpy as np
+        stop = (ctypes.c_uint32 * max(1, len(stop_tokens)))(*stop_tokens)
+        p = RWKVBeam(width, len(stop_tokens), stop, length_penalty, check_every)
+        out = {'tokens': np.zeros((max(1, width), max(1, n)), np.uint32), 'scores': np.zeros(max(1, width), np.float64)}
+        out.update({k: np.zeros(max(1, width), np.uint32) for k in ('lengths', 'finished', 'rows')})
+        steps = ctypes.c_uint32(0)
+        P_U32 = ctypes.POINTER(ctypes.c_uint32)
+        if not self.library.rwkv_mi355x_generate_beam(
+                ctx.ptr, ctypes.byref(p), n, out['tokens'].ctypes.data_as(P_U32), out['lengths'].ctypes.data_as(P_U32),
+                out['scores'].ctypes.data_as(ctypes.POINTER(ctypes.c_double)), out['finished'].ctypes.data_as(P_U32),
+                out['rows'].ctypes.data_as(P_U32), ctypes.byref(steps)):
+            raise ValueError('rwkv_mi355x_generate_beam failed, check stderr')
+        out['steps'] = steps.value
+        return out
+
+    def rwkv_mi355x_selftest_beam_step(self, logits, scores, finished, stop_tokens=()):
+        """One beam step (k_beam_rows, k_beam_select) on host operands: logits float32 [W, V], scores
+        float64 [W], finished [W] (0 / 1).  Returns (parent, token, score, finished), as
+        sampling.beam_step does."""
+        import numpy as np
+        lg = np.ascontiguousarray(logits, dtype=np.float32)
+        W, V = lg.shape
+        sc = np.ascontiguousarray(scores, dtype=np.float64)
+        fin = np.ascontiguousarray(finished, dtype=np.uint32)
+        stop = (ctypes.c_uint32 * max(1, len(stop_tokens)))(*stop_tokens)
+        parent, token, fin_out = (np.zeros(W, np.uint32) for _ in range(3))
+        score = np.zeros(W, np.float64)
+        P_U32, P_D = ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_double)
+        if not self.library.rwkv_mi355x_selftest_beam_step(
+                lg.ctypes.data_as(P_FLOAT), sc.ctypes.data_as(P_D), fin.ctypes.data_as(P_U32), W, V, len(stop_tokens), stop,
+                parent.ctypes.data_as(P_U32), token.ctypes.data_as(P_U32), score.ctypes.data_as(P_D),
+                fin_out.ctypes.data_as(P_U32)):
+            raise ValueError('rwkv_mi355x_selftest_beam_step failed')
+        return parent, token, score, fin_out
 
     # ---- additive: byte-DFA constraints ----------------------------------------------------
     def rwkv_mi355x_vocab_bytes(self, ctx: RWKVContext, vocab) -> None:

@@ -112,6 +112,56 @@ def logprobs(l, top_k: int):
         return float(log_z), top.astype(np.uint32), ld[top] - log_z
 
 
+def beam_step(logits, scores, finished, stop_tokens=()):
+    """One step of librwkv.so's beam search (rwkv_mi355x_generate_beam) in float64 numpy; the
+    specification the device kernels are measured against.
+
+    logits float32 [W, V]; scores float64 [W]; finished [W]: 0 a live beam, 1 a finished one, 2 an empty
+    one (beams 1 .. W-1 before step 0), which has no candidate.
+      live beam b:      logZ_b = logprobs(logits[b], 0)[0]; candidate (b, v) scores
+                        scores[b] + (float64(logits[b, v]) - logZ_b); a NaN element is no candidate
+      finished beam b:  one candidate, (b, v = 0), with scores[b] unchanged
+    The new beams are the W first candidates in the order: larger score first (float64, compared
+    exactly), then lower b, then lower v.  New beam j continues beam parent[j] and appends token[j]
+    (0xFFFFFFFF for a beam that was finished already); it is finished when it was, or when its token is
+    one of stop_tokens.  A new beam that no candidate reaches (NaN rows only) is empty.
+    Returns (parent uint32 [W], token uint32 [W], score float64 [W], finished uint32 [W], gap): gap is
+    the smallest nonzero score difference between neighbours among the first W + 1 candidates (inf
+    without one): the W-th against the (W+1)-th, and the selected ones against each other.  Where it
+    exceeds the error of the device's logZ, the device selects exactly these beams in this order
+    (equal scores are exact ties on both sides: equal logits under one logZ word)."""
+    l32 = np.asarray(logits, dtype=np.float32)
+    W, V = l32.shape
+    scores = np.asarray(scores, dtype=np.float64)
+    stop = {int(t) for t in stop_tokens}
+    cands = []  # (-score, b, v): only the rows' W best can be among the W best of all
+    for b in range(W):
+        if int(finished[b]) == 1:
+            cands.append((-float(scores[b]), b, 0))
+        elif int(finished[b]) == 0:
+            log_z, ids, lp = logprobs(l32[b], min(W + 1, V))
+            cands += [(-float(scores[b] + x), b, int(v)) for v, x in zip(ids, lp)]
+    cands.sort()
+    parent, token = np.arange(W, dtype=np.uint32), np.full(W, 0xFFFFFFFF, np.uint32)
+    score, fin = np.full(W, -np.inf), np.full(W, 2, np.uint32)
+    for j, (s, b, v) in enumerate(cands[:W]):
+        was = int(finished[b]) == 1
+        parent[j], score[j] = b, -s
+        token[j] = 0xFFFFFFFF if was else v
+        fin[j] = 1 if was or v in stop else 0
+    with np.errstate(all='ignore'):
+        steps = np.diff([c[0] for c in cands[:W + 1]])
+    gap = steps[steps > 0].min() if (steps > 0).any() else np.inf
+    return parent, token, score, fin, float(gap)
+
+
+def beam_rank(scores, lengths, length_penalty: float = 0.0):
+    """The order in which rwkv_mi355x_generate_beam returns its beams: score / max(len, 1) **
+    length_penalty descending, ties to the lower working row.  Returns the working rows, best first."""
+    key = np.asarray(scores, np.float64) / np.maximum(np.asarray(lengths, np.float64), 1.0) ** float(length_penalty)
+    return np.argsort(-key, kind='stable')
+
+
 def _cutoff(key, mass, target: float) -> float:
     """The first key, in ascending order, at which the mass of all elements with a key <= it exceeds
     target (ties are one step)."""
