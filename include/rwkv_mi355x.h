@@ -433,6 +433,41 @@ RWKV_API bool rwkv_mi355x_generate_beam(struct rwkv_context * ctx, const struct 
                                         double * scores_out /* [W] */, uint32_t * finished_out /* [W] */,
                                         uint32_t * row_out /* [W] */, uint32_t * steps_out);
 
+/* Speculative generation: rwkv_mi355x_generate's n tokens, final state and final logits, bit for bit (at
+ * temperature 0 and for sampled draws), in steps that can emit several tokens per pass over the weights.
+ * Preconditions, argument errors and the post-condition are rwkv_mi355x_generate's: the state has consumed
+ * all n tokens, the device logits follow the last one, and a second call with offset + n continues the
+ * stream.  Scope: single-sequence generation only -- batches, queues, beams, log-probabilities, filters and
+ * constraints are not part of this call.
+ * A step, with e tokens emitted so far and the corpus = history followed by the emitted tokens:
+ *   1. x0 is draw offset + e from the live logits; it is emitted and joins the corpus (length L).
+ *   2. The draft: for g = ngram_max down to ngram_min with g < L, the largest p < L - g with
+ *      corpus[p, p + g) == corpus[L - g, L); the first g that matches gives the draft
+ *      corpus[p + g, min(p + g + draft_len, L)), cut to the tokens the call still lacks
+ *      (rwkv_cpp.sampling.ngram_draft restates the rule).  No second model is involved.
+ *   3. No draft: one ordinary decode step on x0.  A draft of d tokens: one sequence pass over the d + 1
+ *      rows x0, d_1 .. d_d that keeps the state after every row, the head on all rows, and row r is
+ *      sampled as draw offset + e + 1 + r.  m = the first r whose draw differs from d_(r + 1), else d:
+ *      d_1 .. d_m are emitted, the state after row m and the logits of row m become the live ones.
+ * Serial and sequence evaluation are bit-identical and draw i of a stream is a function of (seed, i) and
+ * its logits alone, which is why the result does not depend on the history or on the switches here: they
+ * change the speed only.  history (host; may be NULL with n_history 0) seeds the corpus: the prompt, a
+ * prediction of the output, or both.  stats (may be NULL): the steps, and the drafted and accepted tokens
+ * summed over them; steps + accepted == n.  The host waits once per step, for two words.
+ * Errors before anything is enqueued (RWKV_ERROR_ARGS): those of rwkv_mi355x_generate; spec NULL, draft_len
+ * outside [1, 15], ngram_min 0, ngram_min > ngram_max, ngram_max > 8, a history token >= n_vocab,
+ * n_history + n > 1 << 20.  A pipeline or stage context: RWKV_ERROR_CTX | RWKV_ERROR_UNSUPPORTED. */
+struct rwkv_mi355x_speculation {
+    uint32_t draft_len;             /* k: 1..15 drafted tokens per step (a pass is at most 16 rows) */
+    uint32_t ngram_min, ngram_max;  /* 1 <= ngram_min <= ngram_max <= 8 */
+    const uint32_t * history;       /* host, n_history tokens (< n_vocab); may be NULL with 0 */
+    size_t n_history;               /* n_history + n <= 1 << 20 */
+};
+struct rwkv_mi355x_spec_stats { uint64_t steps, drafted, accepted; };
+RWKV_API bool rwkv_mi355x_generate_speculative(struct rwkv_context * ctx, const struct rwkv_mi355x_sampling * params,
+                                               const struct rwkv_mi355x_speculation * spec, size_t n, uint32_t * tokens_out,
+                                               float * logits_out, struct rwkv_mi355x_spec_stats * stats /* may be NULL */);
+
 /* Batched prefill: n_rows prompts, concatenated in `tokens` (lengths[i] >= 1 tokens each), are
  * evaluated together in packed sequence passes and land in slots[i] (distinct, each < the reserved
  * slots).  cont == NULL or cont[i] == 0: row i starts from the fresh state (the slot need not have
@@ -842,6 +877,21 @@ RWKV_API bool rwkv_mi355x_selftest_dfa_advance(uint32_t * states, const uint32_t
 RWKV_API bool rwkv_mi355x_selftest_beam_step(const float * logits /* [W][V] */, const double * scores, const uint32_t * finished,
                                              int W, int V, uint32_t n_stop, const uint32_t * stop_tokens,
                                              uint32_t * parent, uint32_t * token, double * score_out, uint32_t * finished_out);
+
+/* The draft search of rwkv_mi355x_generate_speculative (k_spec_draft) on a host corpus of L >= 1 tokens
+ * (L <= 1 << 20): its last token is the step's x0, the others the history, nothing emitted yet and
+ * `limit` (1 .. 15) tokens still missing after x0.  draft [15] receives *d_out tokens. */
+RWKV_API bool rwkv_mi355x_selftest_spec_draft(const uint32_t * corpus, size_t L, uint32_t k, uint32_t ngram_min,
+                                              uint32_t ngram_max, uint32_t limit, uint32_t * draft, uint32_t * d_out);
+/* The accept and commit kernels behind the rows' sampler, on host operands: logits [d + 1][V] (1 <= d <= 15),
+ * row r sampled as draw params->offset + r; drafts [d]; a model geometry (arch 4 .. 7, n_layer layers, H
+ * heads of size S <= 64) and trace [d + 1][state_len] in the trace layout (WKV-6: heads value-major).
+ * Returns m, the corpus behind x0 (appended [d], 0xFFFFFFFF past m), the next step's x0, the committed
+ * state [state_len] and logits row [V]. */
+RWKV_API bool rwkv_mi355x_selftest_spec_accept(const float * logits, int d, int V, const struct rwkv_mi355x_sampling * params,
+                                               const uint32_t * drafts, int arch, uint32_t n_layer, uint32_t H, uint32_t S,
+                                               const float * trace, uint32_t * m_out, uint32_t * appended, uint32_t * next_x0,
+                                               float * state_out, float * logits_out);
 
 /* The turnover kernel of rwkv_mi355x_generate_queue (k_gen_turnover) on host operands, as before step
  * `step`: lane_seq [lanes] (a sequence id < Q or 0xFFFFFFFF: idle), done / lane / start [Q], *next

@@ -94,6 +94,7 @@ Engine::~Engine() {
     // (device memory: the DevBuf members free themselves)
     if (htokens_) (void)hipHostFree(htokens_);
     if (herr_h_) (void)hipHostFree(herr_h_);
+    if (spec_h_) (void)hipHostFree(spec_h_);
     collect_timing();
     for (hipEvent_t e : event_pool_) (void)hipEventDestroy(e);
     if (tok_event_) (void)hipEventDestroy(tok_event_);

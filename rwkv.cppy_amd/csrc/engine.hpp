@@ -188,6 +188,7 @@ struct SeqRun {
     bool tile_acts;       // the layers' Q8 activations go into sequence-GEMM token tiles
     TokArg tok;           // one token of its own sequence: the step's id; else read from dtokens_
     float * head_out;     // where the head writes its rows; NULL: no head
+    float * trace;        // a traced pass (one sequence, T <= SPEC_ROWS): entry t = the state after row t; else NULL
 };
 
 // The scope of the launch timer (common.hpp): while one made with `on` lives, every RK_LAUNCH of
@@ -259,6 +260,16 @@ struct ConstraintParams {
     const uint8_t * accepting = nullptr;
     uint32_t * state = nullptr;
     uint32_t * ended = nullptr;
+};
+
+// rwkv_mi355x_speculation / rwkv_mi355x_spec_stats, checked by the caller (include/rwkv_mi355x.h)
+struct SpecParams {
+    uint32_t draft_len = 4, ngram_min = 1, ngram_max = 4;
+    const uint32_t * history = nullptr;
+    size_t n_history = 0;
+};
+struct SpecStats {
+    uint64_t steps = 0, drafted = 0, accepted = 0;
 };
 
 // The optional parts of a generation call, each NULL or checked by the caller as its type says
@@ -365,6 +376,14 @@ class Engine : public KLaunchTimer, private Workspace, private GenSlots {
     // history is walked back on the device, the final ranking is the host's.  A live beam's slot holds
     // its state and logits on return; a failed call leaves slots [0, width) invalid.
     bool generate_beam(const BeamParams & p, size_t n, const BeamOut & out);
+    // Speculative generation (rwkv_mi355x_generate_speculative; engine_spec.hip): generate's
+    // tokens, state and logits, bit for bit, in steps that emit 1 + (accepted drafts) tokens.  Per step: the
+    // draw of x0 (k_sample; after a traced step the accept's draw of the row that went live is that draw),
+    // k_spec_draft over history + emitted tokens, one synchronous read of two words, then either the
+    // one-token decode step or a traced sequence pass over x0 and the d drafts with the head on all rows
+    // (score_chunk's), k_sample over the rows, k_spec_accept and k_spec_commit.  stats may be NULL.
+    bool generate_speculative(const SamplingParams & p, const SpecParams & sp, size_t n, uint32_t * tokens_out,
+                              float * logits_out, SpecStats * stats);
     // Batched prefill (rwkv_mi355x_prefill_batch; engine_prefill.hip): n_rows prompts, concatenated in
     // tokens, are packed into chunks of at most prefill_chunk_ tokens (prefill_plan.hpp) and each chunk
     // runs as one sequence pass whose token shift and WKV kernels follow a segment table (SegTab);
@@ -496,7 +515,9 @@ class Engine : public KLaunchTimer, private Workspace, private GenSlots {
     DevBuf<double> score_loss_;
     DevBuf<uint32_t> score_argmax_;
     bool layer_v4(const SeqRun & s, int l, const float * si, float * so);
-    bool wkv6(const SeqRun & s, int H, int S, const float * u, const float * w, int wpt, const float * sin, float * sout);
+    bool wkv6(const SeqRun & s, int l, int H, int S, const float * u, const float * w, int wpt, const float * sin, float * sout);
+    bool ln_mix_traced(const SeqRun & s, LnMixArgs & a, int l, size_t row);
+    WkvTrace wkv_trace(const SeqRun & s, int l) const;
     bool layer_v5(const SeqRun & s, int l, const float * si, float * so);
     bool layer_v6(const SeqRun & s, int l, const float * si, float * so);
     bool layer_v7(const SeqRun & s, int l, const float * si, float * so);
@@ -659,6 +680,14 @@ class Engine : public KLaunchTimer, private Workspace, private GenSlots {
     DevBuf<double> beam_words_;
     DevBuf<uint32_t> beam_hist_;
     std::vector<uint32_t> beam_h_;
+    // generate_speculative: the states after each row of a traced pass [SPEC_ROWS][state_len] (the WKV
+    // kernels' trace layout), the head's rows [SPEC_ROWS][n_vocab], the corpus [n_history + n], the rows'
+    // draws, the call's words (SpecWords) and the pinned pair the host reads every step
+    DevBuf<float> spec_trace_, spec_tile_;
+    DevBuf<uint32_t> spec_corpus_, spec_draws_;
+    DevBuf<unsigned long long> spec_words_;
+    uint32_t * spec_h_ = nullptr;
+    bool spec_traced_step(int T);
     void free_slots();
     // generate_batch and generate_queue are one driver (engine_batch.hip): sequences [0, Q) over the
     // rows of a batched step; with a QueueCall the rows are lanes the sequences pass through

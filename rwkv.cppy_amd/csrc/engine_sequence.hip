@@ -23,15 +23,15 @@ SeqRun Engine::make_run(SeqRun s) const {
 
 SeqRun Engine::seq_run(int T, const float * sin, float * sout, uint32_t l0, uint32_t l1, const TokArg & tok,
                        float * head_out) const {
-    return make_run(SeqRun{T, sin, sout, l0, l1, 0, nullptr, false, false, tok, head_out});
+    return make_run(SeqRun{T, sin, sout, l0, l1, 0, nullptr, false, false, tok, head_out, nullptr});
 }
 
 SeqRun Engine::rows_run(int B, size_t bs, const float * sin, float * sout, float * head_out) const {
-    return make_run(SeqRun{B, sin, sout, 0, m_->n_layer, bs, nullptr, true, false, dtok(), head_out});
+    return make_run(SeqRun{B, sin, sout, 0, m_->n_layer, bs, nullptr, true, false, dtok(), head_out, nullptr});
 }
 
 SeqRun Engine::packed_run(int T, const SegTab * seg, float * states) const {
-    return make_run(SeqRun{T, states, states, 0, m_->n_layer, 0, seg, false, false, dtok(), nullptr});
+    return make_run(SeqRun{T, states, states, 0, m_->n_layer, 0, seg, false, false, dtok(), nullptr, nullptr});
 }
 
 // Collects matmul entries and launches them grouped by weight type.
@@ -216,6 +216,22 @@ LnMixArgs Engine::ln_mix_args(const SeqRun & s, const float * carry_in, float * 
     return a;
 }
 
+// The LayerNorm + mix launch of a layer whose carry is the state row at `row` floats into the layer's
+// state.  A traced pass (s.trace) also keeps every token's LN output -- entry t's row is what the launch
+// would leave in carry_out after t + 1 tokens: the kernel writes them to xa_ (its out_xa, which only v6's
+// attention reads, and has read by the time its channel mix runs) and k_spec_shift_trace copies them in.
+bool Engine::ln_mix_traced(const SeqRun & s, LnMixArgs & a, int l, size_t row) {
+    if (!s.trace) return launch_ln_mix(stream_, a, s.seg);
+    if (!a.out_xa) a.out_xa = xa_;
+    return launch_ln_mix(stream_, a, s.seg) &&
+           launch_spec_shift_trace(stream_, a.out_xa, s.T, a.C, s.trace + (size_t)l * layer_state_len() + row, m_->state_len);
+}
+
+// the WKV kernels' trace argument of layer l: its entries at the layer's WKV-4 base / WKV-6, -7 state
+WkvTrace Engine::wkv_trace(const SeqRun & s, int l) const {
+    return WkvTrace{s.trace + (size_t)l * layer_state_len() + (m_->major == 4 ? 0 : 2 * (size_t)m_->n_embed), m_->state_len};
+}
+
 bool Engine::ffn(const SeqRun & s, int l, const float * si, float * so) {
     const DLayer & L = m_->layers[l];
     const int C = (int)m_->n_embed;
@@ -230,7 +246,7 @@ bool Engine::ffn(const SeqRun & s, int l, const float * si, float * so) {
         a.mu[1] = m_->major == 6 ? L.ffn_maa_r : L.ffn_mix_r;
         a.out[1] = A(s, 1, L.ffn_r);
     }
-    if (!launch_ln_mix(stream_, a, s.seg)) return false;
+    if (!ln_mix_traced(s, a, l, 0)) return false;
     ActBuf kin = A(s, hasr ? 2 : 1, L.ffn_v);
     MMBatch b;
     if (hasr) b.add(L.ffn_r, a.out[1], fr_, C, EPI_STORE);
@@ -275,14 +291,16 @@ bool Engine::layer_v4(const SeqRun & s, int l, const float * si, float * so) {
     a.out[0] = A(s, 0, L.att_k);
     a.out[1] = A(s, 1, L.att_v);
     a.out[2] = A(s, 2, L.att_r);
-    if (!launch_ln_mix(stream_, a, s.seg)) return false;
+    if (!ln_mix_traced(s, a, l, C)) return false;
     MMBatch b;
     b.add(L.att_r, A(s, 2, L.att_r), r_, C, EPI_SIGMOID);
     b.add(L.att_k, A(s, 0, L.att_k), k_, C, EPI_STORE);
     b.add(L.att_v, A(s, 1, L.att_v), v_, C, EPI_STORE);
     if (!b.run(*this, s)) return false;
     ActBuf o = A(s, 3, L.att_o);
-    if (!launch_wkv4(stream_, s.T, C, r_, k_, v_, L.att_first, L.att_decay, si, so, o, (int)s.bs, s.seg)) return false;
+    const WkvTrace tr = wkv_trace(s, l);
+    if (!launch_wkv4(stream_, s.T, C, r_, k_, v_, L.att_first, L.att_decay, si, so, o, (int)s.bs, s.seg, s.trace ? &tr : nullptr))
+        return false;
     b.add(L.att_o, o, x_, C, EPI_ADD);
     if (!b.run(*this, s)) return false;
     return ffn(s, l, si, so);
@@ -292,13 +310,14 @@ bool Engine::layer_v4(const SeqRun & s, int l, const float * si, float * so) {
 // chunk always: its segmented form), or behind the wkv_chunk_ switch the chunk-parallel form (RA / KB
 // in the v7-only nb_ / bb_ buffers, free during a v5/v6 layer; the chunk matrices and states in
 // wkvc_, grown on demand)
-bool Engine::wkv6(const SeqRun & s, int H, int S, const float * u, const float * w, int wpt, const float * sin, float * sout) {
-    if (wkv_chunk_ && !s.seg && wkv6_chunked_supported(s.T, S, (int)s.bs)) {
+bool Engine::wkv6(const SeqRun & s, int l, int H, int S, const float * u, const float * w, int wpt, const float * sin, float * sout) {
+    if (wkv_chunk_ && !s.seg && !s.trace && wkv6_chunked_supported(s.T, S, (int)s.bs)) {
         const size_t need = wkv6_chunked_scratch_floats(s.T, H);
         if (!grow(wkvc_, need, need, GRAPHS_NONE)) return false;
         return launch_wkv6_chunked(stream_, s.T, H, k_, v_, r_, u, w, wpt, sin, sout, y_, nb_, bb_, wkvc_);
     }
-    return launch_wkv6(stream_, s.T, H, S, k_, v_, r_, u, w, wpt, sin, sout, y_, s.seg);
+    const WkvTrace tr = wkv_trace(s, l);
+    return launch_wkv6(stream_, s.T, H, S, k_, v_, r_, u, w, wpt, sin, sout, y_, s.seg, s.trace ? &tr : nullptr);
 }
 
 bool Engine::layer_v5(const SeqRun & s, int l, const float * si, float * so) {
@@ -318,7 +337,7 @@ bool Engine::layer_v5(const SeqRun & s, int l, const float * si, float * so) {
         a.mu[3] = L.att_mix_g;
         a.out[3] = A(s, 3, L.att_g);
     }
-    if (!launch_ln_mix(stream_, a, s.seg)) return false;
+    if (!ln_mix_traced(s, a, l, C)) return false;
     MMBatch b;
     b.add(L.att_r, A(s, 2, L.att_r), r_, C, EPI_STORE);
     b.add(L.att_k, A(s, 0, L.att_k), k_, C, EPI_STORE);
@@ -326,7 +345,7 @@ bool Engine::layer_v5(const SeqRun & s, int l, const float * si, float * so) {
     if (v52) b.add(L.att_g, A(s, 3, L.att_g), g_, C, EPI_SILU);
     if (!b.run(*this, s)) return false;
     if (s.bs) return batch_att_tail(s, att6_args(L, si, so, s.bs), 4, l, si, so);
-    if (!wkv6(s, H, S, L.att_u, L.att_w, 0, si + 2 * C, so + 2 * C)) return false;
+    if (!wkv6(s, l, H, S, L.att_u, L.att_w, 0, si + 2 * C, so + 2 * C)) return false;
     ActBuf o = A(s, 4, L.att_o);
     if (!launch_groupnorm(stream_, s.T, H, S, 1e-5f, y_, L.att_lnx_w, L.att_lnx_b, v52 ? 1 : 0, g_, nullptr, nullptr, o))
         return false;
@@ -345,7 +364,7 @@ bool Engine::layer_v6(const SeqRun & s, int l, const float * si, float * so) {
     a.out[0] = A(s, 0, L.maa_w1);
     a.out_xa = xa_;
     a.out_sx = sx_;
-    if (!launch_ln_mix(stream_, a, s.seg)) return false;
+    if (!ln_mix_traced(s, a, l, C)) return false;
     MMBatch b;
     b.add(L.maa_w1, A(s, 0, L.maa_w1), lora_, 5 * D, EPI_TANH);
     if (!b.run(*this, s)) return false;
@@ -381,7 +400,7 @@ bool Engine::layer_v6(const SeqRun & s, int l, const float * si, float * so) {
         b.add(L.decay_w2, dl, w_, C, EPI_DECAY6, nullptr, L.decay6);
         if (!b.run(*this, s)) return false;
     }
-    if (!wkv6(s, H, S, L.att_u, w_, 1, si + 2 * C, so + 2 * C)) return false;
+    if (!wkv6(s, l, H, S, L.att_u, w_, 1, si + 2 * C, so + 2 * C)) return false;
     ActBuf o = A(s, 7, L.att_o);
     if (!launch_groupnorm(stream_, T, H, S, 64e-5f, y_, L.att_lnx_w, L.att_lnx_b, 1, g_, nullptr, nullptr, o)) return false;
     b.add(L.att_o, o, x_, C, EPI_ADD);
@@ -419,7 +438,7 @@ bool Engine::layer_v7(const SeqRun & s, int l, const float * si, float * so) {
             if (!launch_ln_mix(stream_, a2, s.seg)) return false;
         }
     }
-    if (!launch_ln_mix(stream_, a, s.seg)) return false;
+    if (!ln_mix_traced(s, a, l, C)) return false;
     MMBatch b;
     ActBuf lw = A(s, 6, L.w2), la = A(s, 7, L.a2), lg = A(s, 8, L.g2);
     b.add(L.att_r, a.out[0], r_, C, EPI_STORE);
@@ -444,11 +463,12 @@ bool Engine::layer_v7(const SeqRun & s, int l, const float * si, float * so) {
     if (!launch_v7_prep(stream_, T, H, S, k_, a_, r_, L.k_k, L.k_a, L.r_k, nb_, bb_, bonus_)) return false;
     // the serial recurrence (bit-exact with decode), or behind the wkv_chunk_ switch the chunk-parallel
     // form (wkv7_chunk.hip; scratch in wkvc_)
-    if (wkv_chunk_ && !s.seg && wkv7_chunked_supported(T, S, (int)s.bs)) {
+    const WkvTrace tr = wkv_trace(s, l);
+    if (wkv_chunk_ && !s.seg && !s.trace && wkv7_chunked_supported(T, S, (int)s.bs)) {
         const size_t need = wkv7_chunked_scratch_floats(T, H);
         if (!grow(wkvc_, need, need, GRAPHS_NONE)) return false;
         if (!launch_wkv7_chunked(stream_, T, H, r_, w_, k_, v_, nb_, bb_, si + 2 * C, so + 2 * C, y_, wkvc_)) return false;
-    } else if (!launch_wkv7(stream_, T, H, S, r_, w_, k_, v_, nb_, bb_, si + 2 * C, so + 2 * C, y_, s.seg)) {
+    } else if (!launch_wkv7(stream_, T, H, S, r_, w_, k_, v_, nb_, bb_, si + 2 * C, so + 2 * C, y_, s.seg, s.trace ? &tr : nullptr)) {
         return false;
     }
     ActBuf o = A(s, 0, L.att_o);

@@ -70,17 +70,33 @@ bool launch_ln_mix(hipStream_t st, const LnMixArgs & a, const SegTab * seg = nul
 bool launch_v6_mix5(hipStream_t st, int T, int C, int D, const float * lora, const float * w2,
                     const float * const * maa, const float * xa, const float * sx, const ActBuf * outs);
 
+// The trace form of the serial WKV kernels (speculative generation): a template argument of
+// the recurrence bodies.  WkvTrace: one sequence of at most SPEC_ROWS tokens; after token t the kernel
+// also stores its state into entry t, `stride` floats apart, at the layer's WKV offset -- WKV-4 and WKV-7
+// in the state's own layout, WKV-6 value-major ([h][j][i] for the state's [h][i][j]): in every kernel a
+// wave's store is then one contiguous run.  WkvNoTrace: nothing, the kernels as they were.
+constexpr int SPEC_ROWS = 16;
+struct WkvNoTrace {
+    static constexpr bool on = false;
+};
+struct WkvTrace {
+    static constexpr bool on = true;
+    float * base;    // entry 0 at the layer's state offset
+    size_t stride;   // floats between two entries
+    __device__ __forceinline__ float * entry(int t) const { return base + (size_t)t * stride; }
+};
+
 // v4 wkv with aa/bb/pp state (rwkv_graph.inc:119-161); emits r*wkv into `out`.
 // bs > 0 (this wkv launcher only -- batched v5 / v6 / v7 run k_att6_dec / k_att7_dec): batched
 // decode -- the T tokens are T contexts, one token each, context t's state at state_in/out + t * bs.
 bool launch_wkv4(hipStream_t st, int T, int C, const float * r, const float * k, const float * v,
                  const float * first, const float * decay, const float * state_in, float * state_out,
-                 const ActBuf & out, int bs = 0, const SegTab * seg = nullptr);
+                 const ActBuf & out, int bs = 0, const SegTab * seg = nullptr, const WkvTrace * tr = nullptr);
 
 // ggml_rwkv_wkv6 semantics (v5/v6): y[T][C]; w_per_token selects v6 (w [T][C]) vs v5 (w [C]).
 bool launch_wkv6(hipStream_t st, int T, int H, int S, const float * k, const float * v, const float * r,
                  const float * u, const float * w, int w_per_token, const float * state_in,
-                 float * state_out, float * y, const SegTab * seg = nullptr);
+                 float * state_out, float * y, const SegTab * seg = nullptr, const WkvTrace * tr = nullptr);
 
 // Chunk-parallel wkv6 (wkv_chunk.hip, head size 64, T >= 2, no batch): the same recurrence with the
 // sums re-associated (not bit-exact with launch_wkv6).  RA / KB: [T][C] scratch; scratch:
@@ -107,7 +123,7 @@ bool launch_v7_prep(hipStream_t st, int T, int H, int S, float * k, const float 
 // rwkv_operators_wkv_v7.inc:37-107
 bool launch_wkv7(hipStream_t st, int T, int H, int S, const float * r, const float * w, const float * k,
                  const float * v, const float * a, const float * b, const float * state_in,
-                 float * state_out, float * y, const SegTab * seg = nullptr);
+                 float * state_out, float * y, const SegTab * seg = nullptr, const WkvTrace * tr = nullptr);
 
 // GroupNorm over heads + ln_x (+ v7 bonus) (+ gate), emitted as the output projection's input.
 // mode 0: none, 1: *g, 2: + v*bonus then *g
@@ -449,6 +465,47 @@ bool launch_beam_select(hipStream_t st, const BeamArgs & a);
 bool launch_beam_gather(hipStream_t st, const BeamArgs & a, const float * src, float * dst, size_t state_len);
 // tokens [W][n]: beam j's length_out[j] tokens, walked back through `steps` lines of hist, then GEN_NONE
 bool launch_beam_finish(hipStream_t st, const BeamArgs & a, uint32_t steps, uint32_t * tokens, size_t n);
+
+// ---- speculative generation (spec.hip; rwkv_mi355x_generate_speculative) --------------
+constexpr uint32_t SPEC_MAX_NGRAM = 8, SPEC_MAX_CORPUS = 1u << 20;
+// The words of a call, device memory: the step's draft count, the step's accepted count, the tokens
+// emitted before the step; key = the draft search's running maximum, ticket = its workgroups done
+// (both 0 between launches: the last workgroup of a search clears them).
+struct SpecWords {
+    uint32_t *d, *m, *e;
+    unsigned long long * key;
+    uint32_t * ticket;
+};
+// The corpus is history (nh tokens) followed by the tokens emitted so far; rows[0] is the step's drawn
+// token x0 (the sampler's second copy), which the search appends at corpus[nh + e], and the draft goes to
+// rows[1 .. d]: the rows of the sequence pass.  The rule is rwkv_cpp.sampling.ngram_draft over the
+// corpus with x0, cut to n - e - 1 tokens; *w.e >= n: nothing happens but *w.d = 0.
+struct SpecDraft {
+    uint32_t * corpus;   // [nh + n]
+    uint32_t nh, n;
+    uint32_t k, gmin, gmax;
+    uint32_t * rows;     // [1 + k]
+    SpecWords w;
+};
+bool launch_spec_draft(hipStream_t st, const SpecDraft & a);
+// After the sampler has drawn rows 0 .. d (draws[r] from logits row r): m = the first r < d with
+// draws[r] != rows[1 + r], else d; rows[1 .. m] are appended to the corpus behind x0, *w.e += 1 + m,
+// *w.m = m and rows[0] = draws[m], the next step's x0 (it is the draw of counter offset + e + 1 + m from
+// the logits row the commit makes live).  *w.d == 0 (a one-token step): m = 0, rows stays.
+bool launch_spec_accept(hipStream_t st, const SpecDraft & a, const uint32_t * draws);
+// The state layout the commit restores from a trace entry: per layer `shift` floats in the state's own
+// layout (the token-shift rows; WKV-4: all 5 C), then H heads of S x S floats, transposed when the trace
+// is value-major (WKV-6)
+struct SpecGeom {
+    uint32_t n_layer, H, S;
+    size_t shift, per_layer, state_len;
+    int transposed;
+};
+// state = trace entry *m (entries state_len floats apart), logits = row *m of tile [.][V]
+bool launch_spec_commit(hipStream_t st, const SpecGeom & g, const float * trace, float * state, const float * tile,
+                        float * logits, size_t V, const uint32_t * m);
+// trace entry t, floats [off, off + C) = row t of xa [T][C], t < T <= SPEC_ROWS: a layer's token-shift row
+bool launch_spec_shift_trace(hipStream_t st, const float * xa, int T, int C, float * trace_at, size_t stride);
 
 // One workgroup per row of logits [rows][V] (xent.hip): loss[r] = -log softmax(row r)[targets[r]]
 // with the exponentials and their sum in fp64, argmax[r] = the lowest index of the row's maximum.

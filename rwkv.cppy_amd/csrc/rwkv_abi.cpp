@@ -712,9 +712,17 @@ static bool sample_call(struct rwkv_context * ctx, const struct rwkv_mi355x_samp
     return true;
 }
 
+// A speculative call (rwkv_mi355x_generate_speculative) is generate's body with these two: the same
+// checks in the same order, then the speculation's own, then the engine's speculative loop.
+struct SpecCall {
+    const struct rwkv_mi355x_speculation * spec;
+    struct rwkv_mi355x_spec_stats * stats;
+};
+
 static bool generate_call(struct rwkv_context * ctx, const struct rwkv_mi355x_sampling * params, size_t n,
                           uint32_t * tokens_out, float * logits_out, const struct rwkv_mi355x_logprobs * lp,
-                          const struct rwkv_mi355x_filters * f, const struct rwkv_mi355x_constraint * c) {
+                          const struct rwkv_mi355x_filters * f, const struct rwkv_mi355x_constraint * c,
+                          const SpecCall * sc = nullptr) {
     if (!ctx || !ctx->engine) return false;
     ctx->last_error = RWKV_ERROR_NONE;
     SamplingParams sp;
@@ -722,6 +730,29 @@ static bool generate_call(struct rwkv_context * ctx, const struct rwkv_mi355x_sa
     if (!logprobs_ok(ctx, lp, x) || !sampling_ok(ctx, params, sp) || !filters_ok(ctx, f, 1, x)) return false;
     CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, n > 0 && n <= 65536, "Token count %zu is outside [1, 65536]", n);
     CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, tokens_out != nullptr, "NULL tokens_out");
+    if (sc) {
+        const struct rwkv_mi355x_speculation * s = sc->spec;
+        CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, s != nullptr, "NULL speculation parameters");
+        CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, s->draft_len >= 1 && s->draft_len < (uint32_t)SPEC_ROWS,
+                  "draft_len %" PRIu32 " is outside [1, %d]", s->draft_len, SPEC_ROWS - 1);
+        CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, s->ngram_min >= 1 && s->ngram_min <= s->ngram_max && s->ngram_max <= SPEC_MAX_NGRAM,
+                  "n-gram lengths [%" PRIu32 ", %" PRIu32 "] are not 1 <= min <= max <= %" PRIu32, s->ngram_min, s->ngram_max,
+                  SPEC_MAX_NGRAM);
+        CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, s->n_history == 0 || s->history != nullptr, "NULL history");
+        CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, s->n_history <= SPEC_MAX_CORPUS && s->n_history + n <= SPEC_MAX_CORPUS,
+                  "History and output are %zu tokens, above %" PRIu32, s->n_history + n, SPEC_MAX_CORPUS);
+        for (size_t i = 0; i < s->n_history; i++)
+            CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, s->history[i] < ctx->model->dm.n_vocab, "History token %zu out of range", i);
+        SpecParams p;
+        p.draft_len = s->draft_len, p.ngram_min = s->ngram_min, p.ngram_max = s->ngram_max;
+        p.history = s->history, p.n_history = s->n_history;
+        SpecStats st;
+        use_device(ctx);
+        CTX_CHECK(ctx, RWKV_ERROR_CTX, false, ctx->engine->generate_speculative(sp, p, n, tokens_out, logits_out, &st),
+                  "GPU speculative generation failed");
+        if (sc->stats) *sc->stats = rwkv_mi355x_spec_stats{st.steps, st.drafted, st.accepted};
+        return true;
+    }
     if (!constraint_ok(ctx, c, 1, 1, x) || !logprobs_reserve(ctx, lp, 1, n)) return false;
     use_device(ctx);
     CTX_CHECK(ctx, RWKV_ERROR_CTX, false, ctx->engine->generate(sp, n, tokens_out, logits_out, x), "GPU generation failed");
@@ -750,6 +781,12 @@ RWKV_API bool rwkv_mi355x_sample_constrained(struct rwkv_context * ctx, const st
 RWKV_API bool rwkv_mi355x_generate(struct rwkv_context * ctx, const struct rwkv_mi355x_sampling * params, size_t n,
                                    uint32_t * tokens_out, float * logits_out) {
     return generate_call(ctx, params, n, tokens_out, logits_out, nullptr, nullptr, nullptr);
+}
+RWKV_API bool rwkv_mi355x_generate_speculative(struct rwkv_context * ctx, const struct rwkv_mi355x_sampling * params,
+                                               const struct rwkv_mi355x_speculation * spec, size_t n, uint32_t * tokens_out,
+                                               float * logits_out, struct rwkv_mi355x_spec_stats * stats) {
+    const SpecCall sc{spec, stats};
+    return generate_call(ctx, params, n, tokens_out, logits_out, nullptr, nullptr, nullptr, &sc);
 }
 RWKV_API bool rwkv_mi355x_generate_logprobs(struct rwkv_context * ctx, const struct rwkv_mi355x_sampling * params,
                                             size_t n, uint32_t * tokens_out, float * logits_out,

@@ -1190,3 +1190,91 @@ extern "C" RWKV_API bool rwkv_mi355x_selftest_dfa_advance(uint32_t * states, con
     if (!launch_dfa_advance(nullptr, d) || hipDeviceSynchronize() != hipSuccess) return false;
     return hipMemcpy(states, d.state, RB, hipMemcpyDeviceToHost) == hipSuccess;
 }
+
+// ---- speculative generation (spec.hip) -----------------------------------------------------------
+// the words and rows of a call on selftest buffers; rows [SPEC_ROWS], corpus [nh + n]
+static bool selftest_spec_args(DevBufs & b, size_t nh, size_t n, SpecDraft & sd) {
+    memset(&sd, 0, sizeof(sd));
+    sd.corpus = (uint32_t *)b.alloc((nh + n) * 4);
+    sd.rows = (uint32_t *)b.alloc(SPEC_ROWS * 4);
+    unsigned long long * w = (unsigned long long *)b.alloc(4 * 8);  // zeros
+    if (!sd.corpus || !sd.rows || !w) return false;
+    uint32_t * words = (uint32_t *)(w + 1);
+    sd.w = SpecWords{words, words + 1, words + 2, w, words + 3};
+    sd.nh = (uint32_t)nh, sd.n = (uint32_t)n;
+    return true;
+}
+
+// The search runs twice: the second launch finds the words as the first one's last workgroup left them.
+extern "C" RWKV_API bool rwkv_mi355x_selftest_spec_draft(const uint32_t * corpus, size_t L, uint32_t k, uint32_t ngram_min,
+                                                        uint32_t ngram_max, uint32_t limit, uint32_t * draft, uint32_t * d_out) {
+    if (!corpus || L < 1 || L > SPEC_MAX_CORPUS || limit < 1 || limit >= (uint32_t)SPEC_ROWS || !draft || !d_out ||
+        L + limit > SPEC_MAX_CORPUS)
+        return false;
+    DevBufs b;
+    SpecDraft sd;
+    if (!selftest_spec_args(b, L - 1, (size_t)limit + 1, sd)) return false;
+    sd.k = k, sd.gmin = ngram_min, sd.gmax = ngram_max;
+    if ((L > 1 && hipMemcpy(sd.corpus, corpus, (L - 1) * 4, hipMemcpyHostToDevice) != hipSuccess) ||
+        hipMemcpy(sd.rows, corpus + L - 1, 4, hipMemcpyHostToDevice) != hipSuccess)
+        return false;
+    uint32_t first[SPEC_ROWS] = {0}, d1 = 0;
+    for (int pass = 0; pass < 2; pass++) {
+        if (!launch_spec_draft(nullptr, sd) || hipDeviceSynchronize() != hipSuccess ||
+            hipMemcpy(d_out, sd.w.d, 4, hipMemcpyDeviceToHost) != hipSuccess || *d_out >= (uint32_t)SPEC_ROWS ||
+            hipMemcpy(draft, sd.rows + 1, (SPEC_ROWS - 1) * 4, hipMemcpyDeviceToHost) != hipSuccess)
+            return false;
+        if (pass == 0) d1 = *d_out, memcpy(first, draft, (SPEC_ROWS - 1) * 4);
+    }
+    return d1 == *d_out && memcmp(first, draft, d1 * 4) == 0;
+}
+
+extern "C" RWKV_API bool rwkv_mi355x_selftest_spec_accept(const float * logits, int d, int V, const struct rwkv_mi355x_sampling * p,
+                                                         const uint32_t * drafts, int arch, uint32_t n_layer, uint32_t H, uint32_t S,
+                                                         const float * trace, uint32_t * m_out, uint32_t * appended,
+                                                         uint32_t * next_x0, float * state_out, float * logits_out) {
+    if (!logits || !p || !drafts || !trace || !m_out || !appended || !next_x0 || !state_out || !logits_out || d < 1 ||
+        d >= SPEC_ROWS || V < 1 || V > SAMPLE_MAX_VOCAB || arch < 4 || arch > 7 || n_layer < 1 || H < 1 || S < 1 || S > 64 ||
+        p->n_bias != 0 || !(p->temperature >= 0.0f) || !(p->top_p >= 0.0f && p->top_p <= 1.0f))
+        return false;
+    const size_t C = (size_t)H * S, rows = (size_t)d + 1;
+    SpecGeom g;
+    g.n_layer = n_layer;
+    g.H = arch == 4 ? 0u : H, g.S = arch == 4 ? 0u : S;
+    g.per_layer = arch == 4 ? 5 * C : C * (2 + S);
+    g.shift = arch == 4 ? g.per_layer : 2 * C;
+    g.state_len = g.per_layer * n_layer;
+    g.transposed = arch == 5 || arch == 6;
+    DevBufs b;
+    SpecDraft sd;
+    if (!selftest_spec_args(b, 0, rows, sd)) return false;
+    sd.k = (uint32_t)d, sd.gmin = sd.gmax = 1;
+    float * dl = (float *)b.alloc(rows * V * 4);
+    float * dtr = (float *)b.alloc(rows * g.state_len * 4);
+    float * dst = (float *)alloc_poison(b, g.state_len * 4);
+    float * dlo = (float *)alloc_poison(b, (size_t)V * 4);
+    uint32_t * draws = (uint32_t *)alloc_poison(b, SPEC_ROWS * 4);
+    const uint32_t dd = (uint32_t)d;
+    if (!dl || !dtr || !dst || !dlo || !draws || hipMemcpy(dl, logits, rows * V * 4, hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemcpy(dtr, trace, rows * g.state_len * 4, hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemcpy(sd.rows + 1, drafts, (size_t)d * 4, hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemcpy(sd.w.d, &dd, 4, hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemset(sd.corpus, 0xff, rows * 4) != hipSuccess)
+        return false;
+    SampleArgs a;
+    memset(&a, 0, sizeof(a));
+    a.logits = dl, a.rows = (int)rows, a.V = V;
+    a.temperature = p->temperature, a.top_p = p->top_p;
+    a.seed = p->seed, a.counter = p->offset;
+    a.tok = draws;
+    if (!launch_sample(nullptr, a) || !launch_spec_accept(nullptr, sd, draws) ||
+        !launch_spec_commit(nullptr, g, dtr, dst, dl, dlo, (size_t)V, sd.w.m) || hipDeviceSynchronize() != hipSuccess)
+        return false;
+    uint32_t e = 0;
+    if (hipMemcpy(m_out, sd.w.m, 4, hipMemcpyDeviceToHost) != hipSuccess || hipMemcpy(&e, sd.w.e, 4, hipMemcpyDeviceToHost) != hipSuccess ||
+        e != 1 + *m_out || hipMemcpy(appended, sd.corpus + 1, (size_t)d * 4, hipMemcpyDeviceToHost) != hipSuccess ||
+        hipMemcpy(next_x0, sd.rows, 4, hipMemcpyDeviceToHost) != hipSuccess)
+        return false;
+    return hipMemcpy(state_out, dst, g.state_len * 4, hipMemcpyDeviceToHost) == hipSuccess &&
+           hipMemcpy(logits_out, dlo, (size_t)V * 4, hipMemcpyDeviceToHost) == hipSuccess;
+}

@@ -13,10 +13,10 @@ namespace rwkvmi {
 
 // --------------------------------------------------------------------------- v4 wkv
 // tb (both WKV-4 kernels): the output row of the span's token 0
-template <class Span>
+template <class Span, class Tr = WkvNoTrace>
 __global__ __launch_bounds__(256) void k_wkv4(Span sp, int C, const float * r, const float * k, const float * v,
                                               const float * first, const float * decay, const float * sin,
-                                              float * sout, ActBuf out) {
+                                              float * sout, ActBuf out, Tr tr) {
     const int c = blockIdx.x * blockDim.x + threadIdx.x;
     if (c >= C) return;
     const WkvPlace pl = sp.at(blockIdx.z);
@@ -40,6 +40,10 @@ __global__ __launch_bounds__(256) void k_wkv4(Span sp, int C, const float * r, c
         aa = e1 * aa + e2 * vt;
         bb = e1 * bb + e2;
         pp = qq;
+        if constexpr (Tr::on) {
+            float * e = tr.entry(t);
+            e[2 * C + c] = aa, e[3 * C + c] = bb, e[4 * C + c] = pp;
+        }
         emit32(out, tb + t, c, r[i] * (an / bn));
     }
     sout[2 * C + c] = aa;
@@ -54,10 +58,10 @@ __global__ __launch_bounds__(256) void k_wkv4(Span sp, int C, const float * r, c
 // outputs of a chunk are emitted after its recurrence steps, off the chain.  Per channel and
 // token the operations are k_wkv4's, in its order, so decode and sequence stay bit-identical.
 constexpr int WKV4_TT = 16;
-template <class Span>
+template <class Span, class Tr = WkvNoTrace>
 __global__ __launch_bounds__(64) void k_wkv4_seq(Span sp, int C, const float * r, const float * k, const float * v,
                                                  const float * first, const float * decay, const float * sin,
-                                                 float * sout, ActBuf out) {
+                                                 float * sout, ActBuf out, Tr tr) {
     const WkvPlace pl = sp.at(blockIdx.z);
     wkv_advance((size_t)pl.row * C, r, k, v);
     sin += pl.sin, sout += pl.sout;
@@ -101,6 +105,12 @@ __global__ __launch_bounds__(64) void k_wkv4_seq(Span sp, int C, const float * r
                 bb = e1 * bb + e2;
                 pp = qq;
                 y[tt] = rc[tt] * (an / bn);
+                if constexpr (Tr::on) {
+                    if (c < C) {
+                        float * e = tr.entry(t0 + tt);
+                        e[2 * C + c] = aa, e[3 * C + c] = bb, e[4 * C + c] = pp;
+                    }
+                }
             }
         }
 #pragma unroll
@@ -116,7 +126,14 @@ __global__ __launch_bounds__(64) void k_wkv4_seq(Span sp, int C, const float * r
 
 bool launch_wkv4(hipStream_t st, int T, int C, const float * r, const float * k, const float * v,
                  const float * first, const float * decay, const float * state_in, float * state_out,
-                 const ActBuf & out, int bs, const SegTab * seg) {
+                 const ActBuf & out, int bs, const SegTab * seg, const WkvTrace * tr) {
+    if (tr) {  // one sequence of 2 .. 16 tokens (launch_wkv_trace_ok): the same choice of kernel as below
+        const SpanSeq sp{T};
+        if (C % 64 == 0) RK_LAUNCH((k_wkv4_seq<SpanSeq, WkvTrace>), dim3(C / 64), dim3(64), 0, st, sp, C, r, k, v, first, decay, state_in, state_out, out, *tr);
+        else RK_LAUNCH((k_wkv4<SpanSeq, WkvTrace>), dim3((C + 255) / 256), dim3(256), 0, st, sp, C, r, k, v, first, decay, state_in, state_out, out, *tr);
+        HIP_OK(hipGetLastError());
+        return true;
+    }
     return with_span(T, bs, seg, [&](auto sp, int nz) {
         using Span = decltype(sp);
         // k_wkv4_seq for whole waves of channels, except one token of one sequence (decode) and the
@@ -125,13 +142,13 @@ bool launch_wkv4(hipStream_t st, int T, int C, const float * r, const float * k,
         if constexpr (!std::is_same_v<Span, SpanCtx>) {
             if (C % 64 == 0 && (seg || T > 1)) {
                 RK_LAUNCH(k_wkv4_seq<Span>, dim3(C / 64, 1, nz), dim3(64), 0, st, sp, C, r, k, v, first, decay, state_in,
-                          state_out, out);
+                          state_out, out, WkvNoTrace{});
                 HIP_OK(hipGetLastError());
                 return true;
             }
         }
         RK_LAUNCH(k_wkv4<Span>, dim3((C + 255) / 256, 1, nz), dim3(256), 0, st, sp, C, r, k, v, first, decay,
-                  state_in, state_out, out);
+                  state_in, state_out, out, WkvNoTrace{});
         HIP_OK(hipGetLastError());
         return true;
     });
@@ -140,10 +157,10 @@ bool launch_wkv4(hipStream_t st, int T, int C, const float * r, const float * k,
 // --------------------------------------------------------------------------- wkv6 (v5/v6)
 // One workgroup per head; lane group (j, g): j = value index, g splits the key index i.
 // The state column S[i][j] for the lane's IPG keys lives in registers across all T tokens.
-template <int IPG, class Span>
+template <int IPG, class Span, class Tr = WkvNoTrace>
 __global__ void k_wkv6(Span sp, int H, int S, int G, const float * k, const float * v, const float * r,
                        const float * u, const float * w, int w_per_token, const float * sin, float * sout,
-                       float * y) {
+                       float * y, Tr tr) {
     const int h = blockIdx.x;
     const int j = threadIdx.x / G, g = threadIdx.x % G;
     const int C = H * S;
@@ -175,6 +192,11 @@ __global__ void k_wkv6(Span sp, int H, int S, int G, const float * k, const floa
         }
         acc = group_sum(acc, G);
         if (g == 0) y[th + j] = acc;
+        if constexpr (Tr::on) {  // value-major: the thread's IPG keys are IPG consecutive floats
+            float * e = tr.entry(t) + hb + (size_t)j * S + g * IPG;
+#pragma unroll
+            for (int ii = 0; ii < IPG; ii++) e[ii] = st[ii];
+        }
     }
 #pragma unroll
     for (int ii = 0; ii < IPG; ii++) sout[hb + (size_t)(g * IPG + ii) * S + j] = st[ii];
@@ -246,10 +268,10 @@ constexpr int WKV6_PAD = 8;  // >= 2 * the token group
 // operand and thread -- as arrays over a variable width they are kept in scratch)
 constexpr int WKV6_NWV = 4;
 
-template <bool WPT, class Span>
+template <bool WPT, class Span, class Tr = WkvNoTrace>
 __global__ __launch_bounds__(64 * WKV6_NWV) void k_wkv6_s64(Span sp, int H, const float * k, const float * v,
                                                             const float * r, const float * u, const float * w,
-                                                            const float * sin, float * sout, float * y) {
+                                                            const float * sin, float * sout, float * y, Tr tr) {
     constexpr int S = 64, NWV = WKV6_NWV;
     const WkvPlace pl = sp.at(blockIdx.z);
     wkv_advance((size_t)pl.row * H * S, k, v, r, y);
@@ -362,6 +384,11 @@ __global__ __launch_bounds__(64 * WKV6_NWV) void k_wkv6_s64(Span sp, int H, cons
                     ns = ns + kv[p];
                     st[p] = val ? ns : st[p];
                 }
+                if constexpr (Tr::on) {
+                    // value-major: keys i0 .. i0 + 3 of column j are one float4, a wave's 64 of them
+                    // the 4 whole rows j = 16 jb + 4 wv + (0 .. 3): 1 KB contiguous
+                    if (val) *(float4 *)(tr.entry(t0 + tt0 + e) + hb + (size_t)j * S + i0) = make_float4(st[0].x, st[0].y, st[1].x, st[1].y);
+                }
             }
             // p_q (4 keys in order), (p0 + p1) + (p2 + p3) over the quad, TG sums side by side
             float acc[TG];
@@ -425,19 +452,35 @@ __global__ __launch_bounds__(64 * WKV6_NWV) void k_wkv6_s64(Span sp, int H, cons
 
 bool launch_wkv6(hipStream_t st, int T, int H, int S, const float * k, const float * v, const float * r,
                  const float * u, const float * w, int w_per_token, const float * state_in, float * state_out,
-                 float * y, const SegTab * seg) {
+                 float * y, const SegTab * seg, const WkvTrace * tr) {
+    if (tr) {
+        const SpanSeq sp{T};
+        if (S == 64) {
+            const dim3 grid(H, 16 / WKV6_NWV), block(64 * WKV6_NWV);
+            if (w_per_token) RK_LAUNCH((k_wkv6_s64<true, SpanSeq, WkvTrace>), grid, block, 0, st, sp, H, k, v, r, u, w, state_in, state_out, y, *tr);
+            else RK_LAUNCH((k_wkv6_s64<false, SpanSeq, WkvTrace>), grid, block, 0, st, sp, H, k, v, r, u, w, state_in, state_out, y, *tr);
+            HIP_OK(hipGetLastError());
+            return true;
+        }
+        return with_key_groups(S, [&](int G, auto ipg) {
+            RK_LAUNCH((k_wkv6<decltype(ipg)::value, SpanSeq, WkvTrace>), dim3(H), dim3(S * G), 0, st, sp, H, S, G, k, v, r, u, w,
+                      w_per_token, state_in, state_out, y, *tr);
+            HIP_OK(hipGetLastError());
+            return true;
+        });
+    }
     return with_span(T, seg, [&](auto sp, int nz) {
         using Span = decltype(sp);
         if (S == 64) {
             const dim3 grid(H, 16 / WKV6_NWV, nz), block(64 * WKV6_NWV);
-            if (w_per_token) RK_LAUNCH((k_wkv6_s64<true, Span>), grid, block, 0, st, sp, H, k, v, r, u, w, state_in, state_out, y);
-            else RK_LAUNCH((k_wkv6_s64<false, Span>), grid, block, 0, st, sp, H, k, v, r, u, w, state_in, state_out, y);
+            if (w_per_token) RK_LAUNCH((k_wkv6_s64<true, Span>), grid, block, 0, st, sp, H, k, v, r, u, w, state_in, state_out, y, WkvNoTrace{});
+            else RK_LAUNCH((k_wkv6_s64<false, Span>), grid, block, 0, st, sp, H, k, v, r, u, w, state_in, state_out, y, WkvNoTrace{});
             HIP_OK(hipGetLastError());
             return true;
         }
         return with_key_groups(S, [&](int G, auto ipg) {
             RK_LAUNCH((k_wkv6<decltype(ipg)::value, Span>), dim3(H, 1, nz), dim3(S * G), 0, st, sp, H, S, G, k, v, r, u, w,
-                      w_per_token, state_in, state_out, y);
+                      w_per_token, state_in, state_out, y, WkvNoTrace{});
             HIP_OK(hipGetLastError());
             return true;
         });
@@ -484,10 +527,10 @@ bool launch_v7_prep(hipStream_t st, int T, int H, int S, float * k, const float 
 }
 
 // state [h][i(value)][j(key)]; lane group (i, g): g splits j.
-template <int JPG, class Span>
+template <int JPG, class Span, class Tr = WkvNoTrace>
 __global__ void k_wkv7(Span sp, int H, int S, int G, const float * r, const float * w, const float * k,
                        const float * v, const float * a, const float * b, const float * sin, float * sout,
-                       float * y) {
+                       float * y, Tr tr) {
     const int h = blockIdx.x;
     const int i = threadIdx.x / G, g = threadIdx.x % G;
     const int C = H * S;
@@ -516,6 +559,11 @@ __global__ void k_wkv7(Span sp, int H, int S, int G, const float * r, const floa
         }
         acc = group_sum(acc, G);
         if (g == 0) y[(size_t)t * C + (size_t)h * S + i] = acc;
+        if constexpr (Tr::on) {
+            float * e = tr.entry(t) + hb;
+#pragma unroll
+            for (int jj = 0; jj < JPG; jj++) e[jj] = st[jj];
+        }
     }
 #pragma unroll
     for (int jj = 0; jj < JPG; jj++) sout[hb + jj] = st[jj];
@@ -539,10 +587,10 @@ __device__ __forceinline__ float row_bfly16(float v) {
     return v;
 }
 
-template <class Span>
+template <class Span, class Tr = WkvNoTrace>
 __global__ __launch_bounds__(256) void k_wkv7_s64(Span sp, int H, const float * r, const float * w, const float * k,
                                                   const float * v, const float * a, const float * b,
-                                                  const float * sin, float * sout, float * y) {
+                                                  const float * sin, float * sout, float * y, Tr tr) {
     constexpr int S = 64;
     const WkvPlace pl = sp.at(blockIdx.z);
     wkv_advance((size_t)pl.row * H * S, r, w, k, v, a, b, y);
@@ -623,6 +671,8 @@ __global__ __launch_bounds__(256) void k_wkv7_s64(Span sp, int H, const float * 
             }
             acc = row_bfly16(acc);
             if (g == 0) sy[buf][tt][il] = acc;
+            // the state's own layout: a wave's float4s are its 4 whole rows, 1 KB contiguous
+            if constexpr (Tr::on) *(float4 *)(tr.entry(t0 + tt) + hb) = make_float4(st[0], st[1], st[2], st[3]);
         };
         Op cur, nxt;
         rd(cur, 0);
@@ -659,17 +709,31 @@ __global__ __launch_bounds__(256) void k_wkv7_s64(Span sp, int H, const float * 
 
 bool launch_wkv7(hipStream_t st, int T, int H, int S, const float * r, const float * w, const float * k,
                  const float * v, const float * a, const float * b, const float * state_in, float * state_out,
-                 float * y, const SegTab * seg) {
+                 float * y, const SegTab * seg, const WkvTrace * tr) {
+    if (tr) {
+        const SpanSeq sp{T};
+        if (S == 64) {
+            RK_LAUNCH((k_wkv7_s64<SpanSeq, WkvTrace>), dim3(H, 4), dim3(256), 0, st, sp, H, r, w, k, v, a, b, state_in, state_out, y, *tr);
+            HIP_OK(hipGetLastError());
+            return true;
+        }
+        return with_key_groups(S, [&](int G, auto jpg) {
+            RK_LAUNCH((k_wkv7<decltype(jpg)::value, SpanSeq, WkvTrace>), dim3(H), dim3(S * G), 0, st, sp, H, S, G, r, w, k, v, a, b,
+                      state_in, state_out, y, *tr);
+            HIP_OK(hipGetLastError());
+            return true;
+        });
+    }
     return with_span(T, seg, [&](auto sp, int nz) {
         using Span = decltype(sp);
         if (S == 64) {
-            RK_LAUNCH(k_wkv7_s64<Span>, dim3(H, 4, nz), dim3(256), 0, st, sp, H, r, w, k, v, a, b, state_in, state_out, y);
+            RK_LAUNCH(k_wkv7_s64<Span>, dim3(H, 4, nz), dim3(256), 0, st, sp, H, r, w, k, v, a, b, state_in, state_out, y, WkvNoTrace{});
             HIP_OK(hipGetLastError());
             return true;
         }
         return with_key_groups(S, [&](int G, auto jpg) {
             RK_LAUNCH((k_wkv7<decltype(jpg)::value, Span>), dim3(H, 1, nz), dim3(S * G), 0, st, sp, H, S, G, r, w, k, v, a, b,
-                      state_in, state_out, y);
+                      state_in, state_out, y, WkvNoTrace{});
             HIP_OK(hipGetLastError());
             return true;
         });

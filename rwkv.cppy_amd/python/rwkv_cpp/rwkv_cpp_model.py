@@ -276,6 +276,22 @@ class RWKVModel:
                 parts.append(lp)
         return result(out, None)
 
+    def generate_speculative(self, n: int, history=(), draft_len: int = 4, ngram_min: int = 1, ngram_max: int = 4,
+                             temperature: float = 1.0, top_p: float = 0.8, logit_bias=None, seed: int = 0,
+                             offset: int = 0):
+        """MI355X extension (rwkv_mi355x_generate_speculative): exactly the n tokens, the state and the
+        logits of generate(n, block=n) with the same sampling arguments, in steps that emit one drawn
+        token plus every drafted token the model confirms.  The drafts are an n-gram lookup
+        (sampling.ngram_draft) over `history` followed by the tokens emitted so far: pass the prompt, a
+        prediction of the output, or both -- it pays when much of the output repeats them, and costs
+        time when it does not (README).  Single sequence only: no stop tokens, log-probabilities,
+        filters or constraints.  Returns (tokens, stats), stats = {'steps', 'drafted', 'accepted'} with
+        steps + accepted == n."""
+        if not self._valid:
+            raise ValueError('Model was freed')
+        return self._library.rwkv_mi355x_generate_speculative(self._ctx, n, history, draft_len, ngram_min, ngram_max,
+                                                              temperature, top_p, logit_bias, seed, offset)
+
     # ---- batched generation (rwkv_mi355x_generate_batch) --------------------------------------
     def batch_reserve(self, n_slots: int) -> None:
         """MI355X extension: gives the model n_slots <= 256 generation slots (0 frees them).  Every

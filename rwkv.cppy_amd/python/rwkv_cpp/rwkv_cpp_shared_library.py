@@ -65,6 +65,17 @@ class RWKVBeam(ctypes.Structure):
                 ('length_penalty', ctypes.c_float), ('check_every', ctypes.c_uint32)]
 
 
+class RWKVSpeculation(ctypes.Structure):
+    """struct rwkv_mi355x_speculation (include/rwkv_mi355x.h)."""
+    _fields_ = [('draft_len', ctypes.c_uint32), ('ngram_min', ctypes.c_uint32), ('ngram_max', ctypes.c_uint32),
+                ('history', ctypes.POINTER(ctypes.c_uint32)), ('n_history', ctypes.c_size_t)]
+
+
+class RWKVSpecStats(ctypes.Structure):
+    """struct rwkv_mi355x_spec_stats (include/rwkv_mi355x.h)."""
+    _fields_ = [('steps', ctypes.c_uint64), ('drafted', ctypes.c_uint64), ('accepted', ctypes.c_uint64)]
+
+
 class RWKVLogprobs(ctypes.Structure):
     """struct rwkv_mi355x_logprobs (include/rwkv_mi355x.h)."""
     _fields_ = [('top_k', ctypes.c_uint32), ('token_logprob', ctypes.POINTER(ctypes.c_double)),
@@ -407,6 +418,14 @@ class RWKVSharedLibrary:
         L.rwkv_mi355x_selftest_wkv_layouts.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int, P_U32, ctypes.c_int,
                                                        ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint64)]
         L.rwkv_mi355x_selftest_wkv_layouts.restype = ctypes.c_bool
+        L.rwkv_mi355x_generate_speculative.argtypes = [vp, P_SAMPLING, ctypes.POINTER(RWKVSpeculation), sz, P_U32, P_FLOAT,
+                                                       ctypes.POINTER(RWKVSpecStats)]
+        L.rwkv_mi355x_generate_speculative.restype = ctypes.c_bool
+        L.rwkv_mi355x_selftest_spec_draft.argtypes = [P_U32, sz, u32, u32, u32, u32, P_U32, P_U32]
+        L.rwkv_mi355x_selftest_spec_draft.restype = ctypes.c_bool
+        L.rwkv_mi355x_selftest_spec_accept.argtypes = [P_FLOAT, ctypes.c_int, ctypes.c_int, P_SAMPLING, P_U32, ctypes.c_int,
+                                                       u32, u32, u32, P_FLOAT, P_U32, P_U32, P_U32, P_FLOAT, P_FLOAT]
+        L.rwkv_mi355x_selftest_spec_accept.restype = ctypes.c_bool
 
         self.nullptr = ctypes.cast(0, ctypes.c_void_p)
 
@@ -536,6 +555,58 @@ class RWKVSharedLibrary:
         if lp is None:
             return list(tokens[:n])
         return list(tokens[:n]), Logprobs(*(x[0, :n] for x in out))
+
+    def rwkv_mi355x_generate_speculative(self, ctx: RWKVContext, n: int, history=(), draft_len: int = 4,
+                                         ngram_min: int = 1, ngram_max: int = 4, temperature: float = 1.0,
+                                         top_p: float = 0.8, logit_bias=None, seed: int = 0, offset: int = 0,
+                                         logits_out_address: Optional[int] = None):
+        """rwkv_mi355x_generate's tokens, state and logits in speculative steps: drafts from an n-gram
+        lookup over history + the emitted tokens, verified by one traced sequence pass each.  Returns
+        (tokens, stats) with stats = {'steps', 'drafted', 'accepted'}."""
+        import numpy as np
+        hist = np.ascontiguousarray(history, dtype=np.uint32)
+        tokens = (ctypes.c_uint32 * max(1, n))()
+        p = make_sampling(temperature, top_p, logit_bias, seed, offset)
+        s = RWKVSpeculation(draft_len, ngram_min, ngram_max, hist.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)), hist.size)
+        st = RWKVSpecStats()
+        if not self.library.rwkv_mi355x_generate_speculative(ctx.ptr, ctypes.byref(p), ctypes.byref(s), n, tokens,
+                                                             ctypes.cast(logits_out_address or 0, P_FLOAT), ctypes.byref(st)):
+            raise ValueError('rwkv_mi355x_generate_speculative failed, check stderr')
+        return list(tokens[:n]), {'steps': st.steps, 'drafted': st.drafted, 'accepted': st.accepted}
+
+    def rwkv_mi355x_selftest_spec_draft(self, corpus, k: int, ngram_min: int, ngram_max: int, limit: int = 15):
+        """k_spec_draft on a host corpus whose last token is the step's x0; at most `limit` tokens are
+        still wanted behind x0.  Returns the draft, a list."""
+        import numpy as np
+        c = np.ascontiguousarray(corpus, dtype=np.uint32)
+        P_U32 = ctypes.POINTER(ctypes.c_uint32)
+        draft, d = np.zeros(15, np.uint32), ctypes.c_uint32(0)
+        if not self.library.rwkv_mi355x_selftest_spec_draft(c.ctypes.data_as(P_U32), c.size, k, ngram_min, ngram_max, limit,
+                                                            draft.ctypes.data_as(P_U32), ctypes.byref(d)):
+            raise ValueError('rwkv_mi355x_selftest_spec_draft failed')
+        return [int(t) for t in draft[:d.value]]
+
+    def rwkv_mi355x_selftest_spec_accept(self, logits, drafts, arch: int, n_layer: int, H: int, S: int, trace,
+                                         temperature: float = 1.0, top_p: float = 0.8, seed: int = 0, offset: int = 0):
+        """The rows' sampler, k_spec_accept and k_spec_commit on host operands: logits [d + 1, V], row r
+        drawn at counter offset + r; trace [d + 1, state_len] in the trace layout.  Returns (m, appended,
+        next_x0, state, logits_row)."""
+        import numpy as np
+        P_U32 = ctypes.POINTER(ctypes.c_uint32)
+        logits = np.ascontiguousarray(logits, dtype=np.float32)
+        trace = np.ascontiguousarray(trace, dtype=np.float32)
+        drafts = np.ascontiguousarray(drafts, dtype=np.uint32)
+        d, V = drafts.size, logits.shape[1]
+        assert logits.shape[0] == d + 1 and trace.shape[0] == d + 1
+        p = make_sampling(temperature, top_p, None, seed, offset)
+        m, x0 = ctypes.c_uint32(0), ctypes.c_uint32(0)
+        appended, state, row = np.zeros(d, np.uint32), np.zeros(trace.shape[1], np.float32), np.zeros(V, np.float32)
+        if not self.library.rwkv_mi355x_selftest_spec_accept(
+                logits.ctypes.data_as(P_FLOAT), d, V, ctypes.byref(p), drafts.ctypes.data_as(P_U32), arch, n_layer, H, S,
+                trace.ctypes.data_as(P_FLOAT), ctypes.byref(m), appended.ctypes.data_as(P_U32), ctypes.byref(x0),
+                state.ctypes.data_as(P_FLOAT), row.ctypes.data_as(P_FLOAT)):
+            raise ValueError('rwkv_mi355x_selftest_spec_accept failed')
+        return m.value, appended, x0.value, state, row
 
     def rwkv_mi355x_selftest_sample(self, logits, u, temperature: float = 1.0, top_p: float = 0.8, logit_bias=None,
                                     logprobs: Optional[int] = None, fill: int = 0xA5, filters: Optional[dict] = None):

@@ -246,3 +246,23 @@ def sample_probs_u(probs: np.ndarray, u: float, temperature: float = 1.0, top_p:
             return min(int(cdf.searchsorted(u * cdf[-1], side='right')), a - 1)
 
     return sample_probs(probs, temperature, top_p, logit_bias, _Fixed)
+
+
+def ngram_draft(corpus, k: int, ngram_min: int, ngram_max: int):
+    """The draft rule of rwkv_mi355x_generate_speculative over a token corpus of length L (history, the
+    emitted tokens and the step's drawn token): for g = ngram_max down to ngram_min with g < L, the
+    largest p < L - g with corpus[p:p + g] == corpus[L - g:]; the first g that matches gives
+    corpus[p + g:min(p + g + k, L)], a list (the match may overlap the end); no match: []."""
+    c = np.asarray(corpus, dtype=np.int64)
+    L = len(c)
+    for g in range(ngram_max, ngram_min - 1, -1):
+        if g >= L:
+            continue
+        hit = np.ones(L - g, dtype=bool)  # hit[p]: a match at p
+        for i in range(g):
+            hit &= c[i:L - g + i] == c[L - g + i]
+        at = np.flatnonzero(hit)
+        if at.size:
+            p = int(at[-1])
+            return [int(t) for t in c[p + g:min(p + g + k, L)]]
+    return []
