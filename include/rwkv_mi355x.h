@@ -586,6 +586,26 @@ RWKV_API bool rwkv_mi355x_eval_batch(struct rwkv_context * ctx, const uint32_t *
 RWKV_API bool rwkv_mi355x_eval_batch_device(struct rwkv_context * ctx, const uint32_t * tokens, size_t n_contexts,
                                             const float * state_in, float * state_out, float * logits_out);
 
+/* Tokenizes n_texts texts on the device with the vocabulary rwkv_mi355x_vocab_bytes gave the model:
+ * greedy longest match over bytes, the rule of rwkv_cpp.world_tokenizer.WorldTokenizer.encode_bytes.
+ * At byte i of a text the longest token whose bytes are a prefix of the rest of that text is taken
+ * (among tokens with equal bytes the highest id; a token without bytes never matches), and i moves on
+ * by its length.  Text i is bytes[offsets[i] .. offsets[i + 1]); an empty text gives no tokens.  On
+ * success text i's tokens are tokens_out[token_offsets_out[i] .. token_offsets_out[i + 1]).
+ * The call is synchronous; the context's state, logits and slots are untouched.  The byte trie is built
+ * and uploaded by the first call after rwkv_mi355x_vocab_bytes and shared by the model's clones.
+ * Errors, every one with nothing written to tokens_out and token_offsets_out: RWKV_ERROR_ARGS for no
+ * vocabulary bytes on the context, a NULL bytes, offsets, tokens_out or token_offsets_out, decreasing
+ * offsets, n_texts == 0 or above 65536, more than 2^28 bytes in all, a token longer than 255 bytes, and
+ * for a byte at which no token matches -- *error_at then receives the offset into bytes of the first
+ * such byte in text order; RWKV_ERROR_CTX | RWKV_ERROR_UNSUPPORTED on a pipeline or stage context;
+ * RWKV_ERROR_ALLOC for a failed allocation, with nothing enqueued. */
+RWKV_API bool rwkv_mi355x_tokenize(struct rwkv_context * ctx, const uint8_t * bytes,
+                                   const uint64_t * offsets /* [n_texts + 1], non-decreasing */, size_t n_texts,
+                                   uint32_t * tokens_out /* [offsets[n_texts]] */,
+                                   uint64_t * token_offsets_out /* [n_texts + 1] */,
+                                   uint64_t * error_at /* may be NULL */);
+
 /* The context's HIP stream (hipStream_t), so callers can time kernels with events on it. */
 RWKV_API void * rwkv_mi355x_stream(struct rwkv_context * ctx);
 

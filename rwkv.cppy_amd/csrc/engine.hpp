@@ -56,6 +56,13 @@ struct DeviceModel {
     // the tokens' bytes (rwkv_mi355x_vocab_bytes; dfa_pack_vocab's layout), shared by the clones
     DevBuf<uint8_t> vocab_head, vocab_tail;
     DevBuf<uint32_t> vocab_meta;
+    // the same bytes as the caller gave them, and the byte trie rwkv_mi355x_tokenize builds from them
+    // on its first call (TokTrie::blob; tokenize.hip): both follow every rwkv_mi355x_vocab_bytes
+    std::vector<uint32_t> vocab_offsets_h;
+    std::vector<uint8_t> vocab_bytes_h;
+    DevBuf<uint32_t> tok_trie;
+    uint32_t tok_nodes = 0, tok_lds = 0, tok_lmax = 0;
+    enum { TOK_UNBUILT, TOK_BUILT, TOK_REFUSED } tok_state = TOK_UNBUILT;  // refused: a token over TOK_LMAX bytes
 };
 
 bool upload_model(const ModelFile & mf, DeviceModel & dm, uint32_t layer_begin = 0, uint32_t layer_end = UINT32_MAX);
@@ -315,6 +322,16 @@ class Engine : public KLaunchTimer, private Workspace, private GenSlots {
     bool generate(const SamplingParams & p, size_t n, uint32_t * tokens_out, float * logits_out, const GenExtras & x);
     // The vocabulary's bytes to the model (shared by its clones).  0: done, 1: offsets decrease, 2: allocation
     int vocab_bytes(const uint32_t * offsets, const uint8_t * bytes);
+    // Tokenization (rwkv_mi355x_tokenize; engine_tokenize.hip): the texts bytes[offsets[i] ..
+    // offsets[i + 1]) through k_tok_match, k_tok_tile, k_tok_scan and k_tok_emit on the context's stream,
+    // synchronous; the state, logits and slots are untouched.  The caller has checked the pointers, the
+    // order of the offsets, n_texts and the total, and holds the lock that guards the model's tables: the
+    // trie is built and uploaded here on the first call after vocab_bytes.  Nothing is written to the
+    // outputs unless the call succeeds.  0: done; 1: no vocabulary bytes, or a token over TOK_LMAX bytes;
+    // 2: an allocation failed, nothing enqueued; 3: no token matches at *no_match (an offset into bytes);
+    // 4: the GPU
+    int tokenize(const uint8_t * bytes, const uint64_t * offsets, size_t n_texts, uint32_t * tokens_out,
+                 uint64_t * token_offsets_out, uint64_t * no_match);
     // The checks and the allocations of a constrained call over Q sequences in `rows` rows, before
     // anything is enqueued: the table is compressed (dfa_compress) and kept for the call that follows.
     // 0: passed; 1: the arguments (no vocabulary bytes, a bad entry or start state, a table over
@@ -566,6 +583,12 @@ class Engine : public KLaunchTimer, private Workspace, private GenSlots {
     // state, ended, n_allowed [kBatchMax] each; then ticket, and sample / generate's done and fin_step
     DevBuf<uint32_t> dfa_words_;
     std::vector<uint32_t> dfa_h_;
+    // tokenize: the texts as dwords, len / id per byte, the tiles' maps, entries and bases, the ids; the
+    // texts' offsets, the tiles' first texts (TokArgs::tile_end0, tile_start0) and the texts' first
+    // output indices travel through tok_h_
+    DevBuf<uint32_t> tok_text_, tok_off_, tok_tiles_, tok_id_, tok_table_, tok_tile_in_, tok_words_, tok_out_, tok_text_out_;
+    DevBuf<uint8_t> tok_len_;
+    std::vector<uint32_t> tok_h_;
     DevBuf<float> dstate_[2];
     int cur_ = 0;
     unsigned * herr_h_ = nullptr;  // hand-off timeout flag, host-mapped (herr_d_ = its device address)

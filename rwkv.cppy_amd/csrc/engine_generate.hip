@@ -126,6 +126,11 @@ int Engine::vocab_bytes(const uint32_t * offsets, const uint8_t * bytes) {
     m_->vocab_head = std::move(dh);
     m_->vocab_tail = std::move(dt);
     m_->vocab_meta = std::move(dm);
+    // the tokenizer's trie is rebuilt from these on its next call
+    m_->vocab_offsets_h.assign(offsets, offsets + m_->n_vocab + 1);
+    m_->vocab_bytes_h.assign(bytes, bytes + offsets[m_->n_vocab]);
+    m_->tok_trie.reset();
+    m_->tok_state = DeviceModel::TOK_UNBUILT;
     return 0;
 }
 

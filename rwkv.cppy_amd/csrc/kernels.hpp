@@ -715,4 +715,46 @@ struct Att7Lora {
 bool att7_lora_supported(const Att7Lora & a);
 bool launch_att7_lora(hipStream_t st, const Att7Lora & a);
 
+// ---- tokenization (tokenize.hip; rwkv_mi355x_tokenize) ---------------------------------
+constexpr int TOK_TILE = 4096;             // bytes of the concatenated texts per workgroup
+constexpr int TOK_LMAX = 255;              // the longest token the kernels take (len[] is a byte)
+constexpr int TOK_TRIE_LDS = 40 * 1024;    // the LDS a k_tok_match workgroup gives to the trie's first levels
+constexpr uint32_t TOK_NONE = 0xFFFFFFFFu;
+constexpr uint32_t TOK_MAX_NODES = 1u << 23;  // a node's child range is first | count << 23
+// The vocabulary as a byte trie, nodes in breadth-first order (node 0 is the root, the children of a
+// node are consecutive and sorted by their byte).  blob: root [256] (the child for a first byte, 0:
+// none), then node [n_nodes][2] (the token that ends here or TOK_NONE -- among equal tokens the
+// highest id; first child | children << 23), then label [n_nodes] bytes (the byte that leads to
+// the node), padded to a dword.  n_lds: the nodes of the whole levels that fit TOK_TRIE_LDS.
+struct TokTrie {
+    std::vector<uint32_t> blob;
+    uint32_t n_nodes = 0, n_lds = 0, lmax = 0;
+};
+// false: offsets decrease, a token longer than TOK_LMAX bytes or TOK_MAX_NODES nodes
+bool tok_build_trie(const uint32_t * offsets, const uint8_t * bytes, size_t V, TokTrie & out);
+struct TokArgs {
+    const uint32_t * trie;       // TokTrie::blob, device
+    uint32_t n_nodes, n_lds, lmax;
+    const uint32_t * text;       // the texts' bytes, concatenated, as dwords (readable up to a whole dword past total)
+    uint32_t total;              // bytes, 1 .. 2^28
+    const uint32_t * off;        // [n_texts + 1] text i is bytes [off[i], off[i + 1])
+    uint32_t n_texts;
+    uint32_t n_tiles;            // ceil(total / TOK_TILE)
+    // per tile: the first text that ends behind the tile's first byte, the first that starts at or behind it
+    const uint32_t * tile_end0, * tile_start0;
+    uint8_t * len;               // [total] the longest match at every byte, 0: none
+    uint32_t * id;               // [total] its token
+    uint32_t * table;            // [n_tiles][max(lmax, 1)] k_tok_tile: exit | count << 8, or 1 << 31 | the first byte without a match
+    uint32_t * tile_in;          // [n_tiles][2] k_tok_scan: the tile's entry offset, its first output index
+    uint32_t * words;            // [3] k_tok_scan: 1 no match somewhere, that byte, the tokens
+    uint32_t * out;              // [total] the ids
+    uint32_t * text_out;         // [n_texts + 1] the first output index of every text, then the tokens
+};
+// The four phases, in this order on one stream: len / id at every byte; every tile's map from its entry
+// offset to its exit offset and count; the tiles' true entries and output bases; the ids and the texts' counts.
+bool launch_tok_match(hipStream_t st, const TokArgs & a);
+bool launch_tok_tile(hipStream_t st, const TokArgs & a);
+bool launch_tok_scan(hipStream_t st, const TokArgs & a);
+bool launch_tok_emit(hipStream_t st, const TokArgs & a);
+
 }  // namespace rwkvmi

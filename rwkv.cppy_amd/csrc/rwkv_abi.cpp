@@ -1081,6 +1081,32 @@ RWKV_API uint32_t rwkv_mi355x_constraint_table_states(const struct rwkv_context 
     return ctx && ctx->engine ? ctx->engine->constraint_table_states() : 0u;
 }
 
+// ---- tokenization: every check before anything is enqueued, nothing written unless the call succeeds
+RWKV_API bool rwkv_mi355x_tokenize(struct rwkv_context * ctx, const uint8_t * bytes, const uint64_t * offsets, size_t n_texts,
+                                   uint32_t * tokens_out, uint64_t * token_offsets_out, uint64_t * error_at) {
+    if (!ctx || !ctx->engine) return false;
+    ctx->last_error = RWKV_ERROR_NONE;
+    CTX_CHECK(ctx, RWKV_ERROR_CTX | RWKV_ERROR_UNSUPPORTED, false, ctx->pipe == nullptr && !ctx->model->dm.partial(),
+              "Tokenization is not available on a pipeline or stage context");
+    CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, bytes && offsets && tokens_out && token_offsets_out,
+              "NULL bytes, offsets, tokens_out or token_offsets_out");
+    CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, n_texts >= 1 && n_texts <= 65536, "%zu texts (1 to 65536)", n_texts);
+    for (size_t i = 0; i < n_texts; i++)
+        CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, offsets[i] <= offsets[i + 1], "Text offsets must not decrease (text %zu)", i);
+    CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, offsets[n_texts] - offsets[0] <= ((uint64_t)1 << 28), "More than 2^28 bytes of text");
+    // the trie belongs to the model: built here, replaced by rwkv_mi355x_vocab_bytes
+    std::lock_guard<std::mutex> lock(g_model_mutex);
+    uint64_t at = 0;
+    const int e = ctx->engine->tokenize(bytes, offsets, n_texts, tokens_out, token_offsets_out, &at);
+    CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, e != 1, "Tokenization needs the vocabulary's bytes (rwkv_mi355x_vocab_bytes), no token over %d of them",
+              TOK_LMAX);
+    CTX_CHECK(ctx, RWKV_ERROR_ALLOC, false, e != 2, "Tokenizer allocation failed");
+    if (e == 3 && error_at) *error_at = at;
+    CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, e != 3, "No token matches the bytes at offset %" PRIu64, at);
+    CTX_CHECK(ctx, RWKV_ERROR_CTX, false, e == 0, "GPU tokenization failed");
+    return true;
+}
+
 
 RWKV_API bool rwkv_mi355x_prefill_batch(struct rwkv_context * ctx, size_t n_rows, const uint32_t * slots,
                                         const uint32_t * tokens, const size_t * lengths, const uint8_t * cont) {

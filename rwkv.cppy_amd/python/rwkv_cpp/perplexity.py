@@ -71,10 +71,20 @@ def main(argv=None) -> None:
     ap.add_argument('--vocab', default=None, help='World tokenizer vocabulary file (or RWKV_WORLD_VOCAB)')
     ap.add_argument('--device', action='store_true',
                     help='score on the device (measure_device) instead of one rwkv_eval per token')
+    ap.add_argument('--device-tokenizer', action='store_true',
+                    help='with --device: tokenize the file on the device too (RWKVModel.tokenize)')
     a = ap.parse_args(argv)
+    if a.device_tokenizer and not a.device:
+        ap.error('--device-tokenizer requires --device')
     model = RWKVModel(load_rwkv_shared_library(), a.model_path)
-    _, encode = get_world_tokenizer(a.vocab)
-    tokens = encode(open(a.text_path, encoding='utf-8').read())
+    if a.device_tokenizer:
+        import os
+        from .world_tokenizer import WorldTokenizer
+        model.set_vocab_bytes(WorldTokenizer(a.vocab or os.environ['RWKV_WORLD_VOCAB']))
+        tokens = model.tokenize([open(a.text_path, encoding='utf-8').read()])[0]
+    else:
+        _, encode = get_world_tokenizer(a.vocab)
+        tokens = encode(open(a.text_path, encoding='utf-8').read())
     if a.token_limit > 0:
         tokens = tokens[:a.token_limit]
     t0 = time.time()

@@ -63,6 +63,18 @@ class RWKVModel:
             raise ValueError(f'{len(vocab)} tokens for a vocabulary of {self.n_vocab}')
         self._library.rwkv_mi355x_vocab_bytes(self._ctx, vocab)
 
+    def tokenize(self, texts) -> List[List[int]]:
+        """MI355X extension (rwkv_mi355x_tokenize): tokenizes texts, a list of bytes or str (UTF-8), on
+        the device with the vocabulary of set_vocab_bytes -- WorldTokenizer.encode_bytes' greedy longest
+        match, all texts in one call.  Returns one list of ids per text; raises ValueError where no token
+        matches.  The state and logits are untouched."""
+        if not self._valid:
+            raise ValueError('Model was freed')
+        texts = [t.encode('utf-8') if isinstance(t, str) else bytes(t) for t in texts]
+        tokens, at = self._library.rwkv_mi355x_tokenize(self._ctx, texts)
+        tokens = tokens.tolist()
+        return [tokens[int(at[i]):int(at[i + 1])] for i in range(len(texts))]
+
     def set_constraint_table(self, next, accepting=None, start=0):
         """MI355X extension (rwkv_mi355x_constraint_table): keeps a constraint's table on the device,
         compressed and uploaded once, with no limit on its size but the 16-bit state numbers (a table

@@ -147,6 +147,8 @@ def make_constraint(rows: int, dfa) -> Optional[RWKVConstraint]:
 Logprobs = collections.namedtuple('Logprobs', ('token_logprob', 'top_ids', 'top_logprobs'))
 
 MAX_TOP_LOGPROBS = 20
+# rwkv_mi355x_tokenize: the bytes of the concatenated texts one workgroup owns (TOK_TILE, csrc/kernels.hpp)
+TOKENIZE_TILE = 4096
 
 
 def make_logprobs(rows: int, n: int, top_k: int):
@@ -403,6 +405,9 @@ class RWKVSharedLibrary:
         L.rwkv_mi355x_constraint_table.restype = ctypes.c_bool
         L.rwkv_mi355x_constraint_table_states.argtypes = [vp]
         L.rwkv_mi355x_constraint_table_states.restype = ctypes.c_uint32
+        P_U64 = ctypes.POINTER(ctypes.c_uint64)
+        L.rwkv_mi355x_tokenize.argtypes = [vp, P_U8, P_U64, sz, P_U32, P_U64, P_U64]
+        L.rwkv_mi355x_tokenize.restype = ctypes.c_bool
         L.rwkv_mi355x_selftest_dfa_advance.argtypes = [P_U32, P_U32, ctypes.c_int, ctypes.c_int, P_U32, P_U8, u32,
                                                        ctypes.POINTER(ctypes.c_uint16)]
         L.rwkv_mi355x_selftest_dfa_advance.restype = ctypes.c_bool
@@ -788,6 +793,32 @@ class RWKVSharedLibrary:
         if not self.library.rwkv_mi355x_vocab_bytes(ctx.ptr, offsets.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)),
                                                     data.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8))):
             raise ValueError('rwkv_mi355x_vocab_bytes failed, check stderr')
+
+    def rwkv_mi355x_tokenize(self, ctx: RWKVContext, texts):
+        """Tokenizes texts (a sequence of bytes objects) on the device, WorldTokenizer.encode_bytes' rule
+        over the vocabulary of rwkv_mi355x_vocab_bytes.  Returns (tokens uint32 [all], token_offsets
+        uint64 [len(texts) + 1]): text i's tokens are tokens[token_offsets[i]:token_offsets[i + 1]].
+        Where no token matches, raises ValueError as encode_bytes does, with the text's index in `text`
+        and the offset inside it in `offset`."""
+        import numpy as np
+        offsets = np.zeros(len(texts) + 1, np.uint64)
+        np.cumsum([len(t) for t in texts], out=offsets[1:])
+        # one text goes as it is; the byte behind an empty blob gives numpy something to point at
+        data = np.frombuffer(texts[0] if len(texts) == 1 and texts[0] else b''.join(texts) + b'\0', np.uint8)
+        tokens = np.zeros(max(1, int(offsets[-1])), np.uint32)
+        token_offsets = np.zeros(len(texts) + 1, np.uint64)
+        at = ctypes.c_uint64(0xFFFFFFFFFFFFFFFF)
+        P_U64 = ctypes.POINTER(ctypes.c_uint64)
+        if not self.library.rwkv_mi355x_tokenize(
+                ctx.ptr, data.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8)), offsets.ctypes.data_as(P_U64), len(texts),
+                tokens.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)), token_offsets.ctypes.data_as(P_U64), ctypes.byref(at)):
+            if at.value == 0xFFFFFFFFFFFFFFFF:
+                raise ValueError('rwkv_mi355x_tokenize failed, check stderr')
+            i = int(np.searchsorted(offsets, at.value, side='right')) - 1
+            err = ValueError(f'no token matches the bytes at offset {at.value - int(offsets[i])} of text {i}')
+            err.text, err.offset = i, at.value - int(offsets[i])
+            raise err
+        return tokens[:int(token_offsets[-1])], token_offsets
 
     def rwkv_mi355x_constraint_max_entries(self) -> int:
         """The largest n_states * n_cls a constraint's compressed table may have on the current device."""
